@@ -1,7 +1,14 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark of the scattered-interpolation hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C3|C2|C4|C5|C1|C4W] [--only]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C3|C2|C4|C5|C1|C4W] [--dump-outputs DIR]
+                    [--full [--only] [--no-cpu-baseline]]
+
+A plain run sets up the headline configuration, runs W untimed and K timed steps and prints the result line
+(`ms_per_step` = wall time of one timed step).  `--full` adds everything else described below: the checks of the
+last step's result, the rooflines (with their own timed launch of the factorisation's top GEMM), the reference-route
+LU timing of C2, the other configurations, the host-buffer facade and imported-mesh figures and the CPU baseline.
+`--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy (float64; see dump_outputs).
 
 One "step" = one full pass of the hot path over one batch of synthetic input that is
 already resident in HBM (SURVEY.md 8(d) clouds, generated on the device):
@@ -18,8 +25,8 @@ Gaussian: the 16k x 16k fp64 Cholesky the north star's MFMA target is quoted on,
 is C4, the strong-scaling configuration BASELINE.json quotes for 8 GPUs (10^7 targets sharded over the ranks: init
 on rank 0 is serial and reported as such, `eval_only_mpts_aggregate` = all targets / slowest rank's sweep);
 its `roofline` is the dominant kernel, the top-level trailing update of the factorisation (fp64 MFMA).
-The other GPU configurations (C2, C4, C5) run in the same invocation -- a few hundred ms in all -- and are
-reported under `extra.other_configs`, each with its own roofline object (`--only` skips them).
+With --full the other GPU configurations (C2, C4, C5) run in the same invocation -- a few hundred ms in all -- and
+are reported under `extra.other_configs`, each with its own roofline object (`--only` skips them).
 
 For N > 1 the driver launches this file with torch.distributed.run (one rank per GPU).
 """
@@ -39,6 +46,7 @@ HBM_PEAK_GBS = 8000.0        # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec (6.3 TB/
 FP64_PEAK_TFLOPS = 78.6      # MI355X fp64 matrix = vector peak; 256 CU x 128 flop/clk x 2.4 GHz
 VALU_PEAK_LANE_INSTR = 256 * 4 * 16 * 2.4e9   # fp64 VALU issue: 256 CU x 4 SIMD x 16 lanes/clk x 2.4 GHz lane-instructions/s
 PMC_ROUND = "r04"            # committed rocprofv3 --pmc passes the static counter figures are read from
+DUMP_SAMPLE = 2_000_000      # --dump-outputs: elements kept of a longer output array (all ranks together), <= 64 MB in all
 
 CONFIGS = {
     # name: (kind, dim, n_centres, m_targets, sharding)   sharding: per_gpu = weak, total = strong
@@ -66,9 +74,16 @@ def parse():
     ap.add_argument("--config", default=None, choices=sorted(CONFIGS),
                     help="headline configuration; default C3 on one GPU, C4 (strong scaling, the configuration "
                          "BASELINE.json quotes for 8 GPUs) on several")
-    ap.add_argument("--only", action="store_true", help="run the headline configuration only")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run the checks, rooflines, other configurations, side figures and the CPU baseline")
+    ap.add_argument("--only", action="store_true", help="with --full: run the headline configuration only")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step of the headline configuration as DIR/<name>.npy")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 class Env:
@@ -110,9 +125,10 @@ class Env:
         self.torch.cuda.synchronize()
 
 
-def run_config(env, name, steps, warmup):
+def run_config(env, name, steps, warmup, full=True, dump_dir=None):
     """Time `steps` steps of configuration `name` (after `warmup` untimed ones) between two barriers;
-    returns the result dict of this configuration (identical on every rank up to the max-reduction)."""
+    returns the result dict of this configuration (identical on every rank up to the max-reduction).
+    `full`: check the last step's result and add the rooflines; `dump_dir`: write the last step's outputs there."""
     torch, dist, pkg, ctx = env.torch, env.dist, env.pkg, env.ctx
     world, rank = env.world, env.rank
     cfg = CONFIGS[name]
@@ -227,52 +243,62 @@ def run_config(env, name, steps, warmup):
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
     ph_max = {k: float(v) for k, v in zip(names, tmax.tolist()) if v > 0.0}
 
+    # ---- what the last timed step returned: interpolated values (+ located triangles / the weights)
+    if dump_dir is not None:
+        outs = {"values": d_s}
+        if cfg["kind"] == "bary":
+            outs["leaf"] = d_leaf
+        elif rank == 0:
+            outs["weights"] = d_w
+        dump_outputs(env, dump_dir, outs)
+
     # ---- sanity of the result that was just produced (not timed)
-    sample = d_s[: min(m_rank, 4096)].cpu().numpy()
-    assert np.isfinite(sample).all(), "non-finite interpolated values"
-    if cfg["kind"] == "tps" and rank == 0:
-        # the reference's own route for this kernel class (gsl_linalg_LU_decomp + _svx, linalg/lu.c:59-201), forced, timed
-        # beside the default shifted-SPD route: 1 warm-up + 2 timed inits
-        os.environ["GSL_SINTERP_FORCE_LU"] = "1"
-        try:
-            lu_ms = []
-            for rep in range(3):
-                d_w.copy_(d_f)
-                ctx.timer_start()
-                st, route = ctx.rbf_solve(kind, eps, d_x.data_ptr(), n, dim, dim, d_phi.data_ptr(), n, d_w.data_ptr())
-                ms = ctx.timer_stop()
-                assert st == 0 and route == 3, (st, route)
-                if rep:
-                    lu_ms.append(ms)
-            extra["init_ms_reference_route_pivoted_lu"] = round(float(np.mean(lu_ms)), 3)
-        finally:
-            del os.environ["GSL_SINTERP_FORCE_LU"]
-        d_w.copy_(d_f)                                   # leave the default route's weights for the verification below
-        st, route = ctx.rbf_solve(kind, eps, d_x.data_ptr(), n, dim, dim, d_phi.data_ptr(), n, d_w.data_ptr())
-        assert st == 0
-    if cfg["kind"] == "tps" and world > 1:
-        dist.broadcast(d_w, 0)
-    if cfg["kind"] != "bary":
-        # the weights of the LAST timed step must interpolate the data: s(x_i) = f_i at a sample of the
-        # centres (catches a step that ran fast because it computed garbage, e.g. a broken graph replay)
-        ns = min(n, 2048)
-        d_chk = torch.empty(ns, dtype=f64, device="cuda")
-        ctx.rbf_eval(kind, eps, d_x.data_ptr(), n, dim, dim, d_w.data_ptr(), d_x.data_ptr(), ns, dim, d_chk.data_ptr())
-        torch.cuda.synchronize()
-        verify = float((d_chk - d_f[:ns]).abs().max()) / float(d_f.abs().max())
-        assert verify < 1e-6, f"interpolant does not reproduce the data after the timed steps: {verify:.3e}"
-    else:
-        # barycentric: the first values of this rank's shard against the library's host per-point entries
-        # (find_leaf + interp_point; the reference's own API, bit-identical to the oracle per tests/test_host_tree.py)
-        nchk = min(300, m_rank)
-        yh = d_y[:nchk].cpu().numpy()
-        got_v, got_l = d_s[:nchk].cpu().numpy(), d_leaf[:nchk].cpu().numpy()
-        bad = 0
-        for i in range(nchk):
-            leaf = tree.find_leaf(yh[i])
-            bad += int(leaf != got_l[i] or tree.interp_point(leaf, fh, yh[i]) != got_v[i])
-        verify = float(bad)
-        assert bad == 0, f"{bad} of {nchk} GPU barycentric results differ from the host walk"
+    if full:
+        sample = d_s[: min(m_rank, 4096)].cpu().numpy()
+        assert np.isfinite(sample).all(), "non-finite interpolated values"
+        if cfg["kind"] == "tps" and rank == 0:
+            # the reference's own route for this kernel class (gsl_linalg_LU_decomp + _svx, linalg/lu.c:59-201), forced, timed
+            # beside the default shifted-SPD route: 1 warm-up + 2 timed inits
+            os.environ["GSL_SINTERP_FORCE_LU"] = "1"
+            try:
+                lu_ms = []
+                for rep in range(3):
+                    d_w.copy_(d_f)
+                    ctx.timer_start()
+                    st, route = ctx.rbf_solve(kind, eps, d_x.data_ptr(), n, dim, dim, d_phi.data_ptr(), n, d_w.data_ptr())
+                    ms = ctx.timer_stop()
+                    assert st == 0 and route == 3, (st, route)
+                    if rep:
+                        lu_ms.append(ms)
+                extra["init_ms_reference_route_pivoted_lu"] = round(float(np.mean(lu_ms)), 3)
+            finally:
+                del os.environ["GSL_SINTERP_FORCE_LU"]
+            d_w.copy_(d_f)                                   # leave the default route's weights for the verification below
+            st, route = ctx.rbf_solve(kind, eps, d_x.data_ptr(), n, dim, dim, d_phi.data_ptr(), n, d_w.data_ptr())
+            assert st == 0
+        if cfg["kind"] == "tps" and world > 1:
+            dist.broadcast(d_w, 0)
+        if cfg["kind"] != "bary":
+            # the weights of the LAST timed step must interpolate the data: s(x_i) = f_i at a sample of the
+            # centres (catches a step that ran fast because it computed garbage, e.g. a broken graph replay)
+            ns = min(n, 2048)
+            d_chk = torch.empty(ns, dtype=f64, device="cuda")
+            ctx.rbf_eval(kind, eps, d_x.data_ptr(), n, dim, dim, d_w.data_ptr(), d_x.data_ptr(), ns, dim, d_chk.data_ptr())
+            torch.cuda.synchronize()
+            verify = float((d_chk - d_f[:ns]).abs().max()) / float(d_f.abs().max())
+            assert verify < 1e-6, f"interpolant does not reproduce the data after the timed steps: {verify:.3e}"
+        else:
+            # barycentric: the first values of this rank's shard against the library's host per-point entries
+            # (find_leaf + interp_point; the reference's own API, bit-identical to the oracle per tests/test_host_tree.py)
+            nchk = min(300, m_rank)
+            yh = d_y[:nchk].cpu().numpy()
+            got_v, got_l = d_s[:nchk].cpu().numpy(), d_leaf[:nchk].cpu().numpy()
+            bad = 0
+            for i in range(nchk):
+                leaf = tree.find_leaf(yh[i])
+                bad += int(leaf != got_l[i] or tree.interp_point(leaf, fh, yh[i]) != got_v[i])
+            verify = float(bad)
+            assert bad == 0, f"{bad} of {nchk} GPU barycentric results differ from the host walk"
 
     res = {
         "workload": cfg["label"], "config": name, "n_centres": n, "dim": dim,
@@ -281,15 +307,17 @@ def run_config(env, name, steps, warmup):
         "value_mpts": round(value, 4), "ms_per_step": round(ms_per_step, 4), "steps": steps, "warmup": warmup,
         "phase_ms": {k: round(v, 4) for k, v in ph_ms.items()},
         "phase_ms_max_over_ranks": {k: round(v, 4) for k, v in ph_max.items()},
-        "verify_after_timed_steps": verify, "extra": extra,
+        "extra": extra,
     }
+    if full:
+        res["verify_after_timed_steps"] = verify
     t_eval = ph_max.get("bary_eval", ph_max.get("eval"))
     if t_eval:
         res["eval_only_mpts_aggregate"] = round(m_total / (t_eval * 1e-3) / 1e6, 3)   # all ranks' targets / slowest rank's sweep
         res["eval_speedup_vs_1gpu_expected_from"] = (
             "divide by `eval_only_mpts_aggregate` of the SAME config in the --gpus 1 run (headline or extra.other_configs); "
             "whole-step `value_mpts` additionally carries rank 0's serial init (phase_ms_max_over_ranks.init) and the broadcast")
-    if rank == 0:
+    if rank == 0 and full:
         gemm = time_top_gemm(ctx, n) if cfg["kind"] != "bary" and n >= 2048 else None
         res.update(rooflines(cfg, name, n, dim, m_rank, ph_ms, extra, gemm))
     del d_x, d_y, d_s
@@ -305,9 +333,9 @@ def main():
     # over the ranks).  C3 with a fixed M per GPU would read ~N x by construction while rank 0's ~30 ms init pins the
     # step and N-1 GPUs idle (round-2 review); it is still run, labelled weak, under other_configs.
     headline = args.config or ("C3" if env.world == 1 else "C4")
-    head = run_config(env, headline, args.steps, args.warmup)
+    head = run_config(env, headline, args.steps, args.warmup, full=args.full, dump_dir=args.dump_outputs)
     others = {}
-    if not args.only:
+    if args.full and not args.only:
         for name in ("C2", "C3", "C4", "C5"):
             if name != headline and not (name == "C3" and headline != "C3" and env.world == 1):
                 others[name] = run_config(env, name, min(args.steps, 3), min(args.warmup, 1))
@@ -322,8 +350,9 @@ def main():
                        "dim": head["dim"], "targets_per_gpu": head["targets_per_gpu"], "targets_total": head["targets_total"],
                        "parallelism": f"target shards x{world}, weights broadcast (RCCL)" if world > 1 else "1 GPU"},
             "phase_ms": head["phase_ms"], "phase_ms_max_over_ranks": head["phase_ms_max_over_ranks"],
-            "verify_after_timed_steps": head["verify_after_timed_steps"],
         }
+        if args.full:
+            out["verify_after_timed_steps"] = head["verify_after_timed_steps"]
         # the points of the strong-scaling curves, in every run (N = 1 included) so that the curve can be assembled from
         # the per-N lines: whole step and eval only, C4 and C5 (no multi-GPU curve has been MEASURED by the builder:
         # development boxes have one GPU)
@@ -339,7 +368,7 @@ def main():
         out["extra"] = dict(head["extra"], other_configs=others)
         if env.rehearsal:
             out["extra"]["REHEARSAL"] = "ranks share one GPU / non-RCCL backend: control-flow check only, the numbers are meaningless"
-        if world == 1 and not args.only:
+        if args.full and world == 1 and not args.only:
             try:
                 out["facade_host_mpts"] = {k: facade_host_path(env, k) for k in ("C4", "C5")}
             except Exception as exc:                      # never let the side measurement take the line down
@@ -348,11 +377,28 @@ def main():
                 out["extra"]["imported_mesh_C5M"] = mesh_figure(env)
             except Exception as exc:
                 out["extra"]["imported_mesh_C5M"] = {"error": repr(exc)}
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(CONFIGS[headline], head["n_centres"], head["dim"], head["targets_total"])
         print(json.dumps(out))
     if env.world > 1:
         env.dist.destroy_process_group()
+
+
+def dump_outputs(env, out_dir, arrays):
+    """Write each device array of `arrays` as out_dir/<name>.npy in float64 (int32 triangle ids are exact in it).
+    An array longer than DUMP_SAMPLE / world elements is reduced to a fixed sample: sorted indices drawn without
+    replacement by numpy's generator seeded with 0, the same in every run with the same arguments.  With several
+    ranks every rank writes its own shard as <name>_rank<r>.npy."""
+    torch = env.torch
+    os.makedirs(out_dir, exist_ok=True)
+    cap = DUMP_SAMPLE // env.world
+    suffix = f"_rank{env.rank}" if env.world > 1 else ""
+    for name, t in arrays.items():
+        t = t.reshape(-1)
+        if t.numel() > cap:
+            idx = np.sort(np.random.default_rng(0).choice(t.numel(), cap, replace=False))
+            t = t[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(out_dir, name + suffix + ".npy"), t.to(torch.float64).cpu().numpy())
 
 
 def facade_host_path(env, name, reps=3):

@@ -1,8 +1,8 @@
 """Summarises rocprofv3 --pmc passes (one counter per pass, tools/profile_all.sh) into profiles/.
 
-    python tools/pmc_summary.py gpurun_out/pmc [round-tag, default r02]
+    python tools/pmc_summary.py profile_out/pmc [round-tag, default r02]
 
-expects gpurun_out/pmc/<CONFIG>_<COUNTER>/**/*counter_collection.csv.  Writes
+expects profile_out/pmc/<CONFIG>_<COUNTER>/**/*counter_collection.csv.  Writes
   profiles/<tag>_pmc_counters.json     every counter, per config and kernel: launches, sum, max over launches
   profiles/<tag>_pmc_hbm_traffic.csv   FETCH_SIZE / WRITE_SIZE (KB per dispatch, raw)
   profiles/<tag>_pmc_traffic.json      HBM-side bytes of the LARGEST launch of each kernel = (2*FETCH + WRITE)*1024
