@@ -122,6 +122,7 @@ SIGNATURES = {
     "gsl_sinterp_hip_rbf_fill": (_i, [_vp, _i, _d, _vp, _sz, _i, _sz, _vp, _sz]),
     "gsl_sinterp_hip_cholesky_decomp1": (_i, [_vp, _sz, _vp, _sz, _pi]),
     "gsl_sinterp_hip_cholesky_svx": (_i, [_vp, _sz, _vp, _sz, _vp]),
+    "gsl_sinterp_hip_cholesky_factor_solve": (_i, [_vp, _sz, _vp, _sz, _pi, _vp, _sz, _i]),
     "gsl_sinterp_hip_lu_decomp": (_i, [_vp, _sz, _vp, _sz, _vp, _pi]),
     "gsl_sinterp_hip_lu_svx": (_i, [_vp, _sz, _vp, _sz, _vp, _vp]),
     "gsl_sinterp_hip_cholesky_decomp2": (_i, [_vp, _sz, _vp, _sz, _vp, _pi]),
@@ -405,6 +406,12 @@ class HipContext:
     def cholesky_svx(self, n, d_llt, lda, d_x):
         check(lib().gsl_sinterp_hip_cholesky_svx(self._h, n, d_llt, lda, d_x), self._h)
 
+    def cholesky_factor_solve(self, n, d_a, lda, d_x, ldx, nrhs):
+        """cholesky_decomp1 + the solve of nrhs columns d_x + q*ldx in place; returns (status, info)"""
+        info = C.c_int(0)
+        st = lib().gsl_sinterp_hip_cholesky_factor_solve(self._h, n, d_a, lda, C.byref(info), d_x, ldx, nrhs)
+        return st, info.value
+
     def lu_decomp(self, n, d_a, lda, d_perm):
         sg = C.c_int(0)
         check(lib().gsl_sinterp_hip_lu_decomp(self._h, n, d_a, lda, d_perm, C.byref(sg)), self._h)
@@ -464,6 +471,32 @@ class HipContext:
         route = C.c_int(0)
         st = lib().gsl_sinterp_hip_rbf_solve(self._h, kind, eps, d_x, n, dim, xtda, d_phi, lda, d_w, C.byref(route))
         return st, route.value
+
+    def rbf_solve_affine(self, kind, eps, d_x, n, dim, xtda, d_phi, lda, d_w, h_poly):
+        """h_poly: caller's float64 numpy buffer of at least dim + 1 entries (c lands in h_poly[:dim + 1]);
+        returns (status, route)"""
+        assert h_poly.dtype == np.float64 and h_poly.flags.c_contiguous and h_poly.size >= dim + 1
+        route = C.c_int(0)
+        st = lib().gsl_sinterp_hip_rbf_solve_affine(self._h, kind, eps, d_x, n, dim, xtda, d_phi, lda, d_w,
+                                                    h_poly.ctypes.data_as(_pd), C.byref(route))
+        return st, route.value
+
+    def rbf_eval_affine(self, kind, eps, poly, d_x, n, dim, xtda, d_w, d_y, m, ytda, d_s, model_id=0):
+        p = np.ascontiguousarray(poly, dtype=np.float64)
+        assert p.size >= dim + 1
+        check(lib().gsl_sinterp_hip_rbf_eval_affine(self._h, kind, eps, p.ctypes.data_as(_pd), d_x, n, dim, xtda, d_w, d_y,
+                                                    m, ytda, d_s, model_id), self._h)
+
+    def krige_solve(self, kind, eps, nugget, d_x, n, dim, xtda, d_phi, lda, d_w):
+        """returns (status, route, mean)"""
+        route, mean = C.c_int(0), C.c_double(0)
+        st = lib().gsl_sinterp_hip_krige_solve(self._h, kind, eps, nugget, d_x, n, dim, xtda, d_phi, lda, d_w,
+                                               C.byref(mean), C.byref(route))
+        return st, route.value, mean.value
+
+    def krige_eval(self, kind, eps, mean, d_x, n, dim, xtda, d_w, d_y, m, ytda, d_s, model_id=0):
+        check(lib().gsl_sinterp_hip_krige_eval(self._h, kind, eps, mean, d_x, n, dim, xtda, d_w, d_y, m, ytda, d_s,
+                                               model_id), self._h)
 
     def gemm_minus(self, m, n, k, d_a, lda, d_b, ldb, b_is_kn, d_c, ldc, lower_only=0):
         check(lib().gsl_sinterp_hip_gemm_minus(self._h, m, n, k, d_a, lda, d_b, ldb, b_is_kn, d_c, ldc, lower_only),

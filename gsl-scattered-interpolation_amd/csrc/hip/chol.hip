@@ -665,11 +665,11 @@ static int cholesky_decomp1_impl(gsl_sinterp_hip_ctx *ctx, size_t n, double *d_a
   st = sinterp_streamk_prepare(ctx);
   if (st) return st;
   const bool fold = fb != NULL && chol_fold_applicable(n, d_a, lda, nrhs) && ldf >= n;
-  if (!fold) { fb = NULL; nrhs = 0; }
+  if (!fold) { fb = NULL; ldf = 0; nrhs = 0; }
   int replayed = 0;
-  /* graph key: the right-hand-side buffer (16-byte aligned or not, its low bits are free below bit 3), their count and stride */
-  const void *gkey = (const void *)(((uintptr_t)fb & ~(uintptr_t)7) ^ (uintptr_t)(symmetric_input ? 1 : 0) ^ ((uintptr_t)nrhs << 1) ^ ((uintptr_t)ldf << 44));
-  st = sinterp_graph_try_launch(ctx, 0, n, lda, d_a, gkey, &replayed);
+  /* graph key: the matrix, and the right-hand sides (buffer, stride, count) and input form baked into the kernels */
+  const sinterp_graph_key gkey = {{n, lda, (uintptr_t)d_a, (uintptr_t)fb, ldf, (uintptr_t)nrhs, (uintptr_t)(symmetric_input ? 1 : 0)}};
+  st = sinterp_graph_try_launch(ctx, 0, gkey, &replayed);
   if (st) return st;
   if (!replayed) {
     hipStream_t saved;
@@ -689,7 +689,7 @@ static int cholesky_decomp1_impl(gsl_sinterp_hip_ctx *ctx, size_t n, double *d_a
         hipLaunchKernelGGL(chol_diag_writeback_kernel, dim3((unsigned)nblk), dim3(256), 0, ctx->stream, d_a, lda, n,
                            (const double *)d_diag);
     }
-    int st2 = sinterp_capture_end(ctx, saved, 0, n, lda, d_a, gkey);
+    int st2 = sinterp_capture_end(ctx, saved, 0, gkey);
     if (me != hipSuccess) return sinterp_fail(ctx, ST_EFAILED, "zero info", me, __FILE__, __LINE__);
     if (st) return st;
     if (st2) return st2;
@@ -712,23 +712,43 @@ int sinterp_cholesky_decomp1_sym(gsl_sinterp_hip_ctx *ctx, size_t n, double *d_a
   return cholesky_decomp1_impl(ctx, n, d_a, lda, h_info, true, NULL, 0, 0, NULL);
 }
 
-/* factor (symmetric input) and solve: d_x (nrhs vectors, d_x + q * ldx) <- (L L^T)^-1 d_x.  When every panel is 128 wide the
-   forward substitution rides along with the factorisation and only the backward sweep remains (cholesky.c:178-181 does
+/* factor and solve: d_x (nrhs vectors, d_x + q * ldx) <- (L L^T)^-1 d_x.  When every panel is 128 wide the forward
+   substitution rides along with the factorisation and only the backward sweep remains (cholesky.c:178-181 does
    L c = b, then L^T x = c). */
-int sinterp_cholesky_factor_solve_sym(gsl_sinterp_hip_ctx *ctx, size_t n, double *d_a, size_t lda, int *h_info, double *d_x, size_t ldx,
-                                      int nrhs)
+static int chol_factor_solve(gsl_sinterp_hip_ctx *ctx, size_t n, double *d_a, size_t lda, int *h_info, double *d_x, size_t ldx,
+                             int nrhs, bool symmetric_input)
 {
   EXCLUSIVE_SECTION(ctx);
   int folded = 0;
   /* the sweeps are enqueued behind the factorisation without waiting for its pivot status: a failed factorisation
      leaves NaN in L, the sweeps carry them through (their hand-offs wait on epochs, not on values), and the one
      host round trip at the end reports GSL_EDOM */
-  int st = cholesky_decomp1_impl(ctx, n, d_a, lda, h_info, true, d_x, ldx, nrhs, &folded, true);
+  int st = cholesky_decomp1_impl(ctx, n, d_a, lda, h_info, symmetric_input, d_x, ldx, nrhs, &folded, true);
   if (st) return st;
   if (!folded) st = sinterp_cholesky_svx_multi(ctx, n, d_a, lda, d_x, ldx, nrhs);
   else st = sinterp_trsv_multi(ctx, n, d_a, lda, d_x, d_x, ldx, nrhs, 1, 0);                /* L^T x = c, in place */
   if (st) return st;
   return chol_read_info(ctx, n, h_info);
+}
+
+/* symmetric input (both triangles valid, as the RBF fill writes them) */
+int sinterp_cholesky_factor_solve_sym(gsl_sinterp_hip_ctx *ctx, size_t n, double *d_a, size_t lda, int *h_info, double *d_x, size_t ldx,
+                                      int nrhs)
+{
+  return chol_factor_solve(ctx, n, d_a, lda, h_info, d_x, ldx, nrhs, true);
+}
+
+/* the public form: cholesky_decomp1's contract for d_a (lower triangle read, original kept in the strict upper one) */
+extern "C" int gsl_sinterp_hip_cholesky_factor_solve(gsl_sinterp_hip_ctx *ctx, size_t n, double *d_a, size_t lda, int *h_info,
+                                                     double *d_x, size_t ldx, int nrhs)
+{
+  REQUIRE(ctx, ctx != NULL, ST_EFAULT);
+  HIP_OK(ctx, hipSetDevice(ctx->device));      /* one context per device: bind before any launch */
+  REQUIRE(ctx, lda >= n && ldx >= n && nrhs >= 1 && nrhs <= TRSV_MAXR, ST_EINVAL);
+  REQUIRE(ctx, n == 0 || (d_a && d_x), ST_EFAULT);
+  if (h_info) *h_info = 0;
+  if (n == 0) return ST_SUCCESS;
+  return chol_factor_solve(ctx, n, d_a, lda, h_info, d_x, ldx, nrhs, false);
 }
 
 /* ------------------------------------------------------------------------ */
@@ -1226,10 +1246,10 @@ static int trsv_multi_ex(gsl_sinterp_hip_ctx *ctx, size_t n, const double *T, si
   if (nrhs > TRSV_MAXR) return sinterp_fail(ctx, ST_EINVAL, "trsv: too many right-hand sides", hipSuccess, __FILE__, __LINE__);
   /* one cached graph per direction: slot 2 forward, slot 3 backward */
   const int slot = mode == 0 ? 2 : 3;
-  const size_t key_lda = ((ldt * 8 + (size_t)mode * 2 + (size_t)unit) * 8 + (size_t)nrhs) ^ (ldb << 40) ^ ((size_t)inv_ready << 62);
-  const void *p1 = (const void *)((uintptr_t)b ^ ((uintptr_t)xout << 1));
+  const sinterp_graph_key gkey = {{n, ldt, (uintptr_t)T, (uintptr_t)b, (uintptr_t)xout, ldb, (uintptr_t)nrhs, (uintptr_t)mode,
+                                    (uintptr_t)unit, (uintptr_t)inv_ready}};
   int replayed = 0;
-  int st = sinterp_graph_try_launch(ctx, slot, n, key_lda, T, p1, &replayed);
+  int st = sinterp_graph_try_launch(ctx, slot, gkey, &replayed);
   if (st || replayed) return st;
   void *d_inv = NULL;
   const size_t inv_bytes = ((n + TS - 1) / TS) * TS * TS * sizeof(double);
@@ -1269,7 +1289,7 @@ static int trsv_multi_ex(gsl_sinterp_hip_ctx *ctx, size_t n, const double *T, si
     hipLaunchKernelGGL(vec_copy_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, ctx->stream, (const double *)b, b_src, cnt);
   }
   st = trsv_launches(ctx, n, T, ldt, b_src, xout, ldb, nrhs, mode, unit, (double *)d_inv, inv_ready);
-  int st2 = sinterp_capture_end(ctx, saved, slot, n, key_lda, T, p1);
+  int st2 = sinterp_capture_end(ctx, saved, slot, gkey);
   return st ? st : st2;
 }
 

@@ -39,9 +39,12 @@ struct gsl_sinterp_hip_ctx {
   hipStream_t side_stream;  /* bary.hip: independent kernels of one evaluation run beside the main stream */
   hipEvent_t side_ev[4];    /* fork / join events of the side stream (created with the stream) */
   /* hipGraph cache: the recursive factorisation drivers issue ~1-2k small, fully static
-     launches; they are captured once per (routine, n, lda, pointers) and replayed */
+     launches; they are captured once per (routine, arguments) and replayed.  The key holds every
+     argument baked into the captured kernels, one word each (no folding: two different argument
+     sets must never compare equal), plus the workspace pointer the graph was captured with. */
   hipStream_t cap_stream;
-  struct GraphSlot { hipGraphExec_t exec; size_t n, lda; const void *p0, *p1, *work; } graph[4];
+  enum { GRAPH_KEY_WORDS = 12 };
+  struct GraphSlot { hipGraphExec_t exec; uintptr_t key[GRAPH_KEY_WORDS]; } graph[4];
   int use_graphs;
   /* stream-K GEMM (gemm.hip): one partial-tile slot + one flag per persistent workgroup */
   double *d_sk_partial;
@@ -72,14 +75,15 @@ struct gsl_sinterp_hip_ctx {
   char err[512];
 };
 
-/* Graph helpers (shim.hip).  sinterp_graph_lookup returns 1 and launches the cached
-   graph on the context's stream when slot `which` matches the key; otherwise 0.
-   Between sinterp_capture_begin / _end every launch on ctx->stream is recorded. */
-int sinterp_graph_try_launch(gsl_sinterp_hip_ctx *ctx, int which, size_t n, size_t lda, const void *p0, const void *p1,
-                             int *launched);
+/* Graph helpers (shim.hip).  A key is up to GRAPH_KEY_WORDS - 1 argument words (unused words 0); the helpers append
+   ctx->d_work.  sinterp_graph_try_launch sets *launched = 1 and launches the cached graph on the context's stream when
+   slot `which` holds exactly this key.  Between sinterp_capture_begin / _end every launch on ctx->stream is recorded. */
+struct sinterp_graph_key {
+  uintptr_t w[gsl_sinterp_hip_ctx::GRAPH_KEY_WORDS - 1];
+};
+int sinterp_graph_try_launch(gsl_sinterp_hip_ctx *ctx, int which, const sinterp_graph_key &key, int *launched);
 int sinterp_capture_begin(gsl_sinterp_hip_ctx *ctx, hipStream_t *saved);
-int sinterp_capture_end(gsl_sinterp_hip_ctx *ctx, hipStream_t saved, int which, size_t n, size_t lda, const void *p0,
-                        const void *p1);
+int sinterp_capture_end(gsl_sinterp_hip_ctx *ctx, hipStream_t saved, int which, const sinterp_graph_key &key);
 
 static inline int sinterp_fail(gsl_sinterp_hip_ctx *ctx, int status, const char *what, hipError_t e,
                                const char *file, int line)

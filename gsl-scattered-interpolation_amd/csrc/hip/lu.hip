@@ -957,7 +957,8 @@ extern "C" int gsl_sinterp_hip_lu_decomp(gsl_sinterp_hip_ctx *ctx, size_t n, dou
     const unsigned gen0 = 1;                             /* tag 0 = never written */
     HIP_OK(ctx, hipMemcpy(ctx->d_lu_coop, &gen0, sizeof gen0, hipMemcpyHostToDevice));
   }
-  st = sinterp_graph_try_launch(ctx, 1, n, lda, d_a, d_perm, &replayed);
+  const sinterp_graph_key gkey = {{n, lda, (uintptr_t)d_a, (uintptr_t)d_perm}};
+  st = sinterp_graph_try_launch(ctx, 1, gkey, &replayed);
   if (st) return st;
   if (!replayed) {
     hipStream_t saved;
@@ -966,7 +967,7 @@ extern "C" int gsl_sinterp_hip_lu_decomp(gsl_sinterp_hip_ctx *ctx, size_t n, dou
     /* every leaf a 64-wide panel (block or cooperative kernel): its interchanges go to the other columns right away */
     const bool eager = lu_coop_ok(ctx, lda, n, 0);
     st = lu_panel(ctx, d_a, lda, n, 0, n, d_perm, eager);         /* d_perm holds LAPACK-style ipiv for now */
-    int st2 = sinterp_capture_end(ctx, saved, 1, n, lda, d_a, d_perm);
+    int st2 = sinterp_capture_end(ctx, saved, 1, gkey);
     if (st) return st;
     if (st2) return st2;
   }

@@ -212,13 +212,22 @@ int sinterp_exclusive_end(gsl_sinterp_hip_ctx *ctx)
   return ST_SUCCESS;
 }
 
-int sinterp_graph_try_launch(gsl_sinterp_hip_ctx *ctx, int which, size_t n, size_t lda, const void *p0, const void *p1,
-                             int *launched)
+/* the slot's full key: the caller's argument words, then the workspace pointer */
+static void graph_full_key(const gsl_sinterp_hip_ctx *ctx, const sinterp_graph_key &key, uintptr_t *out)
+{
+  const int nw = gsl_sinterp_hip_ctx::GRAPH_KEY_WORDS;
+  for (int i = 0; i < nw - 1; i++) out[i] = key.w[i];
+  out[nw - 1] = (uintptr_t)ctx->d_work;
+}
+
+int sinterp_graph_try_launch(gsl_sinterp_hip_ctx *ctx, int which, const sinterp_graph_key &key, int *launched)
 {
   *launched = 0;
   if (!ctx->use_graphs) return ST_SUCCESS;
   gsl_sinterp_hip_ctx::GraphSlot &g = ctx->graph[which];
-  if (g.exec && g.n == n && g.lda == lda && g.p0 == p0 && g.p1 == p1 && g.work == ctx->d_work) {
+  uintptr_t full[gsl_sinterp_hip_ctx::GRAPH_KEY_WORDS];
+  graph_full_key(ctx, key, full);
+  if (g.exec && memcmp(g.key, full, sizeof full) == 0) {
     HIP_OK(ctx, hipGraphLaunch(g.exec, ctx->stream));
     *launched = 1;
   }
@@ -235,8 +244,7 @@ int sinterp_capture_begin(gsl_sinterp_hip_ctx *ctx, hipStream_t *saved)
   return ST_SUCCESS;
 }
 
-int sinterp_capture_end(gsl_sinterp_hip_ctx *ctx, hipStream_t saved, int which, size_t n, size_t lda, const void *p0,
-                        const void *p1)
+int sinterp_capture_end(gsl_sinterp_hip_ctx *ctx, hipStream_t saved, int which, const sinterp_graph_key &key)
 {
   if (!ctx->use_graphs) return ST_SUCCESS;
   ctx->stream = saved;
@@ -247,7 +255,7 @@ int sinterp_capture_end(gsl_sinterp_hip_ctx *ctx, hipStream_t saved, int which, 
   hipError_t e = hipGraphInstantiate(&g.exec, graph, NULL, NULL, 0);
   (void)hipGraphDestroy(graph);
   if (e != hipSuccess) { g.exec = NULL; return sinterp_fail(ctx, ST_EFAILED, "hipGraphInstantiate", e, __FILE__, __LINE__); }
-  g.n = n; g.lda = lda; g.p0 = p0; g.p1 = p1; g.work = ctx->d_work;
+  graph_full_key(ctx, key, g.key);
   HIP_OK(ctx, hipGraphLaunch(g.exec, ctx->stream));
   return ST_SUCCESS;
 }

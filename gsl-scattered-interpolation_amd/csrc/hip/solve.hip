@@ -351,7 +351,7 @@ extern "C" int gsl_sinterp_hip_rbf_solve_affine(gsl_sinterp_hip_ctx *ctx, int ki
   REQUIRE(ctx, kind == GSL_SINTERP_RBF_TPS, ST_EINVAL);      /* conditionally positive definite of order 2: the kernel the tail belongs to */
   REQUIRE(ctx, h_poly != NULL, ST_EFAULT);
   REQUIRE(ctx, n >= (size_t)dim + 1, ST_EINVAL);
-  for (int a = 0; a < SV_MAXK; a++) h_poly[a] = 0.0;
+  for (int a = 0; a <= dim && a < SV_MAXK; a++) h_poly[a] = 0.0;   /* h_poly[0 .. dim] (the header's size), no more */
   return rbf_solve_impl(ctx, kind, eps, d_x, n, dim, xtda, d_phi, lda, d_w, h_route, false, h_poly);
 }
 

@@ -158,6 +158,13 @@ int gsl_sinterp_hip_cholesky_decomp1(gsl_sinterp_hip_ctx *ctx, size_t n, double 
                                      int *h_info);
 int gsl_sinterp_hip_cholesky_svx(gsl_sinterp_hip_ctx *ctx, size_t n, const double *d_llt,
                                  size_t lda, double *d_x);
+/* cholesky_decomp1 followed by the solve of nrhs (1 <= nrhs <= 5) right-hand sides in place: column q at d_x + q*ldx
+   (ldx >= n) holds b_q on entry and A^-1 b_q on exit.  d_a, *h_info and the status as for cholesky_decomp1 (GSL_EDOM
+   and the failing column; d_x is then undefined).  When n is a multiple of 128, lda is even and d_a is 16-byte
+   aligned, the forward substitution runs inside the factorisation (d_x needs only 8-byte alignment); otherwise the
+   two sweeps of cholesky_svx follow it. */
+int gsl_sinterp_hip_cholesky_factor_solve(gsl_sinterp_hip_ctx *ctx, size_t n, double *d_a, size_t lda, int *h_info,
+                                          double *d_x, size_t ldx, int nrhs);
 /* PA = LU with partial pivoting; d_perm[n] (int32) as gsl_permutation content. */
 int gsl_sinterp_hip_lu_decomp(gsl_sinterp_hip_ctx *ctx, size_t n, double *d_a, size_t lda,
                               int *d_perm, int *h_signum);
@@ -236,7 +243,8 @@ int gsl_sinterp_hip_rbf_solve_ex(gsl_sinterp_hip_ctx *ctx, int kind, double eps,
 
 /* Thin-plate spline WITH its affine tail (the "N + d + 1" system):
        [Phi P; P^T 0] [w; c] = [f; 0],  P = [1, x],     s(y) = sum_j w_j phi(|y - x_j|) + c_0 + sum_a c_a y_a.
-   d_w holds f on entry and w on exit, h_poly[0 .. dim] receives c (raw coordinates).  Route 9: block elimination on the
+   d_w holds f on entry and w on exit, h_poly[0 .. dim] receives c (raw coordinates); h_poly needs dim + 1 doubles, and
+   nothing past h_poly[dim] is read or written (by _eval_affine either).  Route 9: block elimination on the
    shifted SPD matrix of route 2 (one MFMA Cholesky, d + 2 right-hand sides, a (d+1) x (d+1) system on the host);
    route 10: pivoted LU of the augmented matrix (the reference route, linalg/lu.c:59-201; taken when the shifted
    matrix is not SPD or GSL_SINTERP_FORCE_LU=1) -- it needs d_phi with n + dim + 1 rows and lda >= n + dim + 1.
