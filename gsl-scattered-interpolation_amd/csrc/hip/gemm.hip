@@ -21,6 +21,7 @@
  */
 #include "common.h"
 #include <stdlib.h>
+#include <string.h>
 
 typedef double double4_t __attribute__((ext_vector_type(4)));
 
@@ -341,6 +342,51 @@ gemm_minus_dma_nt_kernel(GemmArgs g)
    the 8 XCD L2s) and an explicit vmcnt(0) + barrier before the flag, so no L2 writeback /
    invalidate is needed.  The owner clears the flag it consumed: launches on one stream are
    serialised, so the buffers are reusable by the next launch (and by a hipGraph replay). */
+#ifdef SINTERP_DIAG_PROF
+/* per workgroup: s_memtime at start / end, the summed cycles of the four phases of its segments (prologue until
+   the first MFMA, K loop, partial publish or fix-up wait, C epilogue), s_memrealtime at start / end (tools/gemm_phases.py) */
+__device__ unsigned long long g_gemm_ts[1024 * 8];
+extern "C" int gsl_sinterp_hip_debug_gemm_ts(unsigned long long *out) { return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_gemm_ts), sizeof(g_gemm_ts)); }
+extern "C" int gsl_sinterp_hip_debug_gemm_ts_clear(void)
+{
+  static const unsigned long long zero[1024 * 8] = {0};
+  return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_gemm_ts), zero, sizeof(g_gemm_ts));
+}
+__device__ __forceinline__ unsigned long long gemm_stamp()
+{
+  unsigned long long t;
+  __builtin_amdgcn_sched_barrier(0);
+  asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t) :: "memory");
+  __builtin_amdgcn_sched_barrier(0);
+  return t;
+}
+__device__ __forceinline__ unsigned long long gemm_rstamp()
+{
+  unsigned long long t;
+  __builtin_amdgcn_sched_barrier(0);
+  asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t) :: "memory");
+  __builtin_amdgcn_sched_barrier(0);
+  return t;
+}
+#define GEMM_TS_INIT() unsigned long long ph_[4] = {0, 0, 0, 0}, ts_ = 0; const unsigned long long t0_ = gemm_stamp(), r0_ = gemm_rstamp()
+#define GEMM_TS_BEGIN() (ts_ = gemm_stamp())
+#define GEMM_TS_MARK(slot) do { const unsigned long long t_ = gemm_stamp(); ph_[slot] += t_ - ts_; ts_ = t_; } while (0)
+/* unconditional stamp whose interval goes to slot a when `cond` (wave-uniform), else to slot b: a stamp inside a
+   branch of the non-pipelined K loop, or a condition the compiler takes for divergent, makes the gfx950 backend fail
+   with "illegal VGPR to SGPR copy" */
+#define GEMM_TS_MARK_SEL(cond, a, b) do { const unsigned long long t_ = gemm_stamp(), d_ = t_ - ts_; const bool c_ = (cond); \
+    ph_[a] += c_ ? d_ : 0ull; ph_[b] += c_ ? 0ull : d_; ts_ = t_; } while (0)
+#define GEMM_TS_FINISH() do { const unsigned long long t1_ = gemm_stamp(), r1_ = gemm_rstamp(); \
+    if (threadIdx.x == 0 && blockIdx.x < 1024) { unsigned long long *o_ = g_gemm_ts + blockIdx.x * 8; \
+      o_[0] = t0_; o_[1] = t1_; o_[2] = ph_[0]; o_[3] = ph_[1]; o_[4] = ph_[2]; o_[5] = ph_[3]; o_[6] = r0_; o_[7] = r1_; } } while (0)
+#else
+#define GEMM_TS_INIT() do { } while (0)
+#define GEMM_TS_BEGIN() do { } while (0)
+#define GEMM_TS_MARK(slot) do { } while (0)
+#define GEMM_TS_MARK_SEL(cond, a, b) do { } while (0)
+#define GEMM_TS_FINISH() do { } while (0)
+#endif
+
 struct StreamK {
   unsigned steps;               /* K-steps per tile */
   unsigned total;               /* tiles * steps */
@@ -375,10 +421,13 @@ __device__ __forceinline__ void decode_tile(const GemmArgs &g, unsigned tile, in
 
 /* Tile configurations (block tile BM x BN, wave tile WM x WN):
      256x128 / 64x64, 8 waves, 144 KiB LDS -- large updates, 2 waves per SIMD;
-     128x128 / 64x64, 4 waves,  96 KiB
-      64x64  / 32x32, 4 waves,  48 KiB     -- updates with few 128-tiles (the K <= 512 levels of the
-                                             recursions): 4x the workgroups, a 128-wide panel update
-                                             is otherwise one 13.7 us tile per CU on a fraction of the CUs */
+     128x128 / 64x32, 8 waves,  96 KiB     -- mid-size updates (K = 512 .. 2048 levels of the recursions), 2 waves per SIMD;
+      64x64  / 32x16, 8 waves, 128 KiB     -- updates with few 128-tiles (the K <= 512 levels): 4x the workgroups, a
+                                             128-wide panel update is otherwise one 13.7 us tile per CU on a fraction
+                                             of the CUs; 4-step groups (below), 2 waves per SIMD;
+     128x128 / 64x64 and 64x64 / 32x32 on 4 waves (one per SIMD): the round-4 dispatch (GSL_SINTERP_GEMM_RULE_R4=1).
+   With one wave per SIMD the matrix pipe idles through every LDS round trip, barrier and DMA wait of that wave;
+   the second wave of the 8-wave tiles covers them (K = 256 level of C3: 1.39 -> 1.11 ms). */
 /* SS consecutive 16-wide K sub-steps form one "group" = the unit between two barriers (and the unit of the
    stream-K split); ST groups are resident in the LDS ring.  SS = 1, ST = 3 is the pipeline described above.
    The small 64x64 tile spends only 0.43 us of MFMA work per 16-wide step -- less than a DMA round trip and
@@ -420,11 +469,13 @@ gemm_minus_streamk_kernel(GemmArgs g, StreamK x)
   const unsigned q = G / 8, r = G % 8, xcd = bid % 8;
   const unsigned gl = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + bid / 8;   /* XCD-contiguous ranges */
   auto start_of = [&](unsigned w) -> unsigned { return w * x.base + (w < x.rem ? w : x.rem); };
-  unsigned it = __builtin_amdgcn_readfirstlane(start_of(gl));
-  const unsigned it_end = __builtin_amdgcn_readfirstlane(start_of(gl + 1));
+  auto start_cap = [&](unsigned w) -> unsigned { const unsigned v = start_of(w); return v < x.total ? v : x.total; };
+  unsigned it = __builtin_amdgcn_readfirstlane(start_cap(gl));
+  const unsigned it_end = __builtin_amdgcn_readfirstlane(start_cap(gl + 1));
   unsigned tile = __builtin_amdgcn_readfirstlane(it / x.steps);
   const unsigned dp_tiles = x.dp_rounds * G;
   unsigned round = 0;
+  GEMM_TS_INIT();
 
   /* Whole-tile rounds first: the 32 workgroups of an XCD hold 32 consecutive tiles of the same round and
      walk K more or less in step, so operand panels are shared in their L2; then the stream-K remainder. */
@@ -440,16 +491,19 @@ gemm_minus_streamk_kernel(GemmArgs g, StreamK x)
       decode_tile<BM, BN>(g, tid_, tm, tn);
     }
     const size_t row0 = (size_t)tm * BM, col0 = (size_t)tn * BN;
+    GEMM_TS_BEGIN();
 
     double4_t acc[FM][FN];
-    /* 64 x 64 tiles (the K <= 256 levels: one short tile per workgroup): the owner fetches its C tile BEFORE the K loop
-       -- 16 values per thread, in flight with the first DMA groups -- so the epilogue is a plain store instead of a
-       read-modify-write whose load latency nothing covers (small: the K = 128 level of C3 1.228 -> 1.209 ms, C4 init
-       7.41 -> 7.26 ms, C2 init 2.87 -> 2.81 ms) */
-    constexpr bool CPRE = BM == 64 && BN == 64;
+    /* Tiles with at most 8 fragments per wave (64 x 64, and 128 x 128 on 8 waves): the owner fetches its C tile during
+       its LAST K-step -- 8 to 32 values per thread, issued after the ring's final DMA wait, so no hand-counted vmcnt
+       follows them, and in flight under that step's MFMAs -- and the epilogue is a plain store instead of a
+       read-modify-write whose load latency nothing covers.  Same arithmetic: whole tiles keep their bits.
+       Like every kernel here it relies on the caller having ordered the producer of C before the call on the
+       context's stream; where in the launch C is read does not make an unordered writer safe. */
+    constexpr bool CPRE = FM * FN <= 8;
     double4_t cpre[CPRE ? FM : 1][CPRE ? FN : 1];
-    if constexpr (CPRE) {
-      if (s0 == 0) {
+    auto load_cpre = [&]() {
+      if constexpr (CPRE) {
         int tid = threadIdx.x;
         asm volatile("" : "+v"(tid));
         const int lane = tid & 63, wave = tid >> 6;
@@ -463,7 +517,7 @@ gemm_minus_streamk_kernel(GemmArgs g, StreamK x)
             for (int rg = 0; rg < 4; rg++)
               cpre[i][j][rg] = g.C[(row0 + wr * WM + i * 16 + fq + 4 * rg) * g.ldc + col0 + wc * WN + j * 16 + fr];
       }
-    }
+    };
     {
       /* Everything lane-dependent is derived from a laundered thread id INSIDE the segment: left to
          itself the compiler hoists it all out of the while loop, runs out of VGPRs (the 8-wave
@@ -514,6 +568,7 @@ gemm_minus_streamk_kernel(GemmArgs g, StreamK x)
       __syncthreads();                                   /* the ring is free: previous segment fully read */
       if constexpr (PIPE) {
         auto wait_keep = [&](int groups) {               /* all but the last `groups` issued groups have landed */
+          static_assert(PER_GROUP == 4 || PER_GROUP == 6 || PER_GROUP == 8, "vmcnt immediate");
           if (groups >= 2) {
             if constexpr (PER_GROUP == 8) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
             else if constexpr (PER_GROUP == 6) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
@@ -546,6 +601,7 @@ gemm_minus_streamk_kernel(GemmArgs g, StreamK x)
         wait_keep(nst > 2 ? 2 : (int)nst - 1);
         __builtin_amdgcn_s_barrier();
         __builtin_amdgcn_sched_barrier(0);
+        GEMM_TS_MARK(0);
         double af0[FM], bf0[FN], af1[FM], bf1[FN];
         load_frag(0, 0, af0, bf0);
         /* all steps but the last: the rendezvous sits between the third and the fourth quarter of the step */
@@ -575,6 +631,7 @@ gemm_minus_streamk_kernel(GemmArgs g, StreamK x)
           __builtin_amdgcn_sched_barrier(0);             /* keep the loads in front of the deferred MFMAs */
           mma(af1, bf1);                                 /* runs while the new fragments fly (counted lgkmcnt: no merge of paths here) */
         }
+        if (s0 == 0) load_cpre();                        /* owner: every DMA of the segment has landed, no counted wait follows */
         {
           const int stage = (int)((nst - 1) % 3);
           load_frag(stage, 1, af1, bf1);
@@ -585,6 +642,7 @@ gemm_minus_streamk_kernel(GemmArgs g, StreamK x)
           mma(af0, bf0);
           mma(af1, bf1);
         }
+        GEMM_TS_MARK(1);
       } else {
       issue(0, (size_t)s0 * GK);
       if (s0 + 1 < s1) issue(1, (size_t)(s0 + 1) * GK);
@@ -599,6 +657,8 @@ gemm_minus_streamk_kernel(GemmArgs g, StreamK x)
         } else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
         __builtin_amdgcn_sched_barrier(0);
+        GEMM_TS_MARK_SEL(__builtin_amdgcn_readfirstlane(s) == __builtin_amdgcn_readfirstlane(s0), 0, 1);   /* first group landed */
+        if (s0 == 0 && s + 1 == s1) load_cpre();         /* owner: after the last DMA wait of the segment */
         if constexpr (ST == 3) {
           if (s + 2 < s1) issue((int)((rel + 2) % 3), (size_t)(s + 2) * GK);   /* ring slot read at step s-1 */
         }
@@ -630,6 +690,7 @@ gemm_minus_streamk_kernel(GemmArgs g, StreamK x)
           }
         }
       }
+      GEMM_TS_MARK(1);
       }
     }
 
@@ -655,6 +716,7 @@ gemm_minus_streamk_kernel(GemmArgs g, StreamK x)
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __syncthreads();
       if (tid == 0) __hip_atomic_store(x.flags + gl, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      GEMM_TS_MARK(2);
     } else {
       if (s1 < x.steps) {
         for (unsigned w = gl + 1; w < G; w++) {
@@ -675,6 +737,7 @@ gemm_minus_streamk_kernel(GemmArgs g, StreamK x)
           if (tid == 0) __hip_atomic_store(x.flags + w, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
       }
+      GEMM_TS_MARK(2);
 #pragma unroll
       for (int i = 0; i < FM; i++) {
 #pragma unroll
@@ -692,10 +755,15 @@ gemm_minus_streamk_kernel(GemmArgs g, StreamK x)
         }
         __builtin_amdgcn_sched_barrier(0);
       }
+#ifdef SINTERP_DIAG_PROF
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      GEMM_TS_MARK(3);
+#endif
     }
     if (dp) round++;
     else { it = tile_first + s1; tile++; }
   }
+  GEMM_TS_FINISH();
 }
 
 int sinterp_streamk_prepare(gsl_sinterp_hip_ctx *ctx)
@@ -785,10 +853,47 @@ gemm_minus_smallk_kernel(GemmArgs g)
     }
 }
 
+/* Tile configurations of the stream-K update (the values of GSL_SINTERP_GEMM_CFG) */
+enum { SK_256 = 0,      /* 256x128, 8 waves of 64x64 */
+       SK_128 = 1,      /* 128x128, 4 waves of 64x64 */
+       SK_64 = 2,       /* 64x64,   4 waves of 32x32 (4-step groups when K allows) */
+       SK_128W8 = 5,    /* 128x128, 8 waves of 64x32 */
+       SK_64W8G = 6 };  /* 64x64,   8 waves of 32x16, 4-step groups */
+static inline int sk_tile(int cfg) { return cfg == SK_128 || cfg == SK_128W8 ? 128 : cfg == SK_256 ? 256 : 64; }
+
+template <int BM, int BN, int WM, int WN, int SS = 1, int ST = DM_STAGES, bool PIPE = false>
+static int launch_sk(gsl_sinterp_hip_ctx *ctx, unsigned G, const GemmArgs &h, const StreamK &x)
+{
+  constexpr int NT = (BM / WM) * (BN / WN) * 64;
+  const size_t lds = (size_t)ST * SS * (BM + BN) * GT_BK * sizeof(double);
+  { int ast = sinterp_func_lds(ctx, (const void *)gemm_minus_streamk_kernel<BM, BN, WM, WN, SS, ST, PIPE>, (int)lds); if (ast) return ast; }
+  hipLaunchKernelGGL((gemm_minus_streamk_kernel<BM, BN, WM, WN, SS, ST, PIPE>), dim3(G), dim3(NT), lds, ctx->stream, h, x);
+  LAUNCH_CHECK(ctx);
+  return ST_SUCCESS;
+}
+
+/* the dispatch rule, fitted to every update shape of the N = 4096 / 8192 / 16384 recursions (tools/gemm_cfg_sweep.py,
+   DESIGN.md section 3): the 256x128 tile once every CU gets >= 128 of its K-steps, 64x64 tiles while 128-tiles would
+   fill at most 3/4 of the CUs, 128x128 tiles (8 waves) between; always the hybrid split (whole tiles only lost) */
+template <class TilesOf>
+static int sk_rule(bool can256, TilesOf &tiles_of, unsigned steps, unsigned cus)
+{
+  GemmArgs hh;
+  if (can256 && (unsigned long long)tiles_of(SK_256, hh) * steps >= 128ull * cus) return SK_256;
+  if (4ull * tiles_of(SK_128, hh) <= 3ull * cus) return SK_64W8G;
+  return SK_128W8;
+}
+
+/* the N.T stream-K configuration the last gsl_sinterp_hip_gemm_minus call of the process launched: 2 * cfg + (whole
+   tiles only), or -1 for any other kernel (tests/test_gpu_gemm_mid.py checks that GSL_SINTERP_GEMM_CFG took effect) */
+static int g_gemm_last_cfg = -1;
+extern "C" int gsl_sinterp_hip_debug_gemm_last_cfg(void) { return __atomic_load_n(&g_gemm_last_cfg, __ATOMIC_RELAXED); }
+
 int sinterp_gemm_minus(gsl_sinterp_hip_ctx *ctx, size_t m, size_t n, size_t k, const double *A, size_t lda,
                        const double *B, size_t ldb, int b_is_kn, double *C, size_t ldc, int lower_only)
 {
   if (m == 0 || n == 0 || k == 0) return ST_SUCCESS;
+  __atomic_store_n(&g_gemm_last_cfg, -1, __ATOMIC_RELAXED);
   GemmArgs g;
   g.m = m; g.n = n; g.k = k; g.A = A; g.lda = lda; g.B = B; g.ldb = ldb; g.C = C; g.ldc = ldc;
   g.lower_only = lower_only;
@@ -823,89 +928,92 @@ int sinterp_gemm_minus(gsl_sinterp_hip_ctx *ctx, size_t m, size_t n, size_t k, c
     if (ctx->sk_wgs > 0) {
       /* stream-K: G persistent workgroups share the (tile, K-step) space evenly */
       StreamK x;
-      x.steps = (unsigned)(k / GT_BK);                   /* groups per tile; rescaled below for the grouped 64x64 variant */
+      x.steps = (unsigned)(k / GT_BK);                   /* groups per tile; rescaled below for the grouped 64x64 variants */
       x.partial = ctx->d_sk_partial;
       x.flags = ctx->d_sk_flags;
-      GemmArgs h = g;
-      unsigned tiles = grid;
-      int cfg = 1;                                       /* 0: 256x128, 1: 128x128, 2: 64x64 */
-      if (!no_w8 && (m % 256 == 0) && (!lower_only || (g.tiles_n % 2) == 0)) {
-        GemmArgs h8 = g;
-        h8.tiles_m = (int)(m / 256);
-        unsigned t8 = (unsigned)h8.tiles_m * (unsigned)h8.tiles_n;
-        if (lower_only) {
-          const unsigned fr_ = (unsigned)h8.tiles_n / 2;
-          t8 = 2 * fr_ * (fr_ + 1) / 2 + ((unsigned)h8.tiles_m - fr_) * (unsigned)h8.tiles_n;
+      const unsigned cus = (unsigned)ctx->sk_wgs;
+      const bool can256 = !no_w8 && (m % 256 == 0) && (!lower_only || (g.tiles_n % 2) == 0);
+      /* tiles of configuration c (tile shape only; see the table above gemm_minus_streamk_kernel) */
+      auto tiles_of = [&](int c, GemmArgs &hh) -> unsigned {
+        hh = g;
+        if (c == SK_256) {
+          hh.tiles_m = (int)(m / 256);
+          if (!lower_only) return (unsigned)hh.tiles_m * (unsigned)hh.tiles_n;
+          const unsigned fr_ = (unsigned)hh.tiles_n / 2;
+          return 2 * fr_ * (fr_ + 1) / 2 + ((unsigned)hh.tiles_m - fr_) * (unsigned)hh.tiles_n;
         }
-        /* the big tile only pays when every CU gets a few K-steps of it */
-        if ((unsigned long long)t8 * x.steps >= 16ull * (unsigned)ctx->sk_wgs) { cfg = 0; h = h8; tiles = t8; }
-      }
+        const int bt = sk_tile(c);
+        hh.tiles_m = (int)(m / bt); hh.tiles_n = (int)(n / bt);
+        if (lower_only && hh.tiles_m < hh.tiles_n) hh.tiles_n = hh.tiles_m;
+        const unsigned tm_ = (unsigned)hh.tiles_m, tn_ = (unsigned)hh.tiles_n;
+        return lower_only ? tn_ * (tn_ + 1) / 2 + (tm_ - tn_) * tn_ : tm_ * tn_;
+      };
+      static const bool r4_rule = getenv("GSL_SINTERP_GEMM_RULE_R4") && getenv("GSL_SINTERP_GEMM_RULE_R4")[0] == '1';
       static const bool no_t64 = getenv("GSL_SINTERP_NO_GEMM64") && getenv("GSL_SINTERP_NO_GEMM64")[0] == '1';
-      if (cfg == 1 && !no_t64 && 2u * grid <= (unsigned)ctx->sk_wgs) {
-        /* 128-tiles for at most half of the CUs: quarter tiles, 4x the workgroups (measured: with
-           more tiles than that the extra prologues/epilogues cost more than the idle CUs) */
-        cfg = 2;
-        h.tiles_m = (int)(m / 64); h.tiles_n = (int)(n / 64);
-        if (lower_only && h.tiles_m < h.tiles_n) h.tiles_n = h.tiles_m;
-        tiles = (unsigned)h.tiles_m * (unsigned)h.tiles_n;
-        if (lower_only) { const unsigned tn_ = (unsigned)h.tiles_n; tiles = tn_ * (tn_ + 1) / 2 + ((unsigned)h.tiles_m - tn_) * tn_; }
+      GemmArgs h;
+      int cfg;
+      bool whole = false;
+      if (r4_rule) {
+        /* round 4: 256x128 when every CU gets >= 16 K-steps of it, 64x64 when 128-tiles fill at most half of the CUs */
+        cfg = SK_128;
+        { GemmArgs h8; const unsigned t8 = tiles_of(SK_256, h8);
+          if (can256 && (unsigned long long)t8 * x.steps >= 16ull * cus) cfg = SK_256; }
+        if (cfg == SK_128 && !no_t64 && 2u * grid <= cus) cfg = SK_64;
+      } else {
+        cfg = sk_rule(can256, tiles_of, x.steps, cus);
+        if (no_t64 && cfg == SK_64W8G) cfg = SK_128W8;
       }
-      /* developer override (tools/gemm_cfg_sweep.py): force the tile configuration where the shape allows it */
+      /* developer override (tools/gemm_cfg_sweep.py): "<cfg>" or "<cfg>w" (whole tiles, no K split), where the shape allows it */
       if (getenv("GSL_SINTERP_GEMM_CFG")) {
-        const int want_cfg = atoi(getenv("GSL_SINTERP_GEMM_CFG"));
-        if (want_cfg == 1 || (want_cfg == 2 && m % 64 == 0 && n % 64 == 0)) {
-          cfg = want_cfg; h = g; tiles = grid;
-          if (want_cfg == 2) {
-            h.tiles_m = (int)(m / 64); h.tiles_n = (int)(n / 64);
-            if (lower_only && h.tiles_m < h.tiles_n) h.tiles_n = h.tiles_m;
-            tiles = (unsigned)h.tiles_m * (unsigned)h.tiles_n;
-            if (lower_only) { const unsigned tn_ = (unsigned)h.tiles_n; tiles = tn_ * (tn_ + 1) / 2 + ((unsigned)h.tiles_m - tn_) * tn_; }
-          }
+        const char *ov = getenv("GSL_SINTERP_GEMM_CFG");
+        const int want_cfg = atoi(ov);
+        if ((want_cfg == SK_256 && can256) || want_cfg == SK_128 || want_cfg == SK_64 || want_cfg == SK_128W8 || want_cfg == SK_64W8G) {
+          cfg = want_cfg;
+          whole = strchr(ov, 'w') != NULL;
         }
       }
+      unsigned tiles = tiles_of(cfg, h);
       static const bool no_group = getenv("GSL_SINTERP_NO_GEMM_GROUP") && getenv("GSL_SINTERP_NO_GEMM_GROUP")[0] == '1';
-      const bool grouped = cfg == 2 && !no_group && (k % (4 * GT_BK)) == 0;
-      if (grouped) x.steps = (unsigned)(k / (4 * GT_BK));
-      unsigned long long total64 = (unsigned long long)tiles * x.steps;
-      unsigned long long want = total64 / (grouped ? 4 : 16);   /* >= 16 K-steps (of 16) per workgroup ... */
-      if (want < tiles) want = tiles;                     /* ... but never fewer workgroups than tiles */
-      const unsigned long long wg_cap = (unsigned long long)ctx->sk_wgs;
-      if (want > wg_cap) want = wg_cap;
-      const unsigned G = (unsigned)(want ? want : 1);
-      /* many tiles: all but the last full round (and the remainder) as whole tiles */
-      static const bool no_hybrid = getenv("GSL_SINTERP_NO_HYBRID_SK") && getenv("GSL_SINTERP_NO_HYBRID_SK")[0] == '1';
-      x.dp_rounds = (!no_hybrid && tiles / G >= 2) ? tiles / G - 1 : 0;
-      total64 = (unsigned long long)(tiles - x.dp_rounds * G) * x.steps;
-      if (total64 < 0x7fffffffull) {
-      x.total = (unsigned)total64; x.base = x.total / G; x.rem = x.total % G;
       static const bool no_pipe = getenv("GSL_SINTERP_NO_GEMM_PIPE") && getenv("GSL_SINTERP_NO_GEMM_PIPE")[0] == '1';
-      if (cfg == 0 && !no_pipe) {
-        const size_t lds = (size_t)DM_STAGES * (256 + 128) * GT_BK * sizeof(double);
-        { int ast = sinterp_func_lds(ctx, (const void *)gemm_minus_streamk_kernel<256, 128, 64, 64, 1, 3, true>, (int)lds); if (ast) return ast; }
-        hipLaunchKernelGGL((gemm_minus_streamk_kernel<256, 128, 64, 64, 1, 3, true>), dim3(G), dim3(512), lds, ctx->stream, h, x);
-      } else if (cfg == 0) {
-        const size_t lds = (size_t)DM_STAGES * (256 + 128) * GT_BK * sizeof(double);
-        { int ast = sinterp_func_lds(ctx, (const void *)gemm_minus_streamk_kernel<256, 128, 64, 64>, (int)lds); if (ast) return ast; }
-        hipLaunchKernelGGL((gemm_minus_streamk_kernel<256, 128, 64, 64>), dim3(G), dim3(512), lds, ctx->stream, h, x);
-      } else if (cfg == 1 && !no_pipe) {
-        const size_t lds = (size_t)DM_STAGES * (128 + 128) * GT_BK * sizeof(double);
-        { int ast = sinterp_func_lds(ctx, (const void *)gemm_minus_streamk_kernel<128, 128, 64, 64, 1, 3, true>, (int)lds); if (ast) return ast; }
-        hipLaunchKernelGGL((gemm_minus_streamk_kernel<128, 128, 64, 64, 1, 3, true>), dim3(G), dim3(256), lds, ctx->stream, h, x);
-      } else if (cfg == 1) {
-        const size_t lds = (size_t)DM_STAGES * (128 + 128) * GT_BK * sizeof(double);
-        { int ast = sinterp_func_lds(ctx, (const void *)gemm_minus_streamk_kernel<128, 128, 64, 64>, (int)lds); if (ast) return ast; }
-        hipLaunchKernelGGL((gemm_minus_streamk_kernel<128, 128, 64, 64>), dim3(G), dim3(256), lds, ctx->stream, h, x);
-      } else if (grouped) {
-        const size_t lds = (size_t)2 * 4 * (64 + 64) * GT_BK * sizeof(double);       /* 128 KiB */
-        { int ast = sinterp_func_lds(ctx, (const void *)gemm_minus_streamk_kernel<64, 64, 32, 32, 4, 2>, (int)lds); if (ast) return ast; }
-        hipLaunchKernelGGL((gemm_minus_streamk_kernel<64, 64, 32, 32, 4, 2>), dim3(G), dim3(256), lds, ctx->stream, h, x);
+      if (cfg == SK_64W8G && (no_group || (k % (4 * GT_BK)) != 0)) cfg = SK_64;   /* ungrouped 64x64 tiles */
+      const bool grouped = (cfg == SK_64 && !no_group && (k % (4 * GT_BK)) == 0) || cfg == SK_64W8G;
+      if (grouped) x.steps = (unsigned)(k / (4 * GT_BK));
+      static const bool no_hybrid = getenv("GSL_SINTERP_NO_HYBRID_SK") && getenv("GSL_SINTERP_NO_HYBRID_SK")[0] == '1';
+      if (no_hybrid) whole = false;
+      unsigned G;
+      unsigned long long total64;
+      if (whole) {
+        /* whole tiles only: one tile per workgroup and round, the last round partly filled */
+        G = tiles < cus ? tiles : cus;
+        x.dp_rounds = tiles / G;
+        total64 = (unsigned long long)(tiles - x.dp_rounds * G) * x.steps;
       } else {
-        const size_t lds = (size_t)DM_STAGES * (64 + 64) * GT_BK * sizeof(double);
-        { int ast = sinterp_func_lds(ctx, (const void *)gemm_minus_streamk_kernel<64, 64, 32, 32>, (int)lds); if (ast) return ast; }
-        hipLaunchKernelGGL((gemm_minus_streamk_kernel<64, 64, 32, 32>), dim3(G), dim3(256), lds, ctx->stream, h, x);
+        total64 = (unsigned long long)tiles * x.steps;
+        unsigned long long want = total64 / (grouped ? 4 : 16);   /* >= 16 K-steps (of 16) per workgroup ... */
+        if (want < tiles) want = tiles;                     /* ... but never fewer workgroups than tiles */
+        if (want > cus) want = cus;
+        G = (unsigned)(want ? want : 1);
+        /* many tiles: all but the last full round (and the remainder) as whole tiles */
+        x.dp_rounds = (!no_hybrid && tiles / G >= 2) ? tiles / G - 1 : 0;
+        total64 = (unsigned long long)(tiles - x.dp_rounds * G) * x.steps;
       }
-      LAUNCH_CHECK(ctx);
-      return ST_SUCCESS;
+      if (total64 < 0x7fffffffull) {
+        x.total = (unsigned)total64;
+        if (whole) { x.base = x.steps; x.rem = 0; }      /* workgroup w: the w-th remaining tile, if any */
+        else { x.base = x.total / G; x.rem = x.total % G; }
+        __atomic_store_n(&g_gemm_last_cfg, 2 * cfg + (whole ? 1 : 0), __ATOMIC_RELAXED);
+        switch (cfg) {
+          case SK_256:
+            return no_pipe ? launch_sk<256, 128, 64, 64>(ctx, G, h, x) : launch_sk<256, 128, 64, 64, 1, 3, true>(ctx, G, h, x);
+          case SK_128:
+            return no_pipe ? launch_sk<128, 128, 64, 64>(ctx, G, h, x) : launch_sk<128, 128, 64, 64, 1, 3, true>(ctx, G, h, x);
+          case SK_128W8:
+            return no_pipe ? launch_sk<128, 128, 64, 32>(ctx, G, h, x) : launch_sk<128, 128, 64, 32, 1, 3, true>(ctx, G, h, x);
+          case SK_64W8G:
+            return launch_sk<64, 64, 32, 16, 4, 2>(ctx, G, h, x);
+          default:
+            return grouped ? launch_sk<64, 64, 32, 32, 4, 2>(ctx, G, h, x) : launch_sk<64, 64, 32, 32>(ctx, G, h, x);
+        }
       }
     }
     /* 256x128 tiles (8 waves) when the rows split evenly and there is enough work for every CU */
