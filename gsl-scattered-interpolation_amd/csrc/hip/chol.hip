@@ -29,7 +29,6 @@ extern "C" int gsl_sinterp_hip_debug_diag_ts(unsigned long long *out) { return (
 #endif
 #include "chol_potrf.h"
 
-#define TRSV_MAXR 5   /* right-hand sides solved together (f + the d+1 polynomial columns) */
 
 
 /* ------------------------------------------------------------------------ */
@@ -148,111 +147,12 @@ chol_diag_writeback_kernel(double *__restrict__ A, size_t lda, size_t n, const d
    LDS layout of triangles: packed 32x32 blocks of pitch 34 doubles -- 34 = 2 mod 4 makes the
    (row = lane&15, k = lane>>4) MFMA fragment reads conflict free. */
 
-/* Forward substitution folded into the factorisation (round 4).  With right-hand sides f (nrhs vectors, fb + q * ldf),
-   the driver keeps them "one panel ahead": when panel p is factored, f_p (rows j0 .. j0+127) already carries the updates of
-   every earlier panel, so  y_p = L_pp^-1 f_p  is final (cblas/source_trsv_r.h:56-79 computes the same sums row by row);
-   chol_trsm16_kernel then subtracts L[R, p] y_p from the entries below.  After the last panel fb holds L^-1 f and the
-   solve only needs its backward sweep.  Here: block substitution with the inverted 32 x 32 diagonal blocks that the
-   factorisation leaves in Dv, one right-hand side per wave (wave-local: no workgroup barrier), lanes = 32 rows x 2 halves
-   of the K range. */
-__device__ __forceinline__ void diag128_forward(const double *S, const double *Dv, double *fs, double *tt, int tid, int nrhs)
-{
-  const int lane = tid & 63, wave = tid >> 6, r = lane & 31, half = lane >> 5;
-  for (int q = wave; q < nrhs; q += 4) {
-    double *y = fs + q * PB, *t = tt + q * CB;
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-      double sum = 0.0;
-#pragma unroll
-      for (int kb = 0; kb < i; kb++) {
-        const double *Lr = S + pblk(i, kb) + r * PQ + half * 16;
-        const double *yk = y + kb * 32 + half * 16;
-#pragma unroll
-        for (int k = 0; k < 16; k += 2) {
-          const double2 l2 = *reinterpret_cast<const double2 *>(Lr + k);
-          sum = fma(l2.x, yk[k], sum);
-          sum = fma(l2.y, yk[k + 1], sum);
-        }
-      }
-      sum += __shfl_xor(sum, 32);
-      if (half == 0) t[r] = y[i * 32 + r] - sum;
-      __builtin_amdgcn_wave_barrier();
-      /* y_i = Dinv_i t  (Dinv lower triangular: exact zeros above the diagonal) */
-      const double *Wr = Dv + i * PBLK + (half * 16) * PQ + r;           /* Dinv[r][c] = Dt[c * PQ + r] (stored transposed) */
-      double acc = 0.0;
-#pragma unroll
-      for (int c = 0; c < 16; c++) acc = fma(Wr[c * PQ], t[half * 16 + c], acc);
-      acc += __shfl_xor(acc, 32);
-      if (half == 0) y[i * 32 + r] = acc;
-      __builtin_amdgcn_wave_barrier();
-    }
-  }
-}
-
 __global__ void __launch_bounds__(256)
 chol_diag128_kernel(double *__restrict__ A, size_t lda, size_t j0, int *__restrict__ info, double *__restrict__ diag_store,
                     double *__restrict__ Dinvg, double *__restrict__ fb, size_t ldf, int nrhs)
 {
   extern __shared__ __attribute__((aligned(16))) double sm[];
-  double *S = sm;                       /* 10 packed blocks of the lower triangle */
-  double *Dv = S + 10 * PBLK;           /* 4 blocks: inverses of the diagonal blocks */
-  double *fs = Dv + 4 * PBLK;           /* [TRSV_MAXR][128] right-hand sides of the folded forward substitution */
-  double *tt = fs + 5 * PB;             /* [TRSV_MAXR][32] */
-  const int tid = threadIdx.x;
-  double *Ab = A + j0 * lda + j0;
-  TSTAMP(0);
-
-  /* load the lower triangle (whole 32x32 blocks, coalesced along k): all 40 loads of a thread are
-     issued before the first LDS store (one memory round trip, not 40) */
-  {
-    double v[40], fv[3];
-    const int r8 = tid >> 5, k = tid & 31;
-#pragma unroll
-    for (int t = 0; t < 40; t++) {
-      constexpr int BI[10] = {0, 1, 1, 2, 2, 2, 3, 3, 3, 3}, BJ[10] = {0, 0, 1, 0, 1, 2, 0, 1, 2, 3};
-      const int b = t >> 2, r = (t & 3) * 8 + r8;
-      v[t] = Ab[(size_t)(BI[b] * 32 + r) * lda + BJ[b] * 32 + k];
-    }
-#pragma unroll
-    for (int t = 0; t < 3; t++) { const int e = t * 256 + tid; fv[t] = e < nrhs * PB ? fb[(size_t)(e >> 7) * ldf + j0 + (e & 127)] : 0.0; }
-#pragma unroll
-    for (int t = 0; t < 40; t++) S[(t >> 2) * PBLK + ((t & 3) * 8 + r8) * PQ + k] = v[t];
-#pragma unroll
-    for (int t = 0; t < 16; t++) { const int r = (t & 3) * 8 + r8; Dv[(t >> 2) * PBLK + r * PQ + k] = r == k ? 1.0 : 0.0; }   /* potrf32: identity */
-#pragma unroll
-    for (int t = 0; t < 3; t++) { const int e = t * 256 + tid; if (e < nrhs * PB) fs[e] = fv[t]; }
-  }
-  __syncthreads();
-  TSTAMP(1);
-
-  potrf128_lds<4>(S, Dv, tid, info, j0);
-
-  TSTAMP(18);
-  if (nrhs > 0) {
-    diag128_forward(S, Dv, fs, tt, tid, nrhs);
-    __syncthreads();
-  }
-  /* L -> A (lower part only); the diagonal 32-blocks also -> diag_store in the format of
-     chol_base_kernel, so that chol_diag_writeback_kernel rewrites the same values */
-  {
-    const int r8 = tid >> 5, k = tid & 31;
-#pragma unroll
-    for (int t = 0; t < 40; t++) {
-      constexpr int BI[10] = {0, 1, 1, 2, 2, 2, 3, 3, 3, 3}, BJ[10] = {0, 0, 1, 0, 1, 2, 0, 1, 2, 3};
-      const int b = t >> 2, r = (t & 3) * 8 + r8, bi = BI[b], bj = BJ[b];
-      const double v = S[b * PBLK + r * PQ + k];
-      if (bi != bj || k <= r) Ab[(size_t)(bi * 32 + r) * lda + bj * 32 + k] = v;
-      if (bi == bj && diag_store) diag_store[(j0 / CB + bi) * (CB * CB) + r * CB + k] = (k <= r) ? v : 0.0;
-    }
-#pragma unroll
-    for (int t = 0; t < 16; t++) {
-      const int b = t >> 2, r = (t & 3) * 8 + r8;
-      Dinvg[b * 1024 + r * 32 + k] = Dv[b * PBLK + k * PQ + r];             /* row-major Dinv from the transposed LDS image */
-    }
-#pragma unroll
-    for (int t = 0; t < 3; t++) { const int e = t * 256 + tid; if (e < nrhs * PB) fb[(size_t)(e >> 7) * ldf + j0 + (e & 127)] = fs[e]; }
-  }
-  TSTAMP(19);
+  chol_diag128_block<4>(sm, A + j0 * lda + j0, lda, j0, info, diag_store, Dinvg, fb, ldf, nrhs, threadIdx.x);
 }
 
 /* rows below a 128-wide diagonal block: X = B L^-T in place (round 4).
@@ -557,21 +457,40 @@ static size_t chol_split(size_t w)
   return w1;
 }
 
+/* riders attached by the last factorisation call of the process, whichever context made it (a replay counts what its
+   recording attached: ctx->chol_riders -- graph slot 0 belongs to this routine and holds one key, so a replay is always
+   a replay of the context's last recording).  A debug entry for single-context tests and tools: with several contexts
+   factoring at once it reports one of them. */
+static int g_chol_riders_last = 0;
+extern "C" int gsl_sinterp_hip_debug_chol_riders(void) { return __atomic_load_n(&g_chol_riders_last, __ATOMIC_RELAXED); }
+
+/* the rider route: the update in front of a leaf factors that leaf's diagonal block on one
+   extra workgroup of its own launch.  Needs the layout in which every leaf is a 128-wide panel written straight into A. */
+static bool chol_rider_applicable(size_t n, const double *d_a, size_t lda)
+{
+  static const bool no_p128 = getenv("GSL_SINTERP_NO_PANEL128") && getenv("GSL_SINTERP_NO_PANEL128")[0] == '1';
+  static const bool no_rider = getenv("GSL_SINTERP_NO_DIAG_RIDER") && getenv("GSL_SINTERP_NO_DIAG_RIDER")[0] == '1';
+  return !no_p128 && !no_rider && n >= 2 * PB && n % PB == 0 && (lda & 1) == 0 && ((((uintptr_t)d_a) & 15) == 0);
+}
+
 /* fb != NULL: nrhs right-hand sides (fb + q * ldf) ride along -- only ever passed when every leaf of the recursion is a
-   128-wide panel (chol_fold_applicable), see diag128_forward */
+   128-wide panel (chol_fold_applicable), see diag128_forward.
+   d_cnt: one arrival counter per panel, or NULL when the rider route is off.  diag_done: the diagonal
+   block of the FIRST leaf of this panel was factored by the rider of the update in front of it. */
 static int chol_panel(gsl_sinterp_hip_ctx *ctx, double *A, size_t lda, size_t n, size_t j0, size_t w, int *d_info,
-                      double *d_diag, double *fb, size_t ldf, int nrhs)
+                      double *d_diag, double *fb, size_t ldf, int nrhs, unsigned *d_cnt, bool diag_done)
 {
   int st;
   static const bool no_p128 = getenv("GSL_SINTERP_NO_PANEL128") && getenv("GSL_SINTERP_NO_PANEL128")[0] == '1';
+  double *d_linv = d_diag + ((n + CB - 1) / CB) * (CB * CB);   /* 4 inverted 32x32 blocks */
   if (w == PB && !no_p128 && (lda & 1) == 0 && ((((uintptr_t)(A + j0 * lda + j0)) & 15) == 0)) {
-    double *d_linv = d_diag + ((n + CB - 1) / CB) * (CB * CB);   /* 4 inverted 32x32 blocks */
-    const size_t lds_diag = (size_t)(14 * PBLK + TRSV_MAXR * (PB + CB)) * sizeof(double);
+    const size_t lds_diag = DIAG128_LDS_BYTES;
     { int ast = sinterp_func_lds(ctx, (const void *)chol_diag128_kernel, (int)lds_diag); if (ast) return ast; }
     /* every panel of this factorisation is 128 wide (n a multiple of 128): the blocks are written straight into A and the
        write-back launch of the 32-wide path is skipped, so the side copy is not needed either */
-    hipLaunchKernelGGL(chol_diag128_kernel, dim3(1), dim3(256), lds_diag, ctx->stream, A, lda, j0, d_info,
-                       n % PB == 0 ? (double *)NULL : d_diag, d_linv, fb, ldf, nrhs);
+    if (!diag_done)
+      hipLaunchKernelGGL(chol_diag128_kernel, dim3(1), dim3(256), lds_diag, ctx->stream, A, lda, j0, d_info,
+                         n % PB == 0 ? (double *)NULL : d_diag, d_linv, fb, ldf, nrhs);
     const size_t below = n - j0 - w;
     if (below) {
       /* 16 rows per workgroup while that is at most about one workgroup per CU, 64-row strips above
@@ -594,6 +513,7 @@ static int chol_panel(gsl_sinterp_hip_ctx *ctx, double *A, size_t lda, size_t n,
     return ST_SUCCESS;
   }
   if (w <= PB) {
+    if (diag_done) return sinterp_fail(ctx, ST_EFAILED, "cholesky: rider on a panel that is not 128 wide", hipSuccess, __FILE__, __LINE__);
     if (fb) return sinterp_fail(ctx, ST_EFAILED, "cholesky: folded forward substitution on a panel that is not 128 wide", hipSuccess, __FILE__, __LINE__);
   }
   if (w <= CB) {
@@ -604,12 +524,19 @@ static int chol_panel(gsl_sinterp_hip_ctx *ctx, double *A, size_t lda, size_t n,
     return ST_SUCCESS;
   }
   const size_t w1 = chol_split(w);
-  st = chol_panel(ctx, A, lda, n, j0, w1, d_info, d_diag, fb, ldf, nrhs);
+  st = chol_panel(ctx, A, lda, n, j0, w1, d_info, d_diag, fb, ldf, nrhs, d_cnt, diag_done);
   if (st) return st;
   const size_t r0 = j0 + w1, w2 = w - w1;
-  st = sinterp_gemm_minus(ctx, n - r0, w2, w1, A + r0 * lda + j0, lda, A + r0 * lda + j0, lda, 0, A + r0 * lda + r0, lda, 1);
+  /* C[0:128, 0:128] of this update is the diagonal block of the leaf at r0, the first leaf of the right part */
+  int rode = 0;
+  sinterp_rider rd;
+  rd.info = d_info; rd.j0 = r0; rd.dinv = d_linv; rd.fb = fb; rd.ldf = ldf; rd.nrhs = nrhs;
+  rd.counter = d_cnt ? d_cnt + r0 / PB : NULL; rd.abort_word = (unsigned *)(d_info + 1);
+  st = sinterp_gemm_minus(ctx, n - r0, w2, w1, A + r0 * lda + j0, lda, A + r0 * lda + j0, lda, 0, A + r0 * lda + r0, lda, 1,
+                          d_cnt ? &rd : NULL, &rode);
   if (st) return st;
-  return chol_panel(ctx, A, lda, n, r0, w2, d_info, d_diag, fb, ldf, nrhs);
+  if (rode) ctx->chol_riders++;
+  return chol_panel(ctx, A, lda, n, r0, w2, d_info, d_diag, fb, ldf, nrhs, d_cnt, rode != 0);
 }
 
 /* every leaf of the recursion is a 128-wide panel: the forward substitution can ride along */
@@ -621,7 +548,14 @@ static bool chol_fold_applicable(size_t n, const double *d_a, size_t lda, int nr
 }
 
 
-__global__ void chol_zero_info_kernel(int *info) { *info = 0; }
+/* pivot status, the rider's abort word (info[1]) and the riders' arrival counters, one per panel */
+__global__ void __launch_bounds__(256)
+chol_zero_info_kernel(int *info, unsigned *cnt, unsigned ncnt)
+{
+  const unsigned i = blockIdx.x * 256 + threadIdx.x;
+  if (i < 2) info[i] = 0;
+  if (i < ncnt) cnt[i] = 0u;
+}
 
 /* symmetric_input: both triangles of d_a hold the matrix (the RBF fill writes it that way), so the
    copy that preserves the original in the strict upper triangle (cholesky.c:103) is already there */
@@ -631,11 +565,17 @@ __global__ void chol_zero_info_kernel(int *info) { *info = 0; }
 static int chol_read_info(gsl_sinterp_hip_ctx *ctx, size_t n, int *h_info)
 {
   int *d_info = (int *)ctx->d_scratch + 8;
-  int info = 0;
+  int both[2] = {0, 0};
   HIP_OK(ctx, hipStreamSynchronize(ctx->stream));
-  HIP_OK(ctx, hipMemcpy(&info, d_info, sizeof(int), hipMemcpyDeviceToHost));
+  HIP_OK(ctx, hipMemcpy(both, d_info, sizeof both, hipMemcpyDeviceToHost));
   HIP_OK(ctx, hipStreamSynchronize(ctx->stream));
+  const int info = both[0];
   if (h_info) *h_info = info;
+  if (both[1]) {
+    /* a rider gave up waiting for its block: the leaf behind it skipped its own launch, the factor is not valid */
+    snprintf(ctx->err, sizeof ctx->err, "cholesky_decomp1: a diagonal-block rider timed out (n = %zu)", n);
+    return ST_EFAILED;
+  }
   if (info) {
     snprintf(ctx->err, sizeof ctx->err, "cholesky_decomp1: matrix is not positive definite (pivot %d of %zu <= 0)", info, n);
     return ST_EDOM;
@@ -660,8 +600,11 @@ static int cholesky_decomp1_impl(gsl_sinterp_hip_ctx *ctx, size_t n, double *d_a
   /* diagonal blocks + the inverted 32 x 32 blocks of EVERY 128-wide panel (look-ahead: a panel's row solve on the side
      stream still reads them while the chain factors the next panel) */
   const size_t n_pan = (n + PB - 1) / PB;
-  int st = sinterp_workspace(ctx, (nblk * CB * CB + (n_pan + 1) * (4 * 1024)) * sizeof(double), &d_diag);
+  const size_t diag_doubles = nblk * CB * CB + (n_pan + 1) * (4 * 1024);
+  int st = sinterp_workspace(ctx, diag_doubles * sizeof(double) + (n_pan + 4) * sizeof(unsigned), &d_diag);
   if (st) return st;
+  unsigned *d_cnt = (unsigned *)((double *)d_diag + diag_doubles);   /* the riders' counters */
+  const bool riders = chol_rider_applicable(n, d_a, lda);
   st = sinterp_streamk_prepare(ctx);
   if (st) return st;
   const bool fold = fb != NULL && chol_fold_applicable(n, d_a, lda, nrhs) && ldf >= n;
@@ -677,11 +620,12 @@ static int cholesky_decomp1_impl(gsl_sinterp_hip_ctx *ctx, size_t n, double *d_a
     if (st) return st;
     /* a kernel, not a memset node: a memset node inside a replayed graph was observed not to be
        ordered/visible like the kernels around it (stale flags on the second launch of a sweep graph) */
-    hipLaunchKernelGGL(chol_zero_info_kernel, dim3(1), dim3(1), 0, ctx->stream, d_info);
+    hipLaunchKernelGGL(chol_zero_info_kernel, dim3((unsigned)((n_pan + 255) / 256)), dim3(256), 0, ctx->stream, d_info, d_cnt, (unsigned)n_pan);
+    ctx->chol_riders = 0;
     hipError_t me = hipSuccess;
     const unsigned nt = (unsigned)((n + 31) / 32);
     if (!symmetric_input) hipLaunchKernelGGL(tricpy_lower_to_upper_kernel, dim3(nt, nt), dim3(256), 0, ctx->stream, d_a, lda, n);
-    st = chol_panel(ctx, d_a, lda, n, 0, n, d_info, (double *)d_diag, fb, ldf, nrhs);
+    st = chol_panel(ctx, d_a, lda, n, 0, n, d_info, (double *)d_diag, fb, ldf, nrhs, riders ? d_cnt : NULL, false);
     {
       static const bool no_p128w = getenv("GSL_SINTERP_NO_PANEL128") && getenv("GSL_SINTERP_NO_PANEL128")[0] == '1';
       const bool all128 = !no_p128w && n % PB == 0 && (lda & 1) == 0 && ((((uintptr_t)d_a) & 15) == 0);
@@ -695,6 +639,7 @@ static int cholesky_decomp1_impl(gsl_sinterp_hip_ctx *ctx, size_t n, double *d_a
     if (st2) return st2;
     LAUNCH_CHECK(ctx);
   }
+  __atomic_store_n(&g_chol_riders_last, ctx->chol_riders, __ATOMIC_RELAXED);   /* a replay attaches what its recording did */
   if (h_folded) *h_folded = fold ? 1 : 0;
   if (defer_info) return ST_SUCCESS;
   st = chol_read_info(ctx, n, h_info);

@@ -1,6 +1,6 @@
 /*
  * chol_potrf.h -- the in-LDS factorisation of a 128 x 128 diagonal block (potrf128), shared by the launch-per-panel
- * driver (chol.hip: chol_diag128_kernel) and the persistent task-DAG driver (chol_dag.hip: the chain workgroup).
+ * driver (chol.hip: chol_diag128_kernel) and the rider workgroup of the trailing updates (gemm.hip).
  * Reference semantics: gsl_linalg_cholesky_decomp1, linalg/cholesky.c:88-131.
  */
 #ifndef SINTERP_CHOL_POTRF_H
@@ -275,6 +275,128 @@ __device__ __forceinline__ void potrf128_lds(double *S, double *Dv, int tid, int
     TSTAMP(6 + jb * 4);
   }
 
+}
+
+#ifndef TRSV_MAXR
+#define TRSV_MAXR 5   /* right-hand sides solved together (f + the d+1 polynomial columns) */
+#endif
+
+/* Forward substitution folded into the factorisation (round 4).  With right-hand sides f (nrhs vectors, fb + q * ldf),
+   the driver keeps them "one panel ahead": when panel p is factored, f_p (rows j0 .. j0+127) already carries the updates of
+   every earlier panel, so  y_p = L_pp^-1 f_p  is final (cblas/source_trsv_r.h:56-79 computes the same sums row by row);
+   chol_trsm16_kernel then subtracts L[R, p] y_p from the entries below.  After the last panel fb holds L^-1 f and the
+   solve only needs its backward sweep.  Here: block substitution with the inverted 32 x 32 diagonal blocks that the
+   factorisation leaves in Dv, one right-hand side per wave (wave-local: no workgroup barrier), lanes = 32 rows x 2 halves
+   of the K range. */
+template <int NW>
+__device__ __forceinline__ void diag128_forward(const double *S, const double *Dv, double *fs, double *tt, int tid, int nrhs)
+{
+  const int lane = tid & 63, wave = tid >> 6, r = lane & 31, half = lane >> 5;
+  for (int q = wave; q < nrhs; q += NW) {
+    double *y = fs + q * PB, *t = tt + q * CB;
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+      double sum = 0.0;
+#pragma unroll
+      for (int kb = 0; kb < i; kb++) {
+        const double *Lr = S + pblk(i, kb) + r * PQ + half * 16;
+        const double *yk = y + kb * 32 + half * 16;
+#pragma unroll
+        for (int k = 0; k < 16; k += 2) {
+          const double2 l2 = *reinterpret_cast<const double2 *>(Lr + k);
+          sum = fma(l2.x, yk[k], sum);
+          sum = fma(l2.y, yk[k + 1], sum);
+        }
+      }
+      sum += __shfl_xor(sum, 32);
+      if (half == 0) t[r] = y[i * 32 + r] - sum;
+      __builtin_amdgcn_wave_barrier();
+      /* y_i = Dinv_i t  (Dinv lower triangular: exact zeros above the diagonal) */
+      const double *Wr = Dv + i * PBLK + (half * 16) * PQ + r;           /* Dinv[r][c] = Dt[c * PQ + r] (stored transposed) */
+      double acc = 0.0;
+#pragma unroll
+      for (int c = 0; c < 16; c++) acc = fma(Wr[c * PQ], t[half * 16 + c], acc);
+      acc += __shfl_xor(acc, 32);
+      if (half == 0) y[i * 32 + r] = acc;
+      __builtin_amdgcn_wave_barrier();
+    }
+  }
+}
+
+/* LDS of chol_diag128_block: 10 + 4 packed blocks, the right-hand sides and their scratch */
+#define DIAG128_LDS_BYTES ((size_t)(14 * PBLK + TRSV_MAXR * (PB + CB)) * sizeof(double))
+
+/* One 128-wide diagonal block, start to finish, on the NW * 64 threads of a workgroup: load of its 10 packed 32 x 32 blocks
+   (Ab = &A[j0][j0]) and of the right-hand sides, potrf128, the folded forward substitution, and the stores of L, of the
+   inverted diagonal blocks (Dinvg), of y (fb) and of the side copy (diag_store, may be NULL).  chol_diag128_kernel runs it
+   on 4 waves; the rider workgroup of a trailing update (gemm.hip) on that kernel's 8.  Which wave forms a fragment does
+   not enter its arithmetic: both routes return the same bits for the same block. */
+template <int NW>
+__device__ __forceinline__ void chol_diag128_block(double *sm, double *Ab, size_t lda, size_t j0, int *info, double *diag_store,
+                                                   double *Dinvg, double *fb, size_t ldf, int nrhs, int tid)
+{
+  constexpr int NT = NW * 64;
+  constexpr int RP = NT / 32;                 /* rows of a 32 x 32 block per pass of the workgroup */
+  constexpr int PS = 32 / RP;                 /* passes per block */
+  constexpr int FT = (TRSV_MAXR * PB + NT - 1) / NT;
+  static_assert(RP * PS == 32, "threads per workgroup");
+  double *S = sm;                       /* 10 packed blocks of the lower triangle */
+  double *Dv = S + 10 * PBLK;           /* 4 blocks: inverses of the diagonal blocks */
+  double *fs = Dv + 4 * PBLK;           /* [TRSV_MAXR][128] right-hand sides of the folded forward substitution */
+  double *tt = fs + TRSV_MAXR * PB;     /* [TRSV_MAXR][32] */
+  TSTAMP(0);
+
+  /* load the lower triangle (whole 32x32 blocks, coalesced along k): all loads of a thread are
+     issued before the first LDS store (one memory round trip, not 40) */
+  {
+    double v[10 * PS], fv[FT];
+    const int r8 = tid >> 5, k = tid & 31;
+#pragma unroll
+    for (int t = 0; t < 10 * PS; t++) {
+      constexpr int BI[10] = {0, 1, 1, 2, 2, 2, 3, 3, 3, 3}, BJ[10] = {0, 0, 1, 0, 1, 2, 0, 1, 2, 3};
+      const int b = t / PS, r = (t % PS) * RP + r8;
+      v[t] = Ab[(size_t)(BI[b] * 32 + r) * lda + BJ[b] * 32 + k];
+    }
+#pragma unroll
+    for (int t = 0; t < FT; t++) { const int e = t * NT + tid; fv[t] = e < nrhs * PB ? fb[(size_t)(e >> 7) * ldf + j0 + (e & 127)] : 0.0; }
+#pragma unroll
+    for (int t = 0; t < 10 * PS; t++) S[(t / PS) * PBLK + ((t % PS) * RP + r8) * PQ + k] = v[t];
+#pragma unroll
+    for (int t = 0; t < 4 * PS; t++) { const int r = (t % PS) * RP + r8; Dv[(t / PS) * PBLK + r * PQ + k] = r == k ? 1.0 : 0.0; }   /* potrf32: identity */
+#pragma unroll
+    for (int t = 0; t < FT; t++) { const int e = t * NT + tid; if (e < nrhs * PB) fs[e] = fv[t]; }
+  }
+  __syncthreads();
+  TSTAMP(1);
+
+  potrf128_lds<NW>(S, Dv, tid, info, j0);
+
+  TSTAMP(18);
+  if (nrhs > 0) {
+    diag128_forward<NW>(S, Dv, fs, tt, tid, nrhs);
+    __syncthreads();
+  }
+  /* L -> A (lower part only); the diagonal 32-blocks also -> diag_store in the format of
+     chol_base_kernel, so that chol_diag_writeback_kernel rewrites the same values */
+  {
+    const int r8 = tid >> 5, k = tid & 31;
+#pragma unroll
+    for (int t = 0; t < 10 * PS; t++) {
+      constexpr int BI[10] = {0, 1, 1, 2, 2, 2, 3, 3, 3, 3}, BJ[10] = {0, 0, 1, 0, 1, 2, 0, 1, 2, 3};
+      const int b = t / PS, r = (t % PS) * RP + r8, bi = BI[b], bj = BJ[b];
+      const double v = S[b * PBLK + r * PQ + k];
+      if (bi != bj || k <= r) Ab[(size_t)(bi * 32 + r) * lda + bj * 32 + k] = v;
+      if (bi == bj && diag_store) diag_store[(j0 / CB + bi) * (CB * CB) + r * CB + k] = (k <= r) ? v : 0.0;
+    }
+#pragma unroll
+    for (int t = 0; t < 4 * PS; t++) {
+      const int b = t / PS, r = (t % PS) * RP + r8;
+      Dinvg[b * 1024 + r * 32 + k] = Dv[b * PBLK + k * PQ + r];             /* row-major Dinv from the transposed LDS image */
+    }
+#pragma unroll
+    for (int t = 0; t < FT; t++) { const int e = t * NT + tid; if (e < nrhs * PB) fb[(size_t)(e >> 7) * ldf + j0 + (e & 127)] = fs[e]; }
+  }
+  TSTAMP(19);
 }
 
 #endif

@@ -50,6 +50,7 @@ struct gsl_sinterp_hip_ctx {
   double *d_sk_partial;
   unsigned *d_sk_flags;
   int sk_wgs;               /* persistent workgroups = CUs of the device; 0 = not prepared */
+  int chol_riders;          /* diagonal-block riders attached by the factorisation recorded in graph slot 0 (chol.hip) */
   /* dataflow sweeps (chol.hip): [0] = epoch of the last completed sweep, [1 + J] = epoch in which
      block J was last published.  Never reset (no memset node in the captured graphs): a sweep
      publishes with epoch + 1 and its last block advances the epoch. */
@@ -144,8 +145,21 @@ int sinterp_workspace(gsl_sinterp_hip_ctx *ctx, size_t bytes, void **out);
 /* C[m x n] -= A[m x k] * B^T   with B stored [n][k] (ldb)         -> b_is_kn = 0
    C[m x n] -= A[m x k] * B     with B stored [k][n] (ldb)         -> b_is_kn = 1
    lower_only: C is square on the diagonal, tiles strictly above it are skipped */
+/* rider (optional, the Cholesky driver's trailing updates): one extra workgroup of the update's launch factors
+   C[0:128, 0:128] -- the next panel's diagonal block -- as soon as the tiles that cover it are stored, doing what
+   chol_diag128_kernel does (chol_potrf.h: chol_diag128_block).  It is attached only on the N.T stream-K path; *attached
+   tells the caller whether its leaf may skip the launch of its own. */
+struct sinterp_rider {
+  int *info;                /* pivot status word of the factorisation */
+  size_t j0;                /* first column of the block in the whole matrix */
+  double *dinv;             /* receives the four inverted 32 x 32 diagonal blocks */
+  double *fb; size_t ldf; int nrhs;   /* right-hand sides of the folded forward substitution (nrhs = 0: none) */
+  unsigned *counter;        /* this panel's arrival counter, zero at launch: the owners of the covering tiles add to it */
+  unsigned *abort_word;     /* set (and left set) when the rider gave up waiting */
+};
 int sinterp_gemm_minus(gsl_sinterp_hip_ctx *ctx, size_t m, size_t n, size_t k, const double *A, size_t lda,
-                       const double *B, size_t ldb, int b_is_kn, double *C, size_t ldc, int lower_only);
+                       const double *B, size_t ldb, int b_is_kn, double *C, size_t ldc, int lower_only,
+                       const sinterp_rider *rider = NULL, int *attached = NULL);
 
 /* allocates the stream-K buffers of the context; must be called OUTSIDE stream capture (the
    factorisation drivers call it before they start capturing).  Without it the GEMM falls back to

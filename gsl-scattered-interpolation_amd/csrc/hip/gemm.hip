@@ -22,8 +22,7 @@
 #include "common.h"
 #include <stdlib.h>
 #include <string.h>
-
-typedef double double4_t __attribute__((ext_vector_type(4)));
+#include "chol_potrf.h"
 
 #define GT_BM 128
 #define GT_BN 128
@@ -395,7 +394,49 @@ struct StreamK {
                                    of total/steps tiles AFTER those dp_rounds*G tiles is then split as above */
   double *partial;              /* [G][BM*128] */
   unsigned *flags;              /* [G] */
+  /* RIDER launches of one round only (dp_rounds = 0): the first pri_tiles tiles -- those that cover the block the rider waits
+     for -- are taken out of the (tile, K-step) space above and cut into pri_nsl K-slices of pri_sl steps each; workgroup w <
+     pri_tiles * pri_nsl computes slice w % pri_nsl of tile w / pri_nsl FIRST, and its range of the remaining space is shorter
+     by pri_sl steps.  The holder of a tile's slice 0 adds the other slices in ascending order and stores the tile: it is
+     complete after about pri_sl steps plus the exchange instead of at the end of the launch. */
+  unsigned pri_tiles, pri_sl, pri_nsl;
+  unsigned pri_base;            /* the slices' partials and flags: slot / flag pri_base + w behind the G regular ones (a workgroup
+                                   may hold a slice AND an open partial of its range); one word, the K loop is short of SGPRs */
 };
+
+/* the rider workgroup of a Cholesky trailing update (sinterp_rider, common.h) */
+struct RiderArgs {
+  int *info; size_t j0; double *dinv; double *fb; size_t ldf; int nrhs;
+  unsigned *counter, *abort_word;
+  unsigned need;                /* covering tiles: tile 0 (256x128, 128x128), tiles 0..2 (64x64) */
+};
+#define SK_PRI_SLOTS 32          /* K-slices of priority tiles per launch */
+#define RIDER_MAX_POLLS (1u << 22)   /* x (>= 0.5 us sleep + one L2 miss): seconds, the longest update takes milliseconds */
+
+/* Launched as the LAST workgroup of the update (all owners are resident before it).  One lane polls the panel's counter
+   relaxed, then ONE agent-scope acquire; the owners stored the block write-through and drained before they counted, so the
+   plain (vector) loads of chol_diag128_block see the updated block.  No owner ever waits for the rider.  The poll is
+   bounded: on time-out the rider sets the abort word and leaves, the driver reports GSL_EFAILED. */
+template <int NW>
+__device__ __forceinline__ void gemm_rider(const GemmArgs &g, const RiderArgs &rd, double *smem)
+{
+  const int tid = threadIdx.x;
+  unsigned *okw = reinterpret_cast<unsigned *>(smem + DIAG128_LDS_BYTES / sizeof(double));
+  if (tid == 0) {
+    unsigned ok = 0;
+    for (unsigned spins = 0; spins < RIDER_MAX_POLLS; spins++) {
+      if (__hip_atomic_load(rd.counter, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= rd.need) { ok = 1; break; }
+      __builtin_amdgcn_s_sleep(32);
+    }
+    if (ok) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    else __hip_atomic_store(rd.abort_word, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    *okw = ok;
+  }
+  asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+  __syncthreads();
+  if (*okw == 0) return;
+  chol_diag128_block<NW>(smem, g.C, g.ldc, rd.j0, rd.info, (double *)nullptr, rd.dinv, rd.fb, rd.ldf, rd.nrhs, tid);
+}
 
 template <int BM, int BN>
 __device__ __forceinline__ void decode_tile(const GemmArgs &g, unsigned tile, int &tm, int &tn)
@@ -443,9 +484,12 @@ __device__ __forceinline__ void decode_tile(const GemmArgs &g, unsigned tile, in
    step is then 16 k-rows of BN doubles, each row one linear 1-KiB DMA wave-instruction (BN = 128), rows pitched
    BN + 16 doubles apart so that the (k = lane>>4, n = lane&15) fragment read -- 16 consecutive doubles per k-row,
    k-rows 32 banks apart -- is conflict-free; no swizzle needed. */
-template <int BM, int BN, int WM, int WN, int SS = 1, int ST = DM_STAGES, bool PIPE = false, bool BKN = false>
+/* RIDER: the launch has one workgroup more than the G that share the update; it factors the next panel's diagonal block
+   (gemm_rider).  The owners of the tiles that cover that block store them write-through and count in.  Instantiated for the
+   two 8-wave N.T configurations the dispatch rule ships below the 256x128 tile. */
+template <int BM, int BN, int WM, int WN, int SS = 1, int ST = DM_STAGES, bool PIPE = false, bool BKN = false, bool RIDER = false>
 __global__ void __launch_bounds__((BM / WM) * (BN / WN) * 64)
-gemm_minus_streamk_kernel(GemmArgs g, StreamK x)
+gemm_minus_streamk_kernel(GemmArgs g, StreamK x, RiderArgs rd)
 {
   static_assert(ST == 3 || ST == 2, "ring depth");
   static_assert(!PIPE || (ST == 3 && SS == 1), "pipelined loop: three-deep ring of single steps");
@@ -465,31 +509,48 @@ gemm_minus_streamk_kernel(GemmArgs g, StreamK x)
   double *sA = smem;
   double *sB = smem + ST * SS * A_TILE;
 
-  const unsigned G = gridDim.x, bid = blockIdx.x;
+  /* not the 256x128 tile: its K loop runs at 256 VGPRs with 44 bytes of scratch already, the hand-off code made that 48 to 68 */
+  static_assert(!RIDER || (!BKN && NW == 8 && BM <= 128), "rider: N.T updates on 8 waves");
+  if constexpr (RIDER) {
+    if (blockIdx.x == gridDim.x - 1) { gemm_rider<NW>(g, rd, smem); return; }
+  }
+  const unsigned G = gridDim.x - (RIDER ? 1u : 0u), bid = blockIdx.x;
   const unsigned q = G / 8, r = G % 8, xcd = bid % 8;
   const unsigned gl = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + bid / 8;   /* XCD-contiguous ranges */
-  auto start_of = [&](unsigned w) -> unsigned { return w * x.base + (w < x.rem ? w : x.rem); };
+  constexpr bool PRI = RIDER;
+  constexpr unsigned PRI_SLOT_SCALE = (256 * GT_BN) / (BM * BN);   /* pri_base counts slots of 256 x 128 doubles */
+  const unsigned pri_wgs = PRI ? x.pri_tiles * x.pri_nsl : 0u;   /* holders of a priority K-slice */
+  auto start_of = [&](unsigned w) -> unsigned {
+    const unsigned v = w * x.base + (w < x.rem ? w : x.rem);
+    if constexpr (PRI) return v - (w < pri_wgs ? w : pri_wgs) * x.pri_sl;
+    return v;
+  };
   auto start_cap = [&](unsigned w) -> unsigned { const unsigned v = start_of(w); return v < x.total ? v : x.total; };
   unsigned it = __builtin_amdgcn_readfirstlane(start_cap(gl));
   const unsigned it_end = __builtin_amdgcn_readfirstlane(start_cap(gl + 1));
   unsigned tile = __builtin_amdgcn_readfirstlane(it / x.steps);
   const unsigned dp_tiles = x.dp_rounds * G;
   unsigned round = 0;
+  bool pri_pending = PRI && gl < pri_wgs;
   GEMM_TS_INIT();
 
   /* Whole-tile rounds first: the 32 workgroups of an XCD hold 32 consecutive tiles of the same round and
      walk K more or less in step, so operand panels are shared in their L2; then the stream-K remainder. */
   for (;;) {
     const bool dp = round < x.dp_rounds;
-    if (!dp && it >= it_end) break;
-    const unsigned tile_first = dp ? 0u : tile * x.steps, tile_end = tile_first + x.steps;
-    const unsigned s0 = dp ? 0u : it - tile_first;
-    const unsigned s1 = dp ? x.steps : (it_end < tile_end ? it_end - tile_first : x.steps);
-    int tm, tn;
-    {
-      const unsigned tid_ = dp ? round * G + gl : dp_tiles + tile;
-      decode_tile<BM, BN>(g, tid_, tm, tn);
+    const bool pr = PRI && pri_pending;                /* this workgroup's K-slice of a priority tile (never with dp rounds) */
+    if (!dp && !pr && it >= it_end) break;
+    const unsigned tile_first = (dp || pr) ? 0u : tile * x.steps, tile_end = tile_first + x.steps;
+    unsigned s0 = dp ? 0u : it - tile_first;
+    unsigned s1 = dp ? x.steps : (it_end < tile_end ? it_end - tile_first : x.steps);
+    unsigned gtile = dp ? round * G + gl : dp_tiles + tile;
+    if constexpr (PRI) {
+      if (pr) { s0 = (gl % x.pri_nsl) * x.pri_sl; s1 = s0 + x.pri_sl; gtile = gl / x.pri_nsl; }
+      else if (!dp) gtile += x.pri_tiles;
     }
+    const bool hand = RIDER && gtile < rd.need;          /* a tile the rider waits for */
+    int tm, tn;
+    decode_tile<BM, BN>(g, gtile, tm, tn);
     const size_t row0 = (size_t)tm * BM, col0 = (size_t)tn * BN;
     GEMM_TS_BEGIN();
 
@@ -703,7 +764,7 @@ gemm_minus_streamk_kernel(GemmArgs g, StreamK x)
     const int fr = lane & 15, fq = lane >> 4;
     if (s0 != 0) {
       /* not the owner: publish the partial tile */
-      double *pp = x.partial + (size_t)gl * (BM * BN) + tid;
+      double *pp = x.partial + (size_t)(gl + (pr ? x.pri_base * PRI_SLOT_SCALE : 0u)) * (BM * BN) + tid;
 #pragma unroll
       for (int i = 0; i < FM; i++) {
 #pragma unroll
@@ -715,16 +776,18 @@ gemm_minus_streamk_kernel(GemmArgs g, StreamK x)
       }
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __syncthreads();
-      if (tid == 0) __hip_atomic_store(x.flags + gl, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (tid == 0) __hip_atomic_store(x.flags + gl + (pr ? x.pri_base : 0u), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       GEMM_TS_MARK(2);
     } else {
       if (s1 < x.steps) {
+        unsigned *const fl = x.flags + (pr ? x.pri_base : 0u);
+        const double *const pbase = x.partial + (size_t)(pr ? x.pri_base * PRI_SLOT_SCALE : 0u) * (BM * BN);
         for (unsigned w = gl + 1; w < G; w++) {
-          if (start_of(w) >= tile_end) break;
+          if (pr ? w >= gl + x.pri_nsl : start_of(w) >= tile_end) break;
           if (tid == 0)
-            while (__hip_atomic_load(x.flags + w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u) __builtin_amdgcn_s_sleep(8);
+            while (__hip_atomic_load(fl + w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u) __builtin_amdgcn_s_sleep(8);
           __syncthreads();
-          const double *pp = x.partial + (size_t)w * (BM * BN) + tid;
+          const double *pp = pbase + (size_t)w * (BM * BN) + tid;
 #pragma unroll
           for (int i = 0; i < FM; i++) {
 #pragma unroll
@@ -734,7 +797,7 @@ gemm_minus_streamk_kernel(GemmArgs g, StreamK x)
                 acc[i][j][rg] += __hip_atomic_load(pp + ((i * FN + j) * 4 + rg) * NT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             __builtin_amdgcn_sched_barrier(0);            /* 16 loads in flight at a time */
           }
-          if (tid == 0) __hip_atomic_store(x.flags + w, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          if (tid == 0) __hip_atomic_store(fl + w, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
       }
       GEMM_TS_MARK(2);
@@ -748,12 +811,23 @@ gemm_minus_streamk_kernel(GemmArgs g, StreamK x)
             const size_t grow = row0e + wr * WM + i * 16 + fq + 4 * rg;
             if (!g.lower_only || gcol <= grow) {
               double *p = g.C + grow * g.ldc + gcol;
-              if constexpr (CPRE) *p = cpre[i][j][rg] - acc[i][j][rg];
-              else *p = *p - acc[i][j][rg];
+              double v;
+              if constexpr (CPRE) v = cpre[i][j][rg] - acc[i][j][rg];
+              else v = *p - acc[i][j][rg];
+              if (hand) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   /* write-through: read by the rider */
+              else *p = v;
             }
           }
         }
         __builtin_amdgcn_sched_barrier(0);
+      }
+      if constexpr (RIDER) {
+        if (hand) {
+          /* every storing wave drains, then one lane counts the tile in (cdna_hip_programming.md, Guideline 16) */
+          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+          __syncthreads();
+          if (tid == 0) __hip_atomic_fetch_add(rd.counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
       }
 #ifdef SINTERP_DIAG_PROF
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -761,6 +835,7 @@ gemm_minus_streamk_kernel(GemmArgs g, StreamK x)
 #endif
     }
     if (dp) round++;
+    else if (pr) pri_pending = false;
     else { it = tile_first + s1; tile++; }
   }
   GEMM_TS_FINISH();
@@ -774,8 +849,9 @@ int sinterp_streamk_prepare(gsl_sinterp_hip_ctx *ctx)
   int cus = 0;
   HIP_OK(ctx, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device));
   if (cus <= 0) return ST_SUCCESS;
-  HIP_OK(ctx, hipMalloc((void **)&ctx->d_sk_partial, (size_t)cus * 256 * GT_BN * sizeof(double)));
-  HIP_OK(ctx, hipMalloc((void **)&ctx->d_sk_flags, (size_t)cus * 2 * sizeof(unsigned)));   /* 2 x: the two-workgroups-per-CU variant */
+  /* one slot per workgroup + SK_PRI_SLOTS slots for the K-slices of priority tiles (rider launches) */
+  HIP_OK(ctx, hipMalloc((void **)&ctx->d_sk_partial, (size_t)(cus + SK_PRI_SLOTS) * 256 * GT_BN * sizeof(double)));
+  HIP_OK(ctx, hipMalloc((void **)&ctx->d_sk_flags, (size_t)cus * 2 * sizeof(unsigned)));   /* second half: flags of the priority K-slices */
   HIP_OK(ctx, hipMemset(ctx->d_sk_flags, 0, (size_t)cus * 2 * sizeof(unsigned)));
   HIP_OK(ctx, hipDeviceSynchronize());
   ctx->sk_wgs = cus;
@@ -861,13 +937,14 @@ enum { SK_256 = 0,      /* 256x128, 8 waves of 64x64 */
        SK_64W8G = 6 };  /* 64x64,   8 waves of 32x16, 4-step groups */
 static inline int sk_tile(int cfg) { return cfg == SK_128 || cfg == SK_128W8 ? 128 : cfg == SK_256 ? 256 : 64; }
 
-template <int BM, int BN, int WM, int WN, int SS = 1, int ST = DM_STAGES, bool PIPE = false>
-static int launch_sk(gsl_sinterp_hip_ctx *ctx, unsigned G, const GemmArgs &h, const StreamK &x)
+template <int BM, int BN, int WM, int WN, int SS = 1, int ST = DM_STAGES, bool PIPE = false, bool RIDER = false>
+static int launch_sk(gsl_sinterp_hip_ctx *ctx, unsigned G, const GemmArgs &h, const StreamK &x, const RiderArgs &rd = RiderArgs())
 {
   constexpr int NT = (BM / WM) * (BN / WN) * 64;
-  const size_t lds = (size_t)ST * SS * (BM + BN) * GT_BK * sizeof(double);
-  { int ast = sinterp_func_lds(ctx, (const void *)gemm_minus_streamk_kernel<BM, BN, WM, WN, SS, ST, PIPE>, (int)lds); if (ast) return ast; }
-  hipLaunchKernelGGL((gemm_minus_streamk_kernel<BM, BN, WM, WN, SS, ST, PIPE>), dim3(G), dim3(NT), lds, ctx->stream, h, x);
+  size_t lds = (size_t)ST * SS * (BM + BN) * GT_BK * sizeof(double);
+  if (RIDER && lds < DIAG128_LDS_BYTES + 16) lds = DIAG128_LDS_BYTES + 16;   /* the rider's potrf128 image + its poll result */
+  { int ast = sinterp_func_lds(ctx, (const void *)gemm_minus_streamk_kernel<BM, BN, WM, WN, SS, ST, PIPE, false, RIDER>, (int)lds); if (ast) return ast; }
+  hipLaunchKernelGGL((gemm_minus_streamk_kernel<BM, BN, WM, WN, SS, ST, PIPE, false, RIDER>), dim3(G + (RIDER ? 1u : 0u)), dim3(NT), lds, ctx->stream, h, x, rd);
   LAUNCH_CHECK(ctx);
   return ST_SUCCESS;
 }
@@ -890,8 +967,10 @@ static int g_gemm_last_cfg = -1;
 extern "C" int gsl_sinterp_hip_debug_gemm_last_cfg(void) { return __atomic_load_n(&g_gemm_last_cfg, __ATOMIC_RELAXED); }
 
 int sinterp_gemm_minus(gsl_sinterp_hip_ctx *ctx, size_t m, size_t n, size_t k, const double *A, size_t lda,
-                       const double *B, size_t ldb, int b_is_kn, double *C, size_t ldc, int lower_only)
+                       const double *B, size_t ldb, int b_is_kn, double *C, size_t ldc, int lower_only,
+                       const sinterp_rider *rider, int *attached)
 {
+  if (attached) *attached = 0;
   if (m == 0 || n == 0 || k == 0) return ST_SUCCESS;
   __atomic_store_n(&g_gemm_last_cfg, -1, __ATOMIC_RELAXED);
   GemmArgs g;
@@ -980,6 +1059,14 @@ int sinterp_gemm_minus(gsl_sinterp_hip_ctx *ctx, size_t m, size_t n, size_t k, c
       if (grouped) x.steps = (unsigned)(k / (4 * GT_BK));
       static const bool no_hybrid = getenv("GSL_SINTERP_NO_HYBRID_SK") && getenv("GSL_SINTERP_NO_HYBRID_SK")[0] == '1';
       if (no_hybrid) whole = false;
+      /* the rider rides on the 128x128 and 64x64 8-wave configurations, when the block it factors is covered by the first
+         tiles of the enumeration (lower_only, at least 128 x 128) and a CU can be left to it */
+      const bool ride = rider && attached && lower_only && m >= 128 && n >= 128 && cus >= 2 && !whole &&
+                        ((cfg == SK_128W8 && !no_pipe) || cfg == SK_64W8G) &&
+                        ((((uintptr_t)C) & 15) == 0) && (ldc & 1) == 0;
+      const unsigned cus_g = ride ? cus - 1 : cus;
+      x.pri_tiles = 0; x.pri_sl = 0; x.pri_nsl = 1;
+      x.pri_base = cus;
       unsigned G;
       unsigned long long total64;
       if (whole) {
@@ -991,7 +1078,7 @@ int sinterp_gemm_minus(gsl_sinterp_hip_ctx *ctx, size_t m, size_t n, size_t k, c
         total64 = (unsigned long long)tiles * x.steps;
         unsigned long long want = total64 / (grouped ? 4 : 16);   /* >= 16 K-steps (of 16) per workgroup ... */
         if (want < tiles) want = tiles;                     /* ... but never fewer workgroups than tiles */
-        if (want > cus) want = cus;
+        if (want > cus_g) want = cus_g;
         G = (unsigned)(want ? want : 1);
         /* many tiles: all but the last full round (and the remainder) as whole tiles */
         x.dp_rounds = (!no_hybrid && tiles / G >= 2) ? tiles / G - 1 : 0;
@@ -1001,6 +1088,30 @@ int sinterp_gemm_minus(gsl_sinterp_hip_ctx *ctx, size_t m, size_t n, size_t k, c
         x.total = (unsigned)total64;
         if (whole) { x.base = x.steps; x.rem = 0; }      /* workgroup w: the w-th remaining tile, if any */
         else { x.base = x.total / G; x.rem = x.total % G; }
+        RiderArgs rd = RiderArgs();
+        if (ride) {
+          rd.info = rider->info; rd.j0 = rider->j0; rd.dinv = rider->dinv; rd.fb = rider->fb; rd.ldf = rider->ldf;
+          rd.nrhs = rider->fb ? rider->nrhs : 0; rd.counter = rider->counter; rd.abort_word = rider->abort_word;
+          rd.need = cfg == SK_64W8G ? 3u : 1u;
+          if (x.dp_rounds == 0) {
+            /* one round: without a split the covering tiles end when the launch ends.  S slices per tile (the largest
+               divisor of the step count up to the wanted number), every holder keeping at least half of its share
+               for its own range */
+            static const int s_env = getenv("GSL_SINTERP_RIDER_SLICES") ? atoi(getenv("GSL_SINTERP_RIDER_SLICES")) : 0;
+            unsigned S = s_env > 0 ? (unsigned)s_env : 4u;
+            if (S > x.steps) S = x.steps;
+            while (S > 1 && (x.steps % S) != 0) S--;
+            while (S > 1 && (rd.need * S > G || rd.need * S > SK_PRI_SLOTS || 2 * (x.steps / S) > x.base || rd.need >= tiles)) {
+              S--;
+              while (S > 1 && (x.steps % S) != 0) S--;
+            }
+            if (S > 1) {
+              x.pri_tiles = rd.need; x.pri_nsl = S; x.pri_sl = x.steps / S;
+              x.total -= rd.need * x.steps;               /* the space the ranges share; base / rem still count the slices */
+            }
+          }
+          *attached = 1;
+        }
         __atomic_store_n(&g_gemm_last_cfg, 2 * cfg + (whole ? 1 : 0), __ATOMIC_RELAXED);
         switch (cfg) {
           case SK_256:
@@ -1008,8 +1119,10 @@ int sinterp_gemm_minus(gsl_sinterp_hip_ctx *ctx, size_t m, size_t n, size_t k, c
           case SK_128:
             return no_pipe ? launch_sk<128, 128, 64, 64>(ctx, G, h, x) : launch_sk<128, 128, 64, 64, 1, 3, true>(ctx, G, h, x);
           case SK_128W8:
+            if (ride) return launch_sk<128, 128, 64, 32, 1, 3, true, true>(ctx, G, h, x, rd);
             return no_pipe ? launch_sk<128, 128, 64, 32>(ctx, G, h, x) : launch_sk<128, 128, 64, 32, 1, 3, true>(ctx, G, h, x);
           case SK_64W8G:
+            if (ride) return launch_sk<64, 64, 32, 16, 4, 2, false, true>(ctx, G, h, x, rd);
             return launch_sk<64, 64, 32, 16, 4, 2>(ctx, G, h, x);
           default:
             return grouped ? launch_sk<64, 64, 32, 32, 4, 2>(ctx, G, h, x) : launch_sk<64, 64, 32, 32>(ctx, G, h, x);
@@ -1044,6 +1157,7 @@ int sinterp_gemm_minus(gsl_sinterp_hip_ctx *ctx, size_t m, size_t n, size_t k, c
     StreamK x;
     x.steps = (unsigned)(k / GT_BK);
     x.partial = ctx->d_sk_partial; x.flags = ctx->d_sk_flags;
+    x.pri_tiles = 0; x.pri_sl = 0; x.pri_nsl = 1; x.pri_base = 0;
     GemmArgs h = g;
     unsigned tiles = grid;
     bool big = false;
@@ -1063,11 +1177,11 @@ int sinterp_gemm_minus(gsl_sinterp_hip_ctx *ctx, size_t m, size_t n, size_t k, c
       if (big) {
         const size_t lds = (size_t)DM_STAGES * (256 * GT_BK + GT_BK * (128 + 16)) * sizeof(double);      /* 150 KiB */
         { int ast = sinterp_func_lds(ctx, (const void *)gemm_minus_streamk_kernel<256, 128, 64, 64, 1, 3, true, true>, (int)lds); if (ast) return ast; }
-        hipLaunchKernelGGL((gemm_minus_streamk_kernel<256, 128, 64, 64, 1, 3, true, true>), dim3(G), dim3(512), lds, ctx->stream, h, x);
+        hipLaunchKernelGGL((gemm_minus_streamk_kernel<256, 128, 64, 64, 1, 3, true, true>), dim3(G), dim3(512), lds, ctx->stream, h, x, RiderArgs());
       } else {
         const size_t lds = (size_t)DM_STAGES * (128 * GT_BK + GT_BK * (128 + 16)) * sizeof(double);
         { int ast = sinterp_func_lds(ctx, (const void *)gemm_minus_streamk_kernel<128, 128, 64, 64, 1, 3, true, true>, (int)lds); if (ast) return ast; }
-        hipLaunchKernelGGL((gemm_minus_streamk_kernel<128, 128, 64, 64, 1, 3, true, true>), dim3(G), dim3(256), lds, ctx->stream, h, x);
+        hipLaunchKernelGGL((gemm_minus_streamk_kernel<128, 128, 64, 64, 1, 3, true, true>), dim3(G), dim3(256), lds, ctx->stream, h, x, RiderArgs());
       }
       LAUNCH_CHECK(ctx);
       return ST_SUCCESS;

@@ -1,5 +1,5 @@
 """Developer tool: the SPD factorisation alone (gsl_sinterp_hip_cholesky_decomp1) against numpy, with timings.
-usage: python tools/chol_time.py [n ...]        (GSL_SINTERP_NO_FUSED_POTRF=1, GSL_SINTERP_CHOL_DAG=1, ... select variants)"""
+usage: python tools/chol_time.py [n ...]        (GSL_SINTERP_NO_DIAG_RIDER=1, GSL_SINTERP_NO_FOLD=1, ... select variants)"""
 import os, sys, time
 _R = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, _R); sys.path.insert(0, os.path.join(_R, "tests"))
@@ -25,4 +25,5 @@ for n in [int(v) for v in sys.argv[1:]] or [384, 1024, 4096, 8192, 16384]:
         ctx.timer_start()
         ctx.cholesky_decomp1(n, d.data_ptr(), n)
         ms.append(ctx.timer_stop())
-    print(f"n={n}: st={st} info={info} rel err {err:.2e} upper = original {up}  {min(ms):.3f} ms", flush=True)
+    riders = pkg.lib().gsl_sinterp_hip_debug_chol_riders()    # diagonal blocks factored by a rider of the update in front of them
+    print(f"n={n}: st={st} info={info} rel err {err:.2e} upper = original {up}  {min(ms):.3f} ms  riders {riders} of {max(n // 128 - 1, 0)}", flush=True)
