@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 
 GSL_SUCCESS, GSL_FAILURE = 0, -1
 GSL_EDOM, GSL_EFAULT, GSL_EINVAL, GSL_EFAILED, GSL_ENOMEM = 1, 3, 4, 5, 8
-GSL_EBADLEN, GSL_ENOTSQR, GSL_EUNIMPL = 19, 20, 24
+GSL_EBADLEN, GSL_ENOTSQR, GSL_EUNSUP, GSL_EUNIMPL = 19, 20, 23, 24
 RBF_GAUSSIAN, RBF_TPS, RBF_WENDLAND = 0, 1, 2
 SOLVER_DEFAULT, SOLVER_CHOLESKY2, SOLVER_PCHOLESKY, SOLVER_LU_REFINE = 0, 1, 2, 3
 TREE_DEFAULT, TREE_NOSTANDARDIZE, TREE_ISOSCALE = 0, 1, 2
@@ -92,7 +92,7 @@ class gsl_sinterp(C.Structure):
     _fields_ = [("type", C.c_void_p), ("dim", C.c_size_t), ("size", C.c_size_t), ("device", C.c_int),
                 ("shape", C.c_double), ("init_flags", C.c_int), ("rng", C.c_void_p), ("state", C.c_void_p),
                 ("n_devices", C.c_int), ("devices", C.c_int * 64), ("solver", C.c_int), ("want_rcond", C.c_int),
-                ("rcond", C.c_double), ("route", C.c_int), ("nugget", C.c_double)]
+                ("rcond", C.c_double), ("route", C.c_int), ("nugget", C.c_double), ("want_variance", C.c_int)]
 
 
 _vp, _i, _sz, _d = C.c_void_p, C.c_int, C.c_size_t, C.c_double
@@ -236,6 +236,14 @@ SIGNATURES = {
     "gsl_sinterp_hip_rbf_eval_affine": (_i, [_vp, _i, _d, _pd, _vp, _sz, _i, _sz, _vp, _vp, _sz, _sz, _vp, C.c_uint64]),
     "gsl_sinterp_hip_krige_solve": (_i, [_vp, _i, _d, _d, _vp, _sz, _i, _sz, _vp, _sz, _vp, _pd, _pi]),
     "gsl_sinterp_hip_krige_eval": (_i, [_vp, _i, _d, _d, _vp, _sz, _i, _sz, _vp, _vp, _sz, _sz, _vp, C.c_uint64]),
+    "gsl_sinterp_hip_krige_variance_prepare": (_i, [_vp, _sz, _vp, _sz, _vp, _vp, _pd]),
+    "gsl_sinterp_hip_krige_variance_work": (_sz, [_sz, _sz]),
+    "gsl_sinterp_hip_krige_variance": (_i, [_vp, _i, _d, _vp, _sz, _i, _sz, _vp, _sz, _vp, _vp, _d, _vp, _sz, _sz, _vp, _vp, _sz]),
+    "gsl_sinterp_hip_krige_variance_clamp": (_i, [_vp, _vp, _sz]),
+    "gsl_sinterp_set_variance": (_i, [C.POINTER(gsl_sinterp), _i]),
+    "gsl_sinterp_eval_variance_e": (_i, [C.POINTER(gsl_sinterp), _pv, _pd]),
+    "gsl_sinterp_eval_variance_many": (_i, [C.POINTER(gsl_sinterp), _pm, _pv]),
+    "gsl_sinterp_eval_variance_resident": (_i, [C.POINTER(gsl_sinterp), _vp, _sz, _sz, _vp]),
     "gsl_sinterp_set_rcond": (_i, [C.POINTER(gsl_sinterp), _i]),
     "gsl_sinterp_rcond": (_i, [C.POINTER(gsl_sinterp), _pd]),
     "gsl_sinterp_route": (_i, [C.POINTER(gsl_sinterp)]),
@@ -497,6 +505,21 @@ class HipContext:
     def krige_eval(self, kind, eps, mean, d_x, n, dim, xtda, d_w, d_y, m, ytda, d_s, model_id=0):
         check(lib().gsl_sinterp_hip_krige_eval(self._h, kind, eps, mean, d_x, n, dim, xtda, d_w, d_y, m, ytda, d_s,
                                                model_id), self._h)
+
+    def krige_variance_prepare(self, n, d_llt, lda, d_b, d_dinv):
+        """b = K^-1 1 -> d_b[n], inverted 32x32 diagonal blocks -> d_dinv[ceil(n/32) * 1024]; returns (status, 1^T b)"""
+        denom = C.c_double(0)
+        st = lib().gsl_sinterp_hip_krige_variance_prepare(self._h, n, d_llt, lda, d_b, d_dinv, C.byref(denom))
+        return st, denom.value
+
+    @staticmethod
+    def krige_variance_work(n, chunk):
+        """doubles of d_work that krige_variance needs for `chunk` targets per pass"""
+        return lib().gsl_sinterp_hip_krige_variance_work(n, chunk)
+
+    def krige_variance(self, kind, eps, d_x, n, dim, xtda, d_llt, lda, d_b, d_dinv, denom, d_y, m, ytda, d_var, d_work, chunk):
+        return lib().gsl_sinterp_hip_krige_variance(self._h, kind, eps, d_x, n, dim, xtda, d_llt, lda, d_b, d_dinv, denom,
+                                                    d_y, m, ytda, d_var, d_work, chunk)
 
     def gemm_minus(self, m, n, k, d_a, lda, d_b, ldb, b_is_kn, d_c, ldc, lower_only=0):
         check(lib().gsl_sinterp_hip_gemm_minus(self._h, m, n, k, d_a, lda, d_b, ldb, b_is_kn, d_c, ldc, lower_only),
@@ -858,6 +881,25 @@ class Sinterp:
         v = C.c_double(0)
         st = lib().gsl_sinterp_mean(self._p, C.byref(v))
         return st, v.value
+
+    def set_variance(self, want=True):
+        """kriging: the next init keeps the Cholesky factor (N^2 doubles on the device) for eval_variance_*"""
+        return lib().gsl_sinterp_set_variance(self._p, int(want))
+
+    def eval_variance_e(self, y):
+        out = C.c_double(0)
+        st = lib().gsl_sinterp_eval_variance_e(self._p, C.byref(as_vector(np.ascontiguousarray(y, dtype=np.float64))),
+                                               C.byref(out))
+        return st, out.value
+
+    def eval_variance_many(self, y, out=None):
+        """kriging variance sigma^2 at the rows of y (clamped at 0); returns (status, values)"""
+        v = np.empty(y.shape[0], dtype=np.float64) if out is None else out
+        st = lib().gsl_sinterp_eval_variance_many(self._p, C.byref(as_matrix(y)), C.byref(as_vector(v)))
+        return st, v
+
+    def eval_variance_resident(self, d_y, m, ytda, d_var):
+        return lib().gsl_sinterp_eval_variance_resident(self._p, d_y, m, ytda, d_var)
 
     def poly(self):
         c = np.zeros(self._p.contents.dim + 1, dtype=np.float64)

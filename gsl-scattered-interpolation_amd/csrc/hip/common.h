@@ -138,6 +138,9 @@ int sinterp_rbf_fill_ex(gsl_sinterp_hip_ctx *ctx, int kind, double eps, const do
 int sinterp_tps_fill_shifted(gsl_sinterp_hip_ctx *ctx, const double *d_x, size_t n, int dim, size_t xtda, double *d_phi, size_t lda,
                              const double *d_Pk, int k, double cmul, unsigned long long *d_norm);
 
+/* rbf.hip: device address of the 256-entry exp2 table that rbf_phi.h's exp2_tbl reads (built on first use) */
+int sinterp_rbf_exp2_table(gsl_sinterp_hip_ctx *ctx, const double **d_tbl);
+
 /* grow-only workspace owned by the context */
 int sinterp_workspace(gsl_sinterp_hip_ctx *ctx, size_t bytes, void **out);
 

@@ -1,0 +1,408 @@
+/*
+ * krige_var.hip -- the kriging variance at M targets from the Cholesky factor K = Phi + nugget I = L L^T that the
+ * kriging solve (solve.hip, route 7) leaves behind:
+ *
+ *     sigma^2(y) = C(0) - |L^-1 k(y)|^2 + (1 - b^T k(y))^2 / d,     k(y)_j = C(|y - x_j|),  b = K^-1 1,  d = 1^T b,
+ *
+ * the variance of the underlying field (the nugget is measurement noise), sill C(0) = 1.  The targets are processed in
+ * chunks of rows of a work matrix Z (row = target, column = centre, pitch ldw = N rounded up to 128):
+ *
+ *     fill      Z[k][j] = phi(|y_k - x_j|)                                     (rbf_phi.h: the arithmetic of the fill)
+ *     solve     Z <- Z L^-T, blocked forward substitution from the right over 128-column blocks J:
+ *                 Z[:, J] -= Z[:, :J] L[J, :J]^T                               (gemm.hip, fp64 MFMA, stream-K)
+ *                 Z[:, J] <- Z[:, J] L_JJ^-T,  q_k += sum_j Z[k][J j]^2         (krige_trsm128_kernel, below)
+ *     combine   var_k = 1 - q_k + (1 - a_k)^2 / d,    a = b^T k from the culled sweep (rbf.hip) with b as weights.
+ *
+ * M N^2 flops, all of them in the GEMM; the N^2 doubles of the factor stay resident for as long as variances are wanted.
+ * The inverted 32 x 32 diagonal blocks of L that the diagonal step multiplies with are formed once per model
+ * (gsl_sinterp_hip_krige_variance_prepare).  Only the lower triangle of the factor, diagonal included, is read: the
+ * strict upper triangle holds whatever the factorisation kept there.
+ */
+#include "common.h"
+#include <math.h>
+#include <stdlib.h>
+#include "chol_potrf.h"
+#include "rbf_phi.h"
+
+#define KV_RP 128   /* rows of a pass are padded to this (zero rows): every update then takes the full-tile GEMM path */
+
+static inline size_t kv_round_up(size_t v, size_t to) { return (v + to - 1) / to * to; }
+
+/* ------------------------------------------------------------------------ */
+/* cross-covariance fill: block = 256 threads -> 16 rows (targets) x 128 columns (centres), 2 columns (16 B) per lane.
+   Rows >= rows (padding of the pass) and columns >= n (padding of the last block) are written as zeros, so they pass
+   through the substitution as zeros and add nothing to q.  The column-0 blocks also clear q for the pass. */
+template <int KIND, int DIM>
+__global__ void __launch_bounds__(256)
+krige_cross_fill_kernel(double coef, const double *__restrict__ tbl, const double *__restrict__ x, size_t n, size_t xtda,
+                        const double *__restrict__ y, size_t rows, size_t ytda, double *__restrict__ Z, size_t ldw,
+                        double *__restrict__ q)
+{
+  __shared__ double s_t0[KIND == GSL_SINTERP_RBF_GAUSSIAN ? TBL_N : 1];
+  if (KIND == GSL_SINTERP_RBF_GAUSSIAN) s_t0[threadIdx.x] = tbl[threadIdx.x];      /* TBL_N = 256 = the block */
+  __syncthreads();
+  const size_t j0 = ((size_t)blockIdx.x * 64 + (threadIdx.x & 63)) * 2;
+  const size_t ibase = (size_t)blockIdx.y * 16 + (threadIdx.x >> 6) * 4;
+  if (blockIdx.x == 0 && (threadIdx.x & 63) < 4) q[ibase + (threadIdx.x & 63)] = 0.0;
+  const bool ca = j0 < n, cb = j0 + 1 < n;
+  double xa[DIM], xb[DIM];
+#pragma unroll
+  for (int c = 0; c < DIM; c++) { xa[c] = ca ? x[j0 * xtda + c] : 0.0; xb[c] = cb ? x[(j0 + 1) * xtda + c] : 0.0; }
+#pragma unroll
+  for (int r = 0; r < 4; r++) {
+    const size_t i = ibase + r;
+    double va = 0.0, vb = 0.0;
+    if (i < rows && ca) {
+      double ra = 0.0, rb = 0.0;
+#pragma unroll
+      for (int c = 0; c < DIM; c++) {
+        const double yi = y[i * ytda + c];
+        const double da = yi - xa[c], db = yi - xb[c];
+        ra = fma(da, da, ra); rb = fma(db, db, rb);
+      }
+      va = phi_r2<KIND, 1>(ra, coef, s_t0, s_t0);
+      vb = cb ? phi_r2<KIND, 1>(rb, coef, s_t0, s_t0) : 0.0;
+    }
+    *reinterpret_cast<double2 *>(Z + i * ldw + j0) = make_double2(va, vb);       /* Z 16-byte aligned, ldw and j0 even */
+  }
+}
+
+/* ------------------------------------------------------------------------ */
+/* inverse of every 32 x 32 diagonal block of L (identity padding past n): lane c solves L_bb x = e_c by forward
+   substitution with x in registers, Dinv[b][i][c] = (L_bb^-1)[i][c] -- the layout chol_diag128_block writes and the
+   row solves read as MFMA B fragments */
+__global__ void __launch_bounds__(64)
+krige_inv32_kernel(const double *__restrict__ L, size_t lda, size_t n, double *__restrict__ Dinv)
+{
+  __shared__ double sL[CB][CB + 1];
+  const size_t j0 = (size_t)blockIdx.x * CB;
+  const int nb = (int)((n - j0) < CB ? (n - j0) : CB);
+  const int lane = threadIdx.x;
+  for (int e = lane; e < CB * CB; e += 64) {
+    const int r = e / CB, c = e % CB;
+    double v = r == c ? 1.0 : 0.0;
+    if (r < nb && c <= r) v = L[(j0 + r) * lda + j0 + c];                         /* lower triangle only */
+    sL[r][c] = v;
+  }
+  __syncthreads();
+  if (lane >= CB) return;
+  double xv[CB];
+#pragma unroll
+  for (int i = 0; i < CB; i++) {
+    double v = (i == lane) ? 1.0 : 0.0;
+#pragma unroll
+    for (int k = 0; k < i; k++) v = fma(-sL[i][k], xv[k], v);
+    xv[i] = v / sL[i][i];
+  }
+  double *out = Dinv + (size_t)blockIdx.x * (CB * CB);
+#pragma unroll
+  for (int i = 0; i < CB; i++) out[i * CB + lane] = xv[i];
+}
+
+/* ------------------------------------------------------------------------ */
+/* the diagonal step: Z[:, J] <- Z[:, J] L_JJ^-T for the 128-column block J at j0, and q_k += |Z[k][J]|^2.
+   The scheme of chol_trsm128_kernel (chol.hip): 64 rows per workgroup, wave w owns rows 16w .. 16w+15 for all four
+   32-column steps c (no workgroup barrier between the steps),
+       Y_c = Z_c - sum_{p<c} X_p L_cp^T,     X_c = Y_c Dinv_c^T,
+   the Z tile, the six off-diagonal 32 x 32 blocks of L_JJ and the four Dinv blocks staged in LDS with one round trip.
+   Here the right-hand matrix (Z, ldw) and the factor (L, lda) are different buffers, rows of L past n (the last,
+   partial block) read as zeros, and the squared row norms are accumulated on the way out: a workgroup owns the same
+   rows at every step of the recursion, so q needs no atomics.  rows is a multiple of 64 (KV_RP). */
+__global__ void __launch_bounds__(256)
+krige_trsm128_kernel(double *__restrict__ Z, size_t ldw, const double *__restrict__ L, size_t lda, size_t n, size_t j0,
+                     const double *__restrict__ Dinvg, double *__restrict__ q)
+{
+  extern __shared__ __attribute__((aligned(16))) double sm[];
+  double *Bt = sm;                     /* [64][TR_LD] */
+  double *Lb = Bt + 64 * TR_LD;        /* 6 off-diagonal blocks of L_JJ: (bi, bj) at bi(bi-1)/2 + bj */
+  double *Dvb = Lb + 6 * PBLK;         /* 4 inverted diagonal blocks */
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int fr = lane & 15, fq = lane >> 4;
+  const size_t row0 = (size_t)blockIdx.x * 64;
+  {
+    /* one round trip: every global load is issued before the first LDS store */
+    double2 vb[16];
+    double vl[24], vd[16];
+    const int r8 = tid >> 5, k = tid & 31;
+#pragma unroll
+    for (int t = 0; t < 16; t++) {
+      const int e = t * 256 + tid, r = e >> 6, k2 = (e & 63) * 2;
+      vb[t] = *reinterpret_cast<const double2 *>(Z + (row0 + r) * ldw + j0 + k2);
+    }
+#pragma unroll
+    for (int t = 0; t < 24; t++) {
+      constexpr int BI[6] = {1, 2, 2, 3, 3, 3}, BJ[6] = {0, 0, 1, 0, 1, 2};
+      const int b = t >> 2, r = (t & 3) * 8 + r8;
+      const size_t gr = j0 + BI[b] * 32 + r;
+      vl[t] = gr < n ? L[gr * lda + j0 + BJ[b] * 32 + k] : 0.0;                    /* strictly below the diagonal */
+    }
+#pragma unroll
+    for (int t = 0; t < 16; t++) {
+      const size_t blk = j0 / CB + (t >> 2);
+      vd[t] = blk * CB < n ? Dinvg[blk * 1024 + ((t & 3) * 8 + r8) * 32 + k] : 0.0;
+    }
+#pragma unroll
+    for (int t = 0; t < 16; t++) {
+      const int e = t * 256 + tid, r = e >> 6, k2 = (e & 63) * 2;
+      Bt[r * TR_LD + k2] = vb[t].x; Bt[r * TR_LD + k2 + 1] = vb[t].y;
+    }
+#pragma unroll
+    for (int t = 0; t < 24; t++) Lb[(t >> 2) * PBLK + ((t & 3) * 8 + r8) * PQ + k] = vl[t];
+#pragma unroll
+    for (int t = 0; t < 16; t++) Dvb[(t >> 2) * PBLK + ((t & 3) * 8 + r8) * PQ + k] = vd[t];
+  }
+  __syncthreads();
+
+  double *arow = Bt + (wave * 16 + fr) * TR_LD + fq;        /* A-operand view of this wave's rows */
+  double *drow = Bt + (wave * 16 + fq) * TR_LD + fr;        /* accumulator (D layout) view */
+  double qs[4] = {0.0, 0.0, 0.0, 0.0};                      /* this lane's share of |X[row fq + 4 rg]|^2 */
+#pragma unroll
+  for (int c = 0; c < 4; c++) {
+    double4_t acc[2];
+#pragma unroll
+    for (int f = 0; f < 2; f++)
+#pragma unroll
+      for (int rg = 0; rg < 4; rg++) acc[f][rg] = drow[4 * rg * TR_LD + c * 32 + f * 16];
+#pragma unroll
+    for (int p = 0; p < c; p++) {
+      const double *lb = Lb + (c * (c - 1) / 2 + p) * PBLK + fr * PQ + fq;
+#pragma unroll
+      for (int kk = 0; kk < 8; kk++) {
+        const double a = -arow[p * 32 + kk * 4];
+#pragma unroll
+        for (int f = 0; f < 2; f++) acc[f] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, lb[f * 16 * PQ + kk * 4], acc[f], 0, 0, 0);
+      }
+    }
+    /* Y -> LDS (own rows), then X_c = Y Dinv_c^T (Dinv lower triangular: fragment f needs K = 16(f+1)) */
+#pragma unroll
+    for (int f = 0; f < 2; f++)
+#pragma unroll
+      for (int rg = 0; rg < 4; rg++) drow[4 * rg * TR_LD + c * 32 + f * 16] = acc[f][rg];
+    const double *db = Dvb + c * PBLK + fr * PQ + fq;
+#pragma unroll
+    for (int f = 0; f < 2; f++) {
+      acc[f] = (double4_t){0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+      for (int kk = 0; kk < (f + 1) * 4; kk++)
+        acc[f] = __builtin_amdgcn_mfma_f64_16x16x4f64(arow[c * 32 + kk * 4], db[f * 16 * PQ + kk * 4], acc[f], 0, 0, 0);
+    }
+#pragma unroll
+    for (int f = 0; f < 2; f++)
+#pragma unroll
+      for (int rg = 0; rg < 4; rg++) {
+        drow[4 * rg * TR_LD + c * 32 + f * 16] = acc[f][rg];
+        Z[(row0 + wave * 16 + fq + 4 * rg) * ldw + j0 + c * 32 + f * 16 + fr] = acc[f][rg];
+        qs[rg] = fma(acc[f][rg], acc[f][rg], qs[rg]);
+      }
+  }
+#pragma unroll
+  for (int rg = 0; rg < 4; rg++) {
+    double v = qs[rg];
+    v += __shfl_xor(v, 1);
+    v += __shfl_xor(v, 2);
+    v += __shfl_xor(v, 4);
+    v += __shfl_xor(v, 8);
+    if (fr == 0) q[row0 + wave * 16 + fq + 4 * rg] += v;
+  }
+}
+
+/* var_k = 1 - q_k + (1 - a_k)^2 / d; a_k = b^T k(y_k) is in var[k] on entry.  No clamping: at a data site with nugget 0
+   the result is rounding residue of either sign. */
+__global__ void __launch_bounds__(256)
+krige_combine_kernel(double *__restrict__ var, const double *__restrict__ q, size_t rows, double denom)
+{
+  const size_t k = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (k >= rows) return;
+  const double t = 1.0 - var[k];
+  var[k] = (1.0 - q[k]) + t * t / denom;
+}
+
+__global__ void __launch_bounds__(256)
+krige_ones_kernel(double *__restrict__ b, size_t n)
+{
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < n) b[i] = 1.0;
+}
+
+/* v < 0 -> 0 (a NaN stays a NaN) */
+__global__ void __launch_bounds__(256)
+clamp_nonnegative_kernel(double *__restrict__ v, size_t m)
+{
+  const size_t stride = (size_t)gridDim.x * blockDim.x;
+  for (size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x; k < m; k += stride)
+    if (v[k] < 0.0) v[k] = 0.0;
+}
+
+/* ------------------------------------------------------------------------ */
+template <int KIND>
+static void launch_cross_fill(gsl_sinterp_hip_ctx *ctx, double coef, const double *tbl, const double *d_x, size_t n, int dim, size_t xtda,
+                              const double *d_y, size_t rows, size_t ytda, double *Z, size_t ldw, size_t rows_pad, double *q)
+{
+  const dim3 grid((unsigned)(ldw / 128), (unsigned)(rows_pad / 16));
+  switch (dim) {
+    case 1: hipLaunchKernelGGL((krige_cross_fill_kernel<KIND, 1>), grid, dim3(256), 0, ctx->stream, coef, tbl, d_x, n, xtda, d_y, rows, ytda, Z, ldw, q); break;
+    case 2: hipLaunchKernelGGL((krige_cross_fill_kernel<KIND, 2>), grid, dim3(256), 0, ctx->stream, coef, tbl, d_x, n, xtda, d_y, rows, ytda, Z, ldw, q); break;
+    default: hipLaunchKernelGGL((krige_cross_fill_kernel<KIND, 3>), grid, dim3(256), 0, ctx->stream, coef, tbl, d_x, n, xtda, d_y, rows, ytda, Z, ldw, q); break;
+  }
+}
+
+/* one pass over rows_pad rows of Z */
+struct KvPass {
+  gsl_sinterp_hip_ctx *ctx;
+  double *Z; size_t ldw, rows_pad;
+  const double *L; size_t lda, n;
+  const double *dinv;
+  double *q;
+};
+
+/* Z[:, c0 : c0 + cw] -= Z[:, k0 : k0 + kw] L[c0 : c0 + cw, k0 : k0 + kw]^T; a partial last block (c0 + cw = n, not a
+   multiple of 128) goes in a call of its own so that the blocks before it keep the full-tile path */
+static int kv_update(const KvPass &p, size_t c0, size_t cw, size_t k0, size_t kw)
+{
+  if (cw == 0 || kw == 0) return ST_SUCCESS;
+  const size_t whole = cw / PB * PB;
+  int st = ST_SUCCESS;
+  if (whole)
+    st = sinterp_gemm_minus(p.ctx, p.rows_pad, whole, kw, p.Z + k0, p.ldw, p.L + c0 * p.lda + k0, p.lda, 0, p.Z + c0, p.ldw, 0);
+  if (!st && cw > whole)
+    st = sinterp_gemm_minus(p.ctx, p.rows_pad, cw - whole, kw, p.Z + k0, p.ldw, p.L + (c0 + whole) * p.lda + k0, p.lda, 0,
+                            p.Z + c0 + whole, p.ldw, 0);
+  return st;
+}
+
+static int kv_diag(const KvPass &p, size_t j0)
+{
+  const size_t lds = (size_t)(64 * TR_LD + 10 * PBLK) * sizeof(double);
+  int st = sinterp_func_lds(p.ctx, (const void *)krige_trsm128_kernel, (int)lds);
+  if (st) return st;
+  hipLaunchKernelGGL(krige_trsm128_kernel, dim3((unsigned)(p.rows_pad / 64)), dim3(256), lds, p.ctx->stream, p.Z, p.ldw, p.L, p.lda, p.n,
+                     j0, p.dinv, p.q);
+  return ST_SUCCESS;
+}
+
+/* columns [j0, j0 + w) given that everything left of j0 has been applied: halve (on a 128-column boundary) down to
+   single blocks */
+static int kv_solve_range(const KvPass &p, size_t j0, size_t w)
+{
+  if (w <= PB) return kv_diag(p, j0);
+  size_t w1 = ((w / 2 + PB - 1) / PB) * PB;
+  if (w1 >= w) w1 = w - PB;
+  int st = kv_solve_range(p, j0, w1);
+  if (!st) st = kv_update(p, j0 + w1, w - w1, j0, w1);
+  if (!st) st = kv_solve_range(p, j0 + w1, w - w1);
+  return st;
+}
+
+/* Left-looking over panels of `panel` columns: the update of a panel reads ALL columns left of it in one product with
+   K = j0, then the panel is solved on its own.  panel = 128 (the default) is the plain left-looking recursion: one
+   update and one diagonal step per block.  Wider panels (developer switch GSL_SINTERP_KRIGE_PANEL = columns) recurse
+   inside the panel as the factorisation's chol_split does; kept for tools/krige_variance_time.py, the default is the
+   simpler scheme ("Kriging variance": what has and has not been measured). */
+static int kv_solve(const KvPass &p, size_t panel)
+{
+  for (size_t j0 = 0; j0 < p.n; j0 += panel) {
+    const size_t w = p.n - j0 < panel ? p.n - j0 : panel;
+    int st = kv_update(p, j0, w, 0, j0);
+    if (!st) st = kv_solve_range(p, j0, w);
+    if (st) return st;
+  }
+  return ST_SUCCESS;
+}
+
+extern "C" size_t gsl_sinterp_hip_krige_variance_work(size_t n, size_t chunk)
+{
+  /* Z (rows padded to KV_RP, pitch n rounded up to 128) + q + two words to align Z to 16 bytes */
+  return kv_round_up(chunk ? chunk : 1, KV_RP) * (kv_round_up(n, PB) + 1) + 2;
+}
+
+extern "C" int gsl_sinterp_hip_krige_variance_prepare(gsl_sinterp_hip_ctx *ctx, size_t n, const double *d_llt, size_t lda,
+                                                      double *d_b, double *d_dinv, double *h_denom)
+{
+  REQUIRE(ctx, ctx != NULL, ST_EFAULT);
+  HIP_OK(ctx, hipSetDevice(ctx->device));
+  EXCLUSIVE_SECTION(ctx);
+  REQUIRE(ctx, lda >= n, ST_EINVAL);
+  REQUIRE(ctx, h_denom != NULL && (n == 0 || (d_llt && d_b && d_dinv)), ST_EFAULT);
+  *h_denom = 0.0;
+  if (n == 0) return ST_SUCCESS;
+  hipLaunchKernelGGL(krige_ones_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, d_b, n);
+  hipLaunchKernelGGL(krige_inv32_kernel, dim3((unsigned)((n + CB - 1) / CB)), dim3(64), 0, ctx->stream, d_llt, lda, n, d_dinv);
+  LAUNCH_CHECK(ctx);
+  int st = sinterp_cholesky_svx_multi(ctx, n, d_llt, lda, d_b, n, 1);             /* b = (L L^T)^-1 1 */
+  if (st) return st;
+  double *h_b = (double *)malloc(n * sizeof(double));
+  if (!h_b) return sinterp_fail(ctx, ST_ENOMEM, "krige_variance_prepare: host buffer", hipSuccess, __FILE__, __LINE__);
+  hipError_t e = hipStreamSynchronize(ctx->stream);
+  if (e == hipSuccess) e = hipMemcpy(h_b, d_b, n * sizeof(double), hipMemcpyDeviceToHost);
+  if (e != hipSuccess) { free(h_b); return sinterp_fail(ctx, ST_EFAILED, "krige_variance_prepare: read back", e, __FILE__, __LINE__); }
+  double sum = 0.0;
+  for (size_t i = 0; i < n; i++) sum += h_b[i];                                   /* once per model: fixed order on the host */
+  free(h_b);
+  *h_denom = sum;
+  if (!(sum != 0.0) || sum != sum)
+    return sinterp_fail(ctx, ST_EDOM, "krige_variance_prepare: 1^T K^-1 1 = 0 (degenerate covariance matrix)", hipSuccess, __FILE__, __LINE__);
+  return ST_SUCCESS;
+}
+
+extern "C" int gsl_sinterp_hip_krige_variance(gsl_sinterp_hip_ctx *ctx, int kind, double eps, const double *d_x, size_t n, int dim,
+                                              size_t xtda, const double *d_llt, size_t lda, const double *d_b, const double *d_dinv,
+                                              double denom, const double *d_y, size_t m, size_t ytda, double *d_var, double *d_work,
+                                              size_t chunk)
+{
+  REQUIRE(ctx, ctx != NULL, ST_EFAULT);
+  HIP_OK(ctx, hipSetDevice(ctx->device));
+  EXCLUSIVE_SECTION(ctx);                          /* the stream-K updates spin on sibling workgroups */
+  REQUIRE(ctx, dim >= 1 && dim <= 3 && xtda >= (size_t)dim && ytda >= (size_t)dim && lda >= n && chunk >= 1, ST_EINVAL);
+  REQUIRE(ctx, kind == GSL_SINTERP_RBF_GAUSSIAN || kind == GSL_SINTERP_RBF_WENDLAND, ST_EINVAL);   /* covariances: positive definite kernels */
+  REQUIRE(ctx, (m == 0 || n == 0) || (d_x && d_llt && d_b && d_dinv && d_y && d_var && d_work), ST_EFAULT);
+  if (m == 0 || n == 0) return ST_SUCCESS;
+  if (chunk > ((size_t)1 << 19)) chunk = (size_t)1 << 19;      /* rows / 16 is a grid dimension */
+  /* developer switch (tools/krige_variance_time.py): the panel width of the recursion, read once */
+  static const size_t panel = [] {
+    const char *e = getenv("GSL_SINTERP_KRIGE_PANEL");
+    const long v = e ? atol(e) : 0;
+    return v >= PB ? (size_t)v / PB * PB : (size_t)PB;
+  }();
+  int st = sinterp_streamk_prepare(ctx);
+  if (st) return st;
+  const double *tbl = NULL;
+  st = sinterp_rbf_exp2_table(ctx, &tbl);
+  if (st) return st;
+  const double coef = kind == GSL_SINTERP_RBF_WENDLAND ? eps : -(eps * eps) * 1.44269504088896340735992;   /* rbf.hip: kernel_coef */
+  /* a = b^T k(y) for every target at once, parked in d_var until the combine of its pass */
+  st = gsl_sinterp_hip_rbf_eval(ctx, kind, eps, d_x, n, dim, xtda, d_b, d_y, m, ytda, d_var);
+  if (st) return st;
+  KvPass p;
+  p.ctx = ctx; p.ldw = kv_round_up(n, PB); p.L = d_llt; p.lda = lda; p.n = n; p.dinv = d_dinv;
+  p.Z = (double *)(((uintptr_t)d_work + 15) & ~(uintptr_t)15);
+  const size_t chunk_pad = kv_round_up(chunk, KV_RP);
+  p.q = p.Z + chunk_pad * p.ldw;
+  for (size_t k0 = 0; k0 < m; k0 += chunk) {
+    const size_t rows = m - k0 < chunk ? m - k0 : chunk;
+    p.rows_pad = kv_round_up(rows, KV_RP);
+    if (kind == GSL_SINTERP_RBF_WENDLAND)
+      launch_cross_fill<GSL_SINTERP_RBF_WENDLAND>(ctx, coef, tbl, d_x, n, dim, xtda, d_y + k0 * ytda, rows, ytda, p.Z, p.ldw, p.rows_pad, p.q);
+    else
+      launch_cross_fill<GSL_SINTERP_RBF_GAUSSIAN>(ctx, coef, tbl, d_x, n, dim, xtda, d_y + k0 * ytda, rows, ytda, p.Z, p.ldw, p.rows_pad, p.q);
+    LAUNCH_CHECK(ctx);
+    st = kv_solve(p, panel);
+    if (st) return st;
+    hipLaunchKernelGGL(krige_combine_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, ctx->stream, d_var + k0, (const double *)p.q,
+                       rows, denom);
+    LAUNCH_CHECK(ctx);
+  }
+  return ST_SUCCESS;
+}
+
+extern "C" int gsl_sinterp_hip_krige_variance_clamp(gsl_sinterp_hip_ctx *ctx, double *d_v, size_t m)
+{
+  REQUIRE(ctx, ctx != NULL, ST_EFAULT);
+  HIP_OK(ctx, hipSetDevice(ctx->device));
+  REQUIRE(ctx, m == 0 || d_v, ST_EFAULT);
+  if (m == 0) return ST_SUCCESS;
+  size_t blocks = (m + 255) / 256;
+  if (blocks > 4096) blocks = 4096;
+  hipLaunchKernelGGL(clamp_nonnegative_kernel, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, d_v, m);
+  LAUNCH_CHECK(ctx);
+  return ST_SUCCESS;
+}

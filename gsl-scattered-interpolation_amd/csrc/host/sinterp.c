@@ -791,6 +791,13 @@ typedef struct {
   int affine;
   double poly[4];
   chunk_set cs;                /* single-device: pipelined host batches */
+  /* kriging variance (gsl_sinterp_set_variance): the Cholesky factor of K kept from the init on member 0 with what
+     gsl_sinterp_hip_krige_variance_prepare derives from it, and a grow-only workspace for the evaluation.
+     var_state: 0 nothing kept (not asked for), 1 ready, 2 the init took route 8 (no factor), 3 restored from a checkpoint */
+  int var_state;
+  double *d_llt, *d_b, *d_dinv, *d_vwork;
+  size_t llt_lda, vwork_doubles;
+  double denom;
 } rbf_state;
 
 static unsigned long long next_model_id(void)
@@ -822,8 +829,20 @@ static void *krige_alloc(size_t dim, size_t size)
   return st;
 }
 
+/* the kept factor and everything derived from it (member 0's context must still be alive) */
+static void rbf_release_variance(rbf_state *st)
+{
+  if (st->ctx) {
+    gsl_sinterp_hip_free(st->ctx, st->d_llt); gsl_sinterp_hip_free(st->ctx, st->d_b);
+    gsl_sinterp_hip_free(st->ctx, st->d_dinv); gsl_sinterp_hip_free(st->ctx, st->d_vwork);
+  }
+  st->d_llt = st->d_b = st->d_dinv = st->d_vwork = NULL;
+  st->llt_lda = st->vwork_doubles = 0; st->denom = 0.0; st->var_state = 0;
+}
+
 static void rbf_release_devices(rbf_state *st)
 {
+  rbf_release_variance(st);
   if (st->ss.grp) {
     for (int r = 0; r < st->ss.n; r++) {
       gsl_sinterp_hip_free(gsl_sinterp_hip_group_ctx(st->ss.grp, r), st->m_model[r]);
@@ -853,6 +872,7 @@ static int rbf_init(gsl_sinterp *interp, const gsl_matrix *x, const gsl_vector *
   rbf_state *st = (rbf_state *)interp->state;
   const size_t n = st->n, dim = st->dim;
   const int nd = interp->n_devices > 1 ? interp->n_devices : 1;
+  rbf_release_variance(st);                             /* the factor of the previous model, if one was kept */
   int s = rbf_prepare_devices(interp, st);
   if (s) return s;
   gsl_sinterp_hip_ctx *c = st->ctx;
@@ -888,6 +908,18 @@ static int rbf_init(gsl_sinterp *interp, const gsl_matrix *x, const gsl_vector *
     s = gsl_sinterp_hip_rbf_solve_ex(c, st->kind, st->eps, st->d_x, n, (int)dim, dim, d_phi, lda, st->d_w, interp->solver,
                                      interp->want_rcond ? &rcond : NULL, &route);
   interp->rcond = rcond; interp->route = route;
+  /* kriging variance asked for: route 7 left L in the lower triangle of d_phi -- keep it (N^2 doubles, member 0 only)
+     with b = K^-1 1, the inverted diagonal blocks and 1^T b; route 8 has no Cholesky factor to keep */
+  if (!s && st->krige && interp->want_variance) {
+    if (route == 7) {
+      s = gsl_sinterp_hip_malloc(c, (void **)&st->d_b, n * sizeof(double));
+      if (!s) s = gsl_sinterp_hip_malloc(c, (void **)&st->d_dinv, ((n + 31) / 32) * 1024 * sizeof(double));
+      if (!s) s = gsl_sinterp_hip_krige_variance_prepare(c, n, d_phi, lda, st->d_b, st->d_dinv, &st->denom);
+      if (!s) { st->d_llt = d_phi; st->llt_lda = lda; st->var_state = 1; d_phi = NULL; }
+    } else {
+      st->var_state = 2;
+    }
+  }
   /* replicate the solved model: ONE broadcast of the weight vector (+ centres) */
   if (!s && st->ss.grp) s = gsl_sinterp_hip_group_broadcast(st->ss.grp, (void *const *)st->m_model, model_bytes);
   if (!s) s = gsl_sinterp_hip_sync(c);
@@ -895,6 +927,7 @@ static int rbf_init(gsl_sinterp *interp, const gsl_matrix *x, const gsl_vector *
     for (int r = 1; r < nd; r++) { int s2 = gsl_sinterp_hip_sync(gsl_sinterp_hip_group_ctx(st->ss.grp, r)); if (!s) s = s2; }
   gsl_sinterp_hip_free(c, d_phi);
   free(h_x); free(h_f);
+  if (s) rbf_release_variance(st);
   if (s == GSL_EDOM) GSL_ERROR("gsl_sinterp_init: kernel matrix is not positive definite", GSL_EDOM);
   HIP_TRY(s, c);
   return GSL_SUCCESS;
@@ -1245,6 +1278,94 @@ int gsl_sinterp_set_nugget(gsl_sinterp *interp, double nugget)
   if (!(nugget >= 0.0)) GSL_ERROR("gsl_sinterp_set_nugget: the nugget must be >= 0", GSL_EDOM);
   interp->nugget = nugget;
   return GSL_SUCCESS;
+}
+
+int gsl_sinterp_set_variance(gsl_sinterp *interp, int want)
+{
+  if (!interp) GSL_ERROR("gsl_sinterp_set_variance: null interpolant", GSL_EFAULT);
+  if (interp->type != &krige_type) GSL_ERROR("gsl_sinterp_set_variance: kriging interpolants only", GSL_EINVAL);
+  interp->want_variance = want != 0;
+  return GSL_SUCCESS;
+}
+
+/* whether variances can be evaluated, as a status (the table of include/gsl_sinterp.h) */
+static int variance_status(const gsl_sinterp *interp)
+{
+  if (interp->type != &krige_type) GSL_ERROR("gsl_sinterp_eval_variance: kriging interpolants only", GSL_EINVAL);
+  const rbf_state *st = (const rbf_state *)interp->state;
+  if (!st->d_w) GSL_ERROR("gsl_sinterp_eval_variance: interpolant not initialised", GSL_EINVAL);
+  if (st->var_state == 3)
+    GSL_ERROR("gsl_sinterp_eval_variance: the interpolant was restored by gsl_sinterp_fread; a checkpoint carries no factor", GSL_EINVAL);
+  if (st->var_state == 2)
+    GSL_ERROR("gsl_sinterp_eval_variance: the init took the pivoted LDL^T route (8), which keeps no Cholesky factor", GSL_EUNSUP);
+  if (st->var_state != 1)
+    GSL_ERROR("gsl_sinterp_eval_variance: initialised without gsl_sinterp_set_variance", GSL_EINVAL);
+  return GSL_SUCCESS;
+}
+
+int gsl_sinterp_eval_variance_resident(const gsl_sinterp *interp, const double *d_y, size_t m, size_t ytda, double *d_var)
+{
+  if (!interp) GSL_ERROR("gsl_sinterp_eval_variance: null interpolant", GSL_EFAULT);
+  int vs = variance_status(interp);
+  if (vs) return vs;
+  rbf_state *st = (rbf_state *)interp->state;           /* the workspace is a grow-only cache inside the state */
+  if (m == 0) return GSL_SUCCESS;
+  if (!d_y || !d_var) GSL_ERROR("gsl_sinterp_eval_variance: null argument", GSL_EFAULT);
+  size_t chunk = (m + 63) / 64 * 64;
+  if (chunk > 8192) chunk = 8192;
+  const size_t need = gsl_sinterp_hip_krige_variance_work(st->n, chunk);
+  if (need > st->vwork_doubles) {
+    gsl_sinterp_hip_free(st->ctx, st->d_vwork);
+    st->d_vwork = NULL; st->vwork_doubles = 0;
+    HIP_TRY(gsl_sinterp_hip_malloc(st->ctx, (void **)&st->d_vwork, need * sizeof(double)), st->ctx);
+    st->vwork_doubles = need;
+  }
+  /* the factor lives on member 0, which evaluates every target (as gsl_sinterp_eval_resident does) */
+  HIP_TRY(gsl_sinterp_hip_krige_variance(st->ctx, st->kind, st->eps, st->d_x, st->n, (int)st->dim, st->dim, st->d_llt, st->llt_lda,
+                                         st->d_b, st->d_dinv, st->denom, d_y, m, ytda, d_var, st->d_vwork, chunk), st->ctx);
+  HIP_TRY(gsl_sinterp_hip_krige_variance_clamp(st->ctx, d_var, m), st->ctx);   /* rounding residue where sigma^2 = 0 */
+  return GSL_SUCCESS;
+}
+
+int gsl_sinterp_eval_variance_many(const gsl_sinterp *interp, const gsl_matrix *y, gsl_vector *var)
+{
+  if (!interp || !y || !var) GSL_ERROR("gsl_sinterp_eval_variance_many: null argument", GSL_EFAULT);
+  if (y->size2 != interp->dim) GSL_ERROR("target matrix must have dim columns", GSL_EBADLEN);
+  if (var->size != y->size1) GSL_ERROR("output length must equal the number of targets", GSL_EBADLEN);
+  const size_t m = y->size1, dim = interp->dim;
+  int vs = variance_status(interp);
+  if (vs || m == 0) return vs;
+  const rbf_state *st = (const rbf_state *)interp->state;
+  gsl_sinterp_hip_ctx *c = st->ctx;
+  double *h = (double *)malloc(m * dim * sizeof(double)), *d_y = NULL, *d_v = NULL;
+  if (!h) GSL_ERROR("gsl_sinterp_eval_variance_many: out of memory", GSL_ENOMEM);
+  for (size_t k = 0; k < m; k++)
+    for (size_t a = 0; a < dim; a++) h[k * dim + a] = y->data[k * y->tda + a];
+  int s = gsl_sinterp_hip_malloc(c, (void **)&d_y, m * dim * sizeof(double));
+  if (!s) s = gsl_sinterp_hip_malloc(c, (void **)&d_v, m * sizeof(double));
+  if (!s) s = gsl_sinterp_hip_h2d(c, d_y, h, m * dim * sizeof(double));
+  int es = GSL_SUCCESS;
+  if (!s) es = gsl_sinterp_eval_variance_resident(interp, d_y, m, dim, d_v);
+  if (!s && !es) s = gsl_sinterp_hip_d2h(c, h, d_v, m * sizeof(double));
+  if (!s && !es) for (size_t k = 0; k < m; k++) gsl_vector_set(var, k, h[k]);
+  gsl_sinterp_hip_free(c, d_y); gsl_sinterp_hip_free(c, d_v);
+  free(h);
+  HIP_TRY(s, c);
+  return es;
+}
+
+int gsl_sinterp_eval_variance_e(const gsl_sinterp *interp, const gsl_vector *y, double *var)
+{
+  if (!interp || !y || !var) GSL_ERROR("gsl_sinterp_eval_variance_e: null argument", GSL_EFAULT);
+  *var = GSL_NAN;
+  if (y->size != interp->dim) GSL_ERROR("target must have dim components", GSL_EBADLEN);
+  double yy[3], out = GSL_NAN;
+  for (size_t c = 0; c < interp->dim; c++) yy[c] = gsl_vector_get(y, c);
+  gsl_matrix_view Y = gsl_matrix_view_array(yy, 1, interp->dim);
+  gsl_vector_view V = gsl_vector_view_array(&out, 1);
+  int st = gsl_sinterp_eval_variance_many(interp, &Y.matrix, &V.vector);
+  if (st == GSL_SUCCESS) *var = out;
+  return st;
 }
 
 int gsl_sinterp_poly(const gsl_sinterp *interp, gsl_vector *c)
@@ -1598,8 +1719,10 @@ int gsl_sinterp_fread(FILE *stream, gsl_sinterp *interp)
   if (fread(h, sizeof(double), cnt, stream) != cnt) { free(h); GSL_ERROR("fread failed", GSL_EFAILED); }
   double poly[4] = {0.0, 0.0, 0.0, 0.0};
   if (st->affine && fread(poly, sizeof(double), 4, stream) != 4) { free(h); GSL_ERROR("fread failed", GSL_EFAILED); }
+  rbf_release_variance(st);                             /* a factor kept by an earlier init belongs to another model */
   int s = rbf_prepare_devices(interp, st);
   if (s) { free(h); return s; }
+  st->var_state = 3;                                    /* the checkpoint carries no factor */
   st->eps = eps;
   if (st->krige) memcpy(&st->mean, &flags, sizeof st->mean);
   if (st->affine) memcpy(st->poly, poly, sizeof poly);

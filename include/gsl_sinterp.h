@@ -269,6 +269,7 @@ struct gsl_sinterp_struct {
   double rcond;      /* the estimate of the last init, NaN when none was made                */
   int route;         /* solver route the last init took (gsl_sinterp_hip_rbf_solve_ex)       */
   double nugget;     /* kriging: added to the diagonal of the covariance matrix (>= 0, default 0) */
+  int want_variance; /* kriging: the next init keeps the Cholesky factor for gsl_sinterp_eval_variance_* (default 0) */
 };
 
 extern const gsl_sinterp_type *gsl_sinterp_rbf_gaussian;
@@ -304,6 +305,18 @@ int gsl_sinterp_set_shape(gsl_sinterp *interp, double eps);
    with gsl_sinterp_rcond (GSL_EINVAL when none is available). */
 int gsl_sinterp_set_nugget(gsl_sinterp *interp, double nugget);     /* kriging type only (GSL_EINVAL otherwise) */
 int gsl_sinterp_mean(const gsl_sinterp *interp, double *mean);     /* the estimated mean mu of an initialised kriging interpolant */
+/* Kriging variance sigma^2(y) = C(0) - k^T K^-1 k + (1 - 1^T K^-1 k)^2 / (1^T K^-1 1) of the underlying field (the
+   nugget is measurement noise): 0 at the data sites when nugget = 0, 1 + 1/(1^T K^-1 1) far from every site.
+   gsl_sinterp_set_variance(interp, 1) BEFORE gsl_sinterp_init makes the init keep the Cholesky factor of K on the
+   (first) device -- N^2 doubles for as long as the model lives, which is why it is opt-in; M targets then cost
+   M N^2 flops.  Negative rounding residue is clamped to 0 (sqrt is safe).  GSL_EINVAL: not a kriging interpolant, not
+   initialised, initialised without set_variance, or restored by gsl_sinterp_fread (a checkpoint carries no factor);
+   GSL_EUNSUP: the init took the pivoted LDL^T route 8 (covariance matrix only semi-definite).  With a device list the
+   factor lives on the first device, which evaluates every target. */
+int gsl_sinterp_set_variance(gsl_sinterp *interp, int want);            /* kriging type only (GSL_EINVAL otherwise); before init */
+int gsl_sinterp_eval_variance_e(const gsl_sinterp *interp, const gsl_vector *y, double *var);
+int gsl_sinterp_eval_variance_many(const gsl_sinterp *interp, const gsl_matrix *y, gsl_vector *var);
+int gsl_sinterp_eval_variance_resident(const gsl_sinterp *interp, const double *d_y, size_t m, size_t ytda, double *d_var);
 int gsl_sinterp_poly(const gsl_sinterp *interp, gsl_vector *c);    /* c_0 .. c_dim of an initialised gsl_sinterp_rbf_tps_affine interpolant */
 int gsl_sinterp_set_solver(gsl_sinterp *interp, int solver);
 int gsl_sinterp_set_rcond(gsl_sinterp *interp, int want);

@@ -265,6 +265,28 @@ int gsl_sinterp_hip_krige_eval(gsl_sinterp_hip_ctx *ctx, int kind, double eps, d
                                int dim, size_t xtda, const double *d_w, const double *d_y, size_t m, size_t ytda,
                                double *d_s, unsigned long long model_id);
 
+/* Kriging variance at the targets from the factor K = Phi + nugget I = L L^T that krige_solve (route 7),
+   cholesky_decomp1 or cholesky_factor_solve leave in the lower triangle of their matrix:
+       sigma^2(y) = 1 - |L^-1 k(y)|^2 + (1 - b^T k(y))^2 / (1^T b),    k(y)_j = phi(|y - x_j|),  b = K^-1 1
+   -- the variance of the underlying field (the nugget is measurement noise; sill phi(0) = 1): zero at the data sites
+   when nugget = 0, 1 + 1/(1^T b) far from every site.  Cost: the N^2 doubles of the factor stay resident, M N^2 flops
+   (fp64 MFMA GEMM) for M targets.  Only the lower triangle of d_llt, diagonal included, is read. */
+/* from a factor left by cholesky_decomp1 / factor_solve (lower triangle = L): b = K^-1 1 -> d_b[n], the inverted
+   32x32 diagonal blocks -> d_dinv[ceil(n/32) * 1024], *h_denom = 1^T b.  Synchronises.  GSL_EDOM when denom is 0 or NaN. */
+int gsl_sinterp_hip_krige_variance_prepare(gsl_sinterp_hip_ctx *ctx, size_t n, const double *d_llt, size_t lda,
+                                           double *d_b, double *d_dinv, double *h_denom);
+/* doubles of workspace for `chunk` targets per pass */
+size_t gsl_sinterp_hip_krige_variance_work(size_t n, size_t chunk);
+/* d_var[k] = sigma^2(y_k), k < m; asynchronous on the context's stream; chunk >= 1 rows of d_work per pass.  d_work is
+   the caller's (gsl_sinterp_hip_krige_variance_work doubles): the sweep and the GEMM called inside use the context's own
+   buffers.  kind: GAUSSIAN or WENDLAND.  Not clamped: where sigma^2 = 0 the result is rounding residue of either sign. */
+int gsl_sinterp_hip_krige_variance(gsl_sinterp_hip_ctx *ctx, int kind, double eps, const double *d_x, size_t n, int dim, size_t xtda,
+                                   const double *d_llt, size_t lda, const double *d_b, const double *d_dinv,
+                                   double denom, const double *d_y, size_t m, size_t ytda, double *d_var,
+                                   double *d_work, size_t chunk);
+/* d_v[k] < 0 -> 0 for k < m (NaN stays NaN); asynchronous.  The facade's variance entries apply it. */
+int gsl_sinterp_hip_krige_variance_clamp(gsl_sinterp_hip_ctx *ctx, double *d_v, size_t m);
+
 /* Level-3 building block of both factorisations, exposed for tests and roofline
    measurement (role of gsl_blas_dgemm / dsyrk, blas/blas.c:1334,1649):
      C[m x n] -= A[m x k] * B^T  (b_is_kn = 0, B stored [n][k])
