@@ -137,6 +137,7 @@ SIGNATURES = {
     "gsl_sinterp_hip_rbf_solve_ex": (_i, [_vp, _i, _d, _vp, _sz, _i, _sz, _vp, _sz, _vp, _i, _pd, _pi]),
     "gsl_sinterp_hip_rbf_eval": (_i, [_vp, _i, _d, _vp, _sz, _i, _sz, _vp, _vp, _sz, _sz, _vp]),
     "gsl_sinterp_hip_rbf_eval_model": (_i, [_vp, _i, _d, _vp, _sz, _i, _sz, _vp, _vp, _sz, _sz, _vp, C.c_uint64]),
+    "gsl_sinterp_hip_rbf_eval_grad": (_i, [_vp, _i, _d, _pd, _vp, _sz, _i, _sz, _vp, _vp, _sz, _sz, _vp, _vp, _sz, C.c_uint64]),
     "gsl_sinterp_hip_ctx_device": (_i, [_vp]),
     "gsl_sinterp_hip_rbf_solve": (_i, [_vp, _i, _d, _vp, _sz, _i, _sz, _vp, _sz, _vp, _pi]),
     "gsl_sinterp_hip_gemm_minus": (_i, [_vp, _sz, _sz, _sz, _vp, _sz, _vp, _sz, _i, _vp, _sz, _i]),
@@ -244,6 +245,9 @@ SIGNATURES = {
     "gsl_sinterp_eval_variance_e": (_i, [C.POINTER(gsl_sinterp), _pv, _pd]),
     "gsl_sinterp_eval_variance_many": (_i, [C.POINTER(gsl_sinterp), _pm, _pv]),
     "gsl_sinterp_eval_variance_resident": (_i, [C.POINTER(gsl_sinterp), _vp, _sz, _sz, _vp]),
+    "gsl_sinterp_eval_grad_e": (_i, [C.POINTER(gsl_sinterp), _pv, _pd, _pv]),
+    "gsl_sinterp_eval_grad_many": (_i, [C.POINTER(gsl_sinterp), _pm, _pv, _pm]),
+    "gsl_sinterp_eval_grad_resident": (_i, [C.POINTER(gsl_sinterp), _vp, _sz, _sz, _vp, _vp, _sz]),
     "gsl_sinterp_set_rcond": (_i, [C.POINTER(gsl_sinterp), _i]),
     "gsl_sinterp_rcond": (_i, [C.POINTER(gsl_sinterp), _pd]),
     "gsl_sinterp_route": (_i, [C.POINTER(gsl_sinterp)]),
@@ -432,6 +436,14 @@ class HipContext:
         """model_id != 0: the caller vouches that (d_x, d_w) do not change while it uses this id, so the sweep's
         per-model preprocessing is cached in the context (gsl_sinterp_hip_rbf_eval_model)"""
         check(lib().gsl_sinterp_hip_rbf_eval_model(self._h, kind, eps, d_x, n, dim, xtda, d_w, d_y, m, ytda, d_s, model_id), self._h)
+
+    def rbf_eval_grad(self, kind, eps, d_x, n, dim, xtda, d_w, d_y, m, ytda, d_s, d_g, gtda, tail=None, model_id=0):
+        """value (d_s, may be None) + gradient (row k at d_g + 8 k gtda) from one sweep; tail: None or dim + 1 numbers
+        {c_0, c_1 .. c_dim} of an affine tail.  Returns the status."""
+        t = None if tail is None else np.ascontiguousarray(tail, dtype=np.float64)
+        assert t is None or t.size >= dim + 1
+        return lib().gsl_sinterp_hip_rbf_eval_grad(self._h, kind, eps, None if t is None else t.ctypes.data_as(_pd), d_x, n, dim, xtda,
+                                                   d_w, d_y, m, ytda, d_s, d_g, gtda, model_id)
 
     def device(self):
         return lib().gsl_sinterp_hip_ctx_device(self._h)
@@ -900,6 +912,26 @@ class Sinterp:
 
     def eval_variance_resident(self, d_y, m, ytda, d_var):
         return lib().gsl_sinterp_eval_variance_resident(self._p, d_y, m, ytda, d_var)
+
+    def eval_grad_e(self, y):
+        """(status, s, g): value and gradient (dim entries) at one target; NaN on failure"""
+        out = C.c_double(0)
+        g = np.empty(self._p.contents.dim, dtype=np.float64)
+        st = lib().gsl_sinterp_eval_grad_e(self._p, C.byref(as_vector(np.ascontiguousarray(y, dtype=np.float64))), C.byref(out),
+                                           C.byref(as_vector(g)))
+        return st, out.value, g
+
+    def eval_grad_many(self, y, want_value=True, out=None):
+        """(status, s or None, g): values and the m x dim gradient at the rows of y; out = (s or None, g) preallocated"""
+        m = y.shape[0]
+        s = (np.empty(m, dtype=np.float64) if out is None else out[0]) if want_value else None
+        g = np.empty((m, self._p.contents.dim), dtype=np.float64) if out is None else out[1]
+        st = lib().gsl_sinterp_eval_grad_many(self._p, C.byref(as_matrix(y)), C.byref(as_vector(s)) if want_value else None,
+                                              C.byref(as_matrix(g)))
+        return st, s, g
+
+    def eval_grad_resident(self, d_y, m, ytda, d_s, d_g, gtda):
+        return lib().gsl_sinterp_eval_grad_resident(self._p, d_y, m, ytda, d_s, d_g, gtda)
 
     def poly(self):
         c = np.zeros(self._p.contents.dim + 1, dtype=np.float64)

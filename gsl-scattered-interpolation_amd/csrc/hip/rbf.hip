@@ -436,14 +436,20 @@ rbf_eval_gauss_cull_kernel(double coef, const double *__restrict__ xs, size_t n,
 #endif
 }
 
-template <int KIND, int TPT>
-static int launch_eval_cull(gsl_sinterp_hip_ctx *ctx, double coef, const double *d_x, size_t n, int dim, size_t xtda, const double *d_w,
-                            const double *d_y, size_t m, size_t ytda, double *d_s, const int *d_perm, const unsigned *d_omap,
-                            unsigned long long model_id)
+/* The packed centres of the culled sweeps: Morton order, {x, w} records, one bounding box per tile of ct centres.  They
+   depend on the model only: reused when the caller vouches for the model (model_id != 0), whichever culled sweep -- value
+   or value + gradient -- packed them. */
+struct cull_model {
+  const double *xs, *tbox;
+  unsigned ntiles;
+  int ct;
+};
+
+static int cull_pack(gsl_sinterp_hip_ctx *ctx, int kind, const double *d_x, size_t n, int dim, size_t xtda, const double *d_w,
+                     unsigned long long model_id, cull_model *out)
 {
-  /* the packed centres depend on the model only: reuse them when the caller vouches for the model (model_id != 0) */
   const bool cached = model_id != 0 && ctx->cent_key.id == model_id && ctx->cent_key.x == d_x && ctx->cent_key.w == d_w &&
-                      ctx->cent_key.n == n && ctx->cent_key.xtda == xtda && ctx->cent_key.dim == dim && ctx->cent_key.kind == KIND;
+                      ctx->cent_key.n == n && ctx->cent_key.xtda == xtda && ctx->cent_key.dim == dim && ctx->cent_key.kind == kind;
   int *d_cperm = NULL;
   int st = ST_SUCCESS;
   if (!cached) {
@@ -457,30 +463,53 @@ static int launch_eval_cull(gsl_sinterp_hip_ctx *ctx, double coef, const double 
   st = sinterp_centbuf(ctx, (n * (size_t)(dim + 1) + (size_t)ntiles * 2 * dim) * sizeof(double), &buf);
   if (st) return st;
   double *xs = (double *)buf, *tbox = xs + n * (size_t)(dim + 1);
+  out->xs = xs; out->tbox = tbox; out->ntiles = ntiles; out->ct = ct;
+  if (cached) return ST_SUCCESS;
+#define PACK_LAUNCH(D, C)                                                                                                              \
+  hipLaunchKernelGGL((centre_pack_kernel<D, C>), dim3(ntiles), dim3(CT_THREADS), 0, ctx->stream, d_x, n, xtda, d_w, (const int *)d_cperm, \
+                     xs, tbox)
+  switch (dim) {
+    case 1: PACK_LAUNCH(1, 32); break;
+    case 2:
+      if (ct == 8) PACK_LAUNCH(2, 8);
+      else if (ct == 16) PACK_LAUNCH(2, 16);
+      else PACK_LAUNCH(2, 32);
+      break;
+    default: PACK_LAUNCH(3, 32); break;
+  }
+#undef PACK_LAUNCH
+  LAUNCH_CHECK(ctx);
+  if (model_id != 0) {
+    ctx->cent_key.id = model_id; ctx->cent_key.x = d_x; ctx->cent_key.w = d_w; ctx->cent_key.n = n; ctx->cent_key.xtda = xtda;
+    ctx->cent_key.dim = dim; ctx->cent_key.kind = kind;
+  }
+  return ST_SUCCESS;
+}
+
+template <int KIND, int TPT>
+static int launch_eval_cull(gsl_sinterp_hip_ctx *ctx, double coef, const double *d_x, size_t n, int dim, size_t xtda, const double *d_w,
+                            const double *d_y, size_t m, size_t ytda, double *d_s, const int *d_perm, const unsigned *d_omap,
+                            unsigned long long model_id)
+{
+  cull_model cm;
+  int st = cull_pack(ctx, KIND, d_x, n, dim, xtda, d_w, model_id, &cm);
+  if (st) return st;
   const size_t per_block = (size_t)CULL_THREADS * TPT;
   dim3 grid((unsigned)((m + per_block - 1) / per_block));
 #define CULL_LAUNCH(D, C)                                                                                                              \
-  do {                                                                                                                                 \
-    if (!cached) hipLaunchKernelGGL((centre_pack_kernel<D, C>), dim3(ntiles), dim3(CT_THREADS), 0, ctx->stream, d_x, n, xtda, d_w,    \
-                                    (const int *)d_cperm, xs, tbox);                                                                   \
-    hipLaunchKernelGGL((rbf_eval_gauss_cull_kernel<KIND, D, TPT, C>), grid, dim3(CULL_THREADS), 0, ctx->stream, coef, (const double *)xs, \
-                       n, (const double *)tbox, ntiles, d_y, m, ytda, d_s, d_perm, d_omap);                                            \
-  } while (0)
+  hipLaunchKernelGGL((rbf_eval_gauss_cull_kernel<KIND, D, TPT, C>), grid, dim3(CULL_THREADS), 0, ctx->stream, coef, cm.xs, n, cm.tbox, \
+                     cm.ntiles, d_y, m, ytda, d_s, d_perm, d_omap)
   switch (dim) {
     case 1: CULL_LAUNCH(1, 32); break;
     case 2:
-      if (ct == 8) CULL_LAUNCH(2, 8);
-      else if (ct == 16) CULL_LAUNCH(2, 16);
+      if (cm.ct == 8) CULL_LAUNCH(2, 8);
+      else if (cm.ct == 16) CULL_LAUNCH(2, 16);
       else CULL_LAUNCH(2, 32);
       break;
     default: CULL_LAUNCH(3, 32); break;
   }
 #undef CULL_LAUNCH
   LAUNCH_CHECK(ctx);
-  if (model_id != 0 && !cached) {
-    ctx->cent_key.id = model_id; ctx->cent_key.x = d_x; ctx->cent_key.w = d_w; ctx->cent_key.n = n; ctx->cent_key.xtda = xtda;
-    ctx->cent_key.dim = dim; ctx->cent_key.kind = KIND;
-  }
   return ST_SUCCESS;
 }
 
@@ -702,4 +731,360 @@ static int rbf_eval_dispatch(gsl_sinterp_hip_ctx *ctx, int kind, double coef, co
                  : launch_eval<GSL_SINTERP_RBF_GAUSSIAN, 2>(ctx, coef, d_x, n, dim, xtda, d_w, d_y, m, ytda, d_s, d_perm, d_omap);
   return small ? launch_eval<GSL_SINTERP_RBF_TPS, 1>(ctx, coef, d_x, n, dim, xtda, d_w, d_y, m, ytda, d_s, d_perm, d_omap)
                : launch_eval<GSL_SINTERP_RBF_TPS, 2>(ctx, coef, d_x, n, dim, xtda, d_w, d_y, m, ytda, d_s, d_perm, d_omap);
+}
+
+/* ------------------------------------------------------------------------ */
+/* value + gradient sweeps:  s(y) = sum_j w_j phi(|y - x_j|)  and  grad s(y) = sum_j w_j psi(r_j^2) (y - x_j),  psi = phi'(r) / r
+   (rbf_phi.h: phi_psi_r2), from ONE pass over the centres -- the exp2 / sqrt / log of a (target, centre) pair and the
+   difference y - x_j are shared, the gradient adds one product and DIM FMAs per pair.  The kernels below are the two
+   evaluation kernels above with DIM more accumulators per target; those stay as they are.
+
+   Value.  acc = fma(w_j, phi, acc) with the value sweeps' take-criterion and order, so the value that comes with a gradient
+   has the bits gsl_sinterp_hip_rbf_eval_model returns for the same model and target.
+
+   Take-criterion.  A target takes a gradient term exactly when it takes the value term (Gaussian: term above 2^-72 of the
+   kernel maximum; Wendland: inside the support), per (target, centre) pair -- the gradient too is a function of (model,
+   target) alone, bit-reproducible across batch size and grouping.  A dropped Gaussian gradient term is
+   |w_j| 2 eps^2 r exp(-(eps r)^2) = |w_j| 2 eps t exp(-t^2) with t = eps r beyond the cut-off t_c = sqrt(72 ln 2) = 7.07, where
+   t exp(-t^2) decreases: each is below |w_j| 2 eps t_c 2^-72 < |w_j| 14.2 eps 2^-72, the dropped mass of a component below
+   N max|w| 14.2 eps 2^-72 = N max|w| eps 3e-21.
+
+   Non-finite targets.  A NaN coordinate gives NaN in the value and in every gradient component, for every kind.  The
+   Gaussian / Wendland comparisons are false for NaN, so those sweeps restore the NaN at the end exactly as the value sweeps
+   do.  The thin-plate value needs nothing: r^2 = NaN goes through log_tbl into every term, in the value sweep too, so the
+   value here is that sweep's NaN, bit for bit, and only the gradient is set.  An infinite coordinate of a Gaussian / Wendland
+   target fails the criterion for every centre: no term is taken, value and gradient are 0 (terms are SELECTED, never
+   multiplied by 0, so inf - x_j does no harm).
+
+   Target order.  Batches of >= 4096 targets of the local kinds take the one-level permutation route (sinterp_sort_targets;
+   the kernels read and write through perm) whatever the batch size: the two-level reorder's result path carries one scalar
+   per target. */
+static double rbf_grad_scale(int kind, double eps)
+{
+  if (kind == GSL_SINTERP_RBF_GAUSSIAN) return -2.0 * (eps * eps);
+  return kind == GSL_SINTERP_RBF_WENDLAND ? -20.0 * (eps * eps) : 2.0;    /* thin-plate: the centre tile holds w / 2 */
+}
+
+/* s may be NULL (gradient only); row k of g = g + k * gtda, DIM entries written */
+template <int KIND, int DIM, int TPT>
+__device__ __forceinline__ void grad_store(const size_t (&kidx)[TPT], size_t m, const double (&yy)[TPT][DIM], const double (&acc)[TPT],
+                                           const double (&gacc)[TPT][DIM], double gscale, double *__restrict__ s, double *__restrict__ g,
+                                           size_t gtda)
+{
+#pragma unroll
+  for (int t = 0; t < TPT; t++) {
+    if (kidx[t] >= m) continue;
+    const bool isn = nan_target<DIM>(yy[t]);
+    if (s) s[kidx[t]] = (KIND != GSL_SINTERP_RBF_TPS && isn) ? NAN : acc[t];
+#pragma unroll
+    for (int c = 0; c < DIM; c++) g[kidx[t] * gtda + c] = isn ? NAN : gscale * gacc[t][c];
+  }
+}
+
+template <int KIND, int DIM, int TPT>
+__global__ void __launch_bounds__(EV_THREADS)
+rbf_grad_kernel(double coef, double gscale, const double *__restrict__ x, size_t n, size_t xtda, const double *__restrict__ w,
+                const double *__restrict__ y, size_t m, size_t ytda, double *__restrict__ s, double *__restrict__ g, size_t gtda,
+                const int *__restrict__ perm)
+{
+  __shared__ double s_t0[KIND == GSL_SINTERP_RBF_GAUSSIAN ? TBL_N : 1];
+  __shared__ __attribute__((aligned(16))) double s_lt[KIND == GSL_SINTERP_RBF_TPS ? LOG_LDS : 2];
+  __shared__ double s_c[EV_TJ * (DIM + 1)];       /* per centre: x[0..DIM-1], w */
+  load_tables<LOG_COPIES>(s_t0, s_lt, KIND);
+  const double *lt_lane = s_lt + (threadIdx.x & (LOG_COPIES - 1)) * 2;
+
+  const size_t k0 = (((size_t)blockIdx.x * EV_THREADS) + threadIdx.x) * TPT;
+  size_t kidx[TPT];
+  double yy[TPT][DIM], acc[TPT], gacc[TPT][DIM];
+#pragma unroll
+  for (int t = 0; t < TPT; t++) {
+    const size_t slot = k0 + (size_t)t;
+    kidx[t] = slot < m ? (perm ? (size_t)perm[slot] : slot) : m;
+    acc[t] = 0.0;
+#pragma unroll
+    for (int c = 0; c < DIM; c++) { yy[t][c] = kidx[t] < m ? y[kidx[t] * ytda + c] : 0.0; gacc[t][c] = 0.0; }
+  }
+
+  for (size_t jt = 0; jt < n; jt += EV_TJ) {
+    const int cnt = (int)((n - jt) < (size_t)EV_TJ ? (n - jt) : (size_t)EV_TJ);
+    __syncthreads();
+    for (int e = threadIdx.x; e < cnt; e += EV_THREADS) {
+#pragma unroll
+      for (int c = 0; c < DIM; c++) s_c[e * (DIM + 1) + c] = x[(jt + e) * xtda + c];
+      s_c[e * (DIM + 1) + DIM] = (KIND == GSL_SINTERP_RBF_TPS ? 0.5 : 1.0) * w[jt + e];
+    }
+    __syncthreads();
+#pragma unroll 2
+    for (int e = 0; e < cnt; e++) {
+      double xc[DIM];
+#pragma unroll
+      for (int c = 0; c < DIM; c++) xc[c] = s_c[e * (DIM + 1) + c];
+      const double wj = s_c[e * (DIM + 1) + DIM];
+      double d[TPT][DIM], r2[TPT];
+#pragma unroll
+      for (int t = 0; t < TPT; t++) {
+        r2[t] = 0.0;
+#pragma unroll
+        for (int c = 0; c < DIM; c++) { d[t][c] = yy[t][c] - xc[c]; r2[t] = fma(d[t][c], d[t][c], r2[t]); }
+      }
+      bool take[TPT];
+#pragma unroll
+      for (int t = 0; t < TPT; t++) take[t] = true;
+      if (KIND == GSL_SINTERP_RBF_GAUSSIAN) {        /* the criterion of rbf_eval_kernel, for both sums */
+        bool need = false;
+#pragma unroll
+        for (int t = 0; t < TPT; t++) { take[t] = r2[t] * coef > -72.0; need |= take[t]; }
+        if (__builtin_amdgcn_ballot_w64(need) == 0) continue;
+      }
+      if (KIND == GSL_SINTERP_RBF_WENDLAND) {
+        bool need = false;
+#pragma unroll
+        for (int t = 0; t < TPT; t++) { take[t] = r2[t] * (coef * coef) < 1.0; need |= take[t]; }
+        if (__builtin_amdgcn_ballot_w64(need) == 0) continue;
+      }
+#pragma unroll
+      for (int t = 0; t < TPT; t++) {
+        double psi;
+        const double ph = phi_psi_r2<KIND, LOG_COPIES>(r2[t], KIND == GSL_SINTERP_RBF_TPS ? 1.0 : coef, s_t0, lt_lane, &psi);
+        const double a = fma(wj, ph, acc[t]);
+        const double p = wj * psi;                   /* a product of its own: the value's FMA is untouched */
+        acc[t] = take[t] ? a : acc[t];
+#pragma unroll
+        for (int c = 0; c < DIM; c++) { const double ga = fma(p, d[t][c], gacc[t][c]); gacc[t][c] = take[t] ? ga : gacc[t][c]; }
+      }
+    }
+  }
+  grad_store<KIND, DIM, TPT>(kidx, m, yy, acc, gacc, gscale, s, g, gtda);
+}
+
+/* rbf_eval_gauss_cull_kernel with the gradient accumulators; the packed centres are the value sweep's (cull_pack) */
+template <int KIND, int DIM, int TPT, int CT>
+__global__ void __launch_bounds__(CULL_THREADS)
+rbf_grad_cull_kernel(double coef, double gscale, const double *__restrict__ xs, size_t n, const double *__restrict__ tbox, unsigned ntiles,
+                     const double *__restrict__ y, size_t m, size_t ytda, double *__restrict__ s, double *__restrict__ g, size_t gtda,
+                     const int *__restrict__ perm)
+{
+  __shared__ double s_t0[TBL_N];
+  __shared__ __attribute__((aligned(16))) double s_c[CULL_STAGE * (DIM + 1)];
+  constexpr int NWV = CULL_THREADS / 64;
+  __shared__ double s_blo[DIM][NWV], s_bhi[DIM][NWV];
+  __shared__ unsigned long long s_mask[CULL_MAX_TILES / 64];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  for (int i = tid; i < TBL_N; i += CULL_THREADS) s_t0[i] = g_rbf_tables.exp2_frac[i];
+
+  const size_t k0 = (((size_t)blockIdx.x * CULL_THREADS) + tid) * TPT;
+  size_t kidx[TPT];
+  double yy[TPT][DIM], acc[TPT], gacc[TPT][DIM];
+#pragma unroll
+  for (int t = 0; t < TPT; t++) {
+    const size_t slot = k0 + (size_t)t;
+    kidx[t] = slot < m ? (perm ? (size_t)perm[slot] : slot) : m;
+    acc[t] = 0.0;
+#pragma unroll
+    for (int c = 0; c < DIM; c++) { yy[t][c] = kidx[t] < m ? y[kidx[t] * ytda + c] : 0.0; gacc[t][c] = 0.0; }
+  }
+  /* bounding box of this workgroup's targets */
+#pragma unroll
+  for (int c = 0; c < DIM; c++) {
+    double lo = INFINITY, hi = -INFINITY;
+#pragma unroll
+    for (int t = 0; t < TPT; t++) if (kidx[t] < m) { lo = fmin(lo, yy[t][c]); hi = fmax(hi, yy[t][c]); }
+    for (int off = 32; off > 0; off >>= 1) { lo = fmin(lo, __shfl_xor(lo, off)); hi = fmax(hi, __shfl_xor(hi, off)); }
+    if (lane == 0) { s_blo[c][wave] = lo; s_bhi[c][wave] = hi; }
+  }
+  __syncthreads();
+  double blo[DIM], bhi[DIM];
+#pragma unroll
+  for (int c = 0; c < DIM; c++) {
+    blo[c] = s_blo[c][0]; bhi[c] = s_bhi[c][0];
+#pragma unroll
+    for (int w = 1; w < NWV; w++) { blo[c] = fmin(blo[c], s_blo[c][w]); bhi[c] = fmax(bhi[c], s_bhi[c][w]); }
+  }
+  /* tiles within the cut-off of the box: one bit per tile */
+  const unsigned nmask = (ntiles + 63) / 64;
+  for (unsigned base = 0; base < ntiles; base += CULL_THREADS) {
+    const unsigned t = base + tid;
+    bool keep = false;
+    if (t < ntiles) {
+      double d2 = 0.0;
+#pragma unroll
+      for (int c = 0; c < DIM; c++) {
+        const double tl = tbox[(size_t)t * (2 * DIM) + 2 * c], th = tbox[(size_t)t * (2 * DIM) + 2 * c + 1];
+        const double gap = fmax(0.0, fmax(tl - bhi[c], blo[c] - th));
+        d2 = fma(gap, gap, d2);
+      }
+      keep = KIND == GSL_SINTERP_RBF_GAUSSIAN ? d2 * coef > -72.0 : d2 * (coef * coef) < 1.0;
+    }
+    const unsigned long long b = __builtin_amdgcn_ballot_w64(keep);
+    if (lane == 0 && (base / 64 + wave) < nmask) s_mask[base / 64 + wave] = b;
+  }
+  __syncthreads();
+
+  /* the kept tiles, ascending, CULL_STAGE centres per LDS stage */
+  unsigned mi = 0;
+  unsigned long long mask = nmask ? s_mask[0] : 0ULL;
+  for (;;) {
+    int cnt = 0;
+    __syncthreads();                                       /* the previous stage has been consumed */
+    while (cnt + CT <= CULL_STAGE) {
+      while (!mask && mi + 1 < nmask) mask = s_mask[++mi];
+      if (!mask) break;
+      const unsigned t = mi * 64 + (unsigned)__builtin_ctzll(mask);
+      mask &= mask - 1;
+      const size_t c0 = (size_t)t * CT;
+      const int tc = (int)((n - c0) < (size_t)CT ? (n - c0) : (size_t)CT);
+      for (int e = tid; e < tc * (DIM + 1); e += CULL_THREADS) s_c[cnt * (DIM + 1) + e] = xs[c0 * (DIM + 1) + e];
+      cnt += tc;
+    }
+    if (cnt == 0) break;
+    __syncthreads();
+#pragma unroll 2
+    for (int e = 0; e < cnt; e++) {
+      double xc[DIM];
+#pragma unroll
+      for (int c = 0; c < DIM; c++) xc[c] = s_c[e * (DIM + 1) + c];
+      const double wj = s_c[e * (DIM + 1) + DIM];
+      double d[TPT][DIM], r2[TPT];
+      bool take[TPT], need = false;
+#pragma unroll
+      for (int tt = 0; tt < TPT; tt++) {
+        r2[tt] = 0.0;
+#pragma unroll
+        for (int c = 0; c < DIM; c++) { d[tt][c] = yy[tt][c] - xc[c]; r2[tt] = fma(d[tt][c], d[tt][c], r2[tt]); }
+        take[tt] = KIND == GSL_SINTERP_RBF_GAUSSIAN ? r2[tt] * coef > -72.0 : r2[tt] * (coef * coef) < 1.0;
+        need |= take[tt];
+      }
+      if (__builtin_amdgcn_ballot_w64(need) == 0) continue;
+#pragma unroll
+      for (int tt = 0; tt < TPT; tt++) {
+        double psi;
+        const double ph = phi_psi_r2<KIND, 1>(r2[tt], coef, s_t0, (const double *)NULL, &psi);
+        const double a = fma(wj, ph, acc[tt]);
+        const double p = wj * psi;
+        acc[tt] = take[tt] ? a : acc[tt];
+#pragma unroll
+        for (int c = 0; c < DIM; c++) { const double ga = fma(p, d[tt][c], gacc[tt][c]); gacc[tt][c] = take[tt] ? ga : gacc[tt][c]; }
+      }
+    }
+  }
+  grad_store<KIND, DIM, TPT>(kidx, m, yy, acc, gacc, gscale, s, g, gtda);
+}
+
+/* s[k] += c_0 + sum_a c_a y[k][a] (the operations of add_poly_kernel / add_const_kernel in solve.hip: the same bits) and
+   g[k][a] += c_a; linear = 0: c_1 .. c_dim are all zero (kriging's mean), only c_0 is added */
+__global__ void __launch_bounds__(256)
+grad_tail_kernel(double *__restrict__ s, double *__restrict__ g, size_t gtda, size_t m, const double *__restrict__ y, size_t ytda, int dim,
+                 double c0, double c1, double c2, double c3, int linear)
+{
+  const size_t stride = (size_t)gridDim.x * blockDim.x;
+  for (size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x; k < m; k += stride) {
+    if (s && !linear) s[k] = s[k] + c0;
+    if (!linear) continue;
+    if (s) {
+      double t = fma(c1, y[k * ytda], c0);
+      if (dim > 1) t = fma(c2, y[k * ytda + 1], t);
+      if (dim > 2) t = fma(c3, y[k * ytda + 2], t);
+      s[k] = s[k] + t;
+    }
+    g[k * gtda] += c1;
+    if (dim > 1) g[k * gtda + 1] += c2;
+    if (dim > 2) g[k * gtda + 2] += c3;
+  }
+}
+
+template <int KIND, int TPT>
+static int launch_grad(gsl_sinterp_hip_ctx *ctx, double coef, double gscale, const double *d_x, size_t n, int dim, size_t xtda,
+                       const double *d_w, const double *d_y, size_t m, size_t ytda, double *d_s, double *d_g, size_t gtda, const int *d_perm)
+{
+  const size_t per_block = (size_t)EV_THREADS * TPT;
+  dim3 grid((unsigned)((m + per_block - 1) / per_block));
+#define GRAD_LAUNCH(D)                                                                                                                 \
+  hipLaunchKernelGGL((rbf_grad_kernel<KIND, D, TPT>), grid, dim3(EV_THREADS), 0, ctx->stream, coef, gscale, d_x, n, xtda, d_w, d_y, m, \
+                     ytda, d_s, d_g, gtda, d_perm)
+  switch (dim) {
+    case 1: GRAD_LAUNCH(1); break;
+    case 2: GRAD_LAUNCH(2); break;
+    default: GRAD_LAUNCH(3); break;
+  }
+#undef GRAD_LAUNCH
+  LAUNCH_CHECK(ctx);
+  return ST_SUCCESS;
+}
+
+template <int KIND, int TPT>
+static int launch_grad_cull(gsl_sinterp_hip_ctx *ctx, double coef, double gscale, const double *d_x, size_t n, int dim, size_t xtda,
+                            const double *d_w, const double *d_y, size_t m, size_t ytda, double *d_s, double *d_g, size_t gtda,
+                            const int *d_perm, unsigned long long model_id)
+{
+  cull_model cm;
+  int st = cull_pack(ctx, KIND, d_x, n, dim, xtda, d_w, model_id, &cm);
+  if (st) return st;
+  const size_t per_block = (size_t)CULL_THREADS * TPT;
+  dim3 grid((unsigned)((m + per_block - 1) / per_block));
+#define GRAD_LAUNCH(D, C)                                                                                                              \
+  hipLaunchKernelGGL((rbf_grad_cull_kernel<KIND, D, TPT, C>), grid, dim3(CULL_THREADS), 0, ctx->stream, coef, gscale, cm.xs, n, cm.tbox, \
+                     cm.ntiles, d_y, m, ytda, d_s, d_g, gtda, d_perm)
+  switch (dim) {
+    case 1: GRAD_LAUNCH(1, 32); break;
+    case 2:
+      if (cm.ct == 8) GRAD_LAUNCH(2, 8);
+      else if (cm.ct == 16) GRAD_LAUNCH(2, 16);
+      else GRAD_LAUNCH(2, 32);
+      break;
+    default: GRAD_LAUNCH(3, 32); break;
+  }
+#undef GRAD_LAUNCH
+  LAUNCH_CHECK(ctx);
+  return ST_SUCCESS;
+}
+
+extern "C" int gsl_sinterp_hip_rbf_eval_grad(gsl_sinterp_hip_ctx *ctx, int kind, double eps, const double *h_tail, const double *d_x,
+                                             size_t n, int dim, size_t xtda, const double *d_w, const double *d_y, size_t m,
+                                             size_t ytda, double *d_s, double *d_g, size_t gtda, unsigned long long model_id)
+{
+  REQUIRE(ctx, ctx != NULL, ST_EFAULT);
+  HIP_OK(ctx, hipSetDevice(ctx->device));      /* one context per device: bind before any launch */
+  REQUIRE(ctx, dim >= 1 && dim <= 3 && xtda >= (size_t)dim && ytda >= (size_t)dim && gtda >= (size_t)dim, ST_EINVAL);
+  REQUIRE(ctx, known_kind(kind), ST_EINVAL);
+  REQUIRE(ctx, m == 0 || (d_y && d_g && (n == 0 || (d_x && d_w))), ST_EFAULT);
+  if (m == 0) return ST_SUCCESS;
+  int st = ensure_tables(ctx);
+  if (st) return st;
+  const double coef = kernel_coef(kind, eps), gscale = rbf_grad_scale(kind, eps);
+  const bool local = kind != GSL_SINTERP_RBF_TPS;
+  int *d_perm = NULL;
+  if (local && m >= 4096 && !(getenv("GSL_SINTERP_NO_SORT") && getenv("GSL_SINTERP_NO_SORT")[0] == '1')) {
+    st = sinterp_sort_targets(ctx, d_y, m, ytda, dim, 64, &d_perm);
+    if (st) return st;
+  }
+  /* the kernel by N only, targets per lane by m and dim: the rules of rbf_eval_dispatch */
+  static const bool no_cull = getenv("GSL_SINTERP_NO_CULL") && getenv("GSL_SINTERP_NO_CULL")[0] == '1';
+#define GRAD_ARGS ctx, coef, gscale, d_x, n, dim, xtda, d_w, d_y, m, ytda, d_s, d_g, gtda, d_perm
+  if (local && !no_cull && n >= 1024 && (n + 31) / 32 <= CULL_MAX_TILES) {
+    const bool small = m < (size_t)CULL_THREADS * 2 * 512 || dim == 3;
+    if (kind == GSL_SINTERP_RBF_WENDLAND)
+      st = small ? launch_grad_cull<GSL_SINTERP_RBF_WENDLAND, 1>(GRAD_ARGS, model_id) : launch_grad_cull<GSL_SINTERP_RBF_WENDLAND, 2>(GRAD_ARGS, model_id);
+    else
+      st = small ? launch_grad_cull<GSL_SINTERP_RBF_GAUSSIAN, 1>(GRAD_ARGS, model_id) : launch_grad_cull<GSL_SINTERP_RBF_GAUSSIAN, 2>(GRAD_ARGS, model_id);
+  } else {
+    const bool small = m < (size_t)EV_THREADS * 2 * 512;
+    if (kind == GSL_SINTERP_RBF_WENDLAND)
+      st = small ? launch_grad<GSL_SINTERP_RBF_WENDLAND, 1>(GRAD_ARGS) : launch_grad<GSL_SINTERP_RBF_WENDLAND, 2>(GRAD_ARGS);
+    else if (kind == GSL_SINTERP_RBF_GAUSSIAN)
+      st = small ? launch_grad<GSL_SINTERP_RBF_GAUSSIAN, 1>(GRAD_ARGS) : launch_grad<GSL_SINTERP_RBF_GAUSSIAN, 2>(GRAD_ARGS);
+    else
+      st = small ? launch_grad<GSL_SINTERP_RBF_TPS, 1>(GRAD_ARGS) : launch_grad<GSL_SINTERP_RBF_TPS, 2>(GRAD_ARGS);
+  }
+#undef GRAD_ARGS
+  if (st || !h_tail) return st;
+  /* tail c_0 + sum_a c_a y_a: the affine thin-plate polynomial, or kriging's {mu, 0, ...}; h_tail[0 .. dim] only */
+  int linear = 0;
+  for (int a = 1; a <= dim; a++) linear |= h_tail[a] != 0.0;
+  if (!linear && !d_s) return ST_SUCCESS;
+  size_t blocks = (m + 255) / 256;
+  if (blocks > 4096) blocks = 4096;
+  hipLaunchKernelGGL(grad_tail_kernel, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, d_s, d_g, gtda, m, d_y, ytda, dim, h_tail[0],
+                     h_tail[1], dim > 1 ? h_tail[2] : 0.0, dim > 2 ? h_tail[3] : 0.0, linear);
+  LAUNCH_CHECK(ctx);
+  return ST_SUCCESS;
 }

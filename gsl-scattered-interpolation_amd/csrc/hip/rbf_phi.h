@@ -79,4 +79,31 @@ __device__ __forceinline__ double phi_r2(double r2, double coef, const double *_
   }
 }
 
+/* phi as phi_r2 returns it (the same expressions: the same bits) and, from the same exp2 / sqrt / log, the radial
+   factor of the gradient:  grad_y phi(|y - x|) = psi(r^2) (y - x),  psi = phi'(r) / r.  *psi receives psi WITHOUT
+   its constant, which the sweeps apply once per target (rbf_grad_scale in rbf.hip):
+       Gaussian    psi = -2 eps^2 phi               *psi = phi
+       Wendland    psi = -20 eps^2 (1 - eps r)_+^3  *psi = (1 - eps r)_+^3
+       thin-plate  psi = ln r^2 + 1                 *psi = ln r^2 + 1   (the constant 2 undoes the caller's half weight)
+   None of them divides and none is singular at r = 0: the thin-plate psi is the finite log_tbl(0) + 1 there, and the
+   callers multiply it by y - x = 0. */
+template <int KIND, int COPIES>
+__device__ __forceinline__ double phi_psi_r2(double r2, double coef, const double *__restrict__ t0,
+                                             const double *__restrict__ lt_lane, double *__restrict__ psi)
+{
+  if (KIND == GSL_SINTERP_RBF_GAUSSIAN) {
+    const double v = exp2_tbl(r2 * coef, t0);
+    *psi = v;
+    return v;
+  } else if (KIND == GSL_SINTERP_RBF_WENDLAND) {
+    const double t = coef * sqrt(r2), u = 1.0 - t, u2 = u * u;
+    *psi = u <= 0.0 ? 0.0 : u2 * u;
+    return u <= 0.0 ? 0.0 : (u2 * u2) * fma(4.0, t, 1.0);
+  } else {
+    const double L = log_tbl<COPIES>(r2, lt_lane);
+    *psi = L + 1.0;
+    return (coef * r2) * L;
+  }
+}
+
 #endif

@@ -1368,6 +1368,87 @@ int gsl_sinterp_eval_variance_e(const gsl_sinterp *interp, const gsl_vector *y, 
   return st;
 }
 
+/* ---- value + gradient (RBF family): dispatch on the type here, no slot in gsl_sinterp_type ---- */
+static int grad_status(const gsl_sinterp *interp)
+{
+  if (interp->type == &simplex_type || interp->type == &mesh_type)
+    GSL_ERROR("gsl_sinterp_eval_grad: RBF-family interpolants only (the piecewise-linear gradient is constant per leaf)", GSL_EUNSUP);
+  return GSL_SUCCESS;
+}
+
+int gsl_sinterp_eval_grad_resident(const gsl_sinterp *interp, const double *d_y, size_t m, size_t ytda, double *d_s, double *d_g,
+                                   size_t gtda)
+{
+  if (!interp) GSL_ERROR("gsl_sinterp_eval_grad_resident: null interpolant", GSL_EFAULT);
+  if (m > 0 && (!d_y || !d_g)) GSL_ERROR("gsl_sinterp_eval_grad_resident: null argument", GSL_EFAULT);
+  int gs = grad_status(interp);
+  if (gs) return gs;
+  const rbf_state *st = (const rbf_state *)interp->state;
+  if (!st->d_w) GSL_ERROR("gsl_sinterp_eval_grad: interpolant not initialised", GSL_EINVAL);
+  /* the tail: the affine polynomial, or kriging's constant mean; member 0 evaluates every target (as
+     gsl_sinterp_eval_resident does) */
+  double tail[4] = {st->mean, 0.0, 0.0, 0.0};
+  if (st->affine) memcpy(tail, st->poly, sizeof tail);
+  HIP_TRY(gsl_sinterp_hip_rbf_eval_grad(st->ctx, st->kind, st->eps, (st->affine || st->krige) ? tail : NULL, st->d_x, st->n, (int)st->dim,
+                                        st->dim, st->d_w, d_y, m, ytda, d_s, d_g, gtda, st->model_id), st->ctx);
+  return GSL_SUCCESS;
+}
+
+int gsl_sinterp_eval_grad_many(const gsl_sinterp *interp, const gsl_matrix *y, gsl_vector *sv, gsl_matrix *g)
+{
+  if (!interp || !y || !g) GSL_ERROR("gsl_sinterp_eval_grad_many: null argument", GSL_EFAULT);
+  int gs = grad_status(interp);
+  if (gs) return gs;
+  const size_t m = y->size1, dim = interp->dim;
+  if (y->size2 != dim) GSL_ERROR("target matrix must have dim columns", GSL_EBADLEN);
+  if (g->size1 != m || g->size2 != dim) GSL_ERROR("gradient matrix must be (number of targets) x dim", GSL_EBADLEN);
+  if (sv && sv->size != m) GSL_ERROR("output length must equal the number of targets", GSL_EBADLEN);
+  const rbf_state *st = (const rbf_state *)interp->state;
+  if (!st->d_w) GSL_ERROR("gsl_sinterp_eval_grad: interpolant not initialised", GSL_EINVAL);
+  if (m == 0) return GSL_SUCCESS;
+  gsl_sinterp_hip_ctx *c = st->ctx;
+  /* one staging buffer on either side: [targets m x dim | gradient m x dim | values m] */
+  double *h = (double *)malloc(m * (2 * dim + 1) * sizeof(double)), *d = NULL;
+  if (!h) GSL_ERROR("gsl_sinterp_eval_grad_many: out of memory", GSL_ENOMEM);
+  for (size_t k = 0; k < m; k++)
+    for (size_t a = 0; a < dim; a++) h[k * dim + a] = y->data[k * y->tda + a];
+  int s = gsl_sinterp_hip_malloc(c, (void **)&d, m * (2 * dim + 1) * sizeof(double));
+  if (!s) s = gsl_sinterp_hip_h2d(c, d, h, m * dim * sizeof(double));
+  int es = GSL_SUCCESS;
+  double *d_g = d + m * dim, *d_s = sv ? d_g + m * dim : NULL;
+  if (!s) es = gsl_sinterp_eval_grad_resident(interp, d, m, dim, d_s, d_g, dim);
+  if (!s && !es) s = gsl_sinterp_hip_d2h(c, h, d_g, m * (dim + (sv ? 1 : 0)) * sizeof(double));
+  if (!s && !es) {
+    for (size_t k = 0; k < m; k++)
+      for (size_t a = 0; a < dim; a++) g->data[k * g->tda + a] = h[k * dim + a];
+    if (sv) for (size_t k = 0; k < m; k++) gsl_vector_set(sv, k, h[m * dim + k]);
+  }
+  gsl_sinterp_hip_free(c, d);
+  free(h);
+  HIP_TRY(s, c);
+  return es;
+}
+
+int gsl_sinterp_eval_grad_e(const gsl_sinterp *interp, const gsl_vector *y, double *s, gsl_vector *g)
+{
+  if (s) *s = GSL_NAN;
+  if (g) for (size_t a = 0; a < g->size; a++) gsl_vector_set(g, a, GSL_NAN);
+  if (!interp || !y || !s || !g) GSL_ERROR("gsl_sinterp_eval_grad_e: null argument", GSL_EFAULT);
+  int gs = grad_status(interp);
+  if (gs) return gs;
+  if (y->size != interp->dim) GSL_ERROR("target must have dim components", GSL_EBADLEN);
+  if (g->size != interp->dim) GSL_ERROR("gradient must have dim components", GSL_EBADLEN);
+  double yy[3], gg[3], out = GSL_NAN;
+  for (size_t c = 0; c < interp->dim; c++) yy[c] = gsl_vector_get(y, c);
+  gsl_matrix_view Y = gsl_matrix_view_array(yy, 1, interp->dim), G = gsl_matrix_view_array(gg, 1, interp->dim);
+  gsl_vector_view S = gsl_vector_view_array(&out, 1);
+  int st = gsl_sinterp_eval_grad_many(interp, &Y.matrix, &S.vector, &G.matrix);
+  if (st != GSL_SUCCESS) return st;
+  *s = out;
+  for (size_t c = 0; c < interp->dim; c++) gsl_vector_set(g, c, gg[c]);
+  return GSL_SUCCESS;
+}
+
 int gsl_sinterp_poly(const gsl_sinterp *interp, gsl_vector *c)
 {
   if (!interp || !c) GSL_ERROR("gsl_sinterp_poly: null argument", GSL_EFAULT);

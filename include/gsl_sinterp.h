@@ -334,6 +334,24 @@ double gsl_sinterp_eval(const gsl_sinterp *interp, const gsl_vector *y);
 int gsl_sinterp_eval_many(const gsl_sinterp *interp, const gsl_matrix *y, gsl_vector *s, int *leaf);
 int gsl_sinterp_eval_resident(const gsl_sinterp *interp, const double *d_y, size_t m, size_t ytda,
                               double *d_s, int *d_leaf);
+/* Value and gradient (the counterpart of gsl_interp_eval_deriv_e, interpolation/gsl_interp.h:113-123, in dim dimensions):
+   s(y) and ds/dy_a, a < dim, from one fused sweep (gsl_sinterp_hip_rbf_eval_grad) -- the analytic gradient of the radial
+   sum plus the affine tail (gsl_sinterp_rbf_tps_affine) or nothing (kriging's mean is constant).  The five RBF-family
+   types are supported; gsl_sinterp_linear_simplex and gsl_sinterp_linear_mesh give GSL_EUNSUP (their gradient is constant
+   per leaf: a separate entry).  The value is bit-identical to gsl_sinterp_eval_many's for the same target; a target with a
+   NaN coordinate gets NaN in the value and in every gradient component.
+   eval_grad_many: y is m x dim, g is m x dim (g->tda honoured, padding untouched), s has m entries (s->stride honoured)
+   or is NULL for a gradient-only call.  eval_grad_e: one target, g has dim entries; *s and g are NaN on failure.
+   eval_grad_resident: everything in HBM, row k of the gradient at d_g + k * gtda (gtda >= dim), d_s may be NULL.
+   GSL_EFAULT: a NULL argument; GSL_EUNSUP: a linear type; GSL_EBADLEN: y->size2 != dim, g not y->size1 x dim, s->size
+   != y->size1; GSL_EINVAL: not initialised (or gtda < dim).  An interpolant restored by gsl_sinterp_fread evaluates
+   gradients: centres, weights, mean and polynomial are all a gradient needs.  With a device list the first device
+   evaluates every target, as gsl_sinterp_eval_resident and the variance entries do: gradient batches are not sharded
+   over the group, and eval_grad_many copies through plain (not pinned, not pipelined) staging. */
+int gsl_sinterp_eval_grad_e(const gsl_sinterp *interp, const gsl_vector *y, double *s, gsl_vector *g);
+int gsl_sinterp_eval_grad_many(const gsl_sinterp *interp, const gsl_matrix *y, gsl_vector *s /* may be NULL */, gsl_matrix *g);
+int gsl_sinterp_eval_grad_resident(const gsl_sinterp *interp, const double *d_y, size_t m, size_t ytda,
+                                   double *d_s /* may be NULL */, double *d_g, size_t gtda);
 /* Gridded front-end (interpolation/scattered_interp_example.c:175-217): evaluate on the regular grid
    x_i = min[0] + i (max[0]-min[0])/n0, y_j = min[1] + j (max[1]-min[1])/n1 (the reference's steps: range / n_grid,
    the upper bounds excluded) with n0 = grid->size1, n1 = grid->size2; grid(i, j) receives the value.  The

@@ -217,6 +217,28 @@ int gsl_sinterp_hip_rbf_eval_model(gsl_sinterp_hip_ctx *ctx, int kind, double ep
                                    size_t n, int dim, size_t xtda, const double *d_w,
                                    const double *d_y, size_t m, size_t ytda, double *d_s, unsigned long long model_id);
 
+/* Value and gradient from one fused sweep:  d_s[k] = s(y_k)  and  d_g[k * gtda + a] = ds/dy_a (y_k), a < dim, with
+       grad s(y) = sum_j w_j psi(r_j^2) (y - x_j),   psi = phi'(r) / r
+   (Gaussian -2 eps^2 phi; Wendland -20 eps^2 (1 - eps r)_+^3; thin-plate ln r^2 + 1 -- none divides, none is singular
+   at r = 0).  d_s may be NULL (gradient only); nothing beyond the dim columns of a row of d_g is written.  h_tail: NULL,
+   or dim + 1 host doubles {c_0, c_1 .. c_dim} of an affine tail, s += c_0 + sum_a c_a y_a and g_a += c_a (the affine
+   thin-plate polynomial; kriging passes {mu, 0, ..}); only h_tail[0 .. dim] is read.
+   The value has the bits of gsl_sinterp_hip_rbf_eval_model (_eval_affine / krige_eval with the tail) for the same model
+   and target: same terms, same order, and a target takes a gradient term exactly when it takes the value term, so value
+   and gradient are functions of (model, target) alone whatever the batch.  A NaN coordinate gives NaN in the value and
+   in every gradient component for every kind -- for the thin-plate kinds the value sweep returns that NaN too (r^2 =
+   NaN reaches every term), so the two rules do not collide; an infinite coordinate of a Gaussian / Wendland target takes
+   no term and gives 0.  model_id as for _eval_model: the packed centres are shared with the value sweep, a gradient
+   call after a value call with the same id reuses them.  Batches of >= 4096 Gaussian / Wendland targets are grouped
+   through the one-level permutation for every batch size (GSL_SINTERP_NO_SORT=1 honoured).
+   GSL_EINVAL: dim outside 1..3, unknown kind, xtda / ytda / gtda < dim; GSL_EFAULT: a NULL d_y or d_g with m > 0;
+   m = 0 succeeds and touches nothing. */
+int gsl_sinterp_hip_rbf_eval_grad(gsl_sinterp_hip_ctx *ctx, int kind, double eps, const double *h_tail,
+                                  const double *d_x, size_t n, int dim, size_t xtda, const double *d_w,
+                                  const double *d_y, size_t m, size_t ytda,
+                                  double *d_s /* may be NULL */, double *d_g, size_t gtda,
+                                  unsigned long long model_id);
+
 /* "init" of an RBF interpolant in one call: fill d_phi (n x n scratch, lda), solve Phi w = f
    with d_w holding f on entry and w on exit.  *h_route reports the solver used:
    1 Cholesky (Gaussian, SPD) -- 2 shifted-SPD Cholesky + rank-(d+1) Woodbury correction
