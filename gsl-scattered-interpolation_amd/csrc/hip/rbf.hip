@@ -15,8 +15,43 @@
 #include "common.h"
 #include <math.h>
 #include <stdlib.h>
+#include <type_traits>
 
 #include "rbf_phi.h"
+
+/* host side: a run-time kind / dimension / tile size picks the kernel instance.  f is a generic lambda that receives the
+   value as a std::integral_constant and launches <decltype(arg)::value>; its result is passed on */
+template <int V> using ic = std::integral_constant<int, V>;
+
+template <class F> static auto with_kind(int kind, F &&f)
+{
+  if (kind == GSL_SINTERP_RBF_WENDLAND) return f(ic<GSL_SINTERP_RBF_WENDLAND>());
+  return kind == GSL_SINTERP_RBF_GAUSSIAN ? f(ic<GSL_SINTERP_RBF_GAUSSIAN>()) : f(ic<GSL_SINTERP_RBF_TPS>());
+}
+
+template <class F> static auto with_dim(int dim, F &&f)
+{
+  switch (dim) {
+    case 1: return f(ic<1>());
+    case 2: return f(ic<2>());
+    default: return f(ic<3>());
+  }
+}
+
+/* (dimension, tile size) of the culled sweeps: cull_tile_size gives 8 / 16 / 32 in two dimensions, 32 otherwise */
+template <class F> static auto with_dim_tile(int dim, int ct, F &&f)
+{
+  switch (dim) {
+    case 1: return f(ic<1>(), ic<32>());
+    case 2: return ct == 8 ? f(ic<2>(), ic<8>()) : ct == 16 ? f(ic<2>(), ic<16>()) : f(ic<2>(), ic<32>());
+    default: return f(ic<3>(), ic<32>());
+  }
+}
+
+/* developer switches: "1" turns the target sort (read at every call) / the tile culling (read once per process) off */
+static bool env_is_1(const char *name) { const char *v = getenv(name); return v && v[0] == '1'; }
+static bool no_sort() { return env_is_1("GSL_SINTERP_NO_SORT"); }
+static bool no_cull() { static const bool off = env_is_1("GSL_SINTERP_NO_CULL"); return off; }
 
 struct RbfTables {
   double exp2_frac[TBL_N];      /* 2^(i/256)                          */
@@ -141,15 +176,82 @@ __device__ __forceinline__ bool nan_target(const double (&yy)[DIM])
 }
 
 /* ------------------------------------------------------------------------ */
-/* eval sweep: TPT targets per lane, centre tile of TJ entries in LDS          */
+/* The sweeps:  s(y) = sum_j w_j phi(|y - x_j|)  and, with GRAD,  grad s(y) = sum_j w_j psi(r_j^2) (y - x_j),  psi = phi'(r) / r
+   (rbf_phi.h: phi_psi_r2), from ONE pass over the centres -- the exp2 / sqrt / log of a (target, centre) pair and the
+   difference y - x_j are shared, the gradient adds one product and DIM FMAs per pair and DIM accumulators per target.
+   There is one body per sweep -- rbf_sweep over every centre, rbf_sweep_cull over the tiles near the workgroup -- and
+   GRAD only selects the per-pair term and the store (sweep_term, sweep_store); the four __global__ kernels are wrappers.
+
+   Value.  sweep_term keeps acc = fma(w_j, phi, acc) with one take-criterion and one order whatever GRAD is, so the value
+   that comes with a gradient has the bits gsl_sinterp_hip_rbf_eval_model returns for the same model and target.
+
+   Take-criterion.  One take[] per (target, centre) pair selects the value term and the gradient term (Gaussian: term above
+   2^-72 of the kernel maximum; Wendland: inside the support) -- the gradient too is a function of (model, target) alone,
+   bit-reproducible across batch size and grouping.  A dropped Gaussian gradient term is
+   |w_j| 2 eps^2 r exp(-(eps r)^2) = |w_j| 2 eps t exp(-t^2) with t = eps r beyond the cut-off t_c = sqrt(72 ln 2) = 7.07, where
+   t exp(-t^2) decreases: each is below |w_j| 2 eps t_c 2^-72 < |w_j| 14.2 eps 2^-72, the dropped mass of a component below
+   N max|w| 14.2 eps 2^-72 = N max|w| eps 3e-21.
+
+   Non-finite targets.  A NaN coordinate gives NaN in the value and in every gradient component, for every kind.  The
+   Gaussian / Wendland comparisons are false for NaN, so sweep_store restores the NaN.  The thin-plate value needs nothing:
+   r^2 = NaN goes through log_tbl into every term, and only the gradient is set.  An infinite coordinate of a Gaussian /
+   Wendland target fails the criterion for every centre: no term is taken, value and gradient are 0 (terms are SELECTED,
+   never multiplied by 0, so inf - x_j does no harm).
+
+   Target order.  The value entry sorts large batches with the two-level reorder and stores through its map (omap); the
+   gradient entry takes the one-level permutation route (sinterp_sort_targets; the kernels read and write through perm)
+   whatever the batch size: the two-level reorder's result path carries one scalar per target. */
+
+/* one (target, centre) pair: d = y - x_j, r2 = |d|^2, wj the centre's weight; the term is added only when take is set */
+template <int KIND, int DIM, bool GRAD>
+__device__ __forceinline__ void sweep_term(double r2, const double (&d)[DIM], double wj, double coef, bool take, const double *s_t0,
+                                           const double *lt_lane, double &acc, double (&gacc)[DIM])
+{
+  if constexpr (GRAD) {
+    double psi;
+    const double ph = phi_psi_r2<KIND, LOG_COPIES>(r2, coef, s_t0, lt_lane, &psi);
+    const double a = fma(wj, ph, acc);
+    const double p = wj * psi;                   /* a product of its own: the value's FMA is untouched */
+    acc = take ? a : acc;
+#pragma unroll
+    for (int c = 0; c < DIM; c++) { const double ga = fma(p, d[c], gacc[c]); gacc[c] = take ? ga : gacc[c]; }
+  } else {
+    const double a = fma(wj, phi_r2<KIND, LOG_COPIES>(r2, coef, s_t0, lt_lane), acc);
+    acc = take ? a : acc;
+  }
+}
+
+/* value sweep: s through omap when given.  GRAD: s may be NULL (gradient only); row k of g = g + k * gtda, DIM entries
+   written, the constant of psi (rbf_grad_scale) applied here, once per target */
+template <int KIND, int DIM, int TPT, bool GRAD>
+__device__ __forceinline__ void sweep_store(const size_t (&kidx)[TPT], size_t m, const double (&yy)[TPT][DIM], const double (&acc)[TPT],
+                                            const double (&gacc)[TPT][DIM], double *__restrict__ s, const unsigned *__restrict__ omap,
+                                            double *__restrict__ g, size_t gtda, double gscale)
+{
+#pragma unroll
+  for (int t = 0; t < TPT; t++) {
+    if (kidx[t] >= m) continue;
+    const bool isn = nan_target<DIM>(yy[t]);
+    const double v = (KIND != GSL_SINTERP_RBF_TPS && isn) ? NAN : acc[t];
+    if constexpr (GRAD) {
+      if (s) s[kidx[t]] = v;
+#pragma unroll
+      for (int c = 0; c < DIM; c++) g[kidx[t] * gtda + c] = isn ? NAN : gscale * gacc[t][c];
+    } else {
+      s[omap ? (size_t)omap[kidx[t]] : kidx[t]] = v;
+    }
+  }
+}
+
+/* sweep over every centre: TPT targets per lane, centre tile of TJ entries in LDS */
 #define EV_THREADS 256
 #define EV_TJ 512
 
-template <int KIND, int DIM, int TPT>
-__global__ void __launch_bounds__(EV_THREADS)
-rbf_eval_kernel(double coef, const double *__restrict__ x, size_t n, size_t xtda, const double *__restrict__ w,
-                const double *__restrict__ y, size_t m, size_t ytda, double *__restrict__ s, const int *__restrict__ perm,
-                const unsigned *__restrict__ omap)
+template <int KIND, int DIM, int TPT, bool GRAD>
+__device__ __forceinline__ void rbf_sweep(double coef, const double *__restrict__ x, size_t n, size_t xtda, const double *__restrict__ w,
+                                          const double *__restrict__ y, size_t m, size_t ytda, const int *__restrict__ perm,
+                                          double *__restrict__ s, const unsigned *__restrict__ omap, double *__restrict__ g, size_t gtda,
+                                          double gscale)
 {
   __shared__ double s_t0[KIND == GSL_SINTERP_RBF_GAUSSIAN ? TBL_N : 1];
   __shared__ __attribute__((aligned(16))) double s_lt[KIND == GSL_SINTERP_RBF_TPS ? LOG_LDS : 2];
@@ -161,14 +263,14 @@ rbf_eval_kernel(double coef, const double *__restrict__ x, size_t n, size_t xtda
      ADJACENT slots so they are spatial neighbours too */
   const size_t k0 = (((size_t)blockIdx.x * EV_THREADS) + threadIdx.x) * TPT;
   size_t kidx[TPT];
-  double yy[TPT][DIM], acc[TPT];
+  double yy[TPT][DIM], acc[TPT], gacc[TPT][DIM];
 #pragma unroll
   for (int t = 0; t < TPT; t++) {
     const size_t slot = k0 + (size_t)t;
     kidx[t] = slot < m ? (perm ? (size_t)perm[slot] : slot) : m;
     acc[t] = 0.0;
 #pragma unroll
-    for (int c = 0; c < DIM; c++) yy[t][c] = kidx[t] < m ? y[kidx[t] * ytda + c] : 0.0;
+    for (int c = 0; c < DIM; c++) { yy[t][c] = kidx[t] < m ? y[kidx[t] * ytda + c] : 0.0; gacc[t][c] = 0.0; }
   }
 
   for (size_t jt = 0; jt < n; jt += EV_TJ) {
@@ -186,14 +288,16 @@ rbf_eval_kernel(double coef, const double *__restrict__ x, size_t n, size_t xtda
 #pragma unroll
       for (int c = 0; c < DIM; c++) xc[c] = s_c[e * (DIM + 1) + c];
       const double wj = s_c[e * (DIM + 1) + DIM];
-      double r2[TPT];
+      double d[TPT][DIM], r2[TPT];
 #pragma unroll
       for (int t = 0; t < TPT; t++) {
         r2[t] = 0.0;
 #pragma unroll
-        for (int c = 0; c < DIM; c++) { const double d = yy[t][c] - xc[c]; r2[t] = fma(d, d, r2[t]); }
+        for (int c = 0; c < DIM; c++) { d[t][c] = yy[t][c] - xc[c]; r2[t] = fma(d[t][c], d[t][c], r2[t]); }
       }
       bool take[TPT];
+#pragma unroll
+      for (int t = 0; t < TPT; t++) take[t] = true;          /* thin-plate: no decay, every term */
       if (KIND == GSL_SINTERP_RBF_GAUSSIAN) {
         /* Every distance is computed; a target takes a term only when it is above 2^-72 of the
            kernel's maximum -- a function of the (target, centre) pair alone, so the value does not
@@ -214,16 +318,31 @@ rbf_eval_kernel(double coef, const double *__restrict__ x, size_t n, size_t xtda
         if (__builtin_amdgcn_ballot_w64(need) == 0) continue;
       }
 #pragma unroll
-      for (int t = 0; t < TPT; t++) {
-        const double a = fma(wj, phi_r2<KIND, LOG_COPIES>(r2[t], KIND == GSL_SINTERP_RBF_TPS ? 1.0 : coef, s_t0, lt_lane), acc[t]);
-        acc[t] = (KIND != GSL_SINTERP_RBF_TPS && !take[t]) ? acc[t] : a;
-      }
+      for (int t = 0; t < TPT; t++)
+        sweep_term<KIND, DIM, GRAD>(r2[t], d[t], wj, KIND == GSL_SINTERP_RBF_TPS ? 1.0 : coef, take[t], s_t0, lt_lane, acc[t], gacc[t]);
     }
   }
-#pragma unroll
-  for (int t = 0; t < TPT; t++)
-    if (kidx[t] < m) s[omap ? (size_t)omap[kidx[t]] : kidx[t]] = (KIND != GSL_SINTERP_RBF_TPS && nan_target<DIM>(yy[t])) ? NAN : acc[t];
+  sweep_store<KIND, DIM, TPT, GRAD>(kidx, m, yy, acc, gacc, s, omap, g, gtda, gscale);
 }
+
+template <int KIND, int DIM, int TPT>
+__global__ void __launch_bounds__(EV_THREADS)
+rbf_eval_kernel(double coef, const double *__restrict__ x, size_t n, size_t xtda, const double *__restrict__ w,
+                const double *__restrict__ y, size_t m, size_t ytda, double *__restrict__ s, const int *__restrict__ perm,
+                const unsigned *__restrict__ omap)
+{
+  rbf_sweep<KIND, DIM, TPT, false>(coef, x, n, xtda, w, y, m, ytda, perm, s, omap, nullptr, 0, 0.0);
+}
+
+template <int KIND, int DIM, int TPT>
+__global__ void __launch_bounds__(EV_THREADS)
+rbf_grad_kernel(double coef, double gscale, const double *__restrict__ x, size_t n, size_t xtda, const double *__restrict__ w,
+                const double *__restrict__ y, size_t m, size_t ytda, double *__restrict__ s, double *__restrict__ g, size_t gtda,
+                const int *__restrict__ perm)
+{
+  rbf_sweep<KIND, DIM, TPT, true>(coef, x, n, xtda, w, y, m, ytda, perm, s, nullptr, g, gtda, gscale);
+}
+
 
 /* ------------------------------------------------------------------------ */
 /* Gaussian sweep with tile culling.  At the shape parameters this path is used with
@@ -311,11 +430,11 @@ extern "C" int gsl_sinterp_hip_debug_cull_stats(unsigned long long *out, int res
 #ifndef CULL_THREADS
 #define CULL_THREADS 128   /* 256 / 128 / 64 threads: C3 sweep 1.34 / 1.26 / 1.27 ms, C4 1.71 ms throughout */
 #endif
-template <int KIND, int DIM, int TPT, int CT>
-__global__ void __launch_bounds__(CULL_THREADS)
-rbf_eval_gauss_cull_kernel(double coef, const double *__restrict__ xs, size_t n, const double *__restrict__ tbox, unsigned ntiles,
-                           const double *__restrict__ y, size_t m, size_t ytda, double *__restrict__ s, const int *__restrict__ perm,
-                const unsigned *__restrict__ omap)
+template <int KIND, int DIM, int TPT, int CT, bool GRAD>
+__device__ __forceinline__ void rbf_sweep_cull(double coef, const double *__restrict__ xs, size_t n, const double *__restrict__ tbox,
+                                               unsigned ntiles, const double *__restrict__ y, size_t m, size_t ytda,
+                                               const int *__restrict__ perm, double *__restrict__ s, const unsigned *__restrict__ omap,
+                                               double *__restrict__ g, size_t gtda, double gscale)
 {
   __shared__ double s_t0[TBL_N];
   __shared__ __attribute__((aligned(16))) double s_c[CULL_STAGE * (DIM + 1)];
@@ -327,14 +446,14 @@ rbf_eval_gauss_cull_kernel(double coef, const double *__restrict__ xs, size_t n,
 
   const size_t k0 = (((size_t)blockIdx.x * CULL_THREADS) + tid) * TPT;
   size_t kidx[TPT];
-  double yy[TPT][DIM], acc[TPT];
+  double yy[TPT][DIM], acc[TPT], gacc[TPT][DIM];
 #pragma unroll
   for (int t = 0; t < TPT; t++) {
     const size_t slot = k0 + (size_t)t;
     kidx[t] = slot < m ? (perm ? (size_t)perm[slot] : slot) : m;
     acc[t] = 0.0;
 #pragma unroll
-    for (int c = 0; c < DIM; c++) yy[t][c] = kidx[t] < m ? y[kidx[t] * ytda + c] : 0.0;
+    for (int c = 0; c < DIM; c++) { yy[t][c] = kidx[t] < m ? y[kidx[t] * ytda + c] : 0.0; gacc[t][c] = 0.0; }
   }
   /* bounding box of this workgroup's targets */
 #pragma unroll
@@ -363,8 +482,8 @@ rbf_eval_gauss_cull_kernel(double coef, const double *__restrict__ xs, size_t n,
 #pragma unroll
       for (int c = 0; c < DIM; c++) {
         const double tl = tbox[(size_t)t * (2 * DIM) + 2 * c], th = tbox[(size_t)t * (2 * DIM) + 2 * c + 1];
-        const double g = fmax(0.0, fmax(tl - bhi[c], blo[c] - th));
-        d2 = fma(g, g, d2);
+        const double gap = fmax(0.0, fmax(tl - bhi[c], blo[c] - th));
+        d2 = fma(gap, gap, d2);
       }
       keep = KIND == GSL_SINTERP_RBF_GAUSSIAN ? d2 * coef > -72.0 : d2 * (coef * coef) < 1.0;
     }
@@ -374,7 +493,7 @@ rbf_eval_gauss_cull_kernel(double coef, const double *__restrict__ xs, size_t n,
   __syncthreads();
 
 #ifdef SINTERP_DIAG_PROF
-  unsigned long long st_0 = 0, st_1 = 0, st_2 = 0;
+  unsigned long long st_0 = 0, st_1 = 0, st_2 = 0;       /* counted by every culled sweep, with or without the gradient */
 #endif
   /* the kept tiles, ascending, CULL_STAGE centres per LDS stage (several small tiles share one pair of barriers) */
   unsigned mi = 0;
@@ -394,46 +513,58 @@ rbf_eval_gauss_cull_kernel(double coef, const double *__restrict__ xs, size_t n,
     }
     if (cnt == 0) break;
     __syncthreads();
-    {
 #pragma unroll 2
-      for (int e = 0; e < cnt; e++) {
-        double xc[DIM];
+    for (int e = 0; e < cnt; e++) {
+      double xc[DIM];
 #pragma unroll
-        for (int c = 0; c < DIM; c++) xc[c] = s_c[e * (DIM + 1) + c];
-        const double wj = s_c[e * (DIM + 1) + DIM];
-        double r2[TPT];
-        bool take[TPT], need = false;
+      for (int c = 0; c < DIM; c++) xc[c] = s_c[e * (DIM + 1) + c];
+      const double wj = s_c[e * (DIM + 1) + DIM];
+      double d[TPT][DIM], r2[TPT];
+      bool take[TPT], need = false;
 #pragma unroll
-        for (int tt = 0; tt < TPT; tt++) {
-          r2[tt] = 0.0;
+      for (int tt = 0; tt < TPT; tt++) {
+        r2[tt] = 0.0;
 #pragma unroll
-          for (int c = 0; c < DIM; c++) { const double d = yy[tt][c] - xc[c]; r2[tt] = fma(d, d, r2[tt]); }
-          take[tt] = KIND == GSL_SINTERP_RBF_GAUSSIAN ? r2[tt] * coef > -72.0 : r2[tt] * (coef * coef) < 1.0;
-          need |= take[tt];
-        }
-        CULL_STAT(2, TPT);
-        if (__builtin_amdgcn_ballot_w64(need) == 0) continue;
-        CULL_STAT(0, TPT);
-#pragma unroll
-        for (int tt = 0; tt < TPT; tt++) CULL_STAT(1, take[tt] ? 1 : 0);
-        /* per-target criterion (see rbf_eval_kernel): a culled tile holds only centres every target of
-           the workgroup would reject, so the value is the sum over the centres with term > 2^-72, in
-           Morton order -- independent of the workgroup / wave the target landed in */
-#pragma unroll
-        for (int tt = 0; tt < TPT; tt++) {
-          const double a = fma(wj, phi_r2<KIND, 1>(r2[tt], coef, s_t0, (const double *)NULL), acc[tt]);
-          acc[tt] = take[tt] ? a : acc[tt];
-        }
+        for (int c = 0; c < DIM; c++) { d[tt][c] = yy[tt][c] - xc[c]; r2[tt] = fma(d[tt][c], d[tt][c], r2[tt]); }
+        take[tt] = KIND == GSL_SINTERP_RBF_GAUSSIAN ? r2[tt] * coef > -72.0 : r2[tt] * (coef * coef) < 1.0;
+        need |= take[tt];
       }
+      CULL_STAT(2, TPT);
+      if (__builtin_amdgcn_ballot_w64(need) == 0) continue;
+      CULL_STAT(0, TPT);
+#pragma unroll
+      for (int tt = 0; tt < TPT; tt++) CULL_STAT(1, take[tt] ? 1 : 0);
+      /* per-target criterion (see rbf_sweep): a culled tile holds only centres every target of
+         the workgroup would reject, so the value is the sum over the centres with term > 2^-72, in
+         Morton order -- independent of the workgroup / wave the target landed in */
+#pragma unroll
+      for (int tt = 0; tt < TPT; tt++)
+        sweep_term<KIND, DIM, GRAD>(r2[tt], d[tt], wj, coef, take[tt], s_t0, (const double *)NULL, acc[tt], gacc[tt]);
     }
   }
-#pragma unroll
-  for (int t = 0; t < TPT; t++)
-    if (kidx[t] < m) s[omap ? (size_t)omap[kidx[t]] : kidx[t]] = nan_target<DIM>(yy[t]) ? NAN : acc[t];
+  sweep_store<KIND, DIM, TPT, GRAD>(kidx, m, yy, acc, gacc, s, omap, g, gtda, gscale);
 #ifdef SINTERP_DIAG_PROF
   for (int off = 32; off > 0; off >>= 1) { st_0 += __shfl_xor(st_0, off); st_1 += __shfl_xor(st_1, off); st_2 += __shfl_xor(st_2, off); }
   if (lane == 0) { atomicAdd(&g_cull_stats[0], st_0); atomicAdd(&g_cull_stats[1], st_1); atomicAdd(&g_cull_stats[2], st_2); }
 #endif
+}
+
+template <int KIND, int DIM, int TPT, int CT>
+__global__ void __launch_bounds__(CULL_THREADS)
+rbf_eval_gauss_cull_kernel(double coef, const double *__restrict__ xs, size_t n, const double *__restrict__ tbox, unsigned ntiles,
+                           const double *__restrict__ y, size_t m, size_t ytda, double *__restrict__ s, const int *__restrict__ perm,
+                const unsigned *__restrict__ omap)
+{
+  rbf_sweep_cull<KIND, DIM, TPT, CT, false>(coef, xs, n, tbox, ntiles, y, m, ytda, perm, s, omap, nullptr, 0, 0.0);
+}
+
+template <int KIND, int DIM, int TPT, int CT>
+__global__ void __launch_bounds__(CULL_THREADS)
+rbf_grad_cull_kernel(double coef, double gscale, const double *__restrict__ xs, size_t n, const double *__restrict__ tbox, unsigned ntiles,
+                     const double *__restrict__ y, size_t m, size_t ytda, double *__restrict__ s, double *__restrict__ g, size_t gtda,
+                     const int *__restrict__ perm)
+{
+  rbf_sweep_cull<KIND, DIM, TPT, CT, true>(coef, xs, n, tbox, ntiles, y, m, ytda, perm, s, nullptr, g, gtda, gscale);
 }
 
 /* The packed centres of the culled sweeps: Morton order, {x, w} records, one bounding box per tile of ct centres.  They
@@ -465,19 +596,10 @@ static int cull_pack(gsl_sinterp_hip_ctx *ctx, int kind, const double *d_x, size
   double *xs = (double *)buf, *tbox = xs + n * (size_t)(dim + 1);
   out->xs = xs; out->tbox = tbox; out->ntiles = ntiles; out->ct = ct;
   if (cached) return ST_SUCCESS;
-#define PACK_LAUNCH(D, C)                                                                                                              \
-  hipLaunchKernelGGL((centre_pack_kernel<D, C>), dim3(ntiles), dim3(CT_THREADS), 0, ctx->stream, d_x, n, xtda, d_w, (const int *)d_cperm, \
-                     xs, tbox)
-  switch (dim) {
-    case 1: PACK_LAUNCH(1, 32); break;
-    case 2:
-      if (ct == 8) PACK_LAUNCH(2, 8);
-      else if (ct == 16) PACK_LAUNCH(2, 16);
-      else PACK_LAUNCH(2, 32);
-      break;
-    default: PACK_LAUNCH(3, 32); break;
-  }
-#undef PACK_LAUNCH
+  with_dim_tile(dim, ct, [&](auto D, auto C) {
+    hipLaunchKernelGGL((centre_pack_kernel<decltype(D)::value, decltype(C)::value>), dim3(ntiles), dim3(CT_THREADS), 0, ctx->stream,
+                       d_x, n, xtda, d_w, (const int *)d_cperm, xs, tbox);
+  });
   LAUNCH_CHECK(ctx);
   if (model_id != 0) {
     ctx->cent_key.id = model_id; ctx->cent_key.x = d_x; ctx->cent_key.w = d_w; ctx->cent_key.n = n; ctx->cent_key.xtda = xtda;
@@ -486,38 +608,18 @@ static int cull_pack(gsl_sinterp_hip_ctx *ctx, int kind, const double *d_x, size
   return ST_SUCCESS;
 }
 
-template <int KIND, int TPT>
-static int launch_eval_cull(gsl_sinterp_hip_ctx *ctx, double coef, const double *d_x, size_t n, int dim, size_t xtda, const double *d_w,
-                            const double *d_y, size_t m, size_t ytda, double *d_s, const int *d_perm, const unsigned *d_omap,
-                            unsigned long long model_id)
-{
-  cull_model cm;
-  int st = cull_pack(ctx, KIND, d_x, n, dim, xtda, d_w, model_id, &cm);
-  if (st) return st;
-  const size_t per_block = (size_t)CULL_THREADS * TPT;
-  dim3 grid((unsigned)((m + per_block - 1) / per_block));
-#define CULL_LAUNCH(D, C)                                                                                                              \
-  hipLaunchKernelGGL((rbf_eval_gauss_cull_kernel<KIND, D, TPT, C>), grid, dim3(CULL_THREADS), 0, ctx->stream, coef, cm.xs, n, cm.tbox, \
-                     cm.ntiles, d_y, m, ytda, d_s, d_perm, d_omap)
-  switch (dim) {
-    case 1: CULL_LAUNCH(1, 32); break;
-    case 2:
-      if (cm.ct == 8) CULL_LAUNCH(2, 8);
-      else if (cm.ct == 16) CULL_LAUNCH(2, 16);
-      else CULL_LAUNCH(2, 32);
-      break;
-    default: CULL_LAUNCH(3, 32); break;
-  }
-#undef CULL_LAUNCH
-  LAUNCH_CHECK(ctx);
-  return ST_SUCCESS;
-}
-
 /* ------------------------------------------------------------------------ */
 static double kernel_coef(int kind, double eps)
 {
   if (kind == GSL_SINTERP_RBF_WENDLAND) return eps;
   return kind == GSL_SINTERP_RBF_GAUSSIAN ? -(eps * eps) * 1.44269504088896340735992 : 0.5;
+}
+
+/* the constant of psi (rbf_phi.h), applied once per target by sweep_store */
+static double rbf_grad_scale(int kind, double eps)
+{
+  if (kind == GSL_SINTERP_RBF_GAUSSIAN) return -2.0 * (eps * eps);
+  return kind == GSL_SINTERP_RBF_WENDLAND ? -20.0 * (eps * eps) : 2.0;    /* thin-plate: the centre tile holds w / 2 */
 }
 
 static bool known_kind(int kind)
@@ -530,11 +632,9 @@ static int launch_fill(gsl_sinterp_hip_ctx *ctx, double coef, const double *d_x,
                        double *d_phi, size_t lda, int lower_only)
 {
   dim3 grid((unsigned)((n + 127) / 128), (unsigned)((n + 15) / 16));
-  switch (dim) {
-    case 1: hipLaunchKernelGGL((rbf_fill_kernel<KIND, 1>), grid, dim3(256), 0, ctx->stream, coef, d_x, n, xtda, d_phi, lda, lower_only); break;
-    case 2: hipLaunchKernelGGL((rbf_fill_kernel<KIND, 2>), grid, dim3(256), 0, ctx->stream, coef, d_x, n, xtda, d_phi, lda, lower_only); break;
-    default: hipLaunchKernelGGL((rbf_fill_kernel<KIND, 3>), grid, dim3(256), 0, ctx->stream, coef, d_x, n, xtda, d_phi, lda, lower_only); break;
-  }
+  with_dim(dim, [&](auto D) {
+    hipLaunchKernelGGL((rbf_fill_kernel<KIND, decltype(D)::value>), grid, dim3(256), 0, ctx->stream, coef, d_x, n, xtda, d_phi, lda, lower_only);
+  });
   LAUNCH_CHECK(ctx);
   return ST_SUCCESS;
 }
@@ -593,20 +693,12 @@ int sinterp_tps_fill_shifted(gsl_sinterp_hip_ctx *ctx, const double *d_x, size_t
   const double coef = kernel_coef(GSL_SINTERP_RBF_TPS, 0.0);
   HIP_OK(ctx, hipMemsetAsync(d_norm, 0, sizeof(unsigned long long), ctx->stream));
   const dim3 ngrid((unsigned)((n + 4 * TN_R - 1) / (4 * TN_R))), grid((unsigned)((n + 127) / 128), (unsigned)((n + 15) / 16));
-  switch (dim) {
-    case 1:
-      hipLaunchKernelGGL(tps_rownorm_kernel<1>, ngrid, dim3(256), 0, ctx->stream, coef, d_x, n, xtda, d_norm);
-      hipLaunchKernelGGL((rbf_fill_kernel<GSL_SINTERP_RBF_TPS, 1, true>), grid, dim3(256), 0, ctx->stream, coef, d_x, n, xtda, d_phi, lda, 0, d_Pk, k, cmul, (const unsigned long long *)d_norm);
-      break;
-    case 2:
-      hipLaunchKernelGGL(tps_rownorm_kernel<2>, ngrid, dim3(256), 0, ctx->stream, coef, d_x, n, xtda, d_norm);
-      hipLaunchKernelGGL((rbf_fill_kernel<GSL_SINTERP_RBF_TPS, 2, true>), grid, dim3(256), 0, ctx->stream, coef, d_x, n, xtda, d_phi, lda, 0, d_Pk, k, cmul, (const unsigned long long *)d_norm);
-      break;
-    default:
-      hipLaunchKernelGGL(tps_rownorm_kernel<3>, ngrid, dim3(256), 0, ctx->stream, coef, d_x, n, xtda, d_norm);
-      hipLaunchKernelGGL((rbf_fill_kernel<GSL_SINTERP_RBF_TPS, 3, true>), grid, dim3(256), 0, ctx->stream, coef, d_x, n, xtda, d_phi, lda, 0, d_Pk, k, cmul, (const unsigned long long *)d_norm);
-      break;
-  }
+  with_dim(dim, [&](auto D) {
+    constexpr int DIM = decltype(D)::value;
+    hipLaunchKernelGGL(tps_rownorm_kernel<DIM>, ngrid, dim3(256), 0, ctx->stream, coef, d_x, n, xtda, d_norm);
+    hipLaunchKernelGGL((rbf_fill_kernel<GSL_SINTERP_RBF_TPS, DIM, true>), grid, dim3(256), 0, ctx->stream, coef, d_x, n, xtda, d_phi, lda, 0,
+                       d_Pk, k, cmul, (const unsigned long long *)d_norm);
+  });
   LAUNCH_CHECK(ctx);
   return ST_SUCCESS;
 }
@@ -630,25 +722,84 @@ int sinterp_rbf_fill_ex(gsl_sinterp_hip_ctx *ctx, int kind, double eps, const do
   int st = ensure_tables(ctx);
   if (st) return st;
   const double coef = kernel_coef(kind, eps);
-  if (kind == GSL_SINTERP_RBF_WENDLAND) return launch_fill<GSL_SINTERP_RBF_WENDLAND>(ctx, coef, d_x, n, dim, xtda, d_phi, lda, lower_only);
-  return kind == GSL_SINTERP_RBF_GAUSSIAN ? launch_fill<GSL_SINTERP_RBF_GAUSSIAN>(ctx, coef, d_x, n, dim, xtda, d_phi, lda, lower_only)
-                                          : launch_fill<GSL_SINTERP_RBF_TPS>(ctx, coef, d_x, n, dim, xtda, d_phi, lda, lower_only);
+  return with_kind(kind, [&](auto K) { return launch_fill<decltype(K)::value>(ctx, coef, d_x, n, dim, xtda, d_phi, lda, lower_only); });
 }
 
+/* ------------------------------------------------------------------------ */
+/* One sweep as the host sees it: the model, the targets (read through perm when given) and where the results go.
+   g == NULL: the value sweep, s stored through omap when given; else value + gradient, s may be NULL. */
+struct sweep_job {
+  double coef;
+  const double *x; size_t n; int dim; size_t xtda; const double *w;
+  const double *y; size_t m, ytda; const int *perm;
+  double *s; const unsigned *omap;
+  double *g; size_t gtda; double gscale;
+  unsigned long long model_id;
+};
+
 template <int KIND, int TPT>
-static int launch_eval(gsl_sinterp_hip_ctx *ctx, double coef, const double *d_x, size_t n, int dim, size_t xtda,
-                       const double *d_w, const double *d_y, size_t m, size_t ytda, double *d_s, const int *d_perm, const unsigned *d_omap)
+static int launch_sweep(gsl_sinterp_hip_ctx *ctx, const sweep_job &j)
 {
   const size_t per_block = (size_t)EV_THREADS * TPT;
-  dim3 grid((unsigned)((m + per_block - 1) / per_block));
-  switch (dim) {
-    case 1: hipLaunchKernelGGL((rbf_eval_kernel<KIND, 1, TPT>), grid, dim3(EV_THREADS), 0, ctx->stream, coef, d_x, n, xtda, d_w, d_y, m, ytda, d_s, d_perm, d_omap); break;
-    case 2: hipLaunchKernelGGL((rbf_eval_kernel<KIND, 2, TPT>), grid, dim3(EV_THREADS), 0, ctx->stream, coef, d_x, n, xtda, d_w, d_y, m, ytda, d_s, d_perm, d_omap); break;
-    default: hipLaunchKernelGGL((rbf_eval_kernel<KIND, 3, TPT>), grid, dim3(EV_THREADS), 0, ctx->stream, coef, d_x, n, xtda, d_w, d_y, m, ytda, d_s, d_perm, d_omap); break;
-  }
+  const dim3 grid((unsigned)((j.m + per_block - 1) / per_block)), block(EV_THREADS);
+  with_dim(j.dim, [&](auto D) {
+    constexpr int DIM = decltype(D)::value;
+    if (j.g)
+      hipLaunchKernelGGL((rbf_grad_kernel<KIND, DIM, TPT>), grid, block, 0, ctx->stream, j.coef, j.gscale, j.x, j.n, j.xtda, j.w, j.y, j.m,
+                         j.ytda, j.s, j.g, j.gtda, j.perm);
+    else
+      hipLaunchKernelGGL((rbf_eval_kernel<KIND, DIM, TPT>), grid, block, 0, ctx->stream, j.coef, j.x, j.n, j.xtda, j.w, j.y, j.m, j.ytda,
+                         j.s, j.perm, j.omap);
+  });
   LAUNCH_CHECK(ctx);
   return ST_SUCCESS;
 }
+
+template <int KIND, int TPT>
+static int launch_sweep_cull(gsl_sinterp_hip_ctx *ctx, const sweep_job &j)
+{
+  cull_model cm;
+  int st = cull_pack(ctx, KIND, j.x, j.n, j.dim, j.xtda, j.w, j.model_id, &cm);
+  if (st) return st;
+  const size_t per_block = (size_t)CULL_THREADS * TPT;
+  const dim3 grid((unsigned)((j.m + per_block - 1) / per_block)), block(CULL_THREADS);
+  with_dim_tile(j.dim, cm.ct, [&](auto D, auto C) {
+    constexpr int DIM = decltype(D)::value, CT = decltype(C)::value;
+    if (j.g)
+      hipLaunchKernelGGL((rbf_grad_cull_kernel<KIND, DIM, TPT, CT>), grid, block, 0, ctx->stream, j.coef, j.gscale, cm.xs, j.n, cm.tbox,
+                         cm.ntiles, j.y, j.m, j.ytda, j.s, j.g, j.gtda, j.perm);
+    else
+      hipLaunchKernelGGL((rbf_eval_gauss_cull_kernel<KIND, DIM, TPT, CT>), grid, block, 0, ctx->stream, j.coef, cm.xs, j.n, cm.tbox,
+                         cm.ntiles, j.y, j.m, j.ytda, j.s, j.perm, j.omap);
+  });
+  LAUNCH_CHECK(ctx);
+  return ST_SUCCESS;
+}
+
+/* Which kernel runs, for the value and for the value + gradient entry alike. */
+static int rbf_sweep_dispatch(gsl_sinterp_hip_ctx *ctx, int kind, const sweep_job &j)
+{
+  /* The culled kernel sums in the Morton order of the centres, the plain one in input order.  Which of the two
+     runs must not depend on the batch (a target's value is a function of the model and the target alone, so a
+     batch split into shards -- or a single-point call -- returns the bits of the one-batch result): it is chosen
+     by N only; small batches simply run the culled kernel without the target sort. */
+  const bool culled = kind != GSL_SINTERP_RBF_TPS && !no_cull() && j.n >= 1024 && (j.n + 31) / 32 <= CULL_MAX_TILES;
+  /* few targets: 1 per lane keeps more CUs busy; many: 2 per lane for ILP.
+     Culled, 3-D: one target per lane also for large batches -- a workgroup's 256 targets span half the box of 512, and
+     in three dimensions that removes more tested-and-rejected centres than the second accumulator chain gains
+     (C3 sweep 1.70 -> 1.34 ms; 2-D C4: 1.74 vs 1.77 ms, unchanged) */
+  const bool one = j.m < (size_t)(culled ? CULL_THREADS : EV_THREADS) * 2 * 512 || (culled && j.dim == 3);
+  return with_kind(kind, [&](auto K) {
+    constexpr int KIND = decltype(K)::value;
+    if constexpr (KIND != GSL_SINTERP_RBF_TPS)      /* thin-plate has no decay: nothing to cull */
+      if (culled) return one ? launch_sweep_cull<KIND, 1>(ctx, j) : launch_sweep_cull<KIND, 2>(ctx, j);
+    return one ? launch_sweep<KIND, 1>(ctx, j) : launch_sweep<KIND, 2>(ctx, j);
+  });
+}
+
+/* Gaussian / Wendland: group the targets spatially so that whole waves skip negligible (Wendland: zero) terms
+   together (TPS has no decay: nothing to skip, no sort) */
+static bool wants_target_sort(int kind, size_t m) { return kind != GSL_SINTERP_RBF_TPS && m >= 4096 && !no_sort(); }
 
 extern "C" int gsl_sinterp_hip_rbf_eval(gsl_sinterp_hip_ctx *ctx, int kind, double eps, const double *d_x, size_t n,
                                         int dim, size_t xtda, const double *d_w, const double *d_y, size_t m,
@@ -656,10 +807,6 @@ extern "C" int gsl_sinterp_hip_rbf_eval(gsl_sinterp_hip_ctx *ctx, int kind, doub
 {
   return gsl_sinterp_hip_rbf_eval_model(ctx, kind, eps, d_x, n, dim, xtda, d_w, d_y, m, ytda, d_s, 0ULL);
 }
-
-static int rbf_eval_dispatch(gsl_sinterp_hip_ctx *ctx, int kind, double coef, const double *d_x, size_t n, int dim, size_t xtda,
-                             const double *d_w, const double *d_y, size_t m, size_t ytda, double *d_s, const int *d_perm,
-                             const unsigned *d_omap, unsigned long long model_id);
 
 extern "C" int gsl_sinterp_hip_rbf_eval_model(gsl_sinterp_hip_ctx *ctx, int kind, double eps, const double *d_x, size_t n,
                                               int dim, size_t xtda, const double *d_w, const double *d_y, size_t m,
@@ -673,13 +820,8 @@ extern "C" int gsl_sinterp_hip_rbf_eval_model(gsl_sinterp_hip_ctx *ctx, int kind
   if (m == 0) return ST_SUCCESS;
   int st = ensure_tables(ctx);
   if (st) return st;
-  const double coef = kernel_coef(kind, eps);
-  /* Gaussian / Wendland: group the targets spatially so that whole waves skip negligible (Wendland: zero) terms
-     together (TPS has no decay: nothing to skip, no sort) */
-  const bool local = kind != GSL_SINTERP_RBF_TPS;
-  int *d_perm = NULL;
-  const unsigned *d_omap = NULL;
-  if (local && m >= 4096 && !(getenv("GSL_SINTERP_NO_SORT") && getenv("GSL_SINTERP_NO_SORT")[0] == '1')) {
+  sweep_job j = {kernel_coef(kind, eps), d_x, n, dim, xtda, d_w, d_y, m, ytda, NULL, d_s, NULL, NULL, 0, 0.0, model_id};
+  if (wants_target_sort(kind, m)) {
     /* large batches: the targets are physically put in cell order (sort.hip, two-level reorder), swept contiguously, each
        result stored through the order's map, and the values gathered back -- one random pass instead of the three of
        the permutation route (histogram atomics, perm scatter, gather + scatter inside the sweep) */
@@ -688,286 +830,18 @@ extern "C" int gsl_sinterp_hip_rbf_eval_model(gsl_sinterp_hip_ctx *ctx, int kind
       st = sinterp_sort_reorder(ctx, d_y, m, ytda, dim, 64, &srt, m, -1, (const unsigned long long *)NULL);
       if (st) return st;
       if (srt.two_level) {
-        st = rbf_eval_dispatch(ctx, kind, coef, d_x, n, dim, xtda, d_w, (const double *)srt.ys, m, (size_t)dim, srt.res1, (const int *)NULL,
-                               (const unsigned *)srt.inv, model_id);
+        j.y = (const double *)srt.ys; j.ytda = (size_t)dim; j.s = srt.res1; j.omap = (const unsigned *)srt.inv;
+        st = rbf_sweep_dispatch(ctx, kind, j);
         if (st) return st;
         return sinterp_unsort(ctx, &srt, m, d_s, (int *)NULL);
       }
     }
+    int *d_perm = NULL;
     st = sinterp_sort_targets(ctx, d_y, m, ytda, dim, 64, &d_perm);
     if (st) return st;
+    j.perm = d_perm;
   }
-  return rbf_eval_dispatch(ctx, kind, coef, d_x, n, dim, xtda, d_w, d_y, m, ytda, d_s, d_perm, d_omap, model_id);
-}
-
-static int rbf_eval_dispatch(gsl_sinterp_hip_ctx *ctx, int kind, double coef, const double *d_x, size_t n, int dim, size_t xtda,
-                             const double *d_w, const double *d_y, size_t m, size_t ytda, double *d_s, const int *d_perm,
-                             const unsigned *d_omap, unsigned long long model_id)
-{
-  const bool local = kind != GSL_SINTERP_RBF_TPS;
-  /* few targets: 1 per lane keeps more CUs busy; many: 2 per lane for ILP */
-  const bool small = m < (size_t)EV_THREADS * 2 * 512;
-  static const bool no_cull = getenv("GSL_SINTERP_NO_CULL") && getenv("GSL_SINTERP_NO_CULL")[0] == '1';
-  /* The culled kernel sums in the Morton order of the centres, the plain one in input order.  Which of the two
-     runs must not depend on the batch (a target's value is a function of the model and the target alone, so a
-     batch split into shards -- or a single-point call -- returns the bits of the one-batch result): it is chosen
-     by N only; small batches simply run the culled kernel without the target sort. */
-  if (local && !no_cull && n >= 1024 && (n + 31) / 32 <= CULL_MAX_TILES) {
-    /* 3-D: one target per lane also for large batches -- a workgroup's 256 targets span half the box of 512, and
-       in three dimensions that removes more tested-and-rejected centres than the second accumulator chain gains
-       (C3 sweep 1.70 -> 1.34 ms; 2-D C4: 1.74 vs 1.77 ms, unchanged) */
-    const bool small = m < (size_t)CULL_THREADS * 2 * 512 || dim == 3;
-    if (kind == GSL_SINTERP_RBF_WENDLAND)
-      return small ? launch_eval_cull<GSL_SINTERP_RBF_WENDLAND, 1>(ctx, coef, d_x, n, dim, xtda, d_w, d_y, m, ytda, d_s, d_perm, d_omap, model_id)
-                   : launch_eval_cull<GSL_SINTERP_RBF_WENDLAND, 2>(ctx, coef, d_x, n, dim, xtda, d_w, d_y, m, ytda, d_s, d_perm, d_omap, model_id);
-    return small ? launch_eval_cull<GSL_SINTERP_RBF_GAUSSIAN, 1>(ctx, coef, d_x, n, dim, xtda, d_w, d_y, m, ytda, d_s, d_perm, d_omap, model_id)
-                 : launch_eval_cull<GSL_SINTERP_RBF_GAUSSIAN, 2>(ctx, coef, d_x, n, dim, xtda, d_w, d_y, m, ytda, d_s, d_perm, d_omap, model_id);
-  }
-  if (kind == GSL_SINTERP_RBF_WENDLAND)
-    return small ? launch_eval<GSL_SINTERP_RBF_WENDLAND, 1>(ctx, coef, d_x, n, dim, xtda, d_w, d_y, m, ytda, d_s, d_perm, d_omap)
-                 : launch_eval<GSL_SINTERP_RBF_WENDLAND, 2>(ctx, coef, d_x, n, dim, xtda, d_w, d_y, m, ytda, d_s, d_perm, d_omap);
-  if (kind == GSL_SINTERP_RBF_GAUSSIAN)
-    return small ? launch_eval<GSL_SINTERP_RBF_GAUSSIAN, 1>(ctx, coef, d_x, n, dim, xtda, d_w, d_y, m, ytda, d_s, d_perm, d_omap)
-                 : launch_eval<GSL_SINTERP_RBF_GAUSSIAN, 2>(ctx, coef, d_x, n, dim, xtda, d_w, d_y, m, ytda, d_s, d_perm, d_omap);
-  return small ? launch_eval<GSL_SINTERP_RBF_TPS, 1>(ctx, coef, d_x, n, dim, xtda, d_w, d_y, m, ytda, d_s, d_perm, d_omap)
-               : launch_eval<GSL_SINTERP_RBF_TPS, 2>(ctx, coef, d_x, n, dim, xtda, d_w, d_y, m, ytda, d_s, d_perm, d_omap);
-}
-
-/* ------------------------------------------------------------------------ */
-/* value + gradient sweeps:  s(y) = sum_j w_j phi(|y - x_j|)  and  grad s(y) = sum_j w_j psi(r_j^2) (y - x_j),  psi = phi'(r) / r
-   (rbf_phi.h: phi_psi_r2), from ONE pass over the centres -- the exp2 / sqrt / log of a (target, centre) pair and the
-   difference y - x_j are shared, the gradient adds one product and DIM FMAs per pair.  The kernels below are the two
-   evaluation kernels above with DIM more accumulators per target; those stay as they are.
-
-   Value.  acc = fma(w_j, phi, acc) with the value sweeps' take-criterion and order, so the value that comes with a gradient
-   has the bits gsl_sinterp_hip_rbf_eval_model returns for the same model and target.
-
-   Take-criterion.  A target takes a gradient term exactly when it takes the value term (Gaussian: term above 2^-72 of the
-   kernel maximum; Wendland: inside the support), per (target, centre) pair -- the gradient too is a function of (model,
-   target) alone, bit-reproducible across batch size and grouping.  A dropped Gaussian gradient term is
-   |w_j| 2 eps^2 r exp(-(eps r)^2) = |w_j| 2 eps t exp(-t^2) with t = eps r beyond the cut-off t_c = sqrt(72 ln 2) = 7.07, where
-   t exp(-t^2) decreases: each is below |w_j| 2 eps t_c 2^-72 < |w_j| 14.2 eps 2^-72, the dropped mass of a component below
-   N max|w| 14.2 eps 2^-72 = N max|w| eps 3e-21.
-
-   Non-finite targets.  A NaN coordinate gives NaN in the value and in every gradient component, for every kind.  The
-   Gaussian / Wendland comparisons are false for NaN, so those sweeps restore the NaN at the end exactly as the value sweeps
-   do.  The thin-plate value needs nothing: r^2 = NaN goes through log_tbl into every term, in the value sweep too, so the
-   value here is that sweep's NaN, bit for bit, and only the gradient is set.  An infinite coordinate of a Gaussian / Wendland
-   target fails the criterion for every centre: no term is taken, value and gradient are 0 (terms are SELECTED, never
-   multiplied by 0, so inf - x_j does no harm).
-
-   Target order.  Batches of >= 4096 targets of the local kinds take the one-level permutation route (sinterp_sort_targets;
-   the kernels read and write through perm) whatever the batch size: the two-level reorder's result path carries one scalar
-   per target. */
-static double rbf_grad_scale(int kind, double eps)
-{
-  if (kind == GSL_SINTERP_RBF_GAUSSIAN) return -2.0 * (eps * eps);
-  return kind == GSL_SINTERP_RBF_WENDLAND ? -20.0 * (eps * eps) : 2.0;    /* thin-plate: the centre tile holds w / 2 */
-}
-
-/* s may be NULL (gradient only); row k of g = g + k * gtda, DIM entries written */
-template <int KIND, int DIM, int TPT>
-__device__ __forceinline__ void grad_store(const size_t (&kidx)[TPT], size_t m, const double (&yy)[TPT][DIM], const double (&acc)[TPT],
-                                           const double (&gacc)[TPT][DIM], double gscale, double *__restrict__ s, double *__restrict__ g,
-                                           size_t gtda)
-{
-#pragma unroll
-  for (int t = 0; t < TPT; t++) {
-    if (kidx[t] >= m) continue;
-    const bool isn = nan_target<DIM>(yy[t]);
-    if (s) s[kidx[t]] = (KIND != GSL_SINTERP_RBF_TPS && isn) ? NAN : acc[t];
-#pragma unroll
-    for (int c = 0; c < DIM; c++) g[kidx[t] * gtda + c] = isn ? NAN : gscale * gacc[t][c];
-  }
-}
-
-template <int KIND, int DIM, int TPT>
-__global__ void __launch_bounds__(EV_THREADS)
-rbf_grad_kernel(double coef, double gscale, const double *__restrict__ x, size_t n, size_t xtda, const double *__restrict__ w,
-                const double *__restrict__ y, size_t m, size_t ytda, double *__restrict__ s, double *__restrict__ g, size_t gtda,
-                const int *__restrict__ perm)
-{
-  __shared__ double s_t0[KIND == GSL_SINTERP_RBF_GAUSSIAN ? TBL_N : 1];
-  __shared__ __attribute__((aligned(16))) double s_lt[KIND == GSL_SINTERP_RBF_TPS ? LOG_LDS : 2];
-  __shared__ double s_c[EV_TJ * (DIM + 1)];       /* per centre: x[0..DIM-1], w */
-  load_tables<LOG_COPIES>(s_t0, s_lt, KIND);
-  const double *lt_lane = s_lt + (threadIdx.x & (LOG_COPIES - 1)) * 2;
-
-  const size_t k0 = (((size_t)blockIdx.x * EV_THREADS) + threadIdx.x) * TPT;
-  size_t kidx[TPT];
-  double yy[TPT][DIM], acc[TPT], gacc[TPT][DIM];
-#pragma unroll
-  for (int t = 0; t < TPT; t++) {
-    const size_t slot = k0 + (size_t)t;
-    kidx[t] = slot < m ? (perm ? (size_t)perm[slot] : slot) : m;
-    acc[t] = 0.0;
-#pragma unroll
-    for (int c = 0; c < DIM; c++) { yy[t][c] = kidx[t] < m ? y[kidx[t] * ytda + c] : 0.0; gacc[t][c] = 0.0; }
-  }
-
-  for (size_t jt = 0; jt < n; jt += EV_TJ) {
-    const int cnt = (int)((n - jt) < (size_t)EV_TJ ? (n - jt) : (size_t)EV_TJ);
-    __syncthreads();
-    for (int e = threadIdx.x; e < cnt; e += EV_THREADS) {
-#pragma unroll
-      for (int c = 0; c < DIM; c++) s_c[e * (DIM + 1) + c] = x[(jt + e) * xtda + c];
-      s_c[e * (DIM + 1) + DIM] = (KIND == GSL_SINTERP_RBF_TPS ? 0.5 : 1.0) * w[jt + e];
-    }
-    __syncthreads();
-#pragma unroll 2
-    for (int e = 0; e < cnt; e++) {
-      double xc[DIM];
-#pragma unroll
-      for (int c = 0; c < DIM; c++) xc[c] = s_c[e * (DIM + 1) + c];
-      const double wj = s_c[e * (DIM + 1) + DIM];
-      double d[TPT][DIM], r2[TPT];
-#pragma unroll
-      for (int t = 0; t < TPT; t++) {
-        r2[t] = 0.0;
-#pragma unroll
-        for (int c = 0; c < DIM; c++) { d[t][c] = yy[t][c] - xc[c]; r2[t] = fma(d[t][c], d[t][c], r2[t]); }
-      }
-      bool take[TPT];
-#pragma unroll
-      for (int t = 0; t < TPT; t++) take[t] = true;
-      if (KIND == GSL_SINTERP_RBF_GAUSSIAN) {        /* the criterion of rbf_eval_kernel, for both sums */
-        bool need = false;
-#pragma unroll
-        for (int t = 0; t < TPT; t++) { take[t] = r2[t] * coef > -72.0; need |= take[t]; }
-        if (__builtin_amdgcn_ballot_w64(need) == 0) continue;
-      }
-      if (KIND == GSL_SINTERP_RBF_WENDLAND) {
-        bool need = false;
-#pragma unroll
-        for (int t = 0; t < TPT; t++) { take[t] = r2[t] * (coef * coef) < 1.0; need |= take[t]; }
-        if (__builtin_amdgcn_ballot_w64(need) == 0) continue;
-      }
-#pragma unroll
-      for (int t = 0; t < TPT; t++) {
-        double psi;
-        const double ph = phi_psi_r2<KIND, LOG_COPIES>(r2[t], KIND == GSL_SINTERP_RBF_TPS ? 1.0 : coef, s_t0, lt_lane, &psi);
-        const double a = fma(wj, ph, acc[t]);
-        const double p = wj * psi;                   /* a product of its own: the value's FMA is untouched */
-        acc[t] = take[t] ? a : acc[t];
-#pragma unroll
-        for (int c = 0; c < DIM; c++) { const double ga = fma(p, d[t][c], gacc[t][c]); gacc[t][c] = take[t] ? ga : gacc[t][c]; }
-      }
-    }
-  }
-  grad_store<KIND, DIM, TPT>(kidx, m, yy, acc, gacc, gscale, s, g, gtda);
-}
-
-/* rbf_eval_gauss_cull_kernel with the gradient accumulators; the packed centres are the value sweep's (cull_pack) */
-template <int KIND, int DIM, int TPT, int CT>
-__global__ void __launch_bounds__(CULL_THREADS)
-rbf_grad_cull_kernel(double coef, double gscale, const double *__restrict__ xs, size_t n, const double *__restrict__ tbox, unsigned ntiles,
-                     const double *__restrict__ y, size_t m, size_t ytda, double *__restrict__ s, double *__restrict__ g, size_t gtda,
-                     const int *__restrict__ perm)
-{
-  __shared__ double s_t0[TBL_N];
-  __shared__ __attribute__((aligned(16))) double s_c[CULL_STAGE * (DIM + 1)];
-  constexpr int NWV = CULL_THREADS / 64;
-  __shared__ double s_blo[DIM][NWV], s_bhi[DIM][NWV];
-  __shared__ unsigned long long s_mask[CULL_MAX_TILES / 64];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  for (int i = tid; i < TBL_N; i += CULL_THREADS) s_t0[i] = g_rbf_tables.exp2_frac[i];
-
-  const size_t k0 = (((size_t)blockIdx.x * CULL_THREADS) + tid) * TPT;
-  size_t kidx[TPT];
-  double yy[TPT][DIM], acc[TPT], gacc[TPT][DIM];
-#pragma unroll
-  for (int t = 0; t < TPT; t++) {
-    const size_t slot = k0 + (size_t)t;
-    kidx[t] = slot < m ? (perm ? (size_t)perm[slot] : slot) : m;
-    acc[t] = 0.0;
-#pragma unroll
-    for (int c = 0; c < DIM; c++) { yy[t][c] = kidx[t] < m ? y[kidx[t] * ytda + c] : 0.0; gacc[t][c] = 0.0; }
-  }
-  /* bounding box of this workgroup's targets */
-#pragma unroll
-  for (int c = 0; c < DIM; c++) {
-    double lo = INFINITY, hi = -INFINITY;
-#pragma unroll
-    for (int t = 0; t < TPT; t++) if (kidx[t] < m) { lo = fmin(lo, yy[t][c]); hi = fmax(hi, yy[t][c]); }
-    for (int off = 32; off > 0; off >>= 1) { lo = fmin(lo, __shfl_xor(lo, off)); hi = fmax(hi, __shfl_xor(hi, off)); }
-    if (lane == 0) { s_blo[c][wave] = lo; s_bhi[c][wave] = hi; }
-  }
-  __syncthreads();
-  double blo[DIM], bhi[DIM];
-#pragma unroll
-  for (int c = 0; c < DIM; c++) {
-    blo[c] = s_blo[c][0]; bhi[c] = s_bhi[c][0];
-#pragma unroll
-    for (int w = 1; w < NWV; w++) { blo[c] = fmin(blo[c], s_blo[c][w]); bhi[c] = fmax(bhi[c], s_bhi[c][w]); }
-  }
-  /* tiles within the cut-off of the box: one bit per tile */
-  const unsigned nmask = (ntiles + 63) / 64;
-  for (unsigned base = 0; base < ntiles; base += CULL_THREADS) {
-    const unsigned t = base + tid;
-    bool keep = false;
-    if (t < ntiles) {
-      double d2 = 0.0;
-#pragma unroll
-      for (int c = 0; c < DIM; c++) {
-        const double tl = tbox[(size_t)t * (2 * DIM) + 2 * c], th = tbox[(size_t)t * (2 * DIM) + 2 * c + 1];
-        const double gap = fmax(0.0, fmax(tl - bhi[c], blo[c] - th));
-        d2 = fma(gap, gap, d2);
-      }
-      keep = KIND == GSL_SINTERP_RBF_GAUSSIAN ? d2 * coef > -72.0 : d2 * (coef * coef) < 1.0;
-    }
-    const unsigned long long b = __builtin_amdgcn_ballot_w64(keep);
-    if (lane == 0 && (base / 64 + wave) < nmask) s_mask[base / 64 + wave] = b;
-  }
-  __syncthreads();
-
-  /* the kept tiles, ascending, CULL_STAGE centres per LDS stage */
-  unsigned mi = 0;
-  unsigned long long mask = nmask ? s_mask[0] : 0ULL;
-  for (;;) {
-    int cnt = 0;
-    __syncthreads();                                       /* the previous stage has been consumed */
-    while (cnt + CT <= CULL_STAGE) {
-      while (!mask && mi + 1 < nmask) mask = s_mask[++mi];
-      if (!mask) break;
-      const unsigned t = mi * 64 + (unsigned)__builtin_ctzll(mask);
-      mask &= mask - 1;
-      const size_t c0 = (size_t)t * CT;
-      const int tc = (int)((n - c0) < (size_t)CT ? (n - c0) : (size_t)CT);
-      for (int e = tid; e < tc * (DIM + 1); e += CULL_THREADS) s_c[cnt * (DIM + 1) + e] = xs[c0 * (DIM + 1) + e];
-      cnt += tc;
-    }
-    if (cnt == 0) break;
-    __syncthreads();
-#pragma unroll 2
-    for (int e = 0; e < cnt; e++) {
-      double xc[DIM];
-#pragma unroll
-      for (int c = 0; c < DIM; c++) xc[c] = s_c[e * (DIM + 1) + c];
-      const double wj = s_c[e * (DIM + 1) + DIM];
-      double d[TPT][DIM], r2[TPT];
-      bool take[TPT], need = false;
-#pragma unroll
-      for (int tt = 0; tt < TPT; tt++) {
-        r2[tt] = 0.0;
-#pragma unroll
-        for (int c = 0; c < DIM; c++) { d[tt][c] = yy[tt][c] - xc[c]; r2[tt] = fma(d[tt][c], d[tt][c], r2[tt]); }
-        take[tt] = KIND == GSL_SINTERP_RBF_GAUSSIAN ? r2[tt] * coef > -72.0 : r2[tt] * (coef * coef) < 1.0;
-        need |= take[tt];
-      }
-      if (__builtin_amdgcn_ballot_w64(need) == 0) continue;
-#pragma unroll
-      for (int tt = 0; tt < TPT; tt++) {
-        double psi;
-        const double ph = phi_psi_r2<KIND, 1>(r2[tt], coef, s_t0, (const double *)NULL, &psi);
-        const double a = fma(wj, ph, acc[tt]);
-        const double p = wj * psi;
-        acc[tt] = take[tt] ? a : acc[tt];
-#pragma unroll
-        for (int c = 0; c < DIM; c++) { const double ga = fma(p, d[tt][c], gacc[tt][c]); gacc[tt][c] = take[tt] ? ga : gacc[tt][c]; }
-      }
-    }
-  }
-  grad_store<KIND, DIM, TPT>(kidx, m, yy, acc, gacc, gscale, s, g, gtda);
+  return rbf_sweep_dispatch(ctx, kind, j);
 }
 
 /* s[k] += c_0 + sum_a c_a y[k][a] (the operations of add_poly_kernel / add_const_kernel in solve.hip: the same bits) and
@@ -992,52 +866,6 @@ grad_tail_kernel(double *__restrict__ s, double *__restrict__ g, size_t gtda, si
   }
 }
 
-template <int KIND, int TPT>
-static int launch_grad(gsl_sinterp_hip_ctx *ctx, double coef, double gscale, const double *d_x, size_t n, int dim, size_t xtda,
-                       const double *d_w, const double *d_y, size_t m, size_t ytda, double *d_s, double *d_g, size_t gtda, const int *d_perm)
-{
-  const size_t per_block = (size_t)EV_THREADS * TPT;
-  dim3 grid((unsigned)((m + per_block - 1) / per_block));
-#define GRAD_LAUNCH(D)                                                                                                                 \
-  hipLaunchKernelGGL((rbf_grad_kernel<KIND, D, TPT>), grid, dim3(EV_THREADS), 0, ctx->stream, coef, gscale, d_x, n, xtda, d_w, d_y, m, \
-                     ytda, d_s, d_g, gtda, d_perm)
-  switch (dim) {
-    case 1: GRAD_LAUNCH(1); break;
-    case 2: GRAD_LAUNCH(2); break;
-    default: GRAD_LAUNCH(3); break;
-  }
-#undef GRAD_LAUNCH
-  LAUNCH_CHECK(ctx);
-  return ST_SUCCESS;
-}
-
-template <int KIND, int TPT>
-static int launch_grad_cull(gsl_sinterp_hip_ctx *ctx, double coef, double gscale, const double *d_x, size_t n, int dim, size_t xtda,
-                            const double *d_w, const double *d_y, size_t m, size_t ytda, double *d_s, double *d_g, size_t gtda,
-                            const int *d_perm, unsigned long long model_id)
-{
-  cull_model cm;
-  int st = cull_pack(ctx, KIND, d_x, n, dim, xtda, d_w, model_id, &cm);
-  if (st) return st;
-  const size_t per_block = (size_t)CULL_THREADS * TPT;
-  dim3 grid((unsigned)((m + per_block - 1) / per_block));
-#define GRAD_LAUNCH(D, C)                                                                                                              \
-  hipLaunchKernelGGL((rbf_grad_cull_kernel<KIND, D, TPT, C>), grid, dim3(CULL_THREADS), 0, ctx->stream, coef, gscale, cm.xs, n, cm.tbox, \
-                     cm.ntiles, d_y, m, ytda, d_s, d_g, gtda, d_perm)
-  switch (dim) {
-    case 1: GRAD_LAUNCH(1, 32); break;
-    case 2:
-      if (cm.ct == 8) GRAD_LAUNCH(2, 8);
-      else if (cm.ct == 16) GRAD_LAUNCH(2, 16);
-      else GRAD_LAUNCH(2, 32);
-      break;
-    default: GRAD_LAUNCH(3, 32); break;
-  }
-#undef GRAD_LAUNCH
-  LAUNCH_CHECK(ctx);
-  return ST_SUCCESS;
-}
-
 extern "C" int gsl_sinterp_hip_rbf_eval_grad(gsl_sinterp_hip_ctx *ctx, int kind, double eps, const double *h_tail, const double *d_x,
                                              size_t n, int dim, size_t xtda, const double *d_w, const double *d_y, size_t m,
                                              size_t ytda, double *d_s, double *d_g, size_t gtda, unsigned long long model_id)
@@ -1050,32 +878,15 @@ extern "C" int gsl_sinterp_hip_rbf_eval_grad(gsl_sinterp_hip_ctx *ctx, int kind,
   if (m == 0) return ST_SUCCESS;
   int st = ensure_tables(ctx);
   if (st) return st;
-  const double coef = kernel_coef(kind, eps), gscale = rbf_grad_scale(kind, eps);
-  const bool local = kind != GSL_SINTERP_RBF_TPS;
+  /* one level of target sort whatever the batch size: the two-level reorder's result path carries one scalar per target */
   int *d_perm = NULL;
-  if (local && m >= 4096 && !(getenv("GSL_SINTERP_NO_SORT") && getenv("GSL_SINTERP_NO_SORT")[0] == '1')) {
+  if (wants_target_sort(kind, m)) {
     st = sinterp_sort_targets(ctx, d_y, m, ytda, dim, 64, &d_perm);
     if (st) return st;
   }
-  /* the kernel by N only, targets per lane by m and dim: the rules of rbf_eval_dispatch */
-  static const bool no_cull = getenv("GSL_SINTERP_NO_CULL") && getenv("GSL_SINTERP_NO_CULL")[0] == '1';
-#define GRAD_ARGS ctx, coef, gscale, d_x, n, dim, xtda, d_w, d_y, m, ytda, d_s, d_g, gtda, d_perm
-  if (local && !no_cull && n >= 1024 && (n + 31) / 32 <= CULL_MAX_TILES) {
-    const bool small = m < (size_t)CULL_THREADS * 2 * 512 || dim == 3;
-    if (kind == GSL_SINTERP_RBF_WENDLAND)
-      st = small ? launch_grad_cull<GSL_SINTERP_RBF_WENDLAND, 1>(GRAD_ARGS, model_id) : launch_grad_cull<GSL_SINTERP_RBF_WENDLAND, 2>(GRAD_ARGS, model_id);
-    else
-      st = small ? launch_grad_cull<GSL_SINTERP_RBF_GAUSSIAN, 1>(GRAD_ARGS, model_id) : launch_grad_cull<GSL_SINTERP_RBF_GAUSSIAN, 2>(GRAD_ARGS, model_id);
-  } else {
-    const bool small = m < (size_t)EV_THREADS * 2 * 512;
-    if (kind == GSL_SINTERP_RBF_WENDLAND)
-      st = small ? launch_grad<GSL_SINTERP_RBF_WENDLAND, 1>(GRAD_ARGS) : launch_grad<GSL_SINTERP_RBF_WENDLAND, 2>(GRAD_ARGS);
-    else if (kind == GSL_SINTERP_RBF_GAUSSIAN)
-      st = small ? launch_grad<GSL_SINTERP_RBF_GAUSSIAN, 1>(GRAD_ARGS) : launch_grad<GSL_SINTERP_RBF_GAUSSIAN, 2>(GRAD_ARGS);
-    else
-      st = small ? launch_grad<GSL_SINTERP_RBF_TPS, 1>(GRAD_ARGS) : launch_grad<GSL_SINTERP_RBF_TPS, 2>(GRAD_ARGS);
-  }
-#undef GRAD_ARGS
+  const sweep_job j = {kernel_coef(kind, eps), d_x, n, dim, xtda, d_w, d_y, m, ytda, d_perm, d_s, NULL, d_g, gtda, rbf_grad_scale(kind, eps),
+                       model_id};
+  st = rbf_sweep_dispatch(ctx, kind, j);
   if (st || !h_tail) return st;
   /* tail c_0 + sum_a c_a y_a: the affine thin-plate polynomial, or kriging's {mu, 0, ...}; h_tail[0 .. dim] only */
   int linear = 0;

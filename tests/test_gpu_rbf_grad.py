@@ -1,5 +1,6 @@
-"""-m gpu: value + gradient of the RBF-family interpolants from the fused sweeps (csrc/hip/rbf.hip: rbf_grad_kernel,
-rbf_grad_cull_kernel).
+"""-m gpu: value + gradient of the RBF-family interpolants from the fused sweeps (csrc/hip/rbf.hip: rbf_grad_kernel and
+rbf_grad_cull_kernel, the GRAD instances of the bodies rbf_sweep / rbf_sweep_cull that rbf_eval_kernel and
+rbf_eval_gauss_cull_kernel share).
 
 The oracle has no gradient.  The reference is the formula in numpy fp64,
     grad s(y) = sum_j w_j psi(r_j^2) (y - x_j) [+ c_1 .. c_dim],   psi = phi'(r) / r
@@ -16,6 +17,7 @@ Non-finite targets: "an infinite coordinate takes no term" is a statement about 
 (Gaussian, Wendland); a thin-plate term at infinite distance is not finite and nothing is asserted about it."""
 import numpy as np
 import pytest
+import torch
 
 from gpu_util import Canaried, bits, dev, ptr
 
@@ -89,7 +91,8 @@ def targets(orc, x, m):
 
 PLAIN = [("gaussian", 2, 513), ("gaussian", 1, 130), ("gaussian", 3, 700), ("tps", 2, 513), ("tps", 3, 333), ("tps", 1, 130),
          ("tps_affine", 2, 600), ("wendland", 2, 513), ("kriging", 2, 513)]
-CULLED = [("gaussian", 2, 1100), ("gaussian", 3, 1200), ("wendland", 2, 1100), ("wendland", 3, 1200), ("kriging", 2, 1100)]
+CULLED = [("gaussian", 2, 1100), ("gaussian", 3, 1200), ("wendland", 2, 1100), ("wendland", 3, 1200), ("kriging", 2, 1100),
+          ("gaussian", 1, 1100), ("wendland", 1, 1100)]        # the 1-D culled kernel (DIM = 1, tiles of 32)
 
 
 @pytest.mark.parametrize("typ,dim,n", PLAIN + CULLED)
@@ -121,7 +124,7 @@ def test_affine_exactness(pkg, orc):
 
 
 @pytest.mark.parametrize("typ,n,m", [("gaussian", 1100, 5000), ("gaussian", 1100, 131077), ("gaussian", 1100, 262147),
-                                     ("tps", 100, 262147)])
+                                     ("tps", 100, 262147), ("wendland", 1100, 131077)])
 def test_sorted_route_and_two_targets_per_lane(pkg, orc, typ, n, m):
     dim = 2
     s, x, w, eps, tail = model(pkg, orc, typ, dim, n)
@@ -251,4 +254,5 @@ def test_device_list(pkg, orc):
     assert st == 0 and np.array_equal(bits(val2), bits(val)) and np.array_equal(bits(g2), bits(g))
     d_y, d_s, d_g = dev(y), dev(np.zeros(len(y))), dev(np.zeros((len(y), dim)))
     assert grp.eval_grad_resident(ptr(d_y), len(y), dim, ptr(d_s), ptr(d_g), dim) == 0
+    torch.cuda.synchronize()                                         # the group's members run on streams of their own
     assert np.array_equal(bits(d_g.cpu().numpy()), bits(g)) and np.array_equal(bits(d_s.cpu().numpy()), bits(val))
