@@ -138,6 +138,11 @@ SIGNATURES = {
     "gsl_sinterp_hip_rbf_eval": (_i, [_vp, _i, _d, _vp, _sz, _i, _sz, _vp, _vp, _sz, _sz, _vp]),
     "gsl_sinterp_hip_rbf_eval_model": (_i, [_vp, _i, _d, _vp, _sz, _i, _sz, _vp, _vp, _sz, _sz, _vp, C.c_uint64]),
     "gsl_sinterp_hip_rbf_eval_grad": (_i, [_vp, _i, _d, _pd, _vp, _sz, _i, _sz, _vp, _vp, _sz, _sz, _vp, _vp, _sz, C.c_uint64]),
+    "gsl_sinterp_hip_rbf_eval_fields": (_i, [_vp, _i, _d, _pd, _vp, _sz, _i, _sz, _vp, _sz, _sz, _vp, _sz, _sz, _vp, _sz, C.c_uint64]),
+    "gsl_sinterp_hip_rbf_fields_block": (_i, []),
+    "gsl_sinterp_hip_rbf_fields_block_small": (_i, []),
+    "gsl_sinterp_hip_rbf_solve_fields": (_i, [_vp, _i, _d, _vp, _sz, _i, _sz, _vp, _sz, _vp, _sz, _sz, _pi]),
+    "gsl_sinterp_hip_krige_solve_fields": (_i, [_vp, _i, _d, _d, _vp, _sz, _i, _sz, _vp, _sz, _vp, _sz, _sz, _pd, _pi]),
     "gsl_sinterp_hip_ctx_device": (_i, [_vp]),
     "gsl_sinterp_hip_rbf_solve": (_i, [_vp, _i, _d, _vp, _sz, _i, _sz, _vp, _sz, _vp, _pi]),
     "gsl_sinterp_hip_gemm_minus": (_i, [_vp, _sz, _sz, _sz, _vp, _sz, _vp, _sz, _i, _vp, _sz, _i]),
@@ -248,6 +253,14 @@ SIGNATURES = {
     "gsl_sinterp_eval_grad_e": (_i, [C.POINTER(gsl_sinterp), _pv, _pd, _pv]),
     "gsl_sinterp_eval_grad_many": (_i, [C.POINTER(gsl_sinterp), _pm, _pv, _pm]),
     "gsl_sinterp_eval_grad_resident": (_i, [C.POINTER(gsl_sinterp), _vp, _sz, _sz, _vp, _vp, _sz]),
+    "gsl_sinterp_init_fields": (_i, [C.POINTER(gsl_sinterp), _pm, _pm]),
+    "gsl_sinterp_n_fields": (_sz, [C.POINTER(gsl_sinterp)]),
+    "gsl_sinterp_eval_fields_e": (_i, [C.POINTER(gsl_sinterp), _pv, _pv]),
+    "gsl_sinterp_eval_fields_many": (_i, [C.POINTER(gsl_sinterp), _pm, _pm]),
+    "gsl_sinterp_eval_fields_resident": (_i, [C.POINTER(gsl_sinterp), _vp, _sz, _sz, _vp, _sz]),
+    "gsl_sinterp_get_field_weights": (_i, [C.POINTER(gsl_sinterp), _sz, _pv]),
+    "gsl_sinterp_field_mean": (_i, [C.POINTER(gsl_sinterp), _sz, _pd]),
+    "gsl_sinterp_field_poly": (_i, [C.POINTER(gsl_sinterp), _sz, _pv]),
     "gsl_sinterp_set_rcond": (_i, [C.POINTER(gsl_sinterp), _i]),
     "gsl_sinterp_rcond": (_i, [C.POINTER(gsl_sinterp), _pd]),
     "gsl_sinterp_route": (_i, [C.POINTER(gsl_sinterp)]),
@@ -444,6 +457,37 @@ class HipContext:
         assert t is None or t.size >= dim + 1
         return lib().gsl_sinterp_hip_rbf_eval_grad(self._h, kind, eps, None if t is None else t.ctypes.data_as(_pd), d_x, n, dim, xtda,
                                                    d_w, d_y, m, ytda, d_s, d_g, gtda, model_id)
+
+    def rbf_eval_fields(self, kind, eps, d_x, n, dim, xtda, d_w, ldw, nf, d_y, m, ytda, d_s, stda, tail=None, model_id=0):
+        """nf fields from one sweep: column q of the weights at d_w + 8 q ldw, target k's field q at d_s + 8 (k stda + q);
+        tail: None or nf x (dim + 1) numbers, {c_0 .. c_dim} per field.  Returns the status."""
+        t = None if tail is None else np.ascontiguousarray(tail, dtype=np.float64).reshape(-1)
+        assert t is None or t.size >= nf * (dim + 1)
+        return lib().gsl_sinterp_hip_rbf_eval_fields(self._h, kind, eps, None if t is None else t.ctypes.data_as(_pd), d_x, n, dim, xtda,
+                                                     d_w, ldw, nf, d_y, m, ytda, d_s, stda, model_id)
+
+    @staticmethod
+    def rbf_fields_block():
+        """fields per pass of the fields sweep (the library's compile-time NF)"""
+        return lib().gsl_sinterp_hip_rbf_fields_block()
+
+    @staticmethod
+    def rbf_fields_block_small():
+        """the last <= this many fields of a sweep go through the small instance"""
+        return lib().gsl_sinterp_hip_rbf_fields_block_small()
+
+    def rbf_solve_fields(self, kind, eps, d_x, n, dim, xtda, d_phi, lda, d_w, ldw, nf):
+        """one fill, one Cholesky, nf solves in place (column q at d_w + 8 q ldw); returns (status, route)"""
+        route = C.c_int(0)
+        st = lib().gsl_sinterp_hip_rbf_solve_fields(self._h, kind, eps, d_x, n, dim, xtda, d_phi, lda, d_w, ldw, nf, C.byref(route))
+        return st, route.value
+
+    def krige_solve_fields(self, kind, eps, nugget, d_x, n, dim, xtda, d_phi, lda, d_w, ldw, nf):
+        """ordinary kriging of nf fields on one factor; returns (status, route, means[nf])"""
+        route, mean = C.c_int(0), np.zeros(nf, dtype=np.float64)
+        st = lib().gsl_sinterp_hip_krige_solve_fields(self._h, kind, eps, nugget, d_x, n, dim, xtda, d_phi, lda, d_w, ldw, nf,
+                                                      mean.ctypes.data_as(_pd), C.byref(route))
+        return st, route.value, mean
 
     def device(self):
         return lib().gsl_sinterp_hip_ctx_device(self._h)
@@ -932,6 +976,43 @@ class Sinterp:
 
     def eval_grad_resident(self, d_y, m, ytda, d_s, d_g, gtda):
         return lib().gsl_sinterp_eval_grad_resident(self._p, d_y, m, ytda, d_s, d_g, gtda)
+
+    def init_fields(self, x, F):
+        """F: size x K responses (row stride honoured); one weight vector per column"""
+        return lib().gsl_sinterp_init_fields(self._p, C.byref(as_matrix(x)), C.byref(as_matrix(F)))
+
+    def n_fields(self):
+        return int(lib().gsl_sinterp_n_fields(self._p))
+
+    def eval_fields_e(self, y):
+        """(status, s): the K values at one target; NaN on failure"""
+        s = np.full(max(self.n_fields(), 1), np.nan)
+        st = lib().gsl_sinterp_eval_fields_e(self._p, C.byref(as_vector(np.ascontiguousarray(y, dtype=np.float64))), C.byref(as_vector(s)))
+        return st, s
+
+    def eval_fields_many(self, y, out=None):
+        """(status, S): the m x K values at the rows of y; out = preallocated S (row stride honoured)"""
+        S = np.empty((y.shape[0], max(self.n_fields(), 1)), dtype=np.float64) if out is None else out
+        st = lib().gsl_sinterp_eval_fields_many(self._p, C.byref(as_matrix(y)), C.byref(as_matrix(S)))
+        return st, S
+
+    def eval_fields_resident(self, d_y, m, ytda, d_s, stda):
+        return lib().gsl_sinterp_eval_fields_resident(self._p, d_y, m, ytda, d_s, stda)
+
+    def field_weights(self, q):
+        w = np.empty(self._p.contents.size, dtype=np.float64)
+        st = lib().gsl_sinterp_get_field_weights(self._p, q, C.byref(as_vector(w)))
+        return st, w
+
+    def field_mean(self, q):
+        v = C.c_double(0)
+        st = lib().gsl_sinterp_field_mean(self._p, q, C.byref(v))
+        return st, v.value
+
+    def field_poly(self, q):
+        c = np.zeros(self._p.contents.dim + 1, dtype=np.float64)
+        st = lib().gsl_sinterp_field_poly(self._p, q, C.byref(as_vector(c)))
+        return st, c
 
     def poly(self):
         c = np.zeros(self._p.contents.dim + 1, dtype=np.float64)

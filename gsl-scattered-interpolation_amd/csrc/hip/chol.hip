@@ -683,6 +683,21 @@ int sinterp_cholesky_factor_solve_sym(gsl_sinterp_hip_ctx *ctx, size_t n, double
   return chol_factor_solve(ctx, n, d_a, lda, h_info, d_x, ldx, nrhs, true);
 }
 
+/* any number of right-hand sides on ONE factor (the fields solves of solve.hip): the first min(nrhs, TRSV_MAXR) ride the
+   factorisation -- the folded forward substitution where it applies, the two sweeps otherwise -- and the remaining columns
+   are solved against the finished factor in groups of <= TRSV_MAXR.  Columns of different groups agree to rounding, not
+   bitwise (the folded and the two-sweep substitutions round differently). */
+int sinterp_cholesky_factor_solve_many_sym(gsl_sinterp_hip_ctx *ctx, size_t n, double *d_a, size_t lda, int *h_info, double *d_x,
+                                           size_t ldx, int nrhs)
+{
+  EXCLUSIVE_SECTION(ctx);
+  const int first = nrhs < TRSV_MAXR ? nrhs : TRSV_MAXR;
+  int st = chol_factor_solve(ctx, n, d_a, lda, h_info, d_x, ldx, first, true);
+  for (int q = first; q < nrhs && !st; q += TRSV_MAXR)
+    st = sinterp_cholesky_svx_multi(ctx, n, d_a, lda, d_x + (size_t)q * ldx, ldx, nrhs - q < TRSV_MAXR ? nrhs - q : TRSV_MAXR);
+  return st;
+}
+
 /* the public form: cholesky_decomp1's contract for d_a (lower triangle read, original kept in the strict upper one) */
 extern "C" int gsl_sinterp_hip_cholesky_factor_solve(gsl_sinterp_hip_ctx *ctx, size_t n, double *d_a, size_t lda, int *h_info,
                                                      double *d_x, size_t ldx, int nrhs)

@@ -33,7 +33,12 @@ struct gsl_sinterp_hip_ctx {
   void *d_cent;             /* cell-ordered packed centres {x, w} + tile boxes of the Gaussian sweep */
   size_t cent_bytes;
   /* key of the packed centres currently in d_cent (gsl_sinterp_hip_rbf_eval_model); id 0 = nothing cached */
-  struct { unsigned long long id; const void *x, *w; size_t n, xtda; int dim, kind; } cent_key;
+  struct CentKey { unsigned long long id; const void *x, *w; size_t n, xtda, ldw; int dim, kind, nf; } cent_key;   /* scalar: nf = 0, ldw = 0 */
+  /* the fields sweep's records {x, w_0 .. w_{K-1}} have a slot of their own (a K-field model and its field 0 used as a
+     scalar model share id, x and w: one slot would be repacked at every change of entry); nf and ldw tell its keys apart */
+  void *d_cent_f;
+  size_t cent_f_bytes;
+  CentKey cent_key_f;
   void *d_walk;             /* affine walk records + queue of the barycentric walk (bary.hip), rebuilt per batch */
   size_t walk_bytes;
   hipStream_t side_stream;  /* bary.hip: independent kernels of one evaluation run beside the main stream */
@@ -184,6 +189,10 @@ int sinterp_cholesky_decomp1_sym(gsl_sinterp_hip_ctx *ctx, size_t n, double *d_a
 /* the same followed by the solve of nrhs right-hand sides in place (forward substitution folded into the factorisation when every panel is 128 wide) */
 int sinterp_cholesky_factor_solve_sym(gsl_sinterp_hip_ctx *ctx, size_t n, double *d_a, size_t lda, int *h_info, double *d_x, size_t ldx,
                                       int nrhs);
+/* the same for ANY number of right-hand sides: the first min(nrhs, 5) ride the factorisation as above, the rest are solved
+   against the finished factor in groups of <= 5 (sinterp_cholesky_svx_multi) */
+int sinterp_cholesky_factor_solve_many_sym(gsl_sinterp_hip_ctx *ctx, size_t n, double *d_a, size_t lda, int *h_info, double *d_x,
+                                           size_t ldx, int nrhs);
 /* second grow-only buffer for vectors that must outlive factorisation workspaces */
 int sinterp_aux(gsl_sinterp_hip_ctx *ctx, size_t bytes, void **out);
 int sinterp_invbuf(gsl_sinterp_hip_ctx *ctx, size_t bytes, void **out);
@@ -226,5 +235,6 @@ int sinterp_walkbuf(gsl_sinterp_hip_ctx *ctx, size_t bytes, void **out);
 /* sort.hip: bounding box of n points as order-preserving keys, box[2c] = min, box[2c+1] = max (device, 48 bytes) */
 int sinterp_bbox_keys(gsl_sinterp_hip_ctx *ctx, const double *d_p, size_t n, size_t tda, int dim, unsigned long long *d_box);
 int sinterp_centbuf(gsl_sinterp_hip_ctx *ctx, size_t bytes, void **out);
+int sinterp_centbuf_fields(gsl_sinterp_hip_ctx *ctx, size_t bytes, void **out);
 
 #endif

@@ -198,41 +198,66 @@ __device__ __forceinline__ bool nan_target(const double (&yy)[DIM])
    Wendland target fails the criterion for every centre: no term is taken, value and gradient are 0 (terms are SELECTED,
    never multiplied by 0, so inf - x_j does no harm).
 
+   Fields.  A third mode of the same two bodies (NF > 1 weights per staged centre, FLD): K weight vectors on the same centres,
+   NF accumulators per target, phi and take still computed once per pair.  Field q has the bits of the value sweep run on
+   column q: the same terms, order, take-criterion and kernel choice (rbf_sweep_dispatch); NF = 1 is the code of the two
+   modes above, instruction for instruction.
+
    Target order.  The value entry sorts large batches with the two-level reorder and stores through its map (omap); the
    gradient entry takes the one-level permutation route (sinterp_sort_targets; the kernels read and write through perm)
    whatever the batch size: the two-level reorder's result path carries one scalar per target. */
 
-/* one (target, centre) pair: d = y - x_j, r2 = |d|^2, wj the centre's weight; the term is added only when take is set */
-template <int KIND, int DIM, bool GRAD>
-__device__ __forceinline__ void sweep_term(double r2, const double (&d)[DIM], double wj, double coef, bool take, const double *s_t0,
-                                           const double *lt_lane, double &acc, double (&gacc)[DIM])
+/* one (target, centre) pair: d = y - x_j, r2 = |d|^2, wj the centre's NF weights (one per field of the block; NF = 1 in
+   the value and value + gradient modes); the terms are added only when take is set.  phi and take are computed once per
+   pair: a further field costs its FMA and its select */
+template <int KIND, int DIM, bool GRAD, int NF>
+__device__ __forceinline__ void sweep_term(double r2, const double (&d)[DIM], const double (&wj)[NF], double coef, bool take,
+                                           const double *s_t0, const double *lt_lane, double (&acc)[NF], double (&gacc)[DIM])
 {
   if constexpr (GRAD) {
+    static_assert(NF == 1, "the gradient sweep carries one field");
     double psi;
     const double ph = phi_psi_r2<KIND, LOG_COPIES>(r2, coef, s_t0, lt_lane, &psi);
-    const double a = fma(wj, ph, acc);
-    const double p = wj * psi;                   /* a product of its own: the value's FMA is untouched */
-    acc = take ? a : acc;
+    const double a = fma(wj[0], ph, acc[0]);
+    const double p = wj[0] * psi;                /* a product of its own: the value's FMA is untouched */
+    acc[0] = take ? a : acc[0];
 #pragma unroll
     for (int c = 0; c < DIM; c++) { const double ga = fma(p, d[c], gacc[c]); gacc[c] = take ? ga : gacc[c]; }
   } else {
-    const double a = fma(wj, phi_r2<KIND, LOG_COPIES>(r2, coef, s_t0, lt_lane), acc);
-    acc = take ? a : acc;
+    const double ph = phi_r2<KIND, LOG_COPIES>(r2, coef, s_t0, lt_lane);
+#pragma unroll
+    for (int q = 0; q < NF; q++) { const double a = fma(wj[q], ph, acc[q]); acc[q] = take ? a : acc[q]; }
   }
 }
 
+/* The fields mode of the two sweeps (FLD): K weight vectors on the same centres, NF of them per pass.  w (plain sweep)
+   points at the first column of the pass, column q at w + q * ldw; xs (culled sweep) holds {x, w_0 .. w_{K-1}} records of
+   rs = DIM + K doubles and q0 is the first field of the pass; s points at the pass's first output column, target k's
+   field q at s[k * stda + q].  nfa <= NF fields are live: a ragged last block neither reads a weight nor writes a result
+   beyond them (the idle accumulators run on zero weights). */
+struct sweep_fields {
+  size_t ldw, stda;
+  int nfa, q0, rs;
+};
+
 /* value sweep: s through omap when given.  GRAD: s may be NULL (gradient only); row k of g = g + k * gtda, DIM entries
    written, the constant of psi (rbf_grad_scale) applied here, once per target */
-template <int KIND, int DIM, int TPT, bool GRAD>
-__device__ __forceinline__ void sweep_store(const size_t (&kidx)[TPT], size_t m, const double (&yy)[TPT][DIM], const double (&acc)[TPT],
+template <int KIND, int DIM, int TPT, bool GRAD, int NF, bool FLD>
+__device__ __forceinline__ void sweep_store(const size_t (&kidx)[TPT], size_t m, const double (&yy)[TPT][DIM], const double (&acc)[TPT][NF],
                                             const double (&gacc)[TPT][DIM], double *__restrict__ s, const unsigned *__restrict__ omap,
-                                            double *__restrict__ g, size_t gtda, double gscale)
+                                            double *__restrict__ g, size_t gtda, double gscale, const sweep_fields &F)
 {
 #pragma unroll
   for (int t = 0; t < TPT; t++) {
     if (kidx[t] >= m) continue;
     const bool isn = nan_target<DIM>(yy[t]);
-    const double v = (KIND != GSL_SINTERP_RBF_TPS && isn) ? NAN : acc[t];
+    if constexpr (FLD) {                         /* the NaN rule holds for every field of the row */
+#pragma unroll
+      for (int q = 0; q < NF; q++)
+        if (q < F.nfa) s[kidx[t] * F.stda + q] = (KIND != GSL_SINTERP_RBF_TPS && isn) ? NAN : acc[t][q];
+      continue;
+    }
+    const double v = (KIND != GSL_SINTERP_RBF_TPS && isn) ? NAN : acc[t][0];
     if constexpr (GRAD) {
       if (s) s[kidx[t]] = v;
 #pragma unroll
@@ -247,15 +272,17 @@ __device__ __forceinline__ void sweep_store(const size_t (&kidx)[TPT], size_t m,
 #define EV_THREADS 256
 #define EV_TJ 512
 
-template <int KIND, int DIM, int TPT, bool GRAD>
+template <int KIND, int DIM, int TPT, bool GRAD, int NF = 1, bool FLD = false, int TJ = EV_TJ>
 __device__ __forceinline__ void rbf_sweep(double coef, const double *__restrict__ x, size_t n, size_t xtda, const double *__restrict__ w,
                                           const double *__restrict__ y, size_t m, size_t ytda, const int *__restrict__ perm,
                                           double *__restrict__ s, const unsigned *__restrict__ omap, double *__restrict__ g, size_t gtda,
-                                          double gscale)
+                                          double gscale, const sweep_fields F = sweep_fields())
 {
+  static_assert(FLD || NF == 1, "several weights per centre: the fields mode");
+  constexpr int REC = DIM + NF;
   __shared__ double s_t0[KIND == GSL_SINTERP_RBF_GAUSSIAN ? TBL_N : 1];
   __shared__ __attribute__((aligned(16))) double s_lt[KIND == GSL_SINTERP_RBF_TPS ? LOG_LDS : 2];
-  __shared__ double s_c[EV_TJ * (DIM + 1)];       /* per centre: x[0..DIM-1], w */
+  __shared__ double s_c[TJ * REC];                /* per centre: x[0..DIM-1], w[0..NF-1] */
   load_tables<LOG_COPIES>(s_t0, s_lt, KIND);
   const double *lt_lane = s_lt + (threadIdx.x & (LOG_COPIES - 1)) * 2;
 
@@ -263,31 +290,39 @@ __device__ __forceinline__ void rbf_sweep(double coef, const double *__restrict_
      ADJACENT slots so they are spatial neighbours too */
   const size_t k0 = (((size_t)blockIdx.x * EV_THREADS) + threadIdx.x) * TPT;
   size_t kidx[TPT];
-  double yy[TPT][DIM], acc[TPT], gacc[TPT][DIM];
+  double yy[TPT][DIM], acc[TPT][NF], gacc[TPT][DIM];
 #pragma unroll
   for (int t = 0; t < TPT; t++) {
     const size_t slot = k0 + (size_t)t;
     kidx[t] = slot < m ? (perm ? (size_t)perm[slot] : slot) : m;
-    acc[t] = 0.0;
+#pragma unroll
+    for (int q = 0; q < NF; q++) acc[t][q] = 0.0;
 #pragma unroll
     for (int c = 0; c < DIM; c++) { yy[t][c] = kidx[t] < m ? y[kidx[t] * ytda + c] : 0.0; gacc[t][c] = 0.0; }
   }
 
-  for (size_t jt = 0; jt < n; jt += EV_TJ) {
-    const int cnt = (int)((n - jt) < (size_t)EV_TJ ? (n - jt) : (size_t)EV_TJ);
+  for (size_t jt = 0; jt < n; jt += TJ) {
+    const int cnt = (int)((n - jt) < (size_t)TJ ? (n - jt) : (size_t)TJ);
     __syncthreads();
     for (int e = threadIdx.x; e < cnt; e += EV_THREADS) {
 #pragma unroll
-      for (int c = 0; c < DIM; c++) s_c[e * (DIM + 1) + c] = x[(jt + e) * xtda + c];
-      s_c[e * (DIM + 1) + DIM] = (KIND == GSL_SINTERP_RBF_TPS ? 0.5 : 1.0) * w[jt + e];
+      for (int c = 0; c < DIM; c++) s_c[e * REC + c] = x[(jt + e) * xtda + c];
+      if constexpr (FLD) {
+#pragma unroll
+        for (int q = 0; q < NF; q++)
+          s_c[e * REC + DIM + q] = q < F.nfa ? (KIND == GSL_SINTERP_RBF_TPS ? 0.5 : 1.0) * w[(size_t)q * F.ldw + jt + e] : 0.0;
+      } else {
+        s_c[e * REC + DIM] = (KIND == GSL_SINTERP_RBF_TPS ? 0.5 : 1.0) * w[jt + e];
+      }
     }
     __syncthreads();
 #pragma unroll 2
     for (int e = 0; e < cnt; e++) {
-      double xc[DIM];
+      double xc[DIM], wj[NF];
 #pragma unroll
-      for (int c = 0; c < DIM; c++) xc[c] = s_c[e * (DIM + 1) + c];
-      const double wj = s_c[e * (DIM + 1) + DIM];
+      for (int c = 0; c < DIM; c++) xc[c] = s_c[e * REC + c];
+#pragma unroll
+      for (int q = 0; q < NF; q++) wj[q] = s_c[e * REC + DIM + q];
       double d[TPT][DIM], r2[TPT];
 #pragma unroll
       for (int t = 0; t < TPT; t++) {
@@ -319,10 +354,10 @@ __device__ __forceinline__ void rbf_sweep(double coef, const double *__restrict_
       }
 #pragma unroll
       for (int t = 0; t < TPT; t++)
-        sweep_term<KIND, DIM, GRAD>(r2[t], d[t], wj, KIND == GSL_SINTERP_RBF_TPS ? 1.0 : coef, take[t], s_t0, lt_lane, acc[t], gacc[t]);
+        sweep_term<KIND, DIM, GRAD, NF>(r2[t], d[t], wj, KIND == GSL_SINTERP_RBF_TPS ? 1.0 : coef, take[t], s_t0, lt_lane, acc[t], gacc[t]);
     }
   }
-  sweep_store<KIND, DIM, TPT, GRAD>(kidx, m, yy, acc, gacc, s, omap, g, gtda, gscale);
+  sweep_store<KIND, DIM, TPT, GRAD, NF, FLD>(kidx, m, yy, acc, gacc, s, omap, g, gtda, gscale, F);
 }
 
 template <int KIND, int DIM, int TPT>
@@ -343,6 +378,31 @@ rbf_grad_kernel(double coef, double gscale, const double *__restrict__ x, size_t
   rbf_sweep<KIND, DIM, TPT, true>(coef, x, n, xtda, w, y, m, ytda, perm, s, nullptr, g, gtda, gscale);
 }
 
+/* Fields: NF accumulators per target, one target per lane (the NF chains give the ILP that the second target buys the
+   scalar sweep).  Two block sizes, both measured ("Several fields"): a pass of RBF_NF = 8 fields costs 1.6 scalar
+   sweeps, a pass of RBF_NF_SMALL = 4 costs 1.25, so K fields go in passes of 8 while more than 4 are left and the last
+   <= 4 in a pass of 4 (fields_pass).  EV_TJ_F: centre records per LDS tile of the plain fields sweep -- 256 keeps the
+   thin-plate instances (32 KiB log table beside the tile) at 3 workgroups per CU, 512 leaves 2 and is 9 % slower. */
+#ifndef RBF_NF
+#define RBF_NF 8
+#endif
+#ifndef RBF_NF_SMALL
+#define RBF_NF_SMALL 4
+#endif
+#ifndef EV_TJ_F
+#define EV_TJ_F 256
+#endif
+/* fields of the pass that starts with `left` fields to go */
+static inline int fields_pass(int left) { return left > RBF_NF_SMALL ? (left < RBF_NF ? left : RBF_NF) : left; }
+
+template <int KIND, int DIM, int NF>
+__global__ void __launch_bounds__(EV_THREADS)
+rbf_fields_kernel(double coef, const double *__restrict__ x, size_t n, size_t xtda, const double *__restrict__ w, size_t ldw, int nfa,
+                  const double *__restrict__ y, size_t m, size_t ytda, double *__restrict__ s, size_t stda, const int *__restrict__ perm)
+{
+  const sweep_fields F = {ldw, stda, nfa, 0, 0};
+  rbf_sweep<KIND, DIM, 1, false, NF, true, EV_TJ_F>(coef, x, n, xtda, w, y, m, ytda, perm, s, nullptr, nullptr, 0, 0.0, F);
+}
 
 /* ------------------------------------------------------------------------ */
 /* Gaussian sweep with tile culling.  At the shape parameters this path is used with
@@ -377,10 +437,10 @@ static inline int cull_tile_size(int dim, size_t n)
 }
 
 #define CT_THREADS 64
-template <int DIM, int CT>
-__global__ void __launch_bounds__(CT_THREADS)
-centre_pack_kernel(const double *__restrict__ x, size_t n, size_t xtda, const double *__restrict__ w,
-                   const int *__restrict__ perm, double *__restrict__ xs, double *__restrict__ tbox)
+/* FLD: records {x, w_0 .. w_{nf-1}} of DIM + nf doubles, every field's weight packed once (column q of w at w + q * ldw) */
+template <int DIM, int CT, bool FLD>
+__device__ __forceinline__ void centre_pack(const double *__restrict__ x, size_t n, size_t xtda, const double *__restrict__ w,
+                                            const int *__restrict__ perm, double *__restrict__ xs, double *__restrict__ tbox, int nf, size_t ldw)
 {
   constexpr int NW = (CT + 63) / 64;
   __shared__ double s_lo[DIM][NW], s_hi[DIM][NW];
@@ -389,9 +449,16 @@ centre_pack_kernel(const double *__restrict__ x, size_t n, size_t xtda, const do
   double v[DIM];
   if (ok) {
     const size_t j = (size_t)perm[i];
+    if constexpr (FLD) {
+      const size_t rs = (size_t)(DIM + nf);
 #pragma unroll
-    for (int c = 0; c < DIM; c++) { v[c] = x[j * xtda + c]; xs[i * (DIM + 1) + c] = v[c]; }
-    xs[i * (DIM + 1) + DIM] = w[j];
+      for (int c = 0; c < DIM; c++) { v[c] = x[j * xtda + c]; xs[i * rs + c] = v[c]; }
+      for (int q = 0; q < nf; q++) xs[i * rs + DIM + q] = w[(size_t)q * ldw + j];
+    } else {
+#pragma unroll
+      for (int c = 0; c < DIM; c++) { v[c] = x[j * xtda + c]; xs[i * (DIM + 1) + c] = v[c]; }
+      xs[i * (DIM + 1) + DIM] = w[j];
+    }
   }
 #pragma unroll
   for (int c = 0; c < DIM; c++) {
@@ -407,6 +474,22 @@ centre_pack_kernel(const double *__restrict__ x, size_t n, size_t xtda, const do
     tbox[(size_t)blockIdx.x * (2 * DIM) + 2 * c] = l;
     tbox[(size_t)blockIdx.x * (2 * DIM) + 2 * c + 1] = h;
   }
+}
+
+template <int DIM, int CT>
+__global__ void __launch_bounds__(CT_THREADS)
+centre_pack_kernel(const double *__restrict__ x, size_t n, size_t xtda, const double *__restrict__ w,
+                   const int *__restrict__ perm, double *__restrict__ xs, double *__restrict__ tbox)
+{
+  centre_pack<DIM, CT, false>(x, n, xtda, w, perm, xs, tbox, 1, 0);
+}
+
+template <int DIM, int CT>
+__global__ void __launch_bounds__(CT_THREADS)
+centre_pack_fields_kernel(const double *__restrict__ x, size_t n, size_t xtda, const double *__restrict__ w, size_t ldw, int nf,
+                          const int *__restrict__ perm, double *__restrict__ xs, double *__restrict__ tbox)
+{
+  centre_pack<DIM, CT, true>(x, n, xtda, w, perm, xs, tbox, nf, ldw);
 }
 
 #ifdef SINTERP_DIAG_PROF
@@ -430,14 +513,16 @@ extern "C" int gsl_sinterp_hip_debug_cull_stats(unsigned long long *out, int res
 #ifndef CULL_THREADS
 #define CULL_THREADS 128   /* 256 / 128 / 64 threads: C3 sweep 1.34 / 1.26 / 1.27 ms, C4 1.71 ms throughout */
 #endif
-template <int KIND, int DIM, int TPT, int CT, bool GRAD>
+template <int KIND, int DIM, int TPT, int CT, bool GRAD, int NF = 1, bool FLD = false>
 __device__ __forceinline__ void rbf_sweep_cull(double coef, const double *__restrict__ xs, size_t n, const double *__restrict__ tbox,
                                                unsigned ntiles, const double *__restrict__ y, size_t m, size_t ytda,
                                                const int *__restrict__ perm, double *__restrict__ s, const unsigned *__restrict__ omap,
-                                               double *__restrict__ g, size_t gtda, double gscale)
+                                               double *__restrict__ g, size_t gtda, double gscale, const sweep_fields F = sweep_fields())
 {
+  static_assert(FLD || NF == 1, "several weights per centre: the fields mode");
+  constexpr int REC = DIM + NF;
   __shared__ double s_t0[TBL_N];
-  __shared__ __attribute__((aligned(16))) double s_c[CULL_STAGE * (DIM + 1)];
+  __shared__ __attribute__((aligned(16))) double s_c[CULL_STAGE * REC];
   constexpr int NWV = CULL_THREADS / 64;
   __shared__ double s_blo[DIM][NWV], s_bhi[DIM][NWV];
   __shared__ unsigned long long s_mask[CULL_MAX_TILES / 64];
@@ -446,12 +531,13 @@ __device__ __forceinline__ void rbf_sweep_cull(double coef, const double *__rest
 
   const size_t k0 = (((size_t)blockIdx.x * CULL_THREADS) + tid) * TPT;
   size_t kidx[TPT];
-  double yy[TPT][DIM], acc[TPT], gacc[TPT][DIM];
+  double yy[TPT][DIM], acc[TPT][NF], gacc[TPT][DIM];
 #pragma unroll
   for (int t = 0; t < TPT; t++) {
     const size_t slot = k0 + (size_t)t;
     kidx[t] = slot < m ? (perm ? (size_t)perm[slot] : slot) : m;
-    acc[t] = 0.0;
+#pragma unroll
+    for (int q = 0; q < NF; q++) acc[t][q] = 0.0;
 #pragma unroll
     for (int c = 0; c < DIM; c++) { yy[t][c] = kidx[t] < m ? y[kidx[t] * ytda + c] : 0.0; gacc[t][c] = 0.0; }
   }
@@ -508,17 +594,27 @@ __device__ __forceinline__ void rbf_sweep_cull(double coef, const double *__rest
       mask &= mask - 1;
       const size_t c0 = (size_t)t * CT;
       const int tc = (int)((n - c0) < (size_t)CT ? (n - c0) : (size_t)CT);
-      for (int e = tid; e < tc * (DIM + 1); e += CULL_THREADS) s_c[cnt * (DIM + 1) + e] = xs[c0 * (DIM + 1) + e];
+      if constexpr (FLD) {
+        /* the pass's NF weights out of the record's K: entry e = (centre r, word c) of the staged tile */
+        for (int e = tid; e < tc * REC; e += CULL_THREADS) {
+          const int r = e / REC, c = e - r * REC;
+          const double *rec = xs + (c0 + (size_t)r) * (size_t)F.rs;
+          s_c[cnt * REC + e] = c < DIM ? rec[c] : (c - DIM < F.nfa ? rec[DIM + F.q0 + (c - DIM)] : 0.0);
+        }
+      } else {
+        for (int e = tid; e < tc * (DIM + 1); e += CULL_THREADS) s_c[cnt * (DIM + 1) + e] = xs[c0 * (DIM + 1) + e];
+      }
       cnt += tc;
     }
     if (cnt == 0) break;
     __syncthreads();
 #pragma unroll 2
     for (int e = 0; e < cnt; e++) {
-      double xc[DIM];
+      double xc[DIM], wj[NF];
 #pragma unroll
-      for (int c = 0; c < DIM; c++) xc[c] = s_c[e * (DIM + 1) + c];
-      const double wj = s_c[e * (DIM + 1) + DIM];
+      for (int c = 0; c < DIM; c++) xc[c] = s_c[e * REC + c];
+#pragma unroll
+      for (int q = 0; q < NF; q++) wj[q] = s_c[e * REC + DIM + q];
       double d[TPT][DIM], r2[TPT];
       bool take[TPT], need = false;
 #pragma unroll
@@ -539,10 +635,10 @@ __device__ __forceinline__ void rbf_sweep_cull(double coef, const double *__rest
          Morton order -- independent of the workgroup / wave the target landed in */
 #pragma unroll
       for (int tt = 0; tt < TPT; tt++)
-        sweep_term<KIND, DIM, GRAD>(r2[tt], d[tt], wj, coef, take[tt], s_t0, (const double *)NULL, acc[tt], gacc[tt]);
+        sweep_term<KIND, DIM, GRAD, NF>(r2[tt], d[tt], wj, coef, take[tt], s_t0, (const double *)NULL, acc[tt], gacc[tt]);
     }
   }
-  sweep_store<KIND, DIM, TPT, GRAD>(kidx, m, yy, acc, gacc, s, omap, g, gtda, gscale);
+  sweep_store<KIND, DIM, TPT, GRAD, NF, FLD>(kidx, m, yy, acc, gacc, s, omap, g, gtda, gscale, F);
 #ifdef SINTERP_DIAG_PROF
   for (int off = 32; off > 0; off >>= 1) { st_0 += __shfl_xor(st_0, off); st_1 += __shfl_xor(st_1, off); st_2 += __shfl_xor(st_2, off); }
   if (lane == 0) { atomicAdd(&g_cull_stats[0], st_0); atomicAdd(&g_cull_stats[1], st_1); atomicAdd(&g_cull_stats[2], st_2); }
@@ -567,6 +663,16 @@ rbf_grad_cull_kernel(double coef, double gscale, const double *__restrict__ xs, 
   rbf_sweep_cull<KIND, DIM, TPT, CT, true>(coef, xs, n, tbox, ntiles, y, m, ytda, perm, s, nullptr, g, gtda, gscale);
 }
 
+template <int KIND, int DIM, int CT, int NF>
+__global__ void __launch_bounds__(CULL_THREADS)
+rbf_fields_cull_kernel(double coef, const double *__restrict__ xs, int rs, int q0, int nfa, size_t n, const double *__restrict__ tbox,
+                       unsigned ntiles, const double *__restrict__ y, size_t m, size_t ytda, double *__restrict__ s, size_t stda,
+                       const int *__restrict__ perm)
+{
+  const sweep_fields F = {0, stda, nfa, q0, rs};
+  rbf_sweep_cull<KIND, DIM, 1, CT, false, NF, true>(coef, xs, n, tbox, ntiles, y, m, ytda, perm, s, nullptr, nullptr, 0, 0.0, F);
+}
+
 /* The packed centres of the culled sweeps: Morton order, {x, w} records, one bounding box per tile of ct centres.  They
    depend on the model only: reused when the caller vouches for the model (model_id != 0), whichever culled sweep -- value
    or value + gradient -- packed them. */
@@ -576,34 +682,42 @@ struct cull_model {
   int ct;
 };
 
+/* nf = 0: the scalar records {x, w} in the context's first slot.  nf >= 1: the fields records {x, w_0 .. w_{nf-1}} in a
+   slot of their own, keyed by nf and ldw too -- a fields model and its field 0 used as a scalar model share id, d_x and
+   d_w, and each of the two is packed once per model id whatever the order of the calls. */
 static int cull_pack(gsl_sinterp_hip_ctx *ctx, int kind, const double *d_x, size_t n, int dim, size_t xtda, const double *d_w,
-                     unsigned long long model_id, cull_model *out)
+                     unsigned long long model_id, cull_model *out, int nf = 0, size_t ldw = 0)
 {
-  const bool cached = model_id != 0 && ctx->cent_key.id == model_id && ctx->cent_key.x == d_x && ctx->cent_key.w == d_w &&
-                      ctx->cent_key.n == n && ctx->cent_key.xtda == xtda && ctx->cent_key.dim == dim && ctx->cent_key.kind == kind;
+  gsl_sinterp_hip_ctx::CentKey &key = nf ? ctx->cent_key_f : ctx->cent_key;
+  const bool cached = model_id != 0 && key.id == model_id && key.x == d_x && key.w == d_w && key.n == n && key.xtda == xtda &&
+                      key.dim == dim && key.kind == kind && key.nf == nf && key.ldw == ldw;
   int *d_cperm = NULL;
   int st = ST_SUCCESS;
   if (!cached) {
-    ctx->cent_key.id = 0;
+    key.id = 0;
     st = sinterp_sort_centres(ctx, d_x, n, xtda, dim, 8, &d_cperm);
     if (st) return st;
   }
   const int ct = cull_tile_size(dim, n);
   const unsigned ntiles = (unsigned)((n + ct - 1) / ct);
+  const size_t rec = (size_t)(dim + (nf ? nf : 1)), bytes = (n * rec + (size_t)ntiles * 2 * dim) * sizeof(double);
   void *buf = NULL;
-  st = sinterp_centbuf(ctx, (n * (size_t)(dim + 1) + (size_t)ntiles * 2 * dim) * sizeof(double), &buf);
+  st = nf ? sinterp_centbuf_fields(ctx, bytes, &buf) : sinterp_centbuf(ctx, bytes, &buf);
   if (st) return st;
-  double *xs = (double *)buf, *tbox = xs + n * (size_t)(dim + 1);
+  double *xs = (double *)buf, *tbox = xs + n * rec;
   out->xs = xs; out->tbox = tbox; out->ntiles = ntiles; out->ct = ct;
   if (cached) return ST_SUCCESS;
   with_dim_tile(dim, ct, [&](auto D, auto C) {
-    hipLaunchKernelGGL((centre_pack_kernel<decltype(D)::value, decltype(C)::value>), dim3(ntiles), dim3(CT_THREADS), 0, ctx->stream,
-                       d_x, n, xtda, d_w, (const int *)d_cperm, xs, tbox);
+    if (nf)
+      hipLaunchKernelGGL((centre_pack_fields_kernel<decltype(D)::value, decltype(C)::value>), dim3(ntiles), dim3(CT_THREADS), 0, ctx->stream,
+                         d_x, n, xtda, d_w, ldw, nf, (const int *)d_cperm, xs, tbox);
+    else
+      hipLaunchKernelGGL((centre_pack_kernel<decltype(D)::value, decltype(C)::value>), dim3(ntiles), dim3(CT_THREADS), 0, ctx->stream,
+                         d_x, n, xtda, d_w, (const int *)d_cperm, xs, tbox);
   });
   LAUNCH_CHECK(ctx);
   if (model_id != 0) {
-    ctx->cent_key.id = model_id; ctx->cent_key.x = d_x; ctx->cent_key.w = d_w; ctx->cent_key.n = n; ctx->cent_key.xtda = xtda;
-    ctx->cent_key.dim = dim; ctx->cent_key.kind = kind;
+    key.id = model_id; key.x = d_x; key.w = d_w; key.n = n; key.xtda = xtda; key.ldw = ldw; key.dim = dim; key.kind = kind; key.nf = nf;
   }
   return ST_SUCCESS;
 }
@@ -735,6 +849,7 @@ struct sweep_job {
   double *s; const unsigned *omap;
   double *g; size_t gtda; double gscale;
   unsigned long long model_id;
+  int nf; size_t ldw, stda;          /* nf >= 1: the fields sweep -- column q of w at w + q * ldw, target k's field q at s[k * stda + q] */
 };
 
 template <int KIND, int TPT>
@@ -744,6 +859,20 @@ static int launch_sweep(gsl_sinterp_hip_ctx *ctx, const sweep_job &j)
   const dim3 grid((unsigned)((j.m + per_block - 1) / per_block)), block(EV_THREADS);
   with_dim(j.dim, [&](auto D) {
     constexpr int DIM = decltype(D)::value;
+    if constexpr (TPT == 1) {
+      if (j.nf) {                                 /* passes of RBF_NF fields, the last <= RBF_NF_SMALL in the small instance */
+        for (int q0 = 0, nfa; q0 < j.nf; q0 += nfa) {
+          nfa = fields_pass(j.nf - q0);
+          if (nfa > RBF_NF_SMALL)
+            hipLaunchKernelGGL((rbf_fields_kernel<KIND, DIM, RBF_NF>), grid, block, 0, ctx->stream, j.coef, j.x, j.n, j.xtda,
+                               j.w + (size_t)q0 * j.ldw, j.ldw, nfa, j.y, j.m, j.ytda, j.s + q0, j.stda, j.perm);
+          else
+            hipLaunchKernelGGL((rbf_fields_kernel<KIND, DIM, RBF_NF_SMALL>), grid, block, 0, ctx->stream, j.coef, j.x, j.n, j.xtda,
+                               j.w + (size_t)q0 * j.ldw, j.ldw, nfa, j.y, j.m, j.ytda, j.s + q0, j.stda, j.perm);
+        }
+        return;
+      }
+    }
     if (j.g)
       hipLaunchKernelGGL((rbf_grad_kernel<KIND, DIM, TPT>), grid, block, 0, ctx->stream, j.coef, j.gscale, j.x, j.n, j.xtda, j.w, j.y, j.m,
                          j.ytda, j.s, j.g, j.gtda, j.perm);
@@ -759,12 +888,26 @@ template <int KIND, int TPT>
 static int launch_sweep_cull(gsl_sinterp_hip_ctx *ctx, const sweep_job &j)
 {
   cull_model cm;
-  int st = cull_pack(ctx, KIND, j.x, j.n, j.dim, j.xtda, j.w, j.model_id, &cm);
+  int st = cull_pack(ctx, KIND, j.x, j.n, j.dim, j.xtda, j.w, j.model_id, &cm, j.nf, j.ldw);
   if (st) return st;
   const size_t per_block = (size_t)CULL_THREADS * TPT;
   const dim3 grid((unsigned)((j.m + per_block - 1) / per_block)), block(CULL_THREADS);
   with_dim_tile(j.dim, cm.ct, [&](auto D, auto C) {
     constexpr int DIM = decltype(D)::value, CT = decltype(C)::value;
+    if constexpr (TPT == 1) {
+      if (j.nf) {
+        for (int q0 = 0, nfa; q0 < j.nf; q0 += nfa) {
+          nfa = fields_pass(j.nf - q0);
+          if (nfa > RBF_NF_SMALL)
+            hipLaunchKernelGGL((rbf_fields_cull_kernel<KIND, DIM, CT, RBF_NF>), grid, block, 0, ctx->stream, j.coef, cm.xs, j.dim + j.nf, q0,
+                               nfa, j.n, cm.tbox, cm.ntiles, j.y, j.m, j.ytda, j.s + q0, j.stda, j.perm);
+          else
+            hipLaunchKernelGGL((rbf_fields_cull_kernel<KIND, DIM, CT, RBF_NF_SMALL>), grid, block, 0, ctx->stream, j.coef, cm.xs, j.dim + j.nf,
+                               q0, nfa, j.n, cm.tbox, cm.ntiles, j.y, j.m, j.ytda, j.s + q0, j.stda, j.perm);
+        }
+        return;
+      }
+    }
     if (j.g)
       hipLaunchKernelGGL((rbf_grad_cull_kernel<KIND, DIM, TPT, CT>), grid, block, 0, ctx->stream, j.coef, j.gscale, cm.xs, j.n, cm.tbox,
                          cm.ntiles, j.y, j.m, j.ytda, j.s, j.g, j.gtda, j.perm);
@@ -788,7 +931,8 @@ static int rbf_sweep_dispatch(gsl_sinterp_hip_ctx *ctx, int kind, const sweep_jo
      Culled, 3-D: one target per lane also for large batches -- a workgroup's 256 targets span half the box of 512, and
      in three dimensions that removes more tested-and-rejected centres than the second accumulator chain gains
      (C3 sweep 1.70 -> 1.34 ms; 2-D C4: 1.74 vs 1.77 ms, unchanged) */
-  const bool one = j.m < (size_t)(culled ? CULL_THREADS : EV_THREADS) * 2 * 512 || (culled && j.dim == 3);
+  /* Fields: the same kernel choice by N (the bit rule: field q = the scalar sweep on column q), always one target per lane */
+  const bool one = j.nf || j.m < (size_t)(culled ? CULL_THREADS : EV_THREADS) * 2 * 512 || (culled && j.dim == 3);
   return with_kind(kind, [&](auto K) {
     constexpr int KIND = decltype(K)::value;
     if constexpr (KIND != GSL_SINTERP_RBF_TPS)      /* thin-plate has no decay: nothing to cull */
@@ -820,7 +964,7 @@ extern "C" int gsl_sinterp_hip_rbf_eval_model(gsl_sinterp_hip_ctx *ctx, int kind
   if (m == 0) return ST_SUCCESS;
   int st = ensure_tables(ctx);
   if (st) return st;
-  sweep_job j = {kernel_coef(kind, eps), d_x, n, dim, xtda, d_w, d_y, m, ytda, NULL, d_s, NULL, NULL, 0, 0.0, model_id};
+  sweep_job j = {kernel_coef(kind, eps), d_x, n, dim, xtda, d_w, d_y, m, ytda, NULL, d_s, NULL, NULL, 0, 0.0, model_id, 0, 0, 0};
   if (wants_target_sort(kind, m)) {
     /* large batches: the targets are physically put in cell order (sort.hip, two-level reorder), swept contiguously, each
        result stored through the order's map, and the values gathered back -- one random pass instead of the three of
@@ -885,7 +1029,7 @@ extern "C" int gsl_sinterp_hip_rbf_eval_grad(gsl_sinterp_hip_ctx *ctx, int kind,
     if (st) return st;
   }
   const sweep_job j = {kernel_coef(kind, eps), d_x, n, dim, xtda, d_w, d_y, m, ytda, d_perm, d_s, NULL, d_g, gtda, rbf_grad_scale(kind, eps),
-                       model_id};
+                       model_id, 0, 0, 0};
   st = rbf_sweep_dispatch(ctx, kind, j);
   if (st || !h_tail) return st;
   /* tail c_0 + sum_a c_a y_a: the affine thin-plate polynomial, or kriging's {mu, 0, ...}; h_tail[0 .. dim] only */
@@ -896,6 +1040,73 @@ extern "C" int gsl_sinterp_hip_rbf_eval_grad(gsl_sinterp_hip_ctx *ctx, int kind,
   if (blocks > 4096) blocks = 4096;
   hipLaunchKernelGGL(grad_tail_kernel, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, d_s, d_g, gtda, m, d_y, ytda, dim, h_tail[0],
                      h_tail[1], dim > 1 ? h_tail[2] : 0.0, dim > 2 ? h_tail[3] : 0.0, linear);
+  LAUNCH_CHECK(ctx);
+  return ST_SUCCESS;
+}
+
+/* ------------------------------------------------------------------------ */
+/* Several fields on one set of centres: field q of the sweep has the bits of gsl_sinterp_hip_rbf_eval_model on column q */
+extern "C" int gsl_sinterp_hip_rbf_fields_block(void) { return RBF_NF; }
+extern "C" int gsl_sinterp_hip_rbf_fields_block_small(void) { return RBF_NF_SMALL; }
+
+/* s[k][q] += c_0(q) + sum_a c_a(q) y[k][a] for FT_Q fields per launch, the coefficients as kernel arguments; per field
+   the operations of grad_tail_kernel (linear = 0: only c_0 is added), so field 0 keeps the bits of the scalar path */
+#define FT_Q 8
+struct fields_tail { double c[FT_Q][4]; int linear[FT_Q]; };
+
+__global__ void __launch_bounds__(256)
+fields_tail_kernel(double *__restrict__ s, size_t stda, int nq, size_t m, const double *__restrict__ y, size_t ytda, int dim, fields_tail T)
+{
+  const size_t stride = (size_t)gridDim.x * blockDim.x;
+  for (size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x; k < m; k += stride) {
+#pragma unroll
+    for (int q = 0; q < FT_Q; q++) {
+      if (q >= nq) break;
+      if (!T.linear[q]) { s[k * stda + q] = s[k * stda + q] + T.c[q][0]; continue; }
+      double t = fma(T.c[q][1], y[k * ytda], T.c[q][0]);
+      if (dim > 1) t = fma(T.c[q][2], y[k * ytda + 1], t);
+      if (dim > 2) t = fma(T.c[q][3], y[k * ytda + 2], t);
+      s[k * stda + q] = s[k * stda + q] + t;
+    }
+  }
+}
+
+extern "C" int gsl_sinterp_hip_rbf_eval_fields(gsl_sinterp_hip_ctx *ctx, int kind, double eps, const double *h_tail, const double *d_x,
+                                               size_t n, int dim, size_t xtda, const double *d_w, size_t ldw, size_t nf,
+                                               const double *d_y, size_t m, size_t ytda, double *d_s, size_t stda,
+                                               unsigned long long model_id)
+{
+  REQUIRE(ctx, ctx != NULL, ST_EFAULT);
+  HIP_OK(ctx, hipSetDevice(ctx->device));      /* one context per device: bind before any launch */
+  REQUIRE(ctx, dim >= 1 && dim <= 3 && xtda >= (size_t)dim && ytda >= (size_t)dim, ST_EINVAL);
+  REQUIRE(ctx, known_kind(kind), ST_EINVAL);
+  REQUIRE(ctx, nf >= 1 && nf <= GSL_SINTERP_MAX_FIELDS && ldw >= n && stda >= nf, ST_EINVAL);
+  REQUIRE(ctx, m == 0 || (d_y && d_s && (n == 0 || (d_x && d_w))), ST_EFAULT);
+  if (m == 0) return ST_SUCCESS;
+  int st = ensure_tables(ctx);
+  if (st) return st;
+  /* one level of target sort, as the gradient entry: the two-level reorder's result path carries one scalar per target */
+  int *d_perm = NULL;
+  if (wants_target_sort(kind, m)) {
+    st = sinterp_sort_targets(ctx, d_y, m, ytda, dim, 64, &d_perm);
+    if (st) return st;
+  }
+  const sweep_job j = {kernel_coef(kind, eps), d_x, n, dim, xtda, d_w, d_y, m, ytda, d_perm, d_s, NULL, NULL, 0, 0.0, model_id,
+                       (int)nf, ldw, stda};
+  st = rbf_sweep_dispatch(ctx, kind, j);
+  if (st || !h_tail) return st;
+  size_t blocks = (m + 255) / 256;
+  if (blocks > 4096) blocks = 4096;
+  for (size_t q0 = 0; q0 < nf; q0 += FT_Q) {
+    fields_tail T;
+    memset(&T, 0, sizeof T);
+    const int nq = (int)(nf - q0 < FT_Q ? nf - q0 : FT_Q);
+    for (int q = 0; q < nq; q++) {
+      const double *c = h_tail + (q0 + q) * (size_t)(dim + 1);
+      for (int a = 0; a <= dim; a++) { T.c[q][a] = c[a]; if (a) T.linear[q] |= c[a] != 0.0; }
+    }
+    hipLaunchKernelGGL(fields_tail_kernel, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, d_s + q0, stda, nq, m, d_y, ytda, dim, T);
+  }
   LAUNCH_CHECK(ctx);
   return ST_SUCCESS;
 }

@@ -555,3 +555,104 @@ extern "C" int gsl_sinterp_hip_krige_eval(gsl_sinterp_hip_ctx *ctx, int kind, do
   LAUNCH_CHECK(ctx);
   return ST_SUCCESS;
 }
+
+
+/* ------------------------------------------------------------------------ */
+/* Several fields on one set of centres: the kernel matrix depends on the centres only, so ONE fill and ONE factorisation
+   serve every right-hand side (chol.hip: sinterp_cholesky_factor_solve_many_sym). */
+static int fields_solve_args(gsl_sinterp_hip_ctx *ctx, int kind, const double *d_x, size_t n, int dim, size_t xtda, const double *d_phi,
+                             size_t lda, const double *d_w, size_t ldw, size_t nf)
+{
+  REQUIRE(ctx, dim >= 1 && dim <= 3 && xtda >= (size_t)dim && lda >= n && ldw >= n, ST_EINVAL);
+  REQUIRE(ctx, nf >= 1 && nf <= GSL_SINTERP_MAX_FIELDS, ST_EINVAL);
+  REQUIRE(ctx, kind == GSL_SINTERP_RBF_GAUSSIAN || kind == GSL_SINTERP_RBF_WENDLAND, ST_EINVAL);   /* positive definite kernels */
+  REQUIRE(ctx, n == 0 || (d_x && d_phi && d_w), ST_EFAULT);
+  return ST_SUCCESS;
+}
+
+extern "C" int gsl_sinterp_hip_rbf_solve_fields(gsl_sinterp_hip_ctx *ctx, int kind, double eps, const double *d_x, size_t n, int dim,
+                                                size_t xtda, double *d_phi, size_t lda, double *d_w, size_t ldw, size_t nf, int *h_route)
+{
+  REQUIRE(ctx, ctx != NULL, ST_EFAULT);
+  HIP_OK(ctx, hipSetDevice(ctx->device));
+  EXCLUSIVE_SECTION(ctx);
+  int st = fields_solve_args(ctx, kind, d_x, n, dim, xtda, d_phi, lda, d_w, ldw, nf);
+  if (st) return st;
+  if (h_route) *h_route = 0;
+  if (n == 0) return ST_SUCCESS;
+  st = sinterp_rbf_fill_ex(ctx, kind, eps, d_x, n, dim, xtda, d_phi, lda, 1);      /* the Cholesky reads the lower triangle only */
+  if (st) return st;
+  int info = 0;
+  st = sinterp_cholesky_factor_solve_many_sym(ctx, n, d_phi, lda, &info, d_w, ldw, (int)nf);
+  if (st) return st;
+  if (h_route) *h_route = 1;
+  return ST_SUCCESS;
+}
+
+/* Y = [f_0 .. f_{nf-1} | 1] (column stride n), ones = 1 */
+__global__ void __launch_bounds__(256)
+krige_rhs_fields_kernel(const double *__restrict__ f, size_t ldw, int nf, size_t n, double *__restrict__ Y, double *__restrict__ ones)
+{
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  for (int q = 0; q < nf; q++) Y[(size_t)q * n + i] = f[(size_t)q * ldw + i];
+  Y[(size_t)nf * n + i] = 1.0;
+  ones[i] = 1.0;
+}
+
+/* w_q = a_q + coef_q b with a_q = Y column q, b = Y column nf (combine_kernel's operation per field) */
+__global__ void __launch_bounds__(256)
+krige_combine_fields_kernel(const double *__restrict__ Y, size_t n, int nf, const double *__restrict__ coef, double *__restrict__ w, size_t ldw)
+{
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const double b = Y[(size_t)nf * n + i];
+  for (int q = 0; q < nf; q++) w[(size_t)q * ldw + i] = fma(coef[q], b, Y[(size_t)q * n + i]);
+}
+
+extern "C" int gsl_sinterp_hip_krige_solve_fields(gsl_sinterp_hip_ctx *ctx, int kind, double eps, double nugget, const double *d_x,
+                                                  size_t n, int dim, size_t xtda, double *d_phi, size_t lda, double *d_w, size_t ldw,
+                                                  size_t nf, double *h_mean, int *h_route)
+{
+  REQUIRE(ctx, ctx != NULL, ST_EFAULT);
+  HIP_OK(ctx, hipSetDevice(ctx->device));
+  EXCLUSIVE_SECTION(ctx);
+  int st = fields_solve_args(ctx, kind, d_x, n, dim, xtda, d_phi, lda, d_w, ldw, nf);
+  if (st) return st;
+  REQUIRE(ctx, nugget >= 0.0, ST_EINVAL);
+  REQUIRE(ctx, h_mean != NULL, ST_EFAULT);
+  if (h_route) *h_route = 0;
+  for (size_t q = 0; q < nf; q++) h_mean[q] = 0.0;
+  if (n == 0) return ST_SUCCESS;
+  const int nr = (int)nf + 1;
+  void *aux = NULL;
+  st = sinterp_aux(ctx, ((size_t)(nr + 1) * n + 2 * (GSL_SINTERP_MAX_FIELDS + 8)) * sizeof(double), &aux);
+  if (st) return st;
+  double *Y = (double *)aux, *ones = Y + (size_t)nr * n, *G = ones + n, *d_coef = G + GSL_SINTERP_MAX_FIELDS + 8;
+  const unsigned nb = (unsigned)((n + 255) / 256);
+  st = gsl_sinterp_hip_rbf_fill(ctx, kind, eps, d_x, n, dim, xtda, d_phi, lda);          /* both triangles, as krige_solve */
+  if (st) return st;
+  if (nugget != 0.0) hipLaunchKernelGGL(diag_add_kernel, dim3(nb), dim3(256), 0, ctx->stream, d_phi, lda, n, nugget);
+  hipLaunchKernelGGL(krige_rhs_fields_kernel, dim3(nb), dim3(256), 0, ctx->stream, (const double *)d_w, ldw, (int)nf, n, Y, ones);
+  LAUNCH_CHECK(ctx);
+  int info = 0;
+  st = sinterp_cholesky_factor_solve_many_sym(ctx, n, d_phi, lda, &info, Y, n, nr);
+  if (st) return st;                              /* GSL_EDOM: only semi-definite -- the caller's per-field fallback */
+  /* G[b] = 1^T Y_b, b <= nf: gram_kernel with one "polynomial" (ones) and nf + 1 columns, block b -> (a = 0, b) */
+  hipLaunchKernelGGL(gram_kernel, dim3((unsigned)nr), dim3(256), 0, ctx->stream, (const double *)ones, (const double *)Y, n, (int)nf, G);
+  LAUNCH_CHECK(ctx);
+  double hG[GSL_SINTERP_MAX_FIELDS + 1], coef[GSL_SINTERP_MAX_FIELDS];
+  HIP_OK(ctx, hipStreamSynchronize(ctx->stream));
+  HIP_OK(ctx, hipMemcpy(hG, G, sizeof(double) * (size_t)nr, hipMemcpyDeviceToHost));
+  const double denom = hG[nf];
+  if (!(denom != 0.0) || denom != denom)
+    return sinterp_fail(ctx, ST_EDOM, "krige_solve_fields: 1^T K^-1 1 = 0 (degenerate covariance matrix)", hipSuccess, __FILE__, __LINE__);
+  for (size_t q = 0; q < nf; q++) { h_mean[q] = hG[q] / denom; coef[q] = -h_mean[q]; }
+  HIP_OK(ctx, hipMemcpyAsync(d_coef, coef, sizeof(double) * nf, hipMemcpyHostToDevice, ctx->stream));
+  hipLaunchKernelGGL(krige_combine_fields_kernel, dim3(nb), dim3(256), 0, ctx->stream, (const double *)Y, n, (int)nf, (const double *)d_coef,
+                     d_w, ldw);
+  LAUNCH_CHECK(ctx);
+  HIP_OK(ctx, hipStreamSynchronize(ctx->stream));                                        /* coef is a stack buffer */
+  if (h_route) *h_route = 7;
+  return ST_SUCCESS;
+}

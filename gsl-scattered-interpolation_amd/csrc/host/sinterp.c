@@ -777,8 +777,13 @@ typedef struct {
   size_t n, dim;
   double eps;
   double *d_x; /* n x dim, packed  (member 0: start of the model buffer) */
-  double *d_w; /* n                (member 0: model buffer + n*dim)      */
-  /* device group (n_devices > 1): the model buffer [x | w] of every member; ss.grp owns the contexts */
+  double *d_w; /* n x nf, column q at d_w + q*n (member 0: model buffer + n*dim); column 0 is the model of every scalar entry */
+  /* several fields (gsl_sinterp_init_fields): nf weight vectors on the same centres, model buffer [x | w_0 | .. | w_{nf-1}];
+     nf = 0 before the first init, 1 after gsl_sinterp_init / fread.  nf_alloc: the field count the buffers were sized for.
+     f_mean / f_poly: kriging mean / affine polynomial of every field (`mean` / `poly` below stay field 0's) */
+  size_t nf, nf_alloc;
+  double f_mean[GSL_SINTERP_MAX_FIELDS], f_poly[GSL_SINTERP_MAX_FIELDS][4];
+  /* device group (n_devices > 1): the model buffer [x | w ..] of every member; ss.grp owns the contexts */
   shard_set ss;
   double *m_model[SINTERP_MAX_DEVICES];
   /* id of the model the buffers hold (fresh after every init / fread): lets the sweep keep its per-model
@@ -854,7 +859,7 @@ static void rbf_release_devices(rbf_state *st)
     gsl_sinterp_hip_free(st->ctx, st->d_x);       /* one buffer: d_w points into it */
     gsl_sinterp_hip_ctx_destroy(st->ctx);
   }
-  st->ctx = NULL; st->d_x = st->d_w = NULL;
+  st->ctx = NULL; st->d_x = st->d_w = NULL; st->nf_alloc = 0; st->nf = 0;
 }
 
 static void rbf_free(void *vstate)
@@ -865,16 +870,31 @@ static void rbf_free(void *vstate)
   free(st);
 }
 
-static int rbf_prepare_devices(gsl_sinterp *interp, rbf_state *st);
+static int rbf_prepare_devices(gsl_sinterp *interp, rbf_state *st, size_t nf);
 
-static int rbf_init(gsl_sinterp *interp, const gsl_matrix *x, const gsl_vector *f)
+/* the solve of ONE field on column d_w (f on entry, weights on exit) through the single-field raw entries */
+static int rbf_solve_column(gsl_sinterp *interp, rbf_state *st, double *d_phi, size_t lda, double *d_w, double *mean, double *poly,
+                            double *rcond, int *route)
+{
+  gsl_sinterp_hip_ctx *c = st->ctx;
+  const size_t n = st->n, dim = st->dim;
+  if (st->krige)
+    return gsl_sinterp_hip_krige_solve(c, st->kind, st->eps, interp->nugget, st->d_x, n, (int)dim, dim, d_phi, lda, d_w, mean, route);
+  if (st->affine)
+    return gsl_sinterp_hip_rbf_solve_affine(c, st->kind, st->eps, st->d_x, n, (int)dim, dim, d_phi, lda, d_w, poly, route);
+  return gsl_sinterp_hip_rbf_solve_ex(c, st->kind, st->eps, st->d_x, n, (int)dim, dim, d_phi, lda, d_w, interp->solver, rcond, route);
+}
+
+/* f(i, q) = fdata[i * frow + q * fcol], nf fields: gsl_sinterp_init (nf = 1) and gsl_sinterp_init_fields */
+static int rbf_init_fields(gsl_sinterp *interp, const gsl_matrix *x, const double *fdata, size_t frow, size_t fcol, size_t nf)
 {
   rbf_state *st = (rbf_state *)interp->state;
   const size_t n = st->n, dim = st->dim;
   const int nd = interp->n_devices > 1 ? interp->n_devices : 1;
   rbf_release_variance(st);                             /* the factor of the previous model, if one was kept */
-  int s = rbf_prepare_devices(interp, st);
+  int s = rbf_prepare_devices(interp, st, nf);
   if (s) return s;
+  st->nf = 0;                                           /* not initialised until the solve succeeds */
   gsl_sinterp_hip_ctx *c = st->ctx;
   /* default shape: Gaussian eps = 2 N^(1/d) (the C-configurations); Wendland: support radius of eight mean
      spacings of a unit box, eps = N^(1/d) / 8 */
@@ -883,30 +903,46 @@ static int rbf_init(gsl_sinterp *interp, const gsl_matrix *x, const gsl_vector *
             : (st->kind == GSL_SINTERP_RBF_WENDLAND ? 0.125 : 2.0) * pow((double)n, 1.0 / (double)dim);
 
   double *h_x = (double *)malloc(n * dim * sizeof(double));
-  double *h_f = (double *)malloc(n * sizeof(double));
+  double *h_f = (double *)malloc(n * nf * sizeof(double));
   if (!h_x || !h_f) { free(h_x); free(h_f); GSL_ERROR("gsl_sinterp_init: out of memory", GSL_ENOMEM); }
   for (size_t i = 0; i < n; i++) {
     for (size_t cdim = 0; cdim < dim; cdim++) h_x[i * dim + cdim] = x->data[i * x->tda + cdim];
-    h_f[i] = gsl_vector_get(f, i);
+    for (size_t q = 0; q < nf; q++) h_f[q * n + i] = fdata[i * frow + q * fcol];
   }
-  const size_t model_bytes = n * (dim + 1) * sizeof(double);
+  const size_t model_bytes = n * (dim + nf) * sizeof(double);
   double *d_phi = NULL;
   int route = 0;
   /* affine thin-plate spline: room for the (n + d + 1) augmented matrix of the pivoted-LU route (lda even) */
   const size_t lda = st->affine ? ((n + dim + 2) & ~(size_t)1) : n, phi_rows = st->affine ? n + dim + 1 : n;
   s = gsl_sinterp_hip_malloc(c, (void **)&d_phi, phi_rows * lda * sizeof(double));
   if (!s) s = gsl_sinterp_hip_h2d(c, st->d_x, h_x, n * dim * sizeof(double));
-  if (!s) s = gsl_sinterp_hip_h2d(c, st->d_w, h_f, n * sizeof(double));
+  if (!s) s = gsl_sinterp_hip_h2d(c, st->d_w, h_f, n * nf * sizeof(double));
   /* fill + dense solve on the device: Cholesky (Gaussian), shifted-SPD Cholesky with a
      Woodbury correction or pivoted LU (thin-plate spline) -- csrc/hip/solve.hip */
   double rcond = GSL_NAN;
-  if (!s && st->krige)
-    s = gsl_sinterp_hip_krige_solve(c, st->kind, st->eps, interp->nugget, st->d_x, n, (int)dim, dim, d_phi, lda, st->d_w, &st->mean, &route);
-  else if (!s && st->affine)
-    s = gsl_sinterp_hip_rbf_solve_affine(c, st->kind, st->eps, st->d_x, n, (int)dim, dim, d_phi, lda, st->d_w, st->poly, &route);
-  else if (!s)
-    s = gsl_sinterp_hip_rbf_solve_ex(c, st->kind, st->eps, st->d_x, n, (int)dim, dim, d_phi, lda, st->d_w, interp->solver,
-                                     interp->want_rcond ? &rcond : NULL, &route);
+  memset(st->f_mean, 0, sizeof st->f_mean); memset(st->f_poly, 0, sizeof st->f_poly);
+  /* Several fields.  The kernel matrix depends on the centres only: Gaussian, Wendland and kriging with the default solver
+     and no condition estimate share ONE fill and ONE factorisation (routes 1 / 7).  Everything else -- both thin-plate
+     types (their shifted-SPD / Woodbury solve is per field), an explicit solver, set_rcond, kriging on a semi-definite
+     matrix (GSL_EDOM from the shared route) -- solves field by field, refilling d_phi each time: nf factorisations. */
+  int shared = nf > 1 && st->kind != GSL_SINTERP_RBF_TPS && interp->solver == GSL_SINTERP_SOLVER_DEFAULT && !interp->want_rcond;
+  if (!s && shared) {
+    if (st->krige) {
+      s = gsl_sinterp_hip_krige_solve_fields(c, st->kind, st->eps, interp->nugget, st->d_x, n, (int)dim, dim, d_phi, lda, st->d_w, n, nf,
+                                             st->f_mean, &route);
+      if (s == GSL_EDOM) {                              /* semi-definite: per field, where route 8 handles it; F again */
+        shared = 0;
+        s = gsl_sinterp_hip_h2d(c, st->d_w, h_f, n * nf * sizeof(double));
+      }
+    } else {
+      s = gsl_sinterp_hip_rbf_solve_fields(c, st->kind, st->eps, st->d_x, n, (int)dim, dim, d_phi, lda, st->d_w, n, nf, &route);
+    }
+  }
+  if (!s && !shared)
+    for (size_t q = 0; q < nf && !s; q++)               /* rcond from the first field, the route of the last */
+      s = rbf_solve_column(interp, st, d_phi, lda, st->d_w + q * n, &st->f_mean[q], st->f_poly[q],
+                           interp->want_rcond && q == 0 ? &rcond : NULL, &route);
+  st->mean = st->f_mean[0]; memcpy(st->poly, st->f_poly[0], sizeof st->poly);
   interp->rcond = rcond; interp->route = route;
   /* kriging variance asked for: route 7 left L in the lower triangle of d_phi -- keep it (N^2 doubles, member 0 only)
      with b = K^-1 1, the inverted diagonal blocks and 1^T b; route 8 has no Cholesky factor to keep */
@@ -930,11 +966,17 @@ static int rbf_init(gsl_sinterp *interp, const gsl_matrix *x, const gsl_vector *
   if (s) rbf_release_variance(st);
   if (s == GSL_EDOM) GSL_ERROR("gsl_sinterp_init: kernel matrix is not positive definite", GSL_EDOM);
   HIP_TRY(s, c);
+  st->nf = nf;
   return GSL_SUCCESS;
 }
 
-/* contexts (one, or a device group) + the model buffer [centres | weights] of every member */
-static int rbf_prepare_devices(gsl_sinterp *interp, rbf_state *st)
+static int rbf_init(gsl_sinterp *interp, const gsl_matrix *x, const gsl_vector *f)
+{
+  return rbf_init_fields(interp, x, f->data, f->stride, 0, 1);
+}
+
+/* contexts (one, or a device group) + the model buffer [centres | weights of nf fields] of every member */
+static int rbf_prepare_devices(gsl_sinterp *interp, rbf_state *st, size_t nf)
 {
   const size_t n = st->n, dim = st->dim;
   const int nd = interp->n_devices > 1 ? interp->n_devices : 1;
@@ -955,9 +997,19 @@ static int rbf_prepare_devices(gsl_sinterp *interp, rbf_state *st)
       GSL_ERROR("gsl_sinterp_init: no usable HIP device (GPU path has no CPU fallback)", GSL_EFAILED);
     }
   }
-  /* the model = [centres | weights], one buffer per member: N (d+1) 8 bytes, the broadcast payload */
-  const size_t model_bytes = n * (dim + 1) * sizeof(double);
+  /* the model = [centres | weights], one buffer per member: N (d + nf) 8 bytes, the broadcast payload; reallocated
+     when the field count changes */
+  const size_t model_bytes = n * (dim + nf) * sizeof(double);
   int s = GSL_SUCCESS;
+  if (st->nf_alloc != nf) {
+    if (st->ss.grp) {
+      for (int r = 0; r < nd; r++) { gsl_sinterp_hip_free(gsl_sinterp_hip_group_ctx(st->ss.grp, r), st->m_model[r]); st->m_model[r] = NULL; }
+    } else {
+      gsl_sinterp_hip_free(st->ctx, st->d_x);
+    }
+    st->d_x = st->d_w = NULL; st->nf = 0;
+    st->nf_alloc = nf;
+  }
   if (st->ss.grp) {
     for (int r = 0; r < nd && !s; r++)
       if (!st->m_model[r]) s = gsl_sinterp_hip_malloc(gsl_sinterp_hip_group_ctx(st->ss.grp, r), (void **)&st->m_model[r], model_bytes);
@@ -1449,6 +1501,155 @@ int gsl_sinterp_eval_grad_e(const gsl_sinterp *interp, const gsl_vector *y, doub
   return GSL_SUCCESS;
 }
 
+/* ---- several fields on one set of centres (RBF family): dispatch on the type here, no slot in gsl_sinterp_type ---- */
+static int fields_status(const gsl_sinterp *interp)
+{
+  if (interp->type == &simplex_type || interp->type == &mesh_type)
+    GSL_ERROR("gsl_sinterp fields: RBF-family interpolants only (several responses per leaf of the linear types: a separate entry)", GSL_EUNSUP);
+  return GSL_SUCCESS;
+}
+
+int gsl_sinterp_init_fields(gsl_sinterp *interp, const gsl_matrix *x, const gsl_matrix *F)
+{
+  if (!interp || !x || !F) GSL_ERROR("gsl_sinterp_init_fields: null argument", GSL_EFAULT);
+  int fs = fields_status(interp);
+  if (fs) return fs;
+  if (F->size1 != interp->size) GSL_ERROR("gsl_sinterp_init_fields: the response matrix must have size rows", GSL_EBADLEN);
+  if (x->size1 != interp->size || x->size2 != interp->dim) GSL_ERROR("gsl_sinterp_init_fields: the centre matrix must be size x dim", GSL_EBADLEN);
+  if (F->size2 < 1 || F->size2 > GSL_SINTERP_MAX_FIELDS) GSL_ERROR("gsl_sinterp_init_fields: 1 .. GSL_SINTERP_MAX_FIELDS fields", GSL_EINVAL);
+  return rbf_init_fields(interp, x, F->data, F->tda, 1, F->size2);
+}
+
+size_t gsl_sinterp_n_fields(const gsl_sinterp *interp)
+{
+  if (!interp || interp->type == &simplex_type || interp->type == &mesh_type) return 0;
+  const rbf_state *st = (const rbf_state *)interp->state;
+  return st->d_w ? st->nf : 0;
+}
+
+int gsl_sinterp_eval_fields_resident(const gsl_sinterp *interp, const double *d_y, size_t m, size_t ytda, double *d_s, size_t stda)
+{
+  if (!interp) GSL_ERROR("gsl_sinterp_eval_fields_resident: null interpolant", GSL_EFAULT);
+  if (m > 0 && (!d_y || !d_s)) GSL_ERROR("gsl_sinterp_eval_fields_resident: null argument", GSL_EFAULT);
+  int fs = fields_status(interp);
+  if (fs) return fs;
+  const rbf_state *st = (const rbf_state *)interp->state;
+  if (!st->d_w || st->nf == 0) GSL_ERROR("gsl_sinterp_eval_fields: interpolant not initialised", GSL_EINVAL);
+  if (stda < st->nf) GSL_ERROR("gsl_sinterp_eval_fields_resident: row pitch below the number of fields", GSL_EINVAL);
+  /* the tails: the affine polynomials, or kriging's constant means; member 0 evaluates every target (as the gradient and
+     variance entries do) */
+  double tail[GSL_SINTERP_MAX_FIELDS * 4];
+  const size_t td = st->dim + 1;
+  for (size_t q = 0; q < st->nf; q++)
+    for (size_t a = 0; a < td; a++) tail[q * td + a] = st->affine ? st->f_poly[q][a] : (a == 0 ? st->f_mean[q] : 0.0);
+  HIP_TRY(gsl_sinterp_hip_rbf_eval_fields(st->ctx, st->kind, st->eps, (st->affine || st->krige) ? tail : NULL, st->d_x, st->n, (int)st->dim,
+                                          st->dim, st->d_w, st->n, st->nf, d_y, m, ytda, d_s, stda, st->model_id), st->ctx);
+  return GSL_SUCCESS;
+}
+
+int gsl_sinterp_eval_fields_many(const gsl_sinterp *interp, const gsl_matrix *y, gsl_matrix *S)
+{
+  if (!interp || !y || !S) GSL_ERROR("gsl_sinterp_eval_fields_many: null argument", GSL_EFAULT);
+  int fs = fields_status(interp);
+  if (fs) return fs;
+  const size_t m = y->size1, dim = interp->dim;
+  if (y->size2 != dim) GSL_ERROR("target matrix must have dim columns", GSL_EBADLEN);
+  if (S->size1 != m) GSL_ERROR("output matrix must have one row per target", GSL_EBADLEN);
+  const rbf_state *st = (const rbf_state *)interp->state;
+  if (!st->d_w || st->nf == 0) GSL_ERROR("gsl_sinterp_eval_fields: interpolant not initialised", GSL_EINVAL);
+  const size_t K = st->nf;
+  if (S->size2 != K) GSL_ERROR("output matrix must have one column per field", GSL_EBADLEN);
+  if (m == 0) return GSL_SUCCESS;
+  gsl_sinterp_hip_ctx *c = st->ctx;
+  /* one staging buffer on either side: [targets m x dim | values m x K] */
+  double *h = (double *)malloc(m * (dim + K) * sizeof(double)), *d = NULL;
+  if (!h) GSL_ERROR("gsl_sinterp_eval_fields_many: out of memory", GSL_ENOMEM);
+  for (size_t k = 0; k < m; k++)
+    for (size_t a = 0; a < dim; a++) h[k * dim + a] = y->data[k * y->tda + a];
+  int s = gsl_sinterp_hip_malloc(c, (void **)&d, m * (dim + K) * sizeof(double));
+  if (!s) s = gsl_sinterp_hip_h2d(c, d, h, m * dim * sizeof(double));
+  int es = GSL_SUCCESS;
+  double *d_s = d + m * dim;
+  if (!s) es = gsl_sinterp_eval_fields_resident(interp, d, m, dim, d_s, K);
+  if (!s && !es) s = gsl_sinterp_hip_d2h(c, h, d_s, m * K * sizeof(double));
+  if (!s && !es)
+    for (size_t k = 0; k < m; k++)
+      for (size_t q = 0; q < K; q++) S->data[k * S->tda + q] = h[k * K + q];
+  gsl_sinterp_hip_free(c, d);
+  free(h);
+  HIP_TRY(s, c);
+  return es;
+}
+
+int gsl_sinterp_eval_fields_e(const gsl_sinterp *interp, const gsl_vector *y, gsl_vector *s)
+{
+  if (s) for (size_t q = 0; q < s->size; q++) gsl_vector_set(s, q, GSL_NAN);
+  if (!interp || !y || !s) GSL_ERROR("gsl_sinterp_eval_fields_e: null argument", GSL_EFAULT);
+  int fs = fields_status(interp);
+  if (fs) return fs;
+  if (y->size != interp->dim) GSL_ERROR("target must have dim components", GSL_EBADLEN);
+  const size_t K = gsl_sinterp_n_fields(interp);
+  if (K == 0) GSL_ERROR("gsl_sinterp_eval_fields: interpolant not initialised", GSL_EINVAL);
+  if (s->size != K) GSL_ERROR("output must have one entry per field", GSL_EBADLEN);
+  double yy[3], out[GSL_SINTERP_MAX_FIELDS];
+  for (size_t c = 0; c < interp->dim; c++) yy[c] = gsl_vector_get(y, c);
+  gsl_matrix_view Y = gsl_matrix_view_array(yy, 1, interp->dim), S = gsl_matrix_view_array(out, 1, K);
+  int st = gsl_sinterp_eval_fields_many(interp, &Y.matrix, &S.matrix);
+  if (st != GSL_SUCCESS) return st;
+  for (size_t q = 0; q < K; q++) gsl_vector_set(s, q, out[q]);
+  return GSL_SUCCESS;
+}
+
+/* the state of an initialised RBF-family interpolant when q names one of its fields, else NULL with *status set */
+static const rbf_state *field_state(const gsl_sinterp *interp, size_t q, int *status)
+{
+  *status = fields_status(interp);
+  if (*status) return NULL;
+  const rbf_state *st = (const rbf_state *)interp->state;
+  if (!st->d_w || st->nf == 0) { *status = GSL_EINVAL; gsl_error("gsl_sinterp fields: interpolant not initialised", __FILE__, __LINE__, GSL_EINVAL); return NULL; }
+  if (q >= st->nf) { *status = GSL_EBADLEN; gsl_error("gsl_sinterp fields: no such field", __FILE__, __LINE__, GSL_EBADLEN); return NULL; }
+  return st;
+}
+
+int gsl_sinterp_get_field_weights(const gsl_sinterp *interp, size_t q, gsl_vector *w)
+{
+  if (!interp || !w) GSL_ERROR("gsl_sinterp_get_field_weights: null argument", GSL_EFAULT);
+  int status;
+  const rbf_state *st = field_state(interp, q, &status);
+  if (!st) return status;
+  if (w->size != st->n) GSL_ERROR("gsl_sinterp_get_field_weights: wrong length", GSL_EBADLEN);
+  double *h = (double *)malloc(st->n * sizeof(double));
+  if (!h) GSL_ERROR("gsl_sinterp_get_field_weights: out of memory", GSL_ENOMEM);
+  int s = gsl_sinterp_hip_d2h(st->ctx, h, st->d_w + q * st->n, st->n * sizeof(double));
+  if (!s) for (size_t i = 0; i < st->n; i++) gsl_vector_set(w, i, h[i]);
+  free(h);
+  HIP_TRY(s, st->ctx);
+  return GSL_SUCCESS;
+}
+
+int gsl_sinterp_field_mean(const gsl_sinterp *interp, size_t q, double *mean)
+{
+  if (!interp || !mean) GSL_ERROR("gsl_sinterp_field_mean: null argument", GSL_EFAULT);
+  int status;
+  const rbf_state *st = field_state(interp, q, &status);
+  if (!st) return status;
+  if (interp->type != &krige_type) GSL_ERROR("gsl_sinterp_field_mean: kriging interpolants only", GSL_EINVAL);
+  *mean = st->f_mean[q];
+  return GSL_SUCCESS;
+}
+
+int gsl_sinterp_field_poly(const gsl_sinterp *interp, size_t q, gsl_vector *c)
+{
+  if (!interp || !c) GSL_ERROR("gsl_sinterp_field_poly: null argument", GSL_EFAULT);
+  int status;
+  const rbf_state *st = field_state(interp, q, &status);
+  if (!st) return status;
+  if (interp->type != &tps_affine_type) GSL_ERROR("gsl_sinterp_field_poly: affine thin-plate-spline interpolants only", GSL_EINVAL);
+  if (c->size != st->dim + 1) GSL_ERROR("gsl_sinterp_field_poly: vector length must be dim + 1", GSL_EBADLEN);
+  for (size_t a = 0; a <= st->dim; a++) gsl_vector_set(c, a, st->f_poly[q][a]);
+  return GSL_SUCCESS;
+}
+
 int gsl_sinterp_poly(const gsl_sinterp *interp, gsl_vector *c)
 {
   if (!interp || !c) GSL_ERROR("gsl_sinterp_poly: null argument", GSL_EFAULT);
@@ -1719,6 +1920,7 @@ int gsl_sinterp_fwrite(FILE *stream, const gsl_sinterp *interp)
   }
   const rbf_state *st = (const rbf_state *)interp->state;
   if (!st->d_w) GSL_ERROR("gsl_sinterp_fwrite: interpolant not initialised", GSL_EINVAL);
+  if (st->nf > 1) GSL_ERROR("gsl_sinterp_fwrite: the GSLSINT1 format holds one weight vector (interpolant with several fields)", GSL_EUNSUP);
   const size_t cnt = st->n * (st->dim + 1);
   double *h = (double *)malloc(cnt * sizeof(double));
   if (!h) GSL_ERROR("gsl_sinterp_fwrite: out of memory", GSL_ENOMEM);
@@ -1801,12 +2003,14 @@ int gsl_sinterp_fread(FILE *stream, gsl_sinterp *interp)
   double poly[4] = {0.0, 0.0, 0.0, 0.0};
   if (st->affine && fread(poly, sizeof(double), 4, stream) != 4) { free(h); GSL_ERROR("fread failed", GSL_EFAILED); }
   rbf_release_variance(st);                             /* a factor kept by an earlier init belongs to another model */
-  int s = rbf_prepare_devices(interp, st);
+  int s = rbf_prepare_devices(interp, st, 1);
   if (s) { free(h); return s; }
+  st->nf = 1;
   st->var_state = 3;                                    /* the checkpoint carries no factor */
   st->eps = eps;
   if (st->krige) memcpy(&st->mean, &flags, sizeof st->mean);
   if (st->affine) memcpy(st->poly, poly, sizeof poly);
+  st->f_mean[0] = st->mean; memcpy(st->f_poly[0], st->poly, sizeof st->poly);
   st->model_id = next_model_id();
   s = gsl_sinterp_hip_h2d(st->ctx, st->d_x, h, cnt * sizeof(double));
   if (!s && st->ss.grp) s = gsl_sinterp_hip_group_broadcast(st->ss.grp, (void *const *)st->m_model, cnt * sizeof(double));

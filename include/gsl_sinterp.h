@@ -352,6 +352,39 @@ int gsl_sinterp_eval_grad_e(const gsl_sinterp *interp, const gsl_vector *y, doub
 int gsl_sinterp_eval_grad_many(const gsl_sinterp *interp, const gsl_matrix *y, gsl_vector *s /* may be NULL */, gsl_matrix *g);
 int gsl_sinterp_eval_grad_resident(const gsl_sinterp *interp, const double *d_y, size_t m, size_t ytda,
                                    double *d_s /* may be NULL */, double *d_g, size_t gtda);
+/* Several fields on one set of centres (the RBF family; SciPy's RBFInterpolator takes d of shape (N, K) the same way):
+   temperature, pressure and humidity at the stations, or the components of a vector field.  gsl_sinterp_init_fields(x, F)
+   takes F of size x K (F->tda honoured, 1 <= K <= GSL_SINTERP_MAX_FIELDS = 64) and solves all K weight vectors; the
+   eval_fields entries return the K values of a target from ONE sweep, in which the distance, the take test and the kernel
+   of a (target, centre) pair are computed once for all fields.
+   WHICH TYPES SHARE THE FACTORISATION: gsl_sinterp_rbf_gaussian, gsl_sinterp_rbf_wendland and gsl_sinterp_kriging with the
+   default solver and without gsl_sinterp_set_rcond pay ONE fill and ONE Cholesky factorisation for all K fields
+   (gsl_sinterp_route 1 / 7).  gsl_sinterp_rbf_tps and gsl_sinterp_rbf_tps_affine, a non-default gsl_sinterp_set_solver,
+   gsl_sinterp_set_rcond, and kriging on a covariance matrix that is only semi-definite solve field by field -- correct, at
+   the price of K factorisations; gsl_sinterp_route is then the last field's, gsl_sinterp_rcond the first field's.
+   To every other entry a K-field interpolant IS field 0's interpolant: eval_e / _many / _resident, the gradient entries,
+   eval_grid, get_weights, mean and poly; gsl_sinterp_eval_many returns the bits of column 0 of eval_fields_many.  The
+   kriging variance does not depend on the responses: gsl_sinterp_set_variance is honoured by init_fields (shared route)
+   and the variance entries work unchanged.  gsl_sinterp_init after init_fields returns the interpolant to one field, a
+   second init_fields may change K; the eval_fields entries work on a one-field interpolant with K = 1.
+   gsl_sinterp_n_fields: 0 before the first init (and for the linear types), 1 after gsl_sinterp_init / gsl_sinterp_fread.
+   eval_fields_many: y is m x dim, S is m x K (S->tda honoured, padding untouched).  eval_fields_e: s has K entries, NaN
+   on failure.  eval_fields_resident: everything in HBM, target k's field q at d_s[k * stda + q] (stda >= K).
+   get_field_weights / field_mean (kriging) / field_poly (affine thin-plate spline) read field q back.
+   GSL_EFAULT: a NULL argument; GSL_EUNSUP: gsl_sinterp_linear_simplex / gsl_sinterp_linear_mesh (several responses per
+   leaf are a separate piece of work); GSL_EBADLEN: F->size1 != size, x not size x dim, y->size2 != dim, S not m x K, a
+   vector whose length is not K / size / dim + 1, q >= K; GSL_EINVAL: not initialised, K = 0 or K > 64, stda < K, mean /
+   poly asked of another type.  With a device list the model is broadcast whole and the first device evaluates every
+   fields batch through plain staging (not sharded, not pipelined).  gsl_sinterp_fwrite of an interpolant with more than
+   one field returns GSL_EUNSUP and writes nothing: the GSLSINT1 format holds one weight vector. */
+int gsl_sinterp_init_fields(gsl_sinterp *interp, const gsl_matrix *x, const gsl_matrix *F);
+size_t gsl_sinterp_n_fields(const gsl_sinterp *interp);
+int gsl_sinterp_eval_fields_e(const gsl_sinterp *interp, const gsl_vector *y, gsl_vector *s);
+int gsl_sinterp_eval_fields_many(const gsl_sinterp *interp, const gsl_matrix *y, gsl_matrix *S);
+int gsl_sinterp_eval_fields_resident(const gsl_sinterp *interp, const double *d_y, size_t m, size_t ytda, double *d_s, size_t stda);
+int gsl_sinterp_get_field_weights(const gsl_sinterp *interp, size_t q, gsl_vector *w);
+int gsl_sinterp_field_mean(const gsl_sinterp *interp, size_t q, double *mean);
+int gsl_sinterp_field_poly(const gsl_sinterp *interp, size_t q, gsl_vector *c);
 /* Gridded front-end (interpolation/scattered_interp_example.c:175-217): evaluate on the regular grid
    x_i = min[0] + i (max[0]-min[0])/n0, y_j = min[1] + j (max[1]-min[1])/n1 (the reference's steps: range / n_grid,
    the upper bounds excluded) with n0 = grid->size1, n1 = grid->size2; grid(i, j) receives the value.  The

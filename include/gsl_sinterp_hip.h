@@ -239,6 +239,47 @@ int gsl_sinterp_hip_rbf_eval_grad(gsl_sinterp_hip_ctx *ctx, int kind, double eps
                                   double *d_s /* may be NULL */, double *d_g, size_t gtda,
                                   unsigned long long model_id);
 
+/* Several fields on one set of centres: K weight vectors, one fused sweep.  The distance, the take test and phi of a
+   (target, centre) pair are computed once and serve every field; a further field costs one FMA and one select per pair.
+   d_w: column q at d_w + q * ldw (ldw >= n); d_s: target k's field q at d_s[k * stda + q] (stda >= nf, the layout of an
+   m x nf gsl_matrix; nothing beyond the nf columns of a row is written).  h_tail: NULL, or nf * (dim + 1) host doubles,
+   {c_0 .. c_dim} of field q at h_tail + q * (dim + 1), added as s_q += c_0 + sum_a c_a y_a (the affine thin-plate
+   polynomials; kriging passes {mu_q, 0, ..}).  1 <= nf <= GSL_SINTERP_MAX_FIELDS.
+   BIT RULE: field q has the bits of gsl_sinterp_hip_rbf_eval_model (_eval_affine / krige_eval with the tail) called with
+   d_w = column q for the same centres, target and kind: the same terms in the same order (input order below N = 1024 and
+   for the thin-plate kind, Morton order above), the same take criterion, the same choice of kernel by N.  A target with
+   a NaN coordinate gives NaN in all nf outputs (Gaussian / Wendland: restored at the store; thin-plate: through every
+   term).  The fields are swept in passes of gsl_sinterp_hip_rbf_fields_block() fields (see there).  Batches of
+   >= 4096 Gaussian / Wendland targets are grouped through the one-level permutation, as for _eval_grad.  model_id as
+   for _eval_model; the packed {x, w_0 .. w_{nf-1}} records of the culled sweep are cached in a slot of their own (keyed by
+   nf and ldw too), so scalar and fields calls on one model id do not evict each other.
+   GSL_EINVAL: dim outside 1..3, unknown kind, xtda / ytda < dim, ldw < n, stda < nf, nf outside 1..64; GSL_EFAULT: a NULL
+   pointer with work to do; m = 0 succeeds and touches nothing. */
+#define GSL_SINTERP_MAX_FIELDS 64
+int gsl_sinterp_hip_rbf_eval_fields(gsl_sinterp_hip_ctx *ctx, int kind, double eps, const double *h_tail,
+                                    const double *d_x, size_t n, int dim, size_t xtda, const double *d_w, size_t ldw,
+                                    size_t nf, const double *d_y, size_t m, size_t ytda, double *d_s, size_t stda,
+                                    unsigned long long model_id);
+/* the two compile-time field blocks of the sweep: passes of _block() fields while more than _block_small() are left, the
+   last <= _block_small() fields in a pass of the small instance */
+int gsl_sinterp_hip_rbf_fields_block(void);
+int gsl_sinterp_hip_rbf_fields_block_small(void);
+/* Gaussian / Wendland, nf right-hand sides: ONE fill, ONE Cholesky factorisation, nf solves.  d_w holds F on entry
+   (column q = f_q at d_w + q * ldw) and the weights on exit; route 1.  The first min(nf, 5) columns ride the
+   factorisation (gsl_sinterp_hip_cholesky_factor_solve), the others are solved against the finished factor five at a
+   time; columns of different groups agree to rounding, not bitwise.  A GEMM-based triangular solve for very many fields
+   is not provided.  GSL_EINVAL: the thin-plate kind (its shifted-SPD / Woodbury solve is per field), dim, lda / ldw < n,
+   nf outside 1..64; GSL_EDOM: not positive definite. */
+int gsl_sinterp_hip_rbf_solve_fields(gsl_sinterp_hip_ctx *ctx, int kind, double eps, const double *d_x, size_t n, int dim,
+                                     size_t xtda, double *d_phi, size_t lda, double *d_w, size_t ldw, size_t nf, int *h_route);
+/* Ordinary kriging of nf fields: nf + 1 right-hand sides (f_0 .. f_{nf-1}, 1) on one factor of K = Phi + nugget I,
+   h_mean[nf] receives the means; route 7.  GSL_EDOM when K is not positive definite (nothing is retried here: the caller
+   falls back to gsl_sinterp_hip_krige_solve per field, whose route 8 handles a semi-definite K; d_w is then undefined).
+   The factor is left in the lower triangle of d_phi as krige_solve leaves it (gsl_sinterp_hip_krige_variance_prepare). */
+int gsl_sinterp_hip_krige_solve_fields(gsl_sinterp_hip_ctx *ctx, int kind, double eps, double nugget, const double *d_x,
+                                       size_t n, int dim, size_t xtda, double *d_phi, size_t lda, double *d_w, size_t ldw,
+                                       size_t nf, double *h_mean, int *h_route);
+
 /* "init" of an RBF interpolant in one call: fill d_phi (n x n scratch, lda), solve Phi w = f
    with d_w holding f on entry and w on exit.  *h_route reports the solver used:
    1 Cholesky (Gaussian, SPD) -- 2 shifted-SPD Cholesky + rank-(d+1) Woodbury correction
