@@ -92,7 +92,8 @@ class gsl_sinterp(C.Structure):
     _fields_ = [("type", C.c_void_p), ("dim", C.c_size_t), ("size", C.c_size_t), ("device", C.c_int),
                 ("shape", C.c_double), ("init_flags", C.c_int), ("rng", C.c_void_p), ("state", C.c_void_p),
                 ("n_devices", C.c_int), ("devices", C.c_int * 64), ("solver", C.c_int), ("want_rcond", C.c_int),
-                ("rcond", C.c_double), ("route", C.c_int), ("nugget", C.c_double), ("want_variance", C.c_int)]
+                ("rcond", C.c_double), ("route", C.c_int), ("nugget", C.c_double), ("want_variance", C.c_int),
+                ("want_loo", C.c_int)]
 
 
 _vp, _i, _sz, _d = C.c_void_p, C.c_int, C.c_size_t, C.c_double
@@ -250,6 +251,12 @@ SIGNATURES = {
     "gsl_sinterp_eval_variance_e": (_i, [C.POINTER(gsl_sinterp), _pv, _pd]),
     "gsl_sinterp_eval_variance_many": (_i, [C.POINTER(gsl_sinterp), _pm, _pv]),
     "gsl_sinterp_eval_variance_resident": (_i, [C.POINTER(gsl_sinterp), _vp, _sz, _sz, _vp]),
+    "gsl_sinterp_hip_chol_inv_diag_work": (_sz, [_sz, _sz]),
+    "gsl_sinterp_hip_chol_inv_diag": (_i, [_vp, _sz, _vp, _sz, _vp, _vp, _sz]),
+    "gsl_sinterp_hip_loo_combine": (_i, [_vp, _sz, _sz, _vp, _vp, _d, _vp, _sz, _vp, _sz, _vp]),
+    "gsl_sinterp_set_loo": (_i, [C.POINTER(gsl_sinterp), _i]),
+    "gsl_sinterp_loo_residuals": (_i, [C.POINTER(gsl_sinterp), _pm]),
+    "gsl_sinterp_loo_variance": (_i, [C.POINTER(gsl_sinterp), _pv]),
     "gsl_sinterp_eval_grad_e": (_i, [C.POINTER(gsl_sinterp), _pv, _pd, _pv]),
     "gsl_sinterp_eval_grad_many": (_i, [C.POINTER(gsl_sinterp), _pm, _pv, _pm]),
     "gsl_sinterp_eval_grad_resident": (_i, [C.POINTER(gsl_sinterp), _vp, _sz, _sz, _vp, _vp, _sz]),
@@ -576,6 +583,19 @@ class HipContext:
     def krige_variance(self, kind, eps, d_x, n, dim, xtda, d_llt, lda, d_b, d_dinv, denom, d_y, m, ytda, d_var, d_work, chunk):
         return lib().gsl_sinterp_hip_krige_variance(self._h, kind, eps, d_x, n, dim, xtda, d_llt, lda, d_b, d_dinv, denom,
                                                     d_y, m, ytda, d_var, d_work, chunk)
+
+    @staticmethod
+    def chol_inv_diag_work(n, chunk):
+        """doubles of d_work that chol_inv_diag needs for `chunk` rows per pass"""
+        return lib().gsl_sinterp_hip_chol_inv_diag_work(n, chunk)
+
+    def chol_inv_diag(self, n, d_llt, lda, d_g, d_work, chunk):
+        """d_g[i] = ((L L^T)^-1)_ii from the lower triangle of d_llt; returns the status"""
+        return lib().gsl_sinterp_hip_chol_inv_diag(self._h, n, d_llt, lda, d_g, d_work, chunk)
+
+    def loo_combine(self, n, nf, d_g, d_b, denom, d_w, ldw, d_e, lde, d_v):
+        """leave-one-out residuals d_e (nf columns) and variances d_v from g; d_b = None: the plain rule; returns the status"""
+        return lib().gsl_sinterp_hip_loo_combine(self._h, n, nf, d_g, d_b, denom, d_w, ldw, d_e, lde, d_v)
 
     def gemm_minus(self, m, n, k, d_a, lda, d_b, ldb, b_is_kn, d_c, ldc, lower_only=0):
         check(lib().gsl_sinterp_hip_gemm_minus(self._h, m, n, k, d_a, lda, d_b, ldb, b_is_kn, d_c, ldc, lower_only),
@@ -956,6 +976,22 @@ class Sinterp:
 
     def eval_variance_resident(self, d_y, m, ytda, d_var):
         return lib().gsl_sinterp_eval_variance_resident(self._p, d_y, m, ytda, d_var)
+
+    def set_loo(self, want=True):
+        """Gaussian / Wendland / kriging: the next init computes the leave-one-out residuals and variances"""
+        return lib().gsl_sinterp_set_loo(self._p, int(want))
+
+    def loo_residuals(self, out=None):
+        """(status, E): the size x K leave-one-out residuals f_i - s^(-i)(x_i); out = preallocated E (row stride honoured)"""
+        E = np.full((self._p.contents.size, max(self.n_fields(), 1)), np.nan) if out is None else out
+        st = lib().gsl_sinterp_loo_residuals(self._p, C.byref(as_matrix(E)))
+        return st, E
+
+    def loo_variance(self, out=None):
+        """(status, v): the leave-one-out variances"""
+        v = np.full(self._p.contents.size, np.nan) if out is None else out
+        st = lib().gsl_sinterp_loo_variance(self._p, C.byref(as_vector(v)))
+        return st, v
 
     def eval_grad_e(self, y):
         """(status, s, g): value and gradient (dim entries) at one target; NaN on failure"""

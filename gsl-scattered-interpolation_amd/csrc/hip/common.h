@@ -193,6 +193,22 @@ int sinterp_cholesky_factor_solve_sym(gsl_sinterp_hip_ctx *ctx, size_t n, double
    against the finished factor in groups of <= 5 (sinterp_cholesky_svx_multi) */
 int sinterp_cholesky_factor_solve_many_sym(gsl_sinterp_hip_ctx *ctx, size_t n, double *d_a, size_t lda, int *h_info, double *d_x,
                                            size_t ldx, int nrhs);
+/* krige_var.hip: the pieces of the blocked substitution Z <- Z L^-T that the kriging variance and the leave-one-out
+   diagonal (loo.hip) share.  One pass works on rows_pad rows (a multiple of 128) of the work matrix Z (pitch ldw = n
+   rounded up to 128, 16-byte aligned) against the lower triangle of L; q receives the squared row norms. */
+struct KvPass {
+  gsl_sinterp_hip_ctx *ctx;
+  double *Z; size_t ldw, rows_pad;
+  const double *L; size_t lda, n;
+  const double *dinv;
+  double *q;
+};
+/* Z[:, c0 : c0 + cw] -= Z[:, k0 : k0 + kw] L[c0 : c0 + cw, k0 : k0 + kw]^T (a partial last block in a call of its own) */
+int sinterp_kv_update(const KvPass &p, size_t c0, size_t cw, size_t k0, size_t kw);
+/* Z[:, j0 : j0 + 128] <- Z[:, j0 : j0 + 128] L_JJ^-T and q_k += |Z[k][j0 : j0 + 128]|^2 (krige_trsm128_kernel) */
+int sinterp_kv_diag(const KvPass &p, size_t j0);
+/* inverse of every 32 x 32 diagonal block of L -> d_dinv[ceil(n / 32) * 1024] (krige_inv32_kernel) */
+int sinterp_krige_inv32(gsl_sinterp_hip_ctx *ctx, size_t n, const double *d_llt, size_t lda, double *d_dinv);
 /* second grow-only buffer for vectors that must outlive factorisation workspaces */
 int sinterp_aux(gsl_sinterp_hip_ctx *ctx, size_t bytes, void **out);
 int sinterp_invbuf(gsl_sinterp_hip_ctx *ctx, size_t bytes, void **out);

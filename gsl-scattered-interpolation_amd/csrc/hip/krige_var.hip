@@ -99,6 +99,13 @@ krige_inv32_kernel(const double *__restrict__ L, size_t lda, size_t n, double *_
   for (int i = 0; i < CB; i++) out[i * CB + lane] = xv[i];
 }
 
+int sinterp_krige_inv32(gsl_sinterp_hip_ctx *ctx, size_t n, const double *d_llt, size_t lda, double *d_dinv)
+{
+  hipLaunchKernelGGL(krige_inv32_kernel, dim3((unsigned)((n + CB - 1) / CB)), dim3(64), 0, ctx->stream, d_llt, lda, n, d_dinv);
+  LAUNCH_CHECK(ctx);
+  return ST_SUCCESS;
+}
+
 /* ------------------------------------------------------------------------ */
 /* the diagonal step: Z[:, J] <- Z[:, J] L_JJ^-T for the 128-column block J at j0, and q_k += |Z[k][J]|^2.
    The scheme of chol_trsm128_kernel (chol.hip): 64 rows per workgroup, wave w owns rows 16w .. 16w+15 for all four
@@ -246,18 +253,9 @@ static void launch_cross_fill(gsl_sinterp_hip_ctx *ctx, double coef, const doubl
   }
 }
 
-/* one pass over rows_pad rows of Z */
-struct KvPass {
-  gsl_sinterp_hip_ctx *ctx;
-  double *Z; size_t ldw, rows_pad;
-  const double *L; size_t lda, n;
-  const double *dinv;
-  double *q;
-};
-
 /* Z[:, c0 : c0 + cw] -= Z[:, k0 : k0 + kw] L[c0 : c0 + cw, k0 : k0 + kw]^T; a partial last block (c0 + cw = n, not a
    multiple of 128) goes in a call of its own so that the blocks before it keep the full-tile path */
-static int kv_update(const KvPass &p, size_t c0, size_t cw, size_t k0, size_t kw)
+int sinterp_kv_update(const KvPass &p, size_t c0, size_t cw, size_t k0, size_t kw)
 {
   if (cw == 0 || kw == 0) return ST_SUCCESS;
   const size_t whole = cw / PB * PB;
@@ -270,7 +268,7 @@ static int kv_update(const KvPass &p, size_t c0, size_t cw, size_t k0, size_t kw
   return st;
 }
 
-static int kv_diag(const KvPass &p, size_t j0)
+int sinterp_kv_diag(const KvPass &p, size_t j0)
 {
   const size_t lds = (size_t)(64 * TR_LD + 10 * PBLK) * sizeof(double);
   int st = sinterp_func_lds(p.ctx, (const void *)krige_trsm128_kernel, (int)lds);
@@ -284,11 +282,11 @@ static int kv_diag(const KvPass &p, size_t j0)
    single blocks */
 static int kv_solve_range(const KvPass &p, size_t j0, size_t w)
 {
-  if (w <= PB) return kv_diag(p, j0);
+  if (w <= PB) return sinterp_kv_diag(p, j0);
   size_t w1 = ((w / 2 + PB - 1) / PB) * PB;
   if (w1 >= w) w1 = w - PB;
   int st = kv_solve_range(p, j0, w1);
-  if (!st) st = kv_update(p, j0 + w1, w - w1, j0, w1);
+  if (!st) st = sinterp_kv_update(p, j0 + w1, w - w1, j0, w1);
   if (!st) st = kv_solve_range(p, j0 + w1, w - w1);
   return st;
 }
@@ -302,7 +300,7 @@ static int kv_solve(const KvPass &p, size_t panel)
 {
   for (size_t j0 = 0; j0 < p.n; j0 += panel) {
     const size_t w = p.n - j0 < panel ? p.n - j0 : panel;
-    int st = kv_update(p, j0, w, 0, j0);
+    int st = sinterp_kv_update(p, j0, w, 0, j0);
     if (!st) st = kv_solve_range(p, j0, w);
     if (st) return st;
   }
@@ -326,9 +324,9 @@ extern "C" int gsl_sinterp_hip_krige_variance_prepare(gsl_sinterp_hip_ctx *ctx, 
   *h_denom = 0.0;
   if (n == 0) return ST_SUCCESS;
   hipLaunchKernelGGL(krige_ones_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, d_b, n);
-  hipLaunchKernelGGL(krige_inv32_kernel, dim3((unsigned)((n + CB - 1) / CB)), dim3(64), 0, ctx->stream, d_llt, lda, n, d_dinv);
-  LAUNCH_CHECK(ctx);
-  int st = sinterp_cholesky_svx_multi(ctx, n, d_llt, lda, d_b, n, 1);             /* b = (L L^T)^-1 1 */
+  int st = sinterp_krige_inv32(ctx, n, d_llt, lda, d_dinv);
+  if (st) return st;
+  st = sinterp_cholesky_svx_multi(ctx, n, d_llt, lda, d_b, n, 1);                 /* b = (L L^T)^-1 1 */
   if (st) return st;
   double *h_b = (double *)malloc(n * sizeof(double));
   if (!h_b) return sinterp_fail(ctx, ST_ENOMEM, "krige_variance_prepare: host buffer", hipSuccess, __FILE__, __LINE__);

@@ -803,7 +803,16 @@ typedef struct {
   double *d_llt, *d_b, *d_dinv, *d_vwork;
   size_t llt_lda, vwork_doubles;
   double denom;
+  /* leave-one-out (gsl_sinterp_set_loo): residuals (column q at loo_e + q * n, loo_nf columns) and variances of the last
+     init, on the host.  loo_state: 0 nothing held (not asked for), 1 ready, 2 the init took a route without a Cholesky
+     factor, 3 restored from a checkpoint */
+  int loo_state;
+  size_t loo_nf;
+  double *loo_e, *loo_v;
 } rbf_state;
+
+/* rows of the work matrix per pass of gsl_sinterp_hip_chol_inv_diag ("Leave-one-out") */
+#define LOO_CHUNK 2048
 
 static unsigned long long next_model_id(void)
 {
@@ -845,6 +854,52 @@ static void rbf_release_variance(rbf_state *st)
   st->llt_lda = st->vwork_doubles = 0; st->denom = 0.0; st->var_state = 0;
 }
 
+static void rbf_release_loo(rbf_state *st)
+{
+  free(st->loo_e); free(st->loo_v);
+  st->loo_e = st->loo_v = NULL; st->loo_nf = 0; st->loo_state = 0;
+}
+
+/* Leave-one-out from the factor in the lower triangle of d_llt (routes 1 and 7) and the solved weights in st->d_w: the
+   diagonal of the inverse, the combine, and the copy to the host arrays of the state.  Kriging takes b = K^-1 1 and
+   1^T b from the kept variance data when there is one, from temporaries otherwise.  Everything allocated here is freed
+   again: the factor is not kept for this. */
+static int rbf_compute_loo(rbf_state *st, const double *d_llt, size_t lda, size_t nf)
+{
+  gsl_sinterp_hip_ctx *c = st->ctx;
+  const size_t n = st->n;
+  size_t chunk = (n + 127) / 128 * 128;
+  if (chunk > LOO_CHUNK) chunk = LOO_CHUNK;
+  double *d_out = NULL, *d_work = NULL, *d_tb = NULL, *d_tdinv = NULL;     /* d_out = [g | v | E] */
+  const double *d_b = NULL;
+  double denom = 0.0;
+  st->loo_e = (double *)malloc(n * nf * sizeof(double));
+  st->loo_v = (double *)malloc(n * sizeof(double));
+  int s = st->loo_e && st->loo_v ? GSL_SUCCESS : GSL_ENOMEM;
+  if (!s && st->krige) {
+    if (st->var_state == 1) {
+      d_b = st->d_b; denom = st->denom;
+    } else {
+      s = gsl_sinterp_hip_malloc(c, (void **)&d_tb, n * sizeof(double));
+      if (!s) s = gsl_sinterp_hip_malloc(c, (void **)&d_tdinv, ((n + 31) / 32) * 1024 * sizeof(double));
+      if (!s) s = gsl_sinterp_hip_krige_variance_prepare(c, n, d_llt, lda, d_tb, d_tdinv, &denom);
+      d_b = d_tb;
+    }
+  }
+  if (!s) s = gsl_sinterp_hip_malloc(c, (void **)&d_out, n * (nf + 2) * sizeof(double));
+  if (!s) s = gsl_sinterp_hip_malloc(c, (void **)&d_work, gsl_sinterp_hip_chol_inv_diag_work(n, chunk) * sizeof(double));
+  if (!s) s = gsl_sinterp_hip_chol_inv_diag(c, n, d_llt, lda, d_out, d_work, chunk);
+  if (!s) s = gsl_sinterp_hip_loo_combine(c, n, nf, d_out, d_b, denom, st->d_w, n, d_out + 2 * n, n, d_out + n);
+  if (!s) s = gsl_sinterp_hip_d2h(c, st->loo_v, d_out + n, n * sizeof(double));
+  if (!s) s = gsl_sinterp_hip_d2h(c, st->loo_e, d_out + 2 * n, n * nf * sizeof(double));
+  if (s) (void)gsl_sinterp_hip_sync(c);                  /* nothing queued may still use the buffers freed below */
+  gsl_sinterp_hip_free(c, d_out); gsl_sinterp_hip_free(c, d_work);
+  gsl_sinterp_hip_free(c, d_tb); gsl_sinterp_hip_free(c, d_tdinv);
+  if (s) { rbf_release_loo(st); return s; }
+  st->loo_nf = nf; st->loo_state = 1;
+  return GSL_SUCCESS;
+}
+
 static void rbf_release_devices(rbf_state *st)
 {
   rbf_release_variance(st);
@@ -867,6 +922,7 @@ static void rbf_free(void *vstate)
   rbf_state *st = (rbf_state *)vstate;
   if (!st) return;
   rbf_release_devices(st);
+  rbf_release_loo(st);
   free(st);
 }
 
@@ -892,6 +948,7 @@ static int rbf_init_fields(gsl_sinterp *interp, const gsl_matrix *x, const doubl
   const size_t n = st->n, dim = st->dim;
   const int nd = interp->n_devices > 1 ? interp->n_devices : 1;
   rbf_release_variance(st);                             /* the factor of the previous model, if one was kept */
+  rbf_release_loo(st);                                  /* ... and its leave-one-out data */
   int s = rbf_prepare_devices(interp, st, nf);
   if (s) return s;
   st->nf = 0;                                           /* not initialised until the solve succeeds */
@@ -956,6 +1013,12 @@ static int rbf_init_fields(gsl_sinterp *interp, const gsl_matrix *x, const doubl
       st->var_state = 2;
     }
   }
+  /* leave-one-out asked for: routes 1 and 7 left L in the lower triangle of d_phi (with set_rcond too: the original
+     stays ABOVE the diagonal), still alive here or just handed to the variance; every other route has no factor */
+  if (!s && interp->want_loo) {
+    if (route == 1 || route == 7) s = rbf_compute_loo(st, st->d_llt ? st->d_llt : d_phi, lda, nf);
+    else st->loo_state = 2;
+  }
   /* replicate the solved model: ONE broadcast of the weight vector (+ centres) */
   if (!s && st->ss.grp) s = gsl_sinterp_hip_group_broadcast(st->ss.grp, (void *const *)st->m_model, model_bytes);
   if (!s) s = gsl_sinterp_hip_sync(c);
@@ -963,7 +1026,7 @@ static int rbf_init_fields(gsl_sinterp *interp, const gsl_matrix *x, const doubl
     for (int r = 1; r < nd; r++) { int s2 = gsl_sinterp_hip_sync(gsl_sinterp_hip_group_ctx(st->ss.grp, r)); if (!s) s = s2; }
   gsl_sinterp_hip_free(c, d_phi);
   free(h_x); free(h_f);
-  if (s) rbf_release_variance(st);
+  if (s) { rbf_release_variance(st); rbf_release_loo(st); }
   if (s == GSL_EDOM) GSL_ERROR("gsl_sinterp_init: kernel matrix is not positive definite", GSL_EDOM);
   HIP_TRY(s, c);
   st->nf = nf;
@@ -1337,6 +1400,54 @@ int gsl_sinterp_set_variance(gsl_sinterp *interp, int want)
   if (!interp) GSL_ERROR("gsl_sinterp_set_variance: null interpolant", GSL_EFAULT);
   if (interp->type != &krige_type) GSL_ERROR("gsl_sinterp_set_variance: kriging interpolants only", GSL_EINVAL);
   interp->want_variance = want != 0;
+  return GSL_SUCCESS;
+}
+
+int gsl_sinterp_set_loo(gsl_sinterp *interp, int want)
+{
+  if (!interp) GSL_ERROR("gsl_sinterp_set_loo: null interpolant", GSL_EFAULT);
+  if (interp->type != &gauss_type && interp->type != &wendland_type && interp->type != &krige_type)
+    GSL_ERROR("gsl_sinterp_set_loo: Gaussian, Wendland and kriging interpolants only", GSL_EINVAL);
+  interp->want_loo = want != 0;
+  return GSL_SUCCESS;
+}
+
+/* whether leave-one-out data is held, as a status (the table of include/gsl_sinterp.h) */
+static int loo_status(const gsl_sinterp *interp)
+{
+  if (interp->type != &gauss_type && interp->type != &wendland_type && interp->type != &krige_type)
+    GSL_ERROR("gsl_sinterp_loo: Gaussian, Wendland and kriging interpolants only", GSL_EINVAL);
+  const rbf_state *st = (const rbf_state *)interp->state;
+  if (!st->d_w || st->nf == 0) GSL_ERROR("gsl_sinterp_loo: interpolant not initialised", GSL_EINVAL);
+  if (st->loo_state == 3)
+    GSL_ERROR("gsl_sinterp_loo: the interpolant was restored by gsl_sinterp_fread; a checkpoint carries no leave-one-out data", GSL_EINVAL);
+  if (st->loo_state == 2)
+    GSL_ERROR("gsl_sinterp_loo: the init took a route without a Cholesky factor", GSL_EUNSUP);
+  if (st->loo_state != 1)
+    GSL_ERROR("gsl_sinterp_loo: initialised without gsl_sinterp_set_loo", GSL_EINVAL);
+  return GSL_SUCCESS;
+}
+
+int gsl_sinterp_loo_residuals(const gsl_sinterp *interp, gsl_matrix *E)
+{
+  if (!interp || !E) GSL_ERROR("gsl_sinterp_loo_residuals: null argument", GSL_EFAULT);
+  int ls = loo_status(interp);
+  if (ls) return ls;
+  const rbf_state *st = (const rbf_state *)interp->state;
+  if (E->size1 != st->n || E->size2 != st->loo_nf) GSL_ERROR("gsl_sinterp_loo_residuals: E must be size x fields", GSL_EBADLEN);
+  for (size_t i = 0; i < st->n; i++)
+    for (size_t q = 0; q < st->loo_nf; q++) E->data[i * E->tda + q] = st->loo_e[q * st->n + i];
+  return GSL_SUCCESS;
+}
+
+int gsl_sinterp_loo_variance(const gsl_sinterp *interp, gsl_vector *v)
+{
+  if (!interp || !v) GSL_ERROR("gsl_sinterp_loo_variance: null argument", GSL_EFAULT);
+  int ls = loo_status(interp);
+  if (ls) return ls;
+  const rbf_state *st = (const rbf_state *)interp->state;
+  if (v->size != st->n) GSL_ERROR("gsl_sinterp_loo_variance: wrong length", GSL_EBADLEN);
+  for (size_t i = 0; i < st->n; i++) gsl_vector_set(v, i, st->loo_v[i]);
   return GSL_SUCCESS;
 }
 
@@ -2007,6 +2118,8 @@ int gsl_sinterp_fread(FILE *stream, gsl_sinterp *interp)
   if (s) { free(h); return s; }
   st->nf = 1;
   st->var_state = 3;                                    /* the checkpoint carries no factor */
+  rbf_release_loo(st);
+  st->loo_state = 3;                                    /* ... and no leave-one-out data */
   st->eps = eps;
   if (st->krige) memcpy(&st->mean, &flags, sizeof st->mean);
   if (st->affine) memcpy(st->poly, poly, sizeof poly);

@@ -270,6 +270,7 @@ struct gsl_sinterp_struct {
   int route;         /* solver route the last init took (gsl_sinterp_hip_rbf_solve_ex)       */
   double nugget;     /* kriging: added to the diagonal of the covariance matrix (>= 0, default 0) */
   int want_variance; /* kriging: the next init keeps the Cholesky factor for gsl_sinterp_eval_variance_* (default 0) */
+  int want_loo;      /* Gaussian / Wendland / kriging: the next init computes the leave-one-out residuals and variances (default 0) */
 };
 
 extern const gsl_sinterp_type *gsl_sinterp_rbf_gaussian;
@@ -317,6 +318,27 @@ int gsl_sinterp_set_variance(gsl_sinterp *interp, int want);            /* krigi
 int gsl_sinterp_eval_variance_e(const gsl_sinterp *interp, const gsl_vector *y, double *var);
 int gsl_sinterp_eval_variance_many(const gsl_sinterp *interp, const gsl_matrix *y, gsl_vector *var);
 int gsl_sinterp_eval_variance_resident(const gsl_sinterp *interp, const double *d_y, size_t m, size_t ytda, double *d_var);
+/* Leave-one-out cross-validation (Rippa's rule for the positive definite RBF types, Dubrule's for ordinary kriging): how
+   good the fit is, and a score for a shape parameter or nugget, without N refits.
+       e_i = f_i - s^(-i)(x_i)     the residual at site i of the model built without site i,
+       v_i                         Gaussian / Wendland: the squared power function phi(0) - k^T K_-i^-1 k at x_i;
+                                   kriging: the variance of the prediction error of the OBSERVATION f_i, i.e. what
+                                   eval_variance of the model without site i returns at x_i, plus the nugget.
+   Both come from the diagonal of the inverse of the Cholesky factor the init computes anyway: diag_i = (K^-1)_ii, for
+   kriging (A^-1)_ii = (K^-1)_ii - b_i^2 / (1^T b) with b = K^-1 1;  e_i = w_i / diag_i, v_i = 1 / diag_i.
+   gsl_sinterp_set_loo(interp, 1) BEFORE the init makes gsl_sinterp_init / gsl_sinterp_init_fields compute them on the
+   (first) device at about the price of a second factorisation (N^3 / 3 flops) and keep N (K + 1) doubles on the host; the
+   factor itself is not kept for it.  K fields share the diagonal: E is size x K.  Nothing is clamped: where rounding left
+   a diag_i non-positive (a kernel matrix at the edge of positive definiteness) v_i is returned as computed.
+   set_loo(0), the default, leaves the init and every evaluation exactly as they are.
+   GSL_EINVAL: another type than gsl_sinterp_rbf_gaussian / _wendland / gsl_sinterp_kriging, not initialised, initialised
+   without set_loo, or restored by gsl_sinterp_fread (a checkpoint carries no leave-one-out data, and reading one drops
+   what was held); GSL_EUNSUP: the init took a route without a Cholesky factor (an explicit gsl_sinterp_set_solver, the
+   pivoted LDL^T route 8 of kriging): gsl_sinterp_route is then neither 1 nor 7; GSL_EBADLEN: E is not size x K
+   (K = gsl_sinterp_n_fields; E->tda honoured, padding untouched), v does not have size entries. */
+int gsl_sinterp_set_loo(gsl_sinterp *interp, int want);
+int gsl_sinterp_loo_residuals(const gsl_sinterp *interp, gsl_matrix *E);
+int gsl_sinterp_loo_variance(const gsl_sinterp *interp, gsl_vector *v);
 int gsl_sinterp_poly(const gsl_sinterp *interp, gsl_vector *c);    /* c_0 .. c_dim of an initialised gsl_sinterp_rbf_tps_affine interpolant */
 int gsl_sinterp_set_solver(gsl_sinterp *interp, int solver);
 int gsl_sinterp_set_rcond(gsl_sinterp *interp, int want);

@@ -350,6 +350,27 @@ int gsl_sinterp_hip_krige_variance(gsl_sinterp_hip_ctx *ctx, int kind, double ep
 /* d_v[k] < 0 -> 0 for k < m (NaN stays NaN); asynchronous.  The facade's variance entries apply it. */
 int gsl_sinterp_hip_krige_variance_clamp(gsl_sinterp_hip_ctx *ctx, double *d_v, size_t m);
 
+/* Leave-one-out from a Cholesky factor K = L L^T (lower triangle of d_llt, as cholesky_decomp1, factor_solve, rbf_solve
+   route 1 and krige_solve route 7 leave it): d_g[i] = (K^-1)_ii = |row i of L^-T|^2, i < n, in N^3 / 3 + O(chunk N^2)
+   flops (fp64 MFMA GEMM) -- the recursion of the variance entry started from the identity, with the rows taken `chunk`
+   at a time (rounded up to 128, at most n rounded up to 128) and the zero part of the triangle skipped.  Only the lower
+   triangle of d_llt, diagonal included, is read; nothing is written outside d_g and d_work
+   (gsl_sinterp_hip_chol_inv_diag_work doubles, which also hold the inverted 32 x 32 diagonal blocks formed here).
+   Asynchronous on the context's stream.  g is the same bit for bit from run to run at a fixed chunk; different chunks
+   agree to rounding only (their updates differ in K range and height, and the stream-K GEMM splits K by the tile count).
+   GSL_EINVAL: lda < n or chunk == 0; GSL_EFAULT: a NULL pointer with n > 0; n == 0 succeeds and launches nothing. */
+size_t gsl_sinterp_hip_chol_inv_diag_work(size_t n, size_t chunk);
+int gsl_sinterp_hip_chol_inv_diag(gsl_sinterp_hip_ctx *ctx, size_t n, const double *d_llt, size_t lda, double *d_g,
+                                  double *d_work, size_t chunk);
+/* Leave-one-out residuals of nf weight vectors (column q at d_w + q * ldw) and the leave-one-out variance:
+       diag_i = g_i (d_b == NULL: plain SPD interpolant, Rippa) or g_i - b_i^2 / denom (ordinary kriging, Dubrule; b = K^-1 1,
+       denom = 1^T b as gsl_sinterp_hip_krige_variance_prepare returns them),
+       d_e[q * lde + i] = d_w[q * ldw + i] / diag_i,   d_v[i] = 1 / diag_i.
+   Not clamped: a diag_i that rounding made non-positive or non-finite is used as computed.  nf = 0 computes d_v only.
+   GSL_EINVAL: nf > 64, ldw or lde < n with nf > 0; GSL_EFAULT: a NULL pointer (other than d_b) with work to do. */
+int gsl_sinterp_hip_loo_combine(gsl_sinterp_hip_ctx *ctx, size_t n, size_t nf, const double *d_g, const double *d_b,
+                                double denom, const double *d_w, size_t ldw, double *d_e, size_t lde, double *d_v);
+
 /* Level-3 building block of both factorisations, exposed for tests and roofline
    measurement (role of gsl_blas_dgemm / dsyrk, blas/blas.c:1334,1649):
      C[m x n] -= A[m x k] * B^T  (b_is_kn = 0, B stored [n][k])
