@@ -14,6 +14,7 @@ GSL_SUCCESS, GSL_FAILURE = 0, -1
 GSL_EDOM, GSL_EFAULT, GSL_EINVAL, GSL_EFAILED, GSL_ENOMEM = 1, 3, 4, 5, 8
 GSL_EBADLEN, GSL_ENOTSQR, GSL_EUNSUP, GSL_EUNIMPL = 19, 20, 23, 24
 RBF_GAUSSIAN, RBF_TPS, RBF_WENDLAND = 0, 1, 2
+RBF_MATERN32, RBF_MATERN52, RBF_IMQ = 3, 4, 5
 SOLVER_DEFAULT, SOLVER_CHOLESKY2, SOLVER_PCHOLESKY, SOLVER_LU_REFINE = 0, 1, 2, 3
 TREE_DEFAULT, TREE_NOSTANDARDIZE, TREE_ISOSCALE = 0, 1, 2
 TREE_RECORD_BYTES, TREE_LEAFTAB_BYTES = 64, 32
@@ -297,6 +298,7 @@ SIGNATURES = {
     "gsl_rng_uniform_int": (C.c_ulong, [_vp, C.c_ulong]),
 }
 DATA_SYMBOLS = ["gsl_sinterp_kriging", "gsl_sinterp_linear_mesh", "gsl_sinterp_rbf_gaussian", "gsl_sinterp_rbf_tps", "gsl_sinterp_rbf_tps_affine", "gsl_sinterp_rbf_wendland", "gsl_sinterp_linear_simplex",
+                "gsl_sinterp_rbf_matern32", "gsl_sinterp_rbf_matern52", "gsl_sinterp_rbf_imq", "gsl_sinterp_kriging_matern32", "gsl_sinterp_kriging_matern52",
                 "gsl_rng_mt19937", "gsl_rng_default"]
 
 
@@ -938,7 +940,9 @@ class DeviceMesh:
 class Sinterp:
     TYPES = {"gaussian": "gsl_sinterp_rbf_gaussian", "tps": "gsl_sinterp_rbf_tps", "tps_affine": "gsl_sinterp_rbf_tps_affine",
              "wendland": "gsl_sinterp_rbf_wendland", "linear_mesh": "gsl_sinterp_linear_mesh",
-             "linear_simplex": "gsl_sinterp_linear_simplex", "kriging": "gsl_sinterp_kriging"}
+             "linear_simplex": "gsl_sinterp_linear_simplex", "kriging": "gsl_sinterp_kriging",
+             "matern32": "gsl_sinterp_rbf_matern32", "matern52": "gsl_sinterp_rbf_matern52", "imq": "gsl_sinterp_rbf_imq",
+             "kriging_matern32": "gsl_sinterp_kriging_matern32", "kriging_matern52": "gsl_sinterp_kriging_matern52"}
 
     def __init__(self, kind, dim, size, device=0):
         self._p = lib().gsl_sinterp_alloc(_ptr(self.TYPES[kind]), dim, size)
@@ -978,7 +982,7 @@ class Sinterp:
         return lib().gsl_sinterp_eval_variance_resident(self._p, d_y, m, ytda, d_var)
 
     def set_loo(self, want=True):
-        """Gaussian / Wendland / kriging: the next init computes the leave-one-out residuals and variances"""
+        """positive definite RBF types and kriging: the next init computes the leave-one-out residuals and variances"""
         return lib().gsl_sinterp_set_loo(self._p, int(want))
 
     def loo_residuals(self, out=None):

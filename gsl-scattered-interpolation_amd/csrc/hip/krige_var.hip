@@ -21,6 +21,7 @@
 #include "common.h"
 #include <math.h>
 #include <stdlib.h>
+#include <type_traits>
 #include "chol_potrf.h"
 #include "rbf_phi.h"
 
@@ -38,8 +39,8 @@ krige_cross_fill_kernel(double coef, const double *__restrict__ tbl, const doubl
                         const double *__restrict__ y, size_t rows, size_t ytda, double *__restrict__ Z, size_t ldw,
                         double *__restrict__ q)
 {
-  __shared__ double s_t0[KIND == GSL_SINTERP_RBF_GAUSSIAN ? TBL_N : 1];
-  if (KIND == GSL_SINTERP_RBF_GAUSSIAN) s_t0[threadIdx.x] = tbl[threadIdx.x];      /* TBL_N = 256 = the block */
+  __shared__ double s_t0[kind_uses_exp2(KIND) ? TBL_N : 1];
+  if (kind_uses_exp2(KIND)) s_t0[threadIdx.x] = tbl[threadIdx.x];      /* TBL_N = 256 = the block */
   __syncthreads();
   const size_t j0 = ((size_t)blockIdx.x * 64 + (threadIdx.x & 63)) * 2;
   const size_t ibase = (size_t)blockIdx.y * 16 + (threadIdx.x >> 6) * 4;
@@ -351,7 +352,7 @@ extern "C" int gsl_sinterp_hip_krige_variance(gsl_sinterp_hip_ctx *ctx, int kind
   HIP_OK(ctx, hipSetDevice(ctx->device));
   EXCLUSIVE_SECTION(ctx);                          /* the stream-K updates spin on sibling workgroups */
   REQUIRE(ctx, dim >= 1 && dim <= 3 && xtda >= (size_t)dim && ytda >= (size_t)dim && lda >= n && chunk >= 1, ST_EINVAL);
-  REQUIRE(ctx, kind == GSL_SINTERP_RBF_GAUSSIAN || kind == GSL_SINTERP_RBF_WENDLAND, ST_EINVAL);   /* covariances: positive definite kernels */
+  REQUIRE(ctx, kind_is_pd(kind), ST_EINVAL);       /* covariances: positive definite kernels */
   REQUIRE(ctx, (m == 0 || n == 0) || (d_x && d_llt && d_b && d_dinv && d_y && d_var && d_work), ST_EFAULT);
   if (m == 0 || n == 0) return ST_SUCCESS;
   if (chunk > ((size_t)1 << 19)) chunk = (size_t)1 << 19;      /* rows / 16 is a grid dimension */
@@ -366,7 +367,7 @@ extern "C" int gsl_sinterp_hip_krige_variance(gsl_sinterp_hip_ctx *ctx, int kind
   const double *tbl = NULL;
   st = sinterp_rbf_exp2_table(ctx, &tbl);
   if (st) return st;
-  const double coef = kind == GSL_SINTERP_RBF_WENDLAND ? eps : -(eps * eps) * 1.44269504088896340735992;   /* rbf.hip: kernel_coef */
+  const double coef = kernel_coef(kind, eps);
   /* a = b^T k(y) for every target at once, parked in d_var until the combine of its pass */
   st = gsl_sinterp_hip_rbf_eval(ctx, kind, eps, d_x, n, dim, xtda, d_b, d_y, m, ytda, d_var);
   if (st) return st;
@@ -378,10 +379,16 @@ extern "C" int gsl_sinterp_hip_krige_variance(gsl_sinterp_hip_ctx *ctx, int kind
   for (size_t k0 = 0; k0 < m; k0 += chunk) {
     const size_t rows = m - k0 < chunk ? m - k0 : chunk;
     p.rows_pad = kv_round_up(rows, KV_RP);
-    if (kind == GSL_SINTERP_RBF_WENDLAND)
-      launch_cross_fill<GSL_SINTERP_RBF_WENDLAND>(ctx, coef, tbl, d_x, n, dim, xtda, d_y + k0 * ytda, rows, ytda, p.Z, p.ldw, p.rows_pad, p.q);
-    else
-      launch_cross_fill<GSL_SINTERP_RBF_GAUSSIAN>(ctx, coef, tbl, d_x, n, dim, xtda, d_y + k0 * ytda, rows, ytda, p.Z, p.ldw, p.rows_pad, p.q);
+    const auto fill = [&](auto K) {
+      launch_cross_fill<decltype(K)::value>(ctx, coef, tbl, d_x, n, dim, xtda, d_y + k0 * ytda, rows, ytda, p.Z, p.ldw, p.rows_pad, p.q);
+    };
+    switch (kind) {
+      case GSL_SINTERP_RBF_WENDLAND: fill(std::integral_constant<int, GSL_SINTERP_RBF_WENDLAND>()); break;
+      case GSL_SINTERP_RBF_MATERN32: fill(std::integral_constant<int, GSL_SINTERP_RBF_MATERN32>()); break;
+      case GSL_SINTERP_RBF_MATERN52: fill(std::integral_constant<int, GSL_SINTERP_RBF_MATERN52>()); break;
+      case GSL_SINTERP_RBF_IMQ: fill(std::integral_constant<int, GSL_SINTERP_RBF_IMQ>()); break;
+      default: fill(std::integral_constant<int, GSL_SINTERP_RBF_GAUSSIAN>()); break;
+    }
     LAUNCH_CHECK(ctx);
     st = kv_solve(p, panel);
     if (st) return st;

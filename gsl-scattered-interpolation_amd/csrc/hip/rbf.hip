@@ -25,8 +25,14 @@ template <int V> using ic = std::integral_constant<int, V>;
 
 template <class F> static auto with_kind(int kind, F &&f)
 {
-  if (kind == GSL_SINTERP_RBF_WENDLAND) return f(ic<GSL_SINTERP_RBF_WENDLAND>());
-  return kind == GSL_SINTERP_RBF_GAUSSIAN ? f(ic<GSL_SINTERP_RBF_GAUSSIAN>()) : f(ic<GSL_SINTERP_RBF_TPS>());
+  switch (kind) {
+    case GSL_SINTERP_RBF_WENDLAND: return f(ic<GSL_SINTERP_RBF_WENDLAND>());
+    case GSL_SINTERP_RBF_GAUSSIAN: return f(ic<GSL_SINTERP_RBF_GAUSSIAN>());
+    case GSL_SINTERP_RBF_MATERN32: return f(ic<GSL_SINTERP_RBF_MATERN32>());
+    case GSL_SINTERP_RBF_MATERN52: return f(ic<GSL_SINTERP_RBF_MATERN52>());
+    case GSL_SINTERP_RBF_IMQ: return f(ic<GSL_SINTERP_RBF_IMQ>());
+    default: return f(ic<GSL_SINTERP_RBF_TPS>());
+  }
 }
 
 template <class F> static auto with_dim(int dim, F &&f)
@@ -91,9 +97,9 @@ int sinterp_rbf_exp2_table(gsl_sinterp_hip_ctx *ctx, const double **d_tbl)
 template <int COPIES>
 __device__ __forceinline__ void load_tables(double *s_t0, double *s_lt, int kind)
 {
-  if (kind == GSL_SINTERP_RBF_GAUSSIAN) {
+  if (kind_uses_exp2(kind)) {
     for (int i = threadIdx.x; i < TBL_N; i += blockDim.x) s_t0[i] = g_rbf_tables.exp2_frac[i];
-  } else {
+  } else if (kind_uses_log(kind)) {
     /* eight loads in flight: one at a time, the 16 trips of the replicated table are 16 global round trips (~25 us) per workgroup */
 #pragma unroll 8
     for (int i = threadIdx.x; i < LOG_N * COPIES * 2; i += blockDim.x) s_lt[i] = g_rbf_tables.log_pair[i / (COPIES * 2)][i & 1];
@@ -113,8 +119,8 @@ rbf_fill_kernel(double coef, const double *__restrict__ x, size_t n, size_t xtda
   /* lower_only: tiles that lie entirely above the diagonal are not written (the Cholesky route reads the lower
      triangle only; half of the HBM writes of the fill) */
   if (lower_only && (size_t)blockIdx.x * 128 > (size_t)blockIdx.y * 16 + 15) return;
-  __shared__ double s_t0[KIND == GSL_SINTERP_RBF_GAUSSIAN ? TBL_N : 1];
-  __shared__ __attribute__((aligned(16))) double s_lt[KIND == GSL_SINTERP_RBF_TPS ? LOG_N * 2 : 2];   /* one copy: the fill is HBM-write bound */
+  __shared__ double s_t0[kind_uses_exp2(KIND) ? TBL_N : 1];
+  __shared__ __attribute__((aligned(16))) double s_lt[kind_uses_log(KIND) ? LOG_N * 2 : 2];   /* one copy: the fill is HBM-write bound */
   load_tables<1>(s_t0, s_lt, KIND);
   const double *lt_lane = s_lt;
   __syncthreads();
@@ -193,7 +199,10 @@ __device__ __forceinline__ bool nan_target(const double (&yy)[DIM])
    N max|w| 14.2 eps 2^-72 = N max|w| eps 3e-21.
 
    Non-finite targets.  A NaN coordinate gives NaN in the value and in every gradient component, for every kind.  The
-   Gaussian / Wendland comparisons are false for NaN, so sweep_store restores the NaN.  The thin-plate value needs nothing:
+   Gaussian / Wendland comparisons are false for NaN, so sweep_store restores the NaN.  The Matern kinds rely on the same
+   restore: exp2_tbl clamps its argument with fmax(t, -1100), which swallows a NaN (the factor 1 + t still carries it into
+   phi, but psi of Matern 3/2 is the bare exponential); the inverse multiquadric carries the NaN through sqrt and is
+   restored all the same.  An infinite coordinate of a Matern target meets inf * 0: not pinned.  The thin-plate value needs nothing:
    r^2 = NaN goes through log_tbl into every term, and only the gradient is set.  An infinite coordinate of a Gaussian /
    Wendland target fails the criterion for every centre: no term is taken, value and gradient are 0 (terms are SELECTED,
    never multiplied by 0, so inf - x_j does no harm).
@@ -280,8 +289,8 @@ __device__ __forceinline__ void rbf_sweep(double coef, const double *__restrict_
 {
   static_assert(FLD || NF == 1, "several weights per centre: the fields mode");
   constexpr int REC = DIM + NF;
-  __shared__ double s_t0[KIND == GSL_SINTERP_RBF_GAUSSIAN ? TBL_N : 1];
-  __shared__ __attribute__((aligned(16))) double s_lt[KIND == GSL_SINTERP_RBF_TPS ? LOG_LDS : 2];
+  __shared__ double s_t0[kind_uses_exp2(KIND) ? TBL_N : 1];
+  __shared__ __attribute__((aligned(16))) double s_lt[kind_uses_log(KIND) ? LOG_LDS : 2];
   __shared__ double s_c[TJ * REC];                /* per centre: x[0..DIM-1], w[0..NF-1] */
   load_tables<LOG_COPIES>(s_t0, s_lt, KIND);
   const double *lt_lane = s_lt + (threadIdx.x & (LOG_COPIES - 1)) * 2;
@@ -332,7 +341,7 @@ __device__ __forceinline__ void rbf_sweep(double coef, const double *__restrict_
       }
       bool take[TPT];
 #pragma unroll
-      for (int t = 0; t < TPT; t++) take[t] = true;          /* thin-plate: no decay, every term */
+      for (int t = 0; t < TPT; t++) take[t] = true;          /* thin-plate, Matern, inverse multiquadric: every term */
       if (KIND == GSL_SINTERP_RBF_GAUSSIAN) {
         /* Every distance is computed; a target takes a term only when it is above 2^-72 of the
            kernel's maximum -- a function of the (target, centre) pair alone, so the value does not
@@ -723,23 +732,20 @@ static int cull_pack(gsl_sinterp_hip_ctx *ctx, int kind, const double *d_x, size
 }
 
 /* ------------------------------------------------------------------------ */
-static double kernel_coef(int kind, double eps)
-{
-  if (kind == GSL_SINTERP_RBF_WENDLAND) return eps;
-  return kind == GSL_SINTERP_RBF_GAUSSIAN ? -(eps * eps) * 1.44269504088896340735992 : 0.5;
-}
-
 /* the constant of psi (rbf_phi.h), applied once per target by sweep_store */
 static double rbf_grad_scale(int kind, double eps)
 {
-  if (kind == GSL_SINTERP_RBF_GAUSSIAN) return -2.0 * (eps * eps);
-  return kind == GSL_SINTERP_RBF_WENDLAND ? -20.0 * (eps * eps) : 2.0;    /* thin-plate: the centre tile holds w / 2 */
+  switch (kind) {
+    case GSL_SINTERP_RBF_GAUSSIAN: return -2.0 * (eps * eps);
+    case GSL_SINTERP_RBF_WENDLAND: return -20.0 * (eps * eps);
+    case GSL_SINTERP_RBF_MATERN32: return -3.0 * (eps * eps);
+    case GSL_SINTERP_RBF_MATERN52: return -(5.0 / 3.0) * (eps * eps);
+    case GSL_SINTERP_RBF_IMQ: return -(eps * eps);
+    default: return 2.0;                                                  /* thin-plate: the centre tile holds w / 2 */
+  }
 }
 
-static bool known_kind(int kind)
-{
-  return kind == GSL_SINTERP_RBF_GAUSSIAN || kind == GSL_SINTERP_RBF_TPS || kind == GSL_SINTERP_RBF_WENDLAND;
-}
+static bool known_kind(int kind) { return kind_is_known(kind); }
 
 template <int KIND>
 static int launch_fill(gsl_sinterp_hip_ctx *ctx, double coef, const double *d_x, size_t n, int dim, size_t xtda,
@@ -926,7 +932,7 @@ static int rbf_sweep_dispatch(gsl_sinterp_hip_ctx *ctx, int kind, const sweep_jo
      runs must not depend on the batch (a target's value is a function of the model and the target alone, so a
      batch split into shards -- or a single-point call -- returns the bits of the one-batch result): it is chosen
      by N only; small batches simply run the culled kernel without the target sort. */
-  const bool culled = kind != GSL_SINTERP_RBF_TPS && !no_cull() && j.n >= 1024 && (j.n + 31) / 32 <= CULL_MAX_TILES;
+  const bool culled = kind_is_culled(kind) && !no_cull() && j.n >= 1024 && (j.n + 31) / 32 <= CULL_MAX_TILES;
   /* few targets: 1 per lane keeps more CUs busy; many: 2 per lane for ILP.
      Culled, 3-D: one target per lane also for large batches -- a workgroup's 256 targets span half the box of 512, and
      in three dimensions that removes more tested-and-rejected centres than the second accumulator chain gains
@@ -935,15 +941,15 @@ static int rbf_sweep_dispatch(gsl_sinterp_hip_ctx *ctx, int kind, const sweep_jo
   const bool one = j.nf || j.m < (size_t)(culled ? CULL_THREADS : EV_THREADS) * 2 * 512 || (culled && j.dim == 3);
   return with_kind(kind, [&](auto K) {
     constexpr int KIND = decltype(K)::value;
-    if constexpr (KIND != GSL_SINTERP_RBF_TPS)      /* thin-plate has no decay: nothing to cull */
+    if constexpr (kind_is_culled(KIND))             /* the other kinds have no culled instances: nothing to cull */
       if (culled) return one ? launch_sweep_cull<KIND, 1>(ctx, j) : launch_sweep_cull<KIND, 2>(ctx, j);
     return one ? launch_sweep<KIND, 1>(ctx, j) : launch_sweep<KIND, 2>(ctx, j);
   });
 }
 
 /* Gaussian / Wendland: group the targets spatially so that whole waves skip negligible (Wendland: zero) terms
-   together (TPS has no decay: nothing to skip, no sort) */
-static bool wants_target_sort(int kind, size_t m) { return kind != GSL_SINTERP_RBF_TPS && m >= 4096 && !no_sort(); }
+   together (the kinds that are not culled take every term: nothing to skip, no sort) */
+static bool wants_target_sort(int kind, size_t m) { return kind_is_culled(kind) && m >= 4096 && !no_sort(); }
 
 extern "C" int gsl_sinterp_hip_rbf_eval(gsl_sinterp_hip_ctx *ctx, int kind, double eps, const double *d_x, size_t n,
                                         int dim, size_t xtda, const double *d_w, const double *d_y, size_t m,

@@ -7,6 +7,35 @@
 #ifndef SINTERP_RBF_PHI_H
 #define SINTERP_RBF_PHI_H
 
+/* What a kind needs and how it is swept, as constexpr traits: every "load the exp2 table", every s_t0 size and the choice
+   between the plain and the culled sweep ask these, so a new kind is one line here and one branch in phi_r2 / phi_psi_r2.
+     kind_uses_exp2   phi goes through exp2_tbl: the 256-entry table is copied to LDS
+     kind_uses_log    phi goes through log_tbl (thin-plate)
+     kind_is_culled   decays fast enough to be cut off: per-pair take test, tile culling, target sort (Gaussian, Wendland).
+                      The Matern kinds and the inverse multiquadric take the plain sweep: every centre, input order
+     kind_is_pd       positive definite: Cholesky route, usable as a kriging covariance */
+constexpr bool kind_uses_exp2(int kind)
+{
+  return kind == GSL_SINTERP_RBF_GAUSSIAN || kind == GSL_SINTERP_RBF_MATERN32 || kind == GSL_SINTERP_RBF_MATERN52;
+}
+constexpr bool kind_uses_log(int kind) { return kind == GSL_SINTERP_RBF_TPS; }
+constexpr bool kind_is_culled(int kind) { return kind == GSL_SINTERP_RBF_GAUSSIAN || kind == GSL_SINTERP_RBF_WENDLAND; }
+constexpr bool kind_is_known(int kind) { return kind >= GSL_SINTERP_RBF_GAUSSIAN && kind <= GSL_SINTERP_RBF_IMQ; }
+constexpr bool kind_is_pd(int kind) { return kind_is_known(kind) && kind != GSL_SINTERP_RBF_TPS; }
+
+/* the per-kind constant that phi_r2 / phi_psi_r2 receive as coef */
+static inline double kernel_coef(int kind, double eps)
+{
+  switch (kind) {
+    case GSL_SINTERP_RBF_GAUSSIAN: return -(eps * eps) * 1.44269504088896340735992;
+    case GSL_SINTERP_RBF_WENDLAND: return eps;
+    case GSL_SINTERP_RBF_MATERN32: return 1.73205080756887729352745 * eps;      /* t = sqrt(3) eps r */
+    case GSL_SINTERP_RBF_MATERN52: return 2.23606797749978969640917 * eps;      /* t = sqrt(5) eps r */
+    case GSL_SINTERP_RBF_IMQ: return eps * eps;
+    default: return 0.5;                                                         /* thin-plate: the half of r^2 ln r^2 */
+  }
+}
+
 #define TBL_BITS 8
 #define TBL_N (1 << TBL_BITS)
 
@@ -72,6 +101,17 @@ __device__ __forceinline__ double phi_r2(double r2, double coef, const double *_
     /* coef = eps; exactly 0 at and beyond the support radius (u <= 0); a NaN distance stays NaN */
     const double t = coef * sqrt(r2), u = 1.0 - t, u2 = u * u;
     return u <= 0.0 ? 0.0 : (u2 * u2) * fma(4.0, t, 1.0);
+  } else if (KIND == GSL_SINTERP_RBF_MATERN32) {
+    /* coef = sqrt(3) eps; (1 + t) e^-t as e + t e: one FMA, exactly 1 at t = 0 (exp2_tbl(-0) = 1) */
+    const double t = coef * sqrt(r2), e = exp2_tbl(t * -1.44269504088896340735992, t0);
+    return fma(t, e, e);
+  } else if (KIND == GSL_SINTERP_RBF_MATERN52) {
+    /* coef = sqrt(5) eps; (1 + t + t^2/3) e^-t, the polynomial by Horner */
+    const double t = coef * sqrt(r2), e = exp2_tbl(t * -1.44269504088896340735992, t0);
+    return fma(t, fma(t, 1.0 / 3.0, 1.0), 1.0) * e;
+  } else if (KIND == GSL_SINTERP_RBF_IMQ) {
+    /* coef = eps^2; the correctly rounded sqrt and division (no rsq refinement): exactly 1 at r2 = 0 */
+    return 1.0 / sqrt(fma(coef, r2, 1.0));
   } else {
     /* r^2 ln r = 0.5 r^2 ln r^2; the 0.5 is folded into the caller's weight (coef = 0.5 in fill).
        r2 = 0 (target on a centre): log_tbl returns a finite value, the product is exactly 0 */
@@ -85,8 +125,11 @@ __device__ __forceinline__ double phi_r2(double r2, double coef, const double *_
        Gaussian    psi = -2 eps^2 phi               *psi = phi
        Wendland    psi = -20 eps^2 (1 - eps r)_+^3  *psi = (1 - eps r)_+^3
        thin-plate  psi = ln r^2 + 1                 *psi = ln r^2 + 1   (the constant 2 undoes the caller's half weight)
-   None of them divides and none is singular at r = 0: the thin-plate psi is the finite log_tbl(0) + 1 there, and the
-   callers multiply it by y - x = 0. */
+       Matern 3/2  psi = -3 eps^2 e^-t              *psi = e^-t                 t = sqrt(3) eps r
+       Matern 5/2  psi = -(5 eps^2 / 3) (1 + t) e^-t   *psi = (1 + t) e^-t      t = sqrt(5) eps r
+       inv. multiquadric  psi = -eps^2 phi^3        *psi = phi^3
+   None of them divides by r and none is singular at r = 0: the thin-plate psi is the finite log_tbl(0) + 1 there, and the
+   callers multiply it by y - x = 0.  (The Matern 1/2 kernel exp(-eps r) is absent for this reason: its psi = -eps e^-t / r.) */
 template <int KIND, int COPIES>
 __device__ __forceinline__ double phi_psi_r2(double r2, double coef, const double *__restrict__ t0,
                                              const double *__restrict__ lt_lane, double *__restrict__ psi)
@@ -99,6 +142,18 @@ __device__ __forceinline__ double phi_psi_r2(double r2, double coef, const doubl
     const double t = coef * sqrt(r2), u = 1.0 - t, u2 = u * u;
     *psi = u <= 0.0 ? 0.0 : u2 * u;
     return u <= 0.0 ? 0.0 : (u2 * u2) * fma(4.0, t, 1.0);
+  } else if (KIND == GSL_SINTERP_RBF_MATERN32) {
+    const double t = coef * sqrt(r2), e = exp2_tbl(t * -1.44269504088896340735992, t0);
+    *psi = e;
+    return fma(t, e, e);
+  } else if (KIND == GSL_SINTERP_RBF_MATERN52) {
+    const double t = coef * sqrt(r2), e = exp2_tbl(t * -1.44269504088896340735992, t0);
+    *psi = fma(t, e, e);
+    return fma(t, fma(t, 1.0 / 3.0, 1.0), 1.0) * e;
+  } else if (KIND == GSL_SINTERP_RBF_IMQ) {
+    const double v = 1.0 / sqrt(fma(coef, r2, 1.0));
+    *psi = (v * v) * v;
+    return v;
   } else {
     const double L = log_tbl<COPIES>(r2, lt_lane);
     *psi = L + 1.0;

@@ -20,6 +20,7 @@
 #include "common.h"
 #include <math.h>
 #include <stdlib.h>
+#include "rbf_phi.h"   /* the traits of a kind (kind_is_pd) */
 
 #define SV_MAXK 4 /* dim + 1 <= 4 polynomial columns */
 
@@ -172,7 +173,7 @@ static int rbf_solve_impl(gsl_sinterp_hip_ctx *ctx, int kind, double eps, const 
   if (n == 0) return ST_SUCCESS;
   /* thin-plate spline: the shift and the row norms need the full matrix; Gaussian: the Cholesky reads the lower
      triangle only, the upper one (the "original kept above the diagonal" of cholesky.c:103) only when asked for */
-  const bool spd = kind != GSL_SINTERP_RBF_TPS;        /* Gaussian, Wendland: positive definite kernels */
+  const bool spd = kind != GSL_SINTERP_RBF_TPS;        /* every other kind is positive definite (an unknown one fails in the fill) */
   static const bool no_fused = getenv("GSL_SINTERP_NO_FUSED_SHIFT") && getenv("GSL_SINTERP_NO_FUSED_SHIFT")[0] == '1';
   const bool force_lu = getenv("GSL_SINTERP_FORCE_LU") && getenv("GSL_SINTERP_FORCE_LU")[0] == '1';
   /* thin-plate spline on the SPD route: the matrix is written once, shifted (sinterp_tps_fill_shifted, below) */
@@ -492,7 +493,7 @@ extern "C" int gsl_sinterp_hip_krige_solve(gsl_sinterp_hip_ctx *ctx, int kind, d
   HIP_OK(ctx, hipSetDevice(ctx->device));
   EXCLUSIVE_SECTION(ctx);
   REQUIRE(ctx, dim >= 1 && dim <= 3 && xtda >= (size_t)dim && lda >= n && nugget >= 0.0, ST_EINVAL);
-  REQUIRE(ctx, kind == GSL_SINTERP_RBF_GAUSSIAN || kind == GSL_SINTERP_RBF_WENDLAND, ST_EINVAL);   /* covariances: positive definite kernels */
+  REQUIRE(ctx, kind_is_pd(kind), ST_EINVAL);       /* covariances: positive definite kernels */
   REQUIRE(ctx, h_mean != NULL && (n == 0 || (d_x && d_phi && d_w)), ST_EFAULT);
   if (h_route) *h_route = 0;
   *h_mean = 0.0;
@@ -565,7 +566,7 @@ static int fields_solve_args(gsl_sinterp_hip_ctx *ctx, int kind, const double *d
 {
   REQUIRE(ctx, dim >= 1 && dim <= 3 && xtda >= (size_t)dim && lda >= n && ldw >= n, ST_EINVAL);
   REQUIRE(ctx, nf >= 1 && nf <= GSL_SINTERP_MAX_FIELDS, ST_EINVAL);
-  REQUIRE(ctx, kind == GSL_SINTERP_RBF_GAUSSIAN || kind == GSL_SINTERP_RBF_WENDLAND, ST_EINVAL);   /* positive definite kernels */
+  REQUIRE(ctx, kind_is_pd(kind), ST_EINVAL);       /* positive definite kernels */
   REQUIRE(ctx, n == 0 || (d_x && d_phi && d_w), ST_EFAULT);
   return ST_SUCCESS;
 }

@@ -830,18 +830,24 @@ static void *rbf_alloc_kind(int kind, size_t dim, size_t size)
 static void *rbf_gauss_alloc(size_t dim, size_t size) { return rbf_alloc_kind(GSL_SINTERP_RBF_GAUSSIAN, dim, size); }
 static void *rbf_tps_alloc(size_t dim, size_t size) { return rbf_alloc_kind(GSL_SINTERP_RBF_TPS, dim, size); }
 static void *rbf_wendland_alloc(size_t dim, size_t size) { return rbf_alloc_kind(GSL_SINTERP_RBF_WENDLAND, dim, size); }
+static void *rbf_matern32_alloc(size_t dim, size_t size) { return rbf_alloc_kind(GSL_SINTERP_RBF_MATERN32, dim, size); }
+static void *rbf_matern52_alloc(size_t dim, size_t size) { return rbf_alloc_kind(GSL_SINTERP_RBF_MATERN52, dim, size); }
+static void *rbf_imq_alloc(size_t dim, size_t size) { return rbf_alloc_kind(GSL_SINTERP_RBF_IMQ, dim, size); }
 static void *rbf_tps_affine_alloc(size_t dim, size_t size)
 {
   rbf_state *st = (rbf_state *)rbf_alloc_kind(GSL_SINTERP_RBF_TPS, dim, size);
   if (st) st->affine = 1;
   return st;
 }
-static void *krige_alloc(size_t dim, size_t size)
+static void *krige_alloc_kind(int kind, size_t dim, size_t size)
 {
-  rbf_state *st = (rbf_state *)rbf_alloc_kind(GSL_SINTERP_RBF_GAUSSIAN, dim, size);      /* Gaussian covariance */
+  rbf_state *st = (rbf_state *)rbf_alloc_kind(kind, dim, size);                          /* the kernel is the covariance */
   if (st) st->krige = 1;
   return st;
 }
+static void *krige_alloc(size_t dim, size_t size) { return krige_alloc_kind(GSL_SINTERP_RBF_GAUSSIAN, dim, size); }
+static void *krige_matern32_alloc(size_t dim, size_t size) { return krige_alloc_kind(GSL_SINTERP_RBF_MATERN32, dim, size); }
+static void *krige_matern52_alloc(size_t dim, size_t size) { return krige_alloc_kind(GSL_SINTERP_RBF_MATERN52, dim, size); }
 
 /* the kept factor and everything derived from it (member 0's context must still be alive) */
 static void rbf_release_variance(rbf_state *st)
@@ -954,10 +960,11 @@ static int rbf_init_fields(gsl_sinterp *interp, const gsl_matrix *x, const doubl
   st->nf = 0;                                           /* not initialised until the solve succeeds */
   gsl_sinterp_hip_ctx *c = st->ctx;
   /* default shape: Gaussian eps = 2 N^(1/d) (the C-configurations); Wendland: support radius of eight mean
-     spacings of a unit box, eps = N^(1/d) / 8 */
+     spacings of a unit box, eps = N^(1/d) / 8; Matern 3/2, 5/2 and inverse multiquadric: eps = N^(1/d), the length scale
+     1/eps equal to the mean spacing */
   st->model_id = next_model_id();                       /* the buffers are about to change */
   st->eps = interp->shape > 0 ? interp->shape
-            : (st->kind == GSL_SINTERP_RBF_WENDLAND ? 0.125 : 2.0) * pow((double)n, 1.0 / (double)dim);
+            : (st->kind == GSL_SINTERP_RBF_WENDLAND ? 0.125 : st->kind == GSL_SINTERP_RBF_GAUSSIAN ? 2.0 : 1.0) * pow((double)n, 1.0 / (double)dim);
 
   double *h_x = (double *)malloc(n * dim * sizeof(double));
   double *h_f = (double *)malloc(n * nf * sizeof(double));
@@ -978,7 +985,7 @@ static int rbf_init_fields(gsl_sinterp *interp, const gsl_matrix *x, const doubl
      Woodbury correction or pivoted LU (thin-plate spline) -- csrc/hip/solve.hip */
   double rcond = GSL_NAN;
   memset(st->f_mean, 0, sizeof st->f_mean); memset(st->f_poly, 0, sizeof st->f_poly);
-  /* Several fields.  The kernel matrix depends on the centres only: Gaussian, Wendland and kriging with the default solver
+  /* Several fields.  The kernel matrix depends on the centres only: every positive definite kind and kriging with the default solver
      and no condition estimate share ONE fill and ONE factorisation (routes 1 / 7).  Everything else -- both thin-plate
      types (their shifted-SPD / Woodbury solve is per field), an explicit solver, set_rcond, kriging on a semi-definite
      matrix (GSL_EDOM from the shared route) -- solves field by field, refilling d_phi each time: nf factorisations. */
@@ -1313,10 +1320,28 @@ static const gsl_sinterp_type tps_affine_type = {"rbf-thin-plate-spline-affine",
 const gsl_sinterp_type *gsl_sinterp_rbf_tps_affine = &tps_affine_type;
 static const gsl_sinterp_type krige_type = {"ordinary-kriging-gaussian", 1, &krige_alloc, &rbf_init, &rbf_eval_many, &rbf_eval_resident, &rbf_free};
 const gsl_sinterp_type *gsl_sinterp_kriging = &krige_type;
+static const gsl_sinterp_type matern32_type = {"rbf-matern-3/2", 1, &rbf_matern32_alloc, &rbf_init, &rbf_eval_many, &rbf_eval_resident, &rbf_free};
+static const gsl_sinterp_type matern52_type = {"rbf-matern-5/2", 1, &rbf_matern52_alloc, &rbf_init, &rbf_eval_many, &rbf_eval_resident, &rbf_free};
+static const gsl_sinterp_type imq_type = {"rbf-inverse-multiquadric", 1, &rbf_imq_alloc, &rbf_init, &rbf_eval_many, &rbf_eval_resident, &rbf_free};
+static const gsl_sinterp_type krige_matern32_type = {"ordinary-kriging-matern-3/2", 1, &krige_matern32_alloc, &rbf_init, &rbf_eval_many, &rbf_eval_resident, &rbf_free};
+static const gsl_sinterp_type krige_matern52_type = {"ordinary-kriging-matern-5/2", 1, &krige_matern52_alloc, &rbf_init, &rbf_eval_many, &rbf_eval_resident, &rbf_free};
+const gsl_sinterp_type *gsl_sinterp_rbf_matern32 = &matern32_type;
+const gsl_sinterp_type *gsl_sinterp_rbf_matern52 = &matern52_type;
+const gsl_sinterp_type *gsl_sinterp_rbf_imq = &imq_type;
+const gsl_sinterp_type *gsl_sinterp_kriging_matern32 = &krige_matern32_type;
+const gsl_sinterp_type *gsl_sinterp_kriging_matern52 = &krige_matern52_type;
 const gsl_sinterp_type *gsl_sinterp_rbf_wendland = &wendland_type;
 const gsl_sinterp_type *gsl_sinterp_rbf_gaussian = &gauss_type;
 const gsl_sinterp_type *gsl_sinterp_rbf_tps = &tps_type;
 const gsl_sinterp_type *gsl_sinterp_linear_simplex = &simplex_type;
+
+/* the kriging types (a covariance + the estimated mean), and the types on a positive definite kernel: Cholesky routes
+   1 / 7, hence leave-one-out */
+static int is_krige_type(const gsl_sinterp_type *T) { return T == &krige_type || T == &krige_matern32_type || T == &krige_matern52_type; }
+static int is_pd_type(const gsl_sinterp_type *T)
+{
+  return T == &gauss_type || T == &wendland_type || T == &matern32_type || T == &matern52_type || T == &imq_type || is_krige_type(T);
+}
 
 gsl_sinterp *gsl_sinterp_alloc(const gsl_sinterp_type *T, size_t dim, size_t size)
 {
@@ -1389,7 +1414,7 @@ int gsl_sinterp_set_shape(gsl_sinterp *interp, double eps)
 int gsl_sinterp_set_nugget(gsl_sinterp *interp, double nugget)
 {
   if (!interp) GSL_ERROR("gsl_sinterp_set_nugget: null interpolant", GSL_EFAULT);
-  if (interp->type != &krige_type) GSL_ERROR("gsl_sinterp_set_nugget: kriging interpolants only", GSL_EINVAL);
+  if (!is_krige_type(interp->type)) GSL_ERROR("gsl_sinterp_set_nugget: kriging interpolants only", GSL_EINVAL);
   if (!(nugget >= 0.0)) GSL_ERROR("gsl_sinterp_set_nugget: the nugget must be >= 0", GSL_EDOM);
   interp->nugget = nugget;
   return GSL_SUCCESS;
@@ -1398,7 +1423,7 @@ int gsl_sinterp_set_nugget(gsl_sinterp *interp, double nugget)
 int gsl_sinterp_set_variance(gsl_sinterp *interp, int want)
 {
   if (!interp) GSL_ERROR("gsl_sinterp_set_variance: null interpolant", GSL_EFAULT);
-  if (interp->type != &krige_type) GSL_ERROR("gsl_sinterp_set_variance: kriging interpolants only", GSL_EINVAL);
+  if (!is_krige_type(interp->type)) GSL_ERROR("gsl_sinterp_set_variance: kriging interpolants only", GSL_EINVAL);
   interp->want_variance = want != 0;
   return GSL_SUCCESS;
 }
@@ -1406,8 +1431,8 @@ int gsl_sinterp_set_variance(gsl_sinterp *interp, int want)
 int gsl_sinterp_set_loo(gsl_sinterp *interp, int want)
 {
   if (!interp) GSL_ERROR("gsl_sinterp_set_loo: null interpolant", GSL_EFAULT);
-  if (interp->type != &gauss_type && interp->type != &wendland_type && interp->type != &krige_type)
-    GSL_ERROR("gsl_sinterp_set_loo: Gaussian, Wendland and kriging interpolants only", GSL_EINVAL);
+  if (!is_pd_type(interp->type))
+    GSL_ERROR("gsl_sinterp_set_loo: positive definite RBF (Gaussian, Wendland, Matern, inverse multiquadric) and kriging interpolants only", GSL_EINVAL);
   interp->want_loo = want != 0;
   return GSL_SUCCESS;
 }
@@ -1415,8 +1440,8 @@ int gsl_sinterp_set_loo(gsl_sinterp *interp, int want)
 /* whether leave-one-out data is held, as a status (the table of include/gsl_sinterp.h) */
 static int loo_status(const gsl_sinterp *interp)
 {
-  if (interp->type != &gauss_type && interp->type != &wendland_type && interp->type != &krige_type)
-    GSL_ERROR("gsl_sinterp_loo: Gaussian, Wendland and kriging interpolants only", GSL_EINVAL);
+  if (!is_pd_type(interp->type))
+    GSL_ERROR("gsl_sinterp_loo: positive definite RBF (Gaussian, Wendland, Matern, inverse multiquadric) and kriging interpolants only", GSL_EINVAL);
   const rbf_state *st = (const rbf_state *)interp->state;
   if (!st->d_w || st->nf == 0) GSL_ERROR("gsl_sinterp_loo: interpolant not initialised", GSL_EINVAL);
   if (st->loo_state == 3)
@@ -1454,7 +1479,7 @@ int gsl_sinterp_loo_variance(const gsl_sinterp *interp, gsl_vector *v)
 /* whether variances can be evaluated, as a status (the table of include/gsl_sinterp.h) */
 static int variance_status(const gsl_sinterp *interp)
 {
-  if (interp->type != &krige_type) GSL_ERROR("gsl_sinterp_eval_variance: kriging interpolants only", GSL_EINVAL);
+  if (!is_krige_type(interp->type)) GSL_ERROR("gsl_sinterp_eval_variance: kriging interpolants only", GSL_EINVAL);
   const rbf_state *st = (const rbf_state *)interp->state;
   if (!st->d_w) GSL_ERROR("gsl_sinterp_eval_variance: interpolant not initialised", GSL_EINVAL);
   if (st->var_state == 3)
@@ -1744,7 +1769,7 @@ int gsl_sinterp_field_mean(const gsl_sinterp *interp, size_t q, double *mean)
   int status;
   const rbf_state *st = field_state(interp, q, &status);
   if (!st) return status;
-  if (interp->type != &krige_type) GSL_ERROR("gsl_sinterp_field_mean: kriging interpolants only", GSL_EINVAL);
+  if (!is_krige_type(interp->type)) GSL_ERROR("gsl_sinterp_field_mean: kriging interpolants only", GSL_EINVAL);
   *mean = st->f_mean[q];
   return GSL_SUCCESS;
 }
@@ -1775,7 +1800,7 @@ int gsl_sinterp_poly(const gsl_sinterp *interp, gsl_vector *c)
 int gsl_sinterp_mean(const gsl_sinterp *interp, double *mean)
 {
   if (!interp || !mean) GSL_ERROR("gsl_sinterp_mean: null argument", GSL_EFAULT);
-  if (interp->type != &krige_type) GSL_ERROR("gsl_sinterp_mean: kriging interpolants only", GSL_EINVAL);
+  if (!is_krige_type(interp->type)) GSL_ERROR("gsl_sinterp_mean: kriging interpolants only", GSL_EINVAL);
   const rbf_state *st = (const rbf_state *)interp->state;
   if (!st->d_w) GSL_ERROR("gsl_sinterp_mean: interpolant not initialised", GSL_EINVAL);
   *mean = st->mean;
@@ -1790,7 +1815,7 @@ int gsl_sinterp_set_solver(gsl_sinterp *interp, int solver)
   if (interp->type == &simplex_type) GSL_ERROR("gsl_sinterp_set_solver: not an RBF interpolant", GSL_EINVAL);
   /* kriging and the affine thin-plate spline solve saddle systems on routes of their own (7 / 8, 9 / 10): accepting a
      solver here and ignoring it at init would be a silent no-op */
-  if ((interp->type == &krige_type || interp->type == &tps_affine_type) && solver != GSL_SINTERP_SOLVER_DEFAULT)
+  if ((is_krige_type(interp->type) || interp->type == &tps_affine_type) && solver != GSL_SINTERP_SOLVER_DEFAULT)
     GSL_ERROR("gsl_sinterp_set_solver: kriging / affine thin-plate-spline interpolants choose their own route", GSL_EINVAL);
   if (interp->type == &tps_type && (solver == GSL_SINTERP_SOLVER_CHOLESKY2 || solver == GSL_SINTERP_SOLVER_PCHOLESKY))
     GSL_ERROR("gsl_sinterp_set_solver: the thin-plate-spline matrix is indefinite (zero diagonal): no Cholesky-type solver", GSL_EINVAL);
@@ -1801,7 +1826,7 @@ int gsl_sinterp_set_solver(gsl_sinterp *interp, int solver)
 int gsl_sinterp_set_rcond(gsl_sinterp *interp, int want)
 {
   if (!interp) GSL_ERROR("gsl_sinterp_set_rcond: null interpolant", GSL_EFAULT);
-  if (want && (interp->type == &krige_type || interp->type == &tps_affine_type))
+  if (want && (is_krige_type(interp->type) || interp->type == &tps_affine_type))
     GSL_ERROR("gsl_sinterp_set_rcond: no condition estimate on the kriging / affine thin-plate-spline routes", GSL_EINVAL);
   interp->want_rcond = want != 0;
   return GSL_SUCCESS;
@@ -1990,6 +2015,12 @@ static const char INTERP_MAGIC[8] = {'G', 'S', 'L', 'S', 'I', 'N', 'T', '1'};
 
 static int type_id(const gsl_sinterp_type *T)
 {
+  /* 7 .. 11: the Matern / inverse multiquadric types; the ids and the GSLSINT1 layout of the older types are unchanged */
+  if (T == &matern32_type) return 7;
+  if (T == &matern52_type) return 8;
+  if (T == &imq_type) return 9;
+  if (T == &krige_matern32_type) return 10;
+  if (T == &krige_matern52_type) return 11;
   return T == &gauss_type ? 0 : (T == &tps_type ? 1 : (T == &wendland_type ? 3 : (T == &krige_type ? 4 : (T == &tps_affine_type ? 5 : (T == &mesh_type ? 6 : 2)))));
 }
 

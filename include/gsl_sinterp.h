@@ -258,7 +258,8 @@ struct gsl_sinterp_struct {
   size_t dim;
   size_t size;
   int device;        /* GPU ordinal; default 0 or $GSL_SINTERP_DEVICE */
-  double shape;      /* Gaussian shape parameter eps; <= 0 -> 2 * size^(1/dim) */
+  double shape;      /* shape parameter eps; <= 0 -> the type's default: Gaussian 2 * size^(1/dim), Wendland size^(1/dim) / 8,
+                        Matern 3/2, 5/2 and inverse multiquadric size^(1/dim) (length scale 1/eps = the mean spacing) */
   int init_flags;    /* SIMPLEX_TREE_* flags (linear simplex type)            */
   gsl_rng *rng;      /* insertion-order rng (linear simplex type), may be NULL */
   void *state;
@@ -270,7 +271,7 @@ struct gsl_sinterp_struct {
   int route;         /* solver route the last init took (gsl_sinterp_hip_rbf_solve_ex)       */
   double nugget;     /* kriging: added to the diagonal of the covariance matrix (>= 0, default 0) */
   int want_variance; /* kriging: the next init keeps the Cholesky factor for gsl_sinterp_eval_variance_* (default 0) */
-  int want_loo;      /* Gaussian / Wendland / kriging: the next init computes the leave-one-out residuals and variances (default 0) */
+  int want_loo;      /* positive definite RBF types (Gaussian / Wendland / Matern / inverse multiquadric) and kriging: the next init computes the leave-one-out residuals and variances (default 0) */
 };
 
 extern const gsl_sinterp_type *gsl_sinterp_rbf_gaussian;
@@ -287,6 +288,20 @@ extern const gsl_sinterp_type *gsl_sinterp_linear_mesh;
    s(y) = mu + sum_j w_j C(|y - x_j|) with [C + nugget I, 1; 1^T, 0] [w; mu] = [f; 0].  nugget = 0 interpolates the data,
    nugget > 0 smooths (s(x_i) = f_i - nugget w_i); far from the data s -> mu.  gsl_sinterp_set_shape sets eps. */
 extern const gsl_sinterp_type *gsl_sinterp_kriging;
+/* Matern 3/2, Matern 5/2 and the inverse multiquadric (the standard menu next to the Gaussian):
+       rbf-matern-3/2             phi(r) = (1 + t) exp(-t),          t = sqrt(3) eps r
+       rbf-matern-5/2             phi(r) = (1 + t + t^2/3) exp(-t),  t = sqrt(5) eps r
+       rbf-inverse-multiquadric   phi(r) = 1 / sqrt(1 + (eps r)^2)
+   Positive definite in every dimension with phi(0) = 1: the Cholesky route (1), and every entry that accepts
+   gsl_sinterp_rbf_gaussian accepts them -- eval, gradients, init_fields / eval_fields, set_loo, get_weights, device
+   lists, checkpoints.  Length scale 1/eps; default eps = size^(1/dim).  Far better conditioned than the Gaussian at
+   the same length scale.  Every centre contributes to every target: these sweeps are not culled.  A target with a NaN
+   coordinate evaluates to NaN; the result for an infinite coordinate is not specified. */
+extern const gsl_sinterp_type *gsl_sinterp_rbf_matern32, *gsl_sinterp_rbf_matern52, *gsl_sinterp_rbf_imq;
+/* ordinary kriging with a Matern 3/2 / 5/2 covariance (sill 1, length scale 1/eps): "ordinary-kriging-matern-3/2" and
+   "ordinary-kriging-matern-5/2"; everything gsl_sinterp_kriging offers -- set_nugget, mean, set_variance and the
+   eval_variance entries, set_loo, fields -- on the covariances that are usually fitted.  Routes 7 / 8 as there. */
+extern const gsl_sinterp_type *gsl_sinterp_kriging_matern32, *gsl_sinterp_kriging_matern52;
 
 gsl_sinterp *gsl_sinterp_alloc(const gsl_sinterp_type *T, size_t dim, size_t size);
 int gsl_sinterp_set_device(gsl_sinterp *interp, int device);
@@ -299,12 +314,12 @@ int gsl_sinterp_set_device_list(gsl_sinterp *interp, const int *devices, int n_d
 int gsl_sinterp_n_devices(const gsl_sinterp *interp);
 int gsl_sinterp_set_shape(gsl_sinterp *interp, double eps);
 /* Solver breadth (linalg/cholesky.c:392-537, linalg/pcholesky.c, linalg/lu.c:204): GSL_SINTERP_SOLVER_DEFAULT picks
-   by kernel class (Gaussian: Cholesky; thin-plate spline: shifted-SPD Cholesky, LU as fall-back); _CHOLESKY2 the
+   by kernel class (Gaussian, Wendland, Matern, inverse multiquadric: Cholesky; thin-plate spline: shifted-SPD Cholesky, LU as fall-back); _CHOLESKY2 the
    diagonally scaled Cholesky; _PCHOLESKY the pivoted LDL^T for semi-definite / nuggeted kernel matrices;
    _LU_REFINE pivoted LU plus one refinement step.  gsl_sinterp_set_rcond(interp, 1) makes the next init estimate
    the reciprocal condition number of the kernel matrix (Cholesky solvers; gsl_linalg_cholesky_rcond), read back
    with gsl_sinterp_rcond (GSL_EINVAL when none is available). */
-int gsl_sinterp_set_nugget(gsl_sinterp *interp, double nugget);     /* kriging type only (GSL_EINVAL otherwise) */
+int gsl_sinterp_set_nugget(gsl_sinterp *interp, double nugget);     /* the three kriging types only (GSL_EINVAL otherwise) */
 int gsl_sinterp_mean(const gsl_sinterp *interp, double *mean);     /* the estimated mean mu of an initialised kriging interpolant */
 /* Kriging variance sigma^2(y) = C(0) - k^T K^-1 k + (1 - 1^T K^-1 k)^2 / (1^T K^-1 1) of the underlying field (the
    nugget is measurement noise): 0 at the data sites when nugget = 0, 1 + 1/(1^T K^-1 1) far from every site.
@@ -314,14 +329,14 @@ int gsl_sinterp_mean(const gsl_sinterp *interp, double *mean);     /* the estima
    initialised, initialised without set_variance, or restored by gsl_sinterp_fread (a checkpoint carries no factor);
    GSL_EUNSUP: the init took the pivoted LDL^T route 8 (covariance matrix only semi-definite).  With a device list the
    factor lives on the first device, which evaluates every target. */
-int gsl_sinterp_set_variance(gsl_sinterp *interp, int want);            /* kriging type only (GSL_EINVAL otherwise); before init */
+int gsl_sinterp_set_variance(gsl_sinterp *interp, int want);            /* the three kriging types only (GSL_EINVAL otherwise); before init */
 int gsl_sinterp_eval_variance_e(const gsl_sinterp *interp, const gsl_vector *y, double *var);
 int gsl_sinterp_eval_variance_many(const gsl_sinterp *interp, const gsl_matrix *y, gsl_vector *var);
 int gsl_sinterp_eval_variance_resident(const gsl_sinterp *interp, const double *d_y, size_t m, size_t ytda, double *d_var);
 /* Leave-one-out cross-validation (Rippa's rule for the positive definite RBF types, Dubrule's for ordinary kriging): how
    good the fit is, and a score for a shape parameter or nugget, without N refits.
        e_i = f_i - s^(-i)(x_i)     the residual at site i of the model built without site i,
-       v_i                         Gaussian / Wendland: the squared power function phi(0) - k^T K_-i^-1 k at x_i;
+       v_i                         positive definite RBF types: the squared power function phi(0) - k^T K_-i^-1 k at x_i;
                                    kriging: the variance of the prediction error of the OBSERVATION f_i, i.e. what
                                    eval_variance of the model without site i returns at x_i, plus the nugget.
    Both come from the diagonal of the inverse of the Cholesky factor the init computes anyway: diag_i = (K^-1)_ii, for
@@ -331,7 +346,8 @@ int gsl_sinterp_eval_variance_resident(const gsl_sinterp *interp, const double *
    factor itself is not kept for it.  K fields share the diagonal: E is size x K.  Nothing is clamped: where rounding left
    a diag_i non-positive (a kernel matrix at the edge of positive definiteness) v_i is returned as computed.
    set_loo(0), the default, leaves the init and every evaluation exactly as they are.
-   GSL_EINVAL: another type than gsl_sinterp_rbf_gaussian / _wendland / gsl_sinterp_kriging, not initialised, initialised
+   GSL_EINVAL: another type than gsl_sinterp_rbf_gaussian / _wendland / _matern32 / _matern52 / _imq and the three kriging
+   types, not initialised, initialised
    without set_loo, or restored by gsl_sinterp_fread (a checkpoint carries no leave-one-out data, and reading one drops
    what was held); GSL_EUNSUP: the init took a route without a Cholesky factor (an explicit gsl_sinterp_set_solver, the
    pivoted LDL^T route 8 of kriging): gsl_sinterp_route is then neither 1 nor 7; GSL_EBADLEN: E is not size x K
@@ -358,8 +374,8 @@ int gsl_sinterp_eval_resident(const gsl_sinterp *interp, const double *d_y, size
                               double *d_s, int *d_leaf);
 /* Value and gradient (the counterpart of gsl_interp_eval_deriv_e, interpolation/gsl_interp.h:113-123, in dim dimensions):
    s(y) and ds/dy_a, a < dim, from one fused sweep (gsl_sinterp_hip_rbf_eval_grad) -- the analytic gradient of the radial
-   sum plus the affine tail (gsl_sinterp_rbf_tps_affine) or nothing (kriging's mean is constant).  The five RBF-family
-   types are supported; gsl_sinterp_linear_simplex and gsl_sinterp_linear_mesh give GSL_EUNSUP (their gradient is constant
+   sum plus the affine tail (gsl_sinterp_rbf_tps_affine) or nothing (kriging's mean is constant).  Every RBF-family
+   type (kriging included) is supported; gsl_sinterp_linear_simplex and gsl_sinterp_linear_mesh give GSL_EUNSUP (their gradient is constant
    per leaf: a separate entry).  The value is bit-identical to gsl_sinterp_eval_many's for the same target; a target with a
    NaN coordinate gets NaN in the value and in every gradient component.
    eval_grad_many: y is m x dim, g is m x dim (g->tda honoured, padding untouched), s has m entries (s->stride honoured)
@@ -379,8 +395,8 @@ int gsl_sinterp_eval_grad_resident(const gsl_sinterp *interp, const double *d_y,
    takes F of size x K (F->tda honoured, 1 <= K <= GSL_SINTERP_MAX_FIELDS = 64) and solves all K weight vectors; the
    eval_fields entries return the K values of a target from ONE sweep, in which the distance, the take test and the kernel
    of a (target, centre) pair are computed once for all fields.
-   WHICH TYPES SHARE THE FACTORISATION: gsl_sinterp_rbf_gaussian, gsl_sinterp_rbf_wendland and gsl_sinterp_kriging with the
-   default solver and without gsl_sinterp_set_rcond pay ONE fill and ONE Cholesky factorisation for all K fields
+   WHICH TYPES SHARE THE FACTORISATION: gsl_sinterp_rbf_gaussian, _wendland, _matern32, _matern52, _imq and the three kriging
+   types with the default solver and without gsl_sinterp_set_rcond pay ONE fill and ONE Cholesky factorisation for all K fields
    (gsl_sinterp_route 1 / 7).  gsl_sinterp_rbf_tps and gsl_sinterp_rbf_tps_affine, a non-default gsl_sinterp_set_solver,
    gsl_sinterp_set_rcond, and kriging on a covariance matrix that is only semi-definite solve field by field -- correct, at
    the price of K factorisations; gsl_sinterp_route is then the last field's, gsl_sinterp_rcond the first field's.

@@ -41,6 +41,14 @@ typedef struct gsl_sinterp_hip_ctx gsl_sinterp_hip_ctx;
 #define GSL_SINTERP_RBF_WENDLAND 2 /* phi(r) = (1 - eps r)_+^4 (4 eps r + 1): Wendland's C2 function, compact support of
                                       radius 1/eps, positive definite for dim <= 3 (the reference's README:18-26 lists
                                       compactly supported kernels as future work); Cholesky route, sweep with EXACT culling */
+/* Matern 3/2 and 5/2 and the inverse multiquadric: positive definite in every dimension, length scale 1/eps, phi(0) = 1
+   exactly.  Cholesky route, kriging covariances, and the PLAIN sweep: every centre in input order, nothing culled (the
+   inverse multiquadric does not decay; the Matern cut-off radius at a usable eps spans a third of the cloud).  A NaN
+   coordinate of a target gives NaN; the result for an INFINITE coordinate is not pinned (the Matern formula meets
+   inf * 0 there).  Every other value of kind is unknown: GSL_EINVAL. */
+#define GSL_SINTERP_RBF_MATERN32 3 /* phi(r) = (1 + t) exp(-t),          t = sqrt(3) eps r  */
+#define GSL_SINTERP_RBF_MATERN52 4 /* phi(r) = (1 + t + t^2/3) exp(-t),  t = sqrt(5) eps r  */
+#define GSL_SINTERP_RBF_IMQ 5      /* phi(r) = 1 / sqrt(1 + (eps r)^2)                      */
 
 /* ---- context / memory --------------------------------------------------- */
 int gsl_sinterp_hip_device_count(void); /* 0 when no GPU is visible */
@@ -219,7 +227,8 @@ int gsl_sinterp_hip_rbf_eval_model(gsl_sinterp_hip_ctx *ctx, int kind, double ep
 
 /* Value and gradient from one fused sweep:  d_s[k] = s(y_k)  and  d_g[k * gtda + a] = ds/dy_a (y_k), a < dim, with
        grad s(y) = sum_j w_j psi(r_j^2) (y - x_j),   psi = phi'(r) / r
-   (Gaussian -2 eps^2 phi; Wendland -20 eps^2 (1 - eps r)_+^3; thin-plate ln r^2 + 1 -- none divides, none is singular
+   (Gaussian -2 eps^2 phi; Wendland -20 eps^2 (1 - eps r)_+^3; thin-plate ln r^2 + 1; Matern 3/2 -3 eps^2 exp(-t);
+   Matern 5/2 -(5 eps^2 / 3) (1 + t) exp(-t); inverse multiquadric -eps^2 phi^3 -- none divides by r, none is singular
    at r = 0).  d_s may be NULL (gradient only); nothing beyond the dim columns of a row of d_g is written.  h_tail: NULL,
    or dim + 1 host doubles {c_0, c_1 .. c_dim} of an affine tail, s += c_0 + sum_a c_a y_a and g_a += c_a (the affine
    thin-plate polynomial; kriging passes {mu, 0, ..}); only h_tail[0 .. dim] is read.
@@ -228,7 +237,7 @@ int gsl_sinterp_hip_rbf_eval_model(gsl_sinterp_hip_ctx *ctx, int kind, double ep
    and gradient are functions of (model, target) alone whatever the batch.  A NaN coordinate gives NaN in the value and
    in every gradient component for every kind -- for the thin-plate kinds the value sweep returns that NaN too (r^2 =
    NaN reaches every term), so the two rules do not collide; an infinite coordinate of a Gaussian / Wendland target takes
-   no term and gives 0.  model_id as for _eval_model: the packed centres are shared with the value sweep, a gradient
+   no term and gives 0 (Matern / inverse multiquadric: not pinned).  model_id as for _eval_model: the packed centres are shared with the value sweep, a gradient
    call after a value call with the same id reuses them.  Batches of >= 4096 Gaussian / Wendland targets are grouped
    through the one-level permutation for every batch size (GSL_SINTERP_NO_SORT=1 honoured).
    GSL_EINVAL: dim outside 1..3, unknown kind, xtda / ytda / gtda < dim; GSL_EFAULT: a NULL d_y or d_g with m > 0;
@@ -247,9 +256,9 @@ int gsl_sinterp_hip_rbf_eval_grad(gsl_sinterp_hip_ctx *ctx, int kind, double eps
    polynomials; kriging passes {mu_q, 0, ..}).  1 <= nf <= GSL_SINTERP_MAX_FIELDS.
    BIT RULE: field q has the bits of gsl_sinterp_hip_rbf_eval_model (_eval_affine / krige_eval with the tail) called with
    d_w = column q for the same centres, target and kind: the same terms in the same order (input order below N = 1024 and
-   for the thin-plate kind, Morton order above), the same take criterion, the same choice of kernel by N.  A target with
-   a NaN coordinate gives NaN in all nf outputs (Gaussian / Wendland: restored at the store; thin-plate: through every
-   term).  The fields are swept in passes of gsl_sinterp_hip_rbf_fields_block() fields (see there).  Batches of
+   for the thin-plate, Matern and inverse multiquadric kinds, Morton order above), the same take criterion, the same choice of kernel by N.  A target with
+   a NaN coordinate gives NaN in all nf outputs (every kind but thin-plate: restored at the store; thin-plate: through
+   every term).  The fields are swept in passes of gsl_sinterp_hip_rbf_fields_block() fields (see there).  Batches of
    >= 4096 Gaussian / Wendland targets are grouped through the one-level permutation, as for _eval_grad.  model_id as
    for _eval_model; the packed {x, w_0 .. w_{nf-1}} records of the culled sweep are cached in a slot of their own (keyed by
    nf and ldw too), so scalar and fields calls on one model id do not evict each other.
@@ -264,7 +273,7 @@ int gsl_sinterp_hip_rbf_eval_fields(gsl_sinterp_hip_ctx *ctx, int kind, double e
    last <= _block_small() fields in a pass of the small instance */
 int gsl_sinterp_hip_rbf_fields_block(void);
 int gsl_sinterp_hip_rbf_fields_block_small(void);
-/* Gaussian / Wendland, nf right-hand sides: ONE fill, ONE Cholesky factorisation, nf solves.  d_w holds F on entry
+/* Positive definite kinds (all but thin-plate), nf right-hand sides: ONE fill, ONE Cholesky factorisation, nf solves.  d_w holds F on entry
    (column q = f_q at d_w + q * ldw) and the weights on exit; route 1.  The first min(nf, 5) columns ride the
    factorisation (gsl_sinterp_hip_cholesky_factor_solve), the others are solved against the finished factor five at a
    time; columns of different groups agree to rounding, not bitwise.  A GEMM-based triangular solve for very many fields
@@ -282,7 +291,7 @@ int gsl_sinterp_hip_krige_solve_fields(gsl_sinterp_hip_ctx *ctx, int kind, doubl
 
 /* "init" of an RBF interpolant in one call: fill d_phi (n x n scratch, lda), solve Phi w = f
    with d_w holding f on entry and w on exit.  *h_route reports the solver used:
-   1 Cholesky (Gaussian, SPD) -- 2 shifted-SPD Cholesky + rank-(d+1) Woodbury correction
+   1 Cholesky (every positive definite kind: Gaussian, Wendland, Matern 3/2 and 5/2, inverse multiquadric) -- 2 shifted-SPD Cholesky + rank-(d+1) Woodbury correction
    (thin-plate spline; values agree with the LU route to ~1e-13) -- 3 pivoted LU (the
    reference's route, taken when the shifted matrix is not SPD or GSL_SINTERP_FORCE_LU=1). */
 int gsl_sinterp_hip_rbf_solve(gsl_sinterp_hip_ctx *ctx, int kind, double eps, const double *d_x, size_t n,
@@ -318,7 +327,7 @@ int gsl_sinterp_hip_rbf_eval_affine(gsl_sinterp_hip_ctx *ctx, int kind, double e
                                     size_t n, int dim, size_t xtda, const double *d_w, const double *d_y, size_t m,
                                     size_t ytda, double *d_s, unsigned long long model_id);
 
-/* Ordinary kriging on a positive definite kernel used as covariance (GAUSSIAN or WENDLAND) with a nugget >= 0 (the
+/* Ordinary kriging on a positive definite kernel used as covariance (GAUSSIAN, WENDLAND, MATERN32, MATERN52 or IMQ) with a nugget >= 0 (the
    reference's README:24 future list): d_w holds f on entry and the dual weights w on exit, *h_mean the estimated
    mean mu; s(y) = mu + sum_j w_j phi(|y - x_j|) (gsl_sinterp_hip_krige_eval = the RBF sweep + mu).  Route 7: Cholesky
    of K = Phi + nugget I with two right-hand sides; route 8: pivoted LDL^T when K is only semi-definite. */
@@ -342,7 +351,7 @@ int gsl_sinterp_hip_krige_variance_prepare(gsl_sinterp_hip_ctx *ctx, size_t n, c
 size_t gsl_sinterp_hip_krige_variance_work(size_t n, size_t chunk);
 /* d_var[k] = sigma^2(y_k), k < m; asynchronous on the context's stream; chunk >= 1 rows of d_work per pass.  d_work is
    the caller's (gsl_sinterp_hip_krige_variance_work doubles): the sweep and the GEMM called inside use the context's own
-   buffers.  kind: GAUSSIAN or WENDLAND.  Not clamped: where sigma^2 = 0 the result is rounding residue of either sign. */
+   buffers.  kind: any positive definite one (not TPS).  Not clamped: where sigma^2 = 0 the result is rounding residue of either sign. */
 int gsl_sinterp_hip_krige_variance(gsl_sinterp_hip_ctx *ctx, int kind, double eps, const double *d_x, size_t n, int dim, size_t xtda,
                                    const double *d_llt, size_t lda, const double *d_b, const double *d_dinv,
                                    double denom, const double *d_y, size_t m, size_t ytda, double *d_var,
