@@ -28,6 +28,7 @@ __device__ unsigned long long g_diag_ts[80];
 extern "C" int gsl_sinterp_hip_debug_diag_ts(unsigned long long *out) { return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_diag_ts), sizeof(unsigned long long) * 80); }
 #endif
 #include "chol_potrf.h"
+#include "trsm128.h"
 
 
 
@@ -141,7 +142,7 @@ chol_diag_writeback_kernel(double *__restrict__ A, size_t lda, size_t n, const d
         substitution, overlapped with the TRSM phase) to a side buffer;
      chol_trsm128_kernel  (64 rows per workgroup, 16 per wave): X = B L^-T by block substitution,
         every step an MFMA product:  X_c = (B_c - sum_{p<c} X_p L_cp^T) Dinv_c^T,  c = 0..3,
-        B tile, the off-diagonal blocks of L and the Dinv blocks staged in LDS.
+        B tile, the off-diagonal blocks of L and the Dinv blocks staged in LDS (the body is trsm128.h).
    Multiplying by explicitly inverted 32x32 diagonal blocks of a Cholesky factor is the standard
    GPU formulation of the panel TRSM (the sweeps further down do the same with 64x64 blocks).
    LDS layout of triangles: packed 32x32 blocks of pitch 34 doubles -- 34 = 2 mod 4 makes the
@@ -321,96 +322,36 @@ static int launch_trsm16(gsl_sinterp_hip_ctx *ctx, double *A, size_t lda, size_t
 }
 
 /* tall panels (more than 4 k rows below the block; round 2): 64 rows per workgroup, wave w owns rows 16w..16w+15 for all
-   four 32-column steps, so the steps need no workgroup barrier; B tile, L blocks and Dinv blocks staged in LDS with
-   coalesced 16-byte loads.  144 dependent MFMAs per wave, which only pays when there is a workgroup for every CU. */
+   four 32-column steps, so the steps need no workgroup barrier.  144 dependent MFMAs per wave, which only pays when there
+   is a workgroup for every CU.  Staging and substitution are the shared body of trsm128.h (krige_trsm128_kernel is its
+   other user); this kernel's own part is where the operands come from -- B and L out of the one buffer A, B rows past n
+   clamped to the last row and never stored -- the guarded store of X into A, and the folded forward substitution. */
 __global__ void __launch_bounds__(256)
 chol_trsm128_kernel(double *__restrict__ A, size_t lda, size_t n, size_t j0, const double *__restrict__ Dinvg, size_t row_start,
                     double *__restrict__ fb, size_t ldf, int nrhs)
 {
   extern __shared__ __attribute__((aligned(16))) double sm[];
-  double *Bt = sm;                     /* [64][TR_LD] */
-  double *Lb = Bt + 64 * TR_LD;        /* 6 off-diagonal blocks of L: (bi, bj) at bi(bi-1)/2 + bj */
-  double *Dvb = Lb + 6 * PBLK;         /* 4 inverted diagonal blocks */
-  double *ys = Dvb + 4 * PBLK;         /* [TRSV_MAXR][PB]: y_p of the folded forward substitution */
+  double *Bt = sm;                     /* [64][TR_LD]: B on the way in, X on the way out */
+  double *ys = sm + TRSM128_LDS;       /* [TRSV_MAXR][PB]: y_p of the folded forward substitution */
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int fr = lane & 15, fq = lane >> 4;
   const size_t row0 = row_start + (size_t)blockIdx.x * 64;    /* rows [row_start, n): the whole panel below the block, or a slice of it */
-  {
-    /* one round trip: every global load is issued before the first LDS store */
-    double2 vb[16];
-    double vl[24], vd[16], yv[3];
-    const int r8 = tid >> 5, k = tid & 31;
+  double yv[3];                        /* y_p rides in the round trip of the staging */
+  trsm128_stage(sm, tid,
+                [=](int r) { return A + (row0 + r < n ? row0 + r : n - 1) * lda + j0; },
+                [=](int bi, int bj, int r, int k) { return A[(j0 + bi * 32 + r) * lda + j0 + bj * 32 + k]; },
+                [=](int b, int r, int k) { return Dinvg[b * 1024 + r * 32 + k]; },
+                [=, &yv] {
 #pragma unroll
-    for (int t = 0; t < 16; t++) {
-      const int e = t * 256 + tid, r = e >> 6, k2 = (e & 63) * 2;
-      const size_t grow = row0 + r < n ? row0 + r : n - 1;
-      vb[t] = *reinterpret_cast<const double2 *>(A + grow * lda + j0 + k2);
-    }
+                  for (int t = 0; t < 3; t++) { const int e = t * 256 + tid; yv[t] = e < nrhs * PB ? fb[(size_t)(e >> 7) * ldf + j0 + (e & 127)] : 0.0; }
+                });
 #pragma unroll
-    for (int t = 0; t < 24; t++) {
-      constexpr int BI[6] = {1, 2, 2, 3, 3, 3}, BJ[6] = {0, 0, 1, 0, 1, 2};
-      const int b = t >> 2, r = (t & 3) * 8 + r8;
-      vl[t] = A[(j0 + BI[b] * 32 + r) * lda + j0 + BJ[b] * 32 + k];
-    }
-#pragma unroll
-    for (int t = 0; t < 16; t++) vd[t] = Dinvg[(t >> 2) * 1024 + ((t & 3) * 8 + r8) * 32 + k];
-#pragma unroll
-    for (int t = 0; t < 3; t++) { const int e = t * 256 + tid; yv[t] = e < nrhs * PB ? fb[(size_t)(e >> 7) * ldf + j0 + (e & 127)] : 0.0; }
-#pragma unroll
-    for (int t = 0; t < 16; t++) {
-      const int e = t * 256 + tid, r = e >> 6, k2 = (e & 63) * 2;
-      Bt[r * TR_LD + k2] = vb[t].x; Bt[r * TR_LD + k2 + 1] = vb[t].y;
-    }
-#pragma unroll
-    for (int t = 0; t < 3; t++) { const int e = t * 256 + tid; if (e < nrhs * PB) ys[e] = yv[t]; }
-#pragma unroll
-    for (int t = 0; t < 24; t++) Lb[(t >> 2) * PBLK + ((t & 3) * 8 + r8) * PQ + k] = vl[t];
-#pragma unroll
-    for (int t = 0; t < 16; t++) Dvb[(t >> 2) * PBLK + ((t & 3) * 8 + r8) * PQ + k] = vd[t];
-  }
+  for (int t = 0; t < 3; t++) { const int e = t * 256 + tid; if (e < nrhs * PB) ys[e] = yv[t]; }
   __syncthreads();
-
-  double *arow = Bt + (wave * 16 + fr) * TR_LD + fq;        /* A-operand view of this wave's rows */
-  double *drow = Bt + (wave * 16 + fq) * TR_LD + fr;        /* accumulator (D layout) view */
-#pragma unroll
-  for (int c = 0; c < 4; c++) {
-    double4_t acc[2];
-#pragma unroll
-    for (int f = 0; f < 2; f++)
-#pragma unroll
-      for (int rg = 0; rg < 4; rg++) acc[f][rg] = drow[4 * rg * TR_LD + c * 32 + f * 16];
-#pragma unroll
-    for (int p = 0; p < c; p++) {
-      const double *lb = Lb + (c * (c - 1) / 2 + p) * PBLK + fr * PQ + fq;
-#pragma unroll
-      for (int kk = 0; kk < 8; kk++) {
-        const double a = -arow[p * 32 + kk * 4];
-#pragma unroll
-        for (int f = 0; f < 2; f++) acc[f] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, lb[f * 16 * PQ + kk * 4], acc[f], 0, 0, 0);
-      }
-    }
-    /* Y -> LDS (own rows), then X_c = Y Dinv_c^T (Dinv lower triangular: fragment f needs K = 16(f+1)) */
-#pragma unroll
-    for (int f = 0; f < 2; f++)
-#pragma unroll
-      for (int rg = 0; rg < 4; rg++) drow[4 * rg * TR_LD + c * 32 + f * 16] = acc[f][rg];
-    const double *db = Dvb + c * PBLK + fr * PQ + fq;
-#pragma unroll
-    for (int f = 0; f < 2; f++) {
-      acc[f] = (double4_t){0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-      for (int kk = 0; kk < (f + 1) * 4; kk++)
-        acc[f] = __builtin_amdgcn_mfma_f64_16x16x4f64(arow[c * 32 + kk * 4], db[f * 16 * PQ + kk * 4], acc[f], 0, 0, 0);
-    }
-#pragma unroll
-    for (int f = 0; f < 2; f++)
-#pragma unroll
-      for (int rg = 0; rg < 4; rg++) {
-        drow[4 * rg * TR_LD + c * 32 + f * 16] = acc[f][rg];
-        const size_t grow = row0 + wave * 16 + fq + 4 * rg;
-        if (grow < n) A[grow * lda + j0 + c * 32 + f * 16 + fr] = acc[f][rg];
-      }
-  }
+  trsm128_solve(sm, tid, [=](int c, int f, int rg, double v) {
+    const size_t grow = row0 + wave * 16 + fq + 4 * rg;
+    if (grow < n) A[grow * lda + j0 + c * 32 + f * 16 + fr] = v;
+  });
   if (nrhs > 0) {
     /* folded forward substitution: f[R] -= X_R y_p, X_R is in Bt now (every wave wrote its own rows) */
     __syncthreads();
@@ -501,7 +442,7 @@ static int chol_panel(gsl_sinterp_hip_ctx *ctx, double *A, size_t lda, size_t n,
       else if (force_rf == 2) ast = launch_trsm16<2>(ctx, A, lda, n, j0, d_linv, j0 + PB, fb, ldf, nrhs);
       else if (force_rf == 4) ast = launch_trsm16<4>(ctx, A, lda, n, j0, d_linv, j0 + PB, fb, ldf, nrhs);
       else {
-        const size_t lds_trsm = (size_t)(64 * TR_LD + 10 * PBLK + TRSV_MAXR * PB) * sizeof(double);
+        const size_t lds_trsm = (size_t)(TRSM128_LDS + TRSV_MAXR * PB) * sizeof(double);
         ast = sinterp_func_lds(ctx, (const void *)chol_trsm128_kernel, (int)lds_trsm);
         if (!ast)
           hipLaunchKernelGGL(chol_trsm128_kernel, dim3((unsigned)((below + 63) / 64)), dim3(256), lds_trsm, ctx->stream, A, lda, n, j0,

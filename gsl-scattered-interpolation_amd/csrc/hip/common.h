@@ -114,6 +114,8 @@ static inline int sinterp_fail(gsl_sinterp_hip_ctx *ctx, int status, const char 
 
 #define LAUNCH_CHECK(ctx) HIP_OK(ctx, hipGetLastError())
 
+static inline size_t round_up(size_t v, size_t to) { return (v + to - 1) / to * to; }
+
 /* hipFuncAttributeMaxDynamicSharedMemorySize is a PER-DEVICE attribute of a kernel: set it once per
    (kernel, device) pair (a process-wide flag would leave the second device of a process without it) */
 int sinterp_func_lds(gsl_sinterp_hip_ctx *ctx, const void *func, int bytes);

@@ -21,13 +21,10 @@
 #include "common.h"
 #include <math.h>
 #include <stdlib.h>
-#include <type_traits>
-#include "chol_potrf.h"
+#include "trsm128.h"
 #include "rbf_phi.h"
 
 #define KV_RP 128   /* rows of a pass are padded to this (zero rows): every update then takes the full-tile GEMM path */
-
-static inline size_t kv_round_up(size_t v, size_t to) { return (v + to - 1) / to * to; }
 
 /* ------------------------------------------------------------------------ */
 /* cross-covariance fill: block = 256 threads -> 16 rows (targets) x 128 columns (centres), 2 columns (16 B) per lane.
@@ -109,100 +106,31 @@ int sinterp_krige_inv32(gsl_sinterp_hip_ctx *ctx, size_t n, const double *d_llt,
 
 /* ------------------------------------------------------------------------ */
 /* the diagonal step: Z[:, J] <- Z[:, J] L_JJ^-T for the 128-column block J at j0, and q_k += |Z[k][J]|^2.
-   The scheme of chol_trsm128_kernel (chol.hip): 64 rows per workgroup, wave w owns rows 16w .. 16w+15 for all four
-   32-column steps c (no workgroup barrier between the steps),
+   The same body as chol_trsm128_kernel (chol.hip), shared through trsm128.h: 64 rows per workgroup, wave w owns rows
+   16w .. 16w+15 for all four 32-column steps c (no workgroup barrier between the steps),
        Y_c = Z_c - sum_{p<c} X_p L_cp^T,     X_c = Y_c Dinv_c^T,
    the Z tile, the six off-diagonal 32 x 32 blocks of L_JJ and the four Dinv blocks staged in LDS with one round trip.
-   Here the right-hand matrix (Z, ldw) and the factor (L, lda) are different buffers, rows of L past n (the last,
-   partial block) read as zeros, and the squared row norms are accumulated on the way out: a workgroup owns the same
-   rows at every step of the recursion, so q needs no atomics.  rows is a multiple of 64 (KV_RP). */
+   This kernel's own part: the right-hand matrix (Z, ldw) and the factor (L, lda) are different buffers, rows of L and
+   Dinv blocks past n (the last, partial block) read as zeros, and the squared row norms are accumulated on the way out:
+   a workgroup owns the same rows at every step of the recursion, so q needs no atomics.  rows is a multiple of 64 (KV_RP). */
 __global__ void __launch_bounds__(256)
 krige_trsm128_kernel(double *__restrict__ Z, size_t ldw, const double *__restrict__ L, size_t lda, size_t n, size_t j0,
                      const double *__restrict__ Dinvg, double *__restrict__ q)
 {
   extern __shared__ __attribute__((aligned(16))) double sm[];
-  double *Bt = sm;                     /* [64][TR_LD] */
-  double *Lb = Bt + 64 * TR_LD;        /* 6 off-diagonal blocks of L_JJ: (bi, bj) at bi(bi-1)/2 + bj */
-  double *Dvb = Lb + 6 * PBLK;         /* 4 inverted diagonal blocks */
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int fr = lane & 15, fq = lane >> 4;
+  const int tid = threadIdx.x;
   const size_t row0 = (size_t)blockIdx.x * 64;
-  {
-    /* one round trip: every global load is issued before the first LDS store */
-    double2 vb[16];
-    double vl[24], vd[16];
-    const int r8 = tid >> 5, k = tid & 31;
-#pragma unroll
-    for (int t = 0; t < 16; t++) {
-      const int e = t * 256 + tid, r = e >> 6, k2 = (e & 63) * 2;
-      vb[t] = *reinterpret_cast<const double2 *>(Z + (row0 + r) * ldw + j0 + k2);
-    }
-#pragma unroll
-    for (int t = 0; t < 24; t++) {
-      constexpr int BI[6] = {1, 2, 2, 3, 3, 3}, BJ[6] = {0, 0, 1, 0, 1, 2};
-      const int b = t >> 2, r = (t & 3) * 8 + r8;
-      const size_t gr = j0 + BI[b] * 32 + r;
-      vl[t] = gr < n ? L[gr * lda + j0 + BJ[b] * 32 + k] : 0.0;                    /* strictly below the diagonal */
-    }
-#pragma unroll
-    for (int t = 0; t < 16; t++) {
-      const size_t blk = j0 / CB + (t >> 2);
-      vd[t] = blk * CB < n ? Dinvg[blk * 1024 + ((t & 3) * 8 + r8) * 32 + k] : 0.0;
-    }
-#pragma unroll
-    for (int t = 0; t < 16; t++) {
-      const int e = t * 256 + tid, r = e >> 6, k2 = (e & 63) * 2;
-      Bt[r * TR_LD + k2] = vb[t].x; Bt[r * TR_LD + k2 + 1] = vb[t].y;
-    }
-#pragma unroll
-    for (int t = 0; t < 24; t++) Lb[(t >> 2) * PBLK + ((t & 3) * 8 + r8) * PQ + k] = vl[t];
-#pragma unroll
-    for (int t = 0; t < 16; t++) Dvb[(t >> 2) * PBLK + ((t & 3) * 8 + r8) * PQ + k] = vd[t];
-  }
+  trsm128_stage(sm, tid,
+                [=](int r) { return Z + (row0 + r) * ldw + j0; },
+                [=](int bi, int bj, int r, int k) { const size_t gr = j0 + bi * 32 + r; return gr < n ? L[gr * lda + j0 + bj * 32 + k] : 0.0; },
+                [=](int b, int r, int k) { const size_t blk = j0 / CB + b; return blk * CB < n ? Dinvg[blk * 1024 + r * 32 + k] : 0.0; });
   __syncthreads();
-
-  double *arow = Bt + (wave * 16 + fr) * TR_LD + fq;        /* A-operand view of this wave's rows */
-  double *drow = Bt + (wave * 16 + fq) * TR_LD + fr;        /* accumulator (D layout) view */
+  const int lane = tid & 63, wave = tid >> 6, fr = lane & 15, fq = lane >> 4;
   double qs[4] = {0.0, 0.0, 0.0, 0.0};                      /* this lane's share of |X[row fq + 4 rg]|^2 */
-#pragma unroll
-  for (int c = 0; c < 4; c++) {
-    double4_t acc[2];
-#pragma unroll
-    for (int f = 0; f < 2; f++)
-#pragma unroll
-      for (int rg = 0; rg < 4; rg++) acc[f][rg] = drow[4 * rg * TR_LD + c * 32 + f * 16];
-#pragma unroll
-    for (int p = 0; p < c; p++) {
-      const double *lb = Lb + (c * (c - 1) / 2 + p) * PBLK + fr * PQ + fq;
-#pragma unroll
-      for (int kk = 0; kk < 8; kk++) {
-        const double a = -arow[p * 32 + kk * 4];
-#pragma unroll
-        for (int f = 0; f < 2; f++) acc[f] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, lb[f * 16 * PQ + kk * 4], acc[f], 0, 0, 0);
-      }
-    }
-    /* Y -> LDS (own rows), then X_c = Y Dinv_c^T (Dinv lower triangular: fragment f needs K = 16(f+1)) */
-#pragma unroll
-    for (int f = 0; f < 2; f++)
-#pragma unroll
-      for (int rg = 0; rg < 4; rg++) drow[4 * rg * TR_LD + c * 32 + f * 16] = acc[f][rg];
-    const double *db = Dvb + c * PBLK + fr * PQ + fq;
-#pragma unroll
-    for (int f = 0; f < 2; f++) {
-      acc[f] = (double4_t){0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-      for (int kk = 0; kk < (f + 1) * 4; kk++)
-        acc[f] = __builtin_amdgcn_mfma_f64_16x16x4f64(arow[c * 32 + kk * 4], db[f * 16 * PQ + kk * 4], acc[f], 0, 0, 0);
-    }
-#pragma unroll
-    for (int f = 0; f < 2; f++)
-#pragma unroll
-      for (int rg = 0; rg < 4; rg++) {
-        drow[4 * rg * TR_LD + c * 32 + f * 16] = acc[f][rg];
-        Z[(row0 + wave * 16 + fq + 4 * rg) * ldw + j0 + c * 32 + f * 16 + fr] = acc[f][rg];
-        qs[rg] = fma(acc[f][rg], acc[f][rg], qs[rg]);
-      }
-  }
+  trsm128_solve(sm, tid, [=, &qs](int c, int f, int rg, double v) {
+    Z[(row0 + wave * 16 + fq + 4 * rg) * ldw + j0 + c * 32 + f * 16 + fr] = v;
+    qs[rg] = fma(v, v, qs[rg]);
+  });
 #pragma unroll
   for (int rg = 0; rg < 4; rg++) {
     double v = qs[rg];
@@ -247,11 +175,10 @@ static void launch_cross_fill(gsl_sinterp_hip_ctx *ctx, double coef, const doubl
                               const double *d_y, size_t rows, size_t ytda, double *Z, size_t ldw, size_t rows_pad, double *q)
 {
   const dim3 grid((unsigned)(ldw / 128), (unsigned)(rows_pad / 16));
-  switch (dim) {
-    case 1: hipLaunchKernelGGL((krige_cross_fill_kernel<KIND, 1>), grid, dim3(256), 0, ctx->stream, coef, tbl, d_x, n, xtda, d_y, rows, ytda, Z, ldw, q); break;
-    case 2: hipLaunchKernelGGL((krige_cross_fill_kernel<KIND, 2>), grid, dim3(256), 0, ctx->stream, coef, tbl, d_x, n, xtda, d_y, rows, ytda, Z, ldw, q); break;
-    default: hipLaunchKernelGGL((krige_cross_fill_kernel<KIND, 3>), grid, dim3(256), 0, ctx->stream, coef, tbl, d_x, n, xtda, d_y, rows, ytda, Z, ldw, q); break;
-  }
+  with_dim(dim, [&](auto D) {
+    hipLaunchKernelGGL((krige_cross_fill_kernel<KIND, decltype(D)::value>), grid, dim3(256), 0, ctx->stream, coef, tbl, d_x, n, xtda, d_y, rows,
+                       ytda, Z, ldw, q);
+  });
 }
 
 /* Z[:, c0 : c0 + cw] -= Z[:, k0 : k0 + kw] L[c0 : c0 + cw, k0 : k0 + kw]^T; a partial last block (c0 + cw = n, not a
@@ -271,7 +198,7 @@ int sinterp_kv_update(const KvPass &p, size_t c0, size_t cw, size_t k0, size_t k
 
 int sinterp_kv_diag(const KvPass &p, size_t j0)
 {
-  const size_t lds = (size_t)(64 * TR_LD + 10 * PBLK) * sizeof(double);
+  const size_t lds = (size_t)TRSM128_LDS * sizeof(double);
   int st = sinterp_func_lds(p.ctx, (const void *)krige_trsm128_kernel, (int)lds);
   if (st) return st;
   hipLaunchKernelGGL(krige_trsm128_kernel, dim3((unsigned)(p.rows_pad / 64)), dim3(256), lds, p.ctx->stream, p.Z, p.ldw, p.L, p.lda, p.n,
@@ -311,7 +238,7 @@ static int kv_solve(const KvPass &p, size_t panel)
 extern "C" size_t gsl_sinterp_hip_krige_variance_work(size_t n, size_t chunk)
 {
   /* Z (rows padded to KV_RP, pitch n rounded up to 128) + q + two words to align Z to 16 bytes */
-  return kv_round_up(chunk ? chunk : 1, KV_RP) * (kv_round_up(n, PB) + 1) + 2;
+  return round_up(chunk ? chunk : 1, KV_RP) * (round_up(n, PB) + 1) + 2;
 }
 
 extern "C" int gsl_sinterp_hip_krige_variance_prepare(gsl_sinterp_hip_ctx *ctx, size_t n, const double *d_llt, size_t lda,
@@ -372,23 +299,17 @@ extern "C" int gsl_sinterp_hip_krige_variance(gsl_sinterp_hip_ctx *ctx, int kind
   st = gsl_sinterp_hip_rbf_eval(ctx, kind, eps, d_x, n, dim, xtda, d_b, d_y, m, ytda, d_var);
   if (st) return st;
   KvPass p;
-  p.ctx = ctx; p.ldw = kv_round_up(n, PB); p.L = d_llt; p.lda = lda; p.n = n; p.dinv = d_dinv;
+  p.ctx = ctx; p.ldw = round_up(n, PB); p.L = d_llt; p.lda = lda; p.n = n; p.dinv = d_dinv;
   p.Z = (double *)(((uintptr_t)d_work + 15) & ~(uintptr_t)15);
-  const size_t chunk_pad = kv_round_up(chunk, KV_RP);
+  const size_t chunk_pad = round_up(chunk, KV_RP);
   p.q = p.Z + chunk_pad * p.ldw;
   for (size_t k0 = 0; k0 < m; k0 += chunk) {
     const size_t rows = m - k0 < chunk ? m - k0 : chunk;
-    p.rows_pad = kv_round_up(rows, KV_RP);
-    const auto fill = [&](auto K) {
-      launch_cross_fill<decltype(K)::value>(ctx, coef, tbl, d_x, n, dim, xtda, d_y + k0 * ytda, rows, ytda, p.Z, p.ldw, p.rows_pad, p.q);
-    };
-    switch (kind) {
-      case GSL_SINTERP_RBF_WENDLAND: fill(std::integral_constant<int, GSL_SINTERP_RBF_WENDLAND>()); break;
-      case GSL_SINTERP_RBF_MATERN32: fill(std::integral_constant<int, GSL_SINTERP_RBF_MATERN32>()); break;
-      case GSL_SINTERP_RBF_MATERN52: fill(std::integral_constant<int, GSL_SINTERP_RBF_MATERN52>()); break;
-      case GSL_SINTERP_RBF_IMQ: fill(std::integral_constant<int, GSL_SINTERP_RBF_IMQ>()); break;
-      default: fill(std::integral_constant<int, GSL_SINTERP_RBF_GAUSSIAN>()); break;
-    }
+    p.rows_pad = round_up(rows, KV_RP);
+    with_kind(kind, [&](auto K) {
+      if constexpr (kind_is_pd(decltype(K)::value))          /* kind_is_pd(kind) was required above */
+        launch_cross_fill<decltype(K)::value>(ctx, coef, tbl, d_x, n, dim, xtda, d_y + k0 * ytda, rows, ytda, p.Z, p.ldw, p.rows_pad, p.q);
+    });
     LAUNCH_CHECK(ctx);
     st = kv_solve(p, panel);
     if (st) return st;

@@ -23,13 +23,11 @@
 #include "common.h"
 #include "chol_potrf.h"
 
-static inline size_t loo_round_up(size_t v, size_t to) { return (v + to - 1) / to * to; }
-
 /* rows of Z per pass: chunk rounded up to 128, at most n rounded up to 128 (and 2^19: rows / 16 is a grid dimension) */
 static inline size_t loo_chunk_rows(size_t n, size_t chunk)
 {
-  size_t c = loo_round_up(chunk ? chunk : 1, PB);
-  const size_t all = loo_round_up(n, PB);
+  size_t c = round_up(chunk ? chunk : 1, PB);
+  const size_t all = round_up(n, PB);
   if (c > all) c = all;
   if (c > ((size_t)1 << 19)) c = (size_t)1 << 19;
   return c;
@@ -73,7 +71,7 @@ extern "C" size_t gsl_sinterp_hip_chol_inv_diag_work(size_t n, size_t chunk)
 {
   /* Z (pitch n rounded up to 128) + q + the inverted 32 x 32 diagonal blocks + two words to align Z to 16 bytes */
   const size_t c = loo_chunk_rows(n, chunk);
-  return c * (loo_round_up(n, PB) + 1) + (n + CB - 1) / CB * (CB * CB) + 2;
+  return c * (round_up(n, PB) + 1) + (n + CB - 1) / CB * (CB * CB) + 2;
 }
 
 extern "C" int gsl_sinterp_hip_chol_inv_diag(gsl_sinterp_hip_ctx *ctx, size_t n, const double *d_llt, size_t lda, double *d_g,
@@ -89,7 +87,7 @@ extern "C" int gsl_sinterp_hip_chol_inv_diag(gsl_sinterp_hip_ctx *ctx, size_t n,
   if (st) return st;
   const size_t c = loo_chunk_rows(n, chunk);
   KvPass p;
-  p.ctx = ctx; p.ldw = loo_round_up(n, PB); p.L = d_llt; p.lda = lda; p.n = n;
+  p.ctx = ctx; p.ldw = round_up(n, PB); p.L = d_llt; p.lda = lda; p.n = n;
   p.Z = (double *)(((uintptr_t)d_work + 15) & ~(uintptr_t)15);
   p.q = p.Z + c * p.ldw;
   double *dinv = p.q + c;

@@ -15,34 +15,7 @@
 #include "common.h"
 #include <math.h>
 #include <stdlib.h>
-#include <type_traits>
-
 #include "rbf_phi.h"
-
-/* host side: a run-time kind / dimension / tile size picks the kernel instance.  f is a generic lambda that receives the
-   value as a std::integral_constant and launches <decltype(arg)::value>; its result is passed on */
-template <int V> using ic = std::integral_constant<int, V>;
-
-template <class F> static auto with_kind(int kind, F &&f)
-{
-  switch (kind) {
-    case GSL_SINTERP_RBF_WENDLAND: return f(ic<GSL_SINTERP_RBF_WENDLAND>());
-    case GSL_SINTERP_RBF_GAUSSIAN: return f(ic<GSL_SINTERP_RBF_GAUSSIAN>());
-    case GSL_SINTERP_RBF_MATERN32: return f(ic<GSL_SINTERP_RBF_MATERN32>());
-    case GSL_SINTERP_RBF_MATERN52: return f(ic<GSL_SINTERP_RBF_MATERN52>());
-    case GSL_SINTERP_RBF_IMQ: return f(ic<GSL_SINTERP_RBF_IMQ>());
-    default: return f(ic<GSL_SINTERP_RBF_TPS>());
-  }
-}
-
-template <class F> static auto with_dim(int dim, F &&f)
-{
-  switch (dim) {
-    case 1: return f(ic<1>());
-    case 2: return f(ic<2>());
-    default: return f(ic<3>());
-  }
-}
 
 /* (dimension, tile size) of the culled sweeps: cull_tile_size gives 8 / 16 / 32 in two dimensions, 32 otherwise */
 template <class F> static auto with_dim_tile(int dim, int ct, F &&f)

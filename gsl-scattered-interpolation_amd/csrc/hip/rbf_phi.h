@@ -1,14 +1,18 @@
 /*
  * rbf_phi.h -- the radial kernels phi(r^2) as the fill and the sweeps evaluate them (table-driven exp2 / log),
- * shared by rbf.hip and krige_var.hip so that a covariance is the same number wherever it is formed.
+ * shared by rbf.hip and krige_var.hip so that a covariance is the same number wherever it is formed, and the host-side
+ * dispatch from a run-time kind / dimension to a kernel instance (with_kind, with_dim).
  * The tables themselves live in rbf.hip (g_rbf_tables); other translation units get the device address of the
  * exp2 table from sinterp_rbf_exp2_table (common.h).
  */
 #ifndef SINTERP_RBF_PHI_H
 #define SINTERP_RBF_PHI_H
 
+#include <type_traits>
+
 /* What a kind needs and how it is swept, as constexpr traits: every "load the exp2 table", every s_t0 size and the choice
-   between the plain and the culled sweep ask these, so a new kind is one line here and one branch in phi_r2 / phi_psi_r2.
+   between the plain and the culled sweep ask these, so a new kind is one line here, one case each in kernel_coef and
+   with_kind below (the only switch that maps a run-time kind to a kernel instance) and one branch in phi_r2 / phi_psi_r2.
      kind_uses_exp2   phi goes through exp2_tbl: the 256-entry table is copied to LDS
      kind_uses_log    phi goes through log_tbl (thin-plate)
      kind_is_culled   decays fast enough to be cut off: per-pair take test, tile culling, target sort (Gaussian, Wendland).
@@ -33,6 +37,32 @@ static inline double kernel_coef(int kind, double eps)
     case GSL_SINTERP_RBF_MATERN52: return 2.23606797749978969640917 * eps;      /* t = sqrt(5) eps r */
     case GSL_SINTERP_RBF_IMQ: return eps * eps;
     default: return 0.5;                                                         /* thin-plate: the half of r^2 ln r^2 */
+  }
+}
+
+/* host side: a run-time kind / dimension picks the kernel instance.  f is a generic lambda that receives the value as a
+   std::integral_constant and launches <decltype(arg)::value>; its result is passed on.  An unknown kind names the
+   thin-plate instance: callers that accept only some kinds check first (kind_is_known, kind_is_pd). */
+template <int V> using ic = std::integral_constant<int, V>;
+
+template <class F> static auto with_kind(int kind, F &&f)
+{
+  switch (kind) {
+    case GSL_SINTERP_RBF_WENDLAND: return f(ic<GSL_SINTERP_RBF_WENDLAND>());
+    case GSL_SINTERP_RBF_GAUSSIAN: return f(ic<GSL_SINTERP_RBF_GAUSSIAN>());
+    case GSL_SINTERP_RBF_MATERN32: return f(ic<GSL_SINTERP_RBF_MATERN32>());
+    case GSL_SINTERP_RBF_MATERN52: return f(ic<GSL_SINTERP_RBF_MATERN52>());
+    case GSL_SINTERP_RBF_IMQ: return f(ic<GSL_SINTERP_RBF_IMQ>());
+    default: return f(ic<GSL_SINTERP_RBF_TPS>());
+  }
+}
+
+template <class F> static auto with_dim(int dim, F &&f)
+{
+  switch (dim) {
+    case 1: return f(ic<1>());
+    case 2: return f(ic<2>());
+    default: return f(ic<3>());
   }
 }
 
