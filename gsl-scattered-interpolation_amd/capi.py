@@ -15,6 +15,7 @@ GSL_EDOM, GSL_EFAULT, GSL_EINVAL, GSL_EFAILED, GSL_ENOMEM = 1, 3, 4, 5, 8
 GSL_EBADLEN, GSL_ENOTSQR, GSL_EUNSUP, GSL_EUNIMPL = 19, 20, 23, 24
 RBF_GAUSSIAN, RBF_TPS, RBF_WENDLAND = 0, 1, 2
 RBF_MATERN32, RBF_MATERN52, RBF_IMQ = 3, 4, 5
+FIT_LOO, FIT_ML = 0, 1
 SOLVER_DEFAULT, SOLVER_CHOLESKY2, SOLVER_PCHOLESKY, SOLVER_LU_REFINE = 0, 1, 2, 3
 TREE_DEFAULT, TREE_NOSTANDARDIZE, TREE_ISOSCALE = 0, 1, 2
 TREE_RECORD_BYTES, TREE_LEAFTAB_BYTES = 64, 32
@@ -258,6 +259,17 @@ SIGNATURES = {
     "gsl_sinterp_set_loo": (_i, [C.POINTER(gsl_sinterp), _i]),
     "gsl_sinterp_loo_residuals": (_i, [C.POINTER(gsl_sinterp), _pm]),
     "gsl_sinterp_loo_variance": (_i, [C.POINTER(gsl_sinterp), _pv]),
+    "gsl_sinterp_hip_d2d_async": (_i, [_vp, _vp, _vp, _sz]),
+    "gsl_sinterp_hip_score_reduce": (_i, [_vp, _sz, _vp, _sz, _vp, _vp, _vp, _vp, _d, _vp]),
+    "gsl_sinterp_fit_alloc": (_vp, [C.POINTER(gsl_sinterp), _pm, _pv]),
+    "gsl_sinterp_fit_free": (None, [_vp]),
+    "gsl_sinterp_fit_score": (_i, [_vp, _i, _d, _d, _pd]),
+    "gsl_sinterp_fit_shape": (_i, [_vp, _i, _d, _d, _d, _pd, _pd]),
+    "gsl_sinterp_fit_nugget": (_i, [_vp, _i, _d, _d, _d, _pd, _pd]),
+    "gsl_sinterp_fit_set_search": (_i, [_vp, _sz, _d, _sz]),
+    "gsl_sinterp_fit_n_eval": (_sz, [_vp]),
+    "gsl_sinterp_fit_trace": (_i, [_vp, _pv, _pv]),
+    "gsl_sinterp_fit_sigma2": (_i, [_vp, _pd]),
     "gsl_sinterp_eval_grad_e": (_i, [C.POINTER(gsl_sinterp), _pv, _pd, _pv]),
     "gsl_sinterp_eval_grad_many": (_i, [C.POINTER(gsl_sinterp), _pm, _pv, _pm]),
     "gsl_sinterp_eval_grad_resident": (_i, [C.POINTER(gsl_sinterp), _vp, _sz, _sz, _vp, _vp, _sz]),
@@ -291,6 +303,7 @@ SIGNATURES = {
     "gsl_sinterp_free": (None, [C.POINTER(gsl_sinterp)]),
     # --- compat slice used by the bindings
     "gsl_set_error_handler_off": (_vp, []),
+    "gsl_set_error_handler": (_vp, [_vp]),
     "gsl_rng_alloc": (_vp, [_vp]),
     "gsl_rng_set": (None, [_vp, C.c_ulong]),
     "gsl_rng_free": (None, [_vp]),
@@ -364,6 +377,22 @@ class GslError(RuntimeError):
     def __init__(self, status, what=""):
         super().__init__(f"GSL status {status} {what}")
         self.status = status
+
+
+class ErrorCalls:
+    """`with ErrorCalls() as calls:` -- the (reason, status) of every call the library makes to the GSL error handler inside
+    the block (the bindings otherwise keep the handler off); the previous handler is restored on exit.  How an entry that
+    returns a pointer reports its status, and how a test sees that the handler was NOT called."""
+    _TYPE = C.CFUNCTYPE(None, C.c_char_p, C.c_char_p, C.c_int, C.c_int)
+
+    def __enter__(self):
+        self.calls = []
+        self._cb = self._TYPE(lambda reason, file, line, status: self.calls.append(((reason or b"").decode(), status)))
+        self._prev = lib().gsl_set_error_handler(C.cast(self._cb, C.c_void_p))
+        return self.calls
+
+    def __exit__(self, *exc):
+        lib().gsl_set_error_handler(self._prev)
 
 
 def check(status, ctx=None):
@@ -598,6 +627,11 @@ class HipContext:
     def loo_combine(self, n, nf, d_g, d_b, denom, d_w, ldw, d_e, lde, d_v):
         """leave-one-out residuals d_e (nf columns) and variances d_v from g; d_b = None: the plain rule; returns the status"""
         return lib().gsl_sinterp_hip_loo_combine(self._h, n, nf, d_g, d_b, denom, d_w, ldw, d_e, lde, d_v)
+
+    def score_reduce(self, n, d_llt, lda, d_f, d_w, d_g, d_b, denom, d_out):
+        """d_out[0..3] = log|K|, f.w, sum of squared leave-one-out residuals (0 without d_g), count of bad sites, from a
+        factor; d_g / d_b may be None; one launch, asynchronous; returns the status"""
+        return lib().gsl_sinterp_hip_score_reduce(self._h, n, d_llt, lda, d_f, d_w, d_g, d_b, denom, d_out)
 
     def gemm_minus(self, m, n, k, d_a, lda, d_b, ldb, b_is_kn, d_c, ldc, lower_only=0):
         check(lib().gsl_sinterp_hip_gemm_minus(self._h, m, n, k, d_a, lda, d_b, ldb, b_is_kn, d_c, ldc, lower_only),
@@ -1136,10 +1170,80 @@ class Sinterp:
         st = lib().gsl_sinterp_get_weights(self._p, C.byref(as_vector(w)))
         return st, w
 
+    def fit_workspace(self, x, f):
+        """a SinterpFit for this interpolant's type, dim, size and (first) device; the interpolant is not changed"""
+        return SinterpFit(self, x, f)
+
     def close(self):
         if self._p:
             lib().gsl_sinterp_free(self._p)
             self._p = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+# ------------------------------------------------------------------ model selection
+class SinterpFit:
+    """gsl_sinterp_fit_workspace: likelihood / leave-one-out scores of (eps, nugget) and the 1-D searches over either,
+    with the centres, the response and the N x N matrix resident on the device.  Raises GslError with the status of
+    gsl_sinterp_fit_alloc when no workspace comes back."""
+    LOO, ML = FIT_LOO, FIT_ML
+
+    def __init__(self, interp, x, f):
+        self._h = None
+        with ErrorCalls() as calls:
+            h = lib().gsl_sinterp_fit_alloc(interp._p if interp is not None else None,
+                                            C.byref(as_matrix(x)) if x is not None else None,
+                                            C.byref(as_vector(f)) if f is not None else None)
+        if not h:
+            raise GslError(calls[-1][1] if calls else GSL_FAILURE, calls[-1][0] if calls else "gsl_sinterp_fit_alloc")
+        self._h = C.c_void_p(h)
+
+    def score(self, criterion, eps, nugget=0.0):
+        """(status, score): +inf for a candidate whose matrix does not factor (status 0), NaN on a real failure"""
+        v = C.c_double(0)
+        st = lib().gsl_sinterp_fit_score(self._h, criterion, eps, nugget, C.byref(v))
+        return st, v.value
+
+    def fit_shape(self, criterion, eps_lo, eps_hi, nugget=0.0):
+        """(status, eps_best, score_best)"""
+        p, v = C.c_double(0), C.c_double(0)
+        st = lib().gsl_sinterp_fit_shape(self._h, criterion, nugget, eps_lo, eps_hi, C.byref(p), C.byref(v))
+        return st, p.value, v.value
+
+    def fit_nugget(self, criterion, eps, nugget_lo, nugget_hi):
+        """(status, nugget_best, score_best)"""
+        p, v = C.c_double(0), C.c_double(0)
+        st = lib().gsl_sinterp_fit_nugget(self._h, criterion, eps, nugget_lo, nugget_hi, C.byref(p), C.byref(v))
+        return st, p.value, v.value
+
+    def set_search(self, n_grid=9, tol=1e-2, max_eval=40):
+        return lib().gsl_sinterp_fit_set_search(self._h, n_grid, tol, max_eval)
+
+    def n_eval(self):
+        return int(lib().gsl_sinterp_fit_n_eval(self._h))
+
+    def trace(self):
+        """(status, params, scores) of the last search, in order of evaluation"""
+        k = self.n_eval()
+        p, v = np.full(k, np.nan), np.full(k, np.nan)
+        st = lib().gsl_sinterp_fit_trace(self._h, C.byref(as_vector(p)), C.byref(as_vector(v)))
+        return st, p, v
+
+    def sigma2(self):
+        """(status, f.w / N of the last finite score handed back)"""
+        v = C.c_double(0)
+        st = lib().gsl_sinterp_fit_sigma2(self._h, C.byref(v))
+        return st, v.value
+
+    def close(self):
+        if self._h:
+            lib().gsl_sinterp_fit_free(self._h)
+            self._h = None
 
     def __del__(self):
         try:

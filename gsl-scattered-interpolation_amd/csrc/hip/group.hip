@@ -220,6 +220,16 @@ extern "C" int gsl_sinterp_hip_d2h_async(gsl_sinterp_hip_ctx *ctx, void *h_dst, 
   return ST_SUCCESS;
 }
 
+extern "C" int gsl_sinterp_hip_d2d_async(gsl_sinterp_hip_ctx *ctx, void *d_dst, const void *d_src, size_t bytes)
+{
+  REQUIRE(ctx, ctx != NULL, ST_EFAULT);
+  HIP_OK(ctx, hipSetDevice(ctx->device));
+  if (!bytes) return ST_SUCCESS;
+  REQUIRE(ctx, d_dst != NULL && d_src != NULL, ST_EFAULT);
+  HIP_OK(ctx, hipMemcpyAsync(d_dst, d_src, bytes, hipMemcpyDeviceToDevice, ctx->stream));
+  return ST_SUCCESS;
+}
+
 /* Copy pipe of ONE context (round 4): an upload and a download stream beside the context's stream, so that a host batch
    cut into chunks overlaps  H2D of chunk i+1 | sweep of chunk i | D2H of chunk i-1  (full-duplex PCIe).  upload: the
    copy runs on the upload stream and everything enqueued on the context's stream AFTERWARDS waits for it; download:

@@ -1476,6 +1476,252 @@ int gsl_sinterp_loo_variance(const gsl_sinterp *interp, gsl_vector *v)
   return GSL_SUCCESS;
 }
 
+/* ------------------------------------------------------------------------ */
+/* Model selection ("Model selection"): a workspace that keeps the centres, the response and the N x N matrix
+   on the device, so that scoring a candidate (eps, nugget) is fill + factorisation + reduction + 32 bytes back. */
+struct gsl_sinterp_fit_workspace {
+  int kind, krige;
+  size_t n, dim;
+  gsl_sinterp_hip_ctx *ctx;
+  double *d_x, *d_f, *d_w, *d_out, *d_phi;       /* d_x: one buffer [x | f | w | out]; d_phi: the matrix */
+  double *d_g, *d_work, *d_b, *d_dinv;           /* leave-one-out: allocated by the first FIT_LOO evaluation */
+  size_t chunk;
+  size_t n_grid, max_eval;                       /* the search */
+  double tol;
+  size_t n_eval;                                 /* the last search: its evaluations in order */
+  double *tr_param, *tr_score;                   /* max_eval entries each */
+  int have_sigma2;
+  double sigma2;
+};
+
+gsl_sinterp_fit_workspace *gsl_sinterp_fit_alloc(const gsl_sinterp *interp, const gsl_matrix *x, const gsl_vector *f)
+{
+  if (!interp || !x || !f) GSL_ERROR_NULL("gsl_sinterp_fit_alloc: null argument", GSL_EFAULT);
+  if (!is_pd_type(interp->type))
+    GSL_ERROR_NULL("gsl_sinterp_fit_alloc: positive definite RBF (Gaussian, Wendland, Matern, inverse multiquadric) and kriging interpolants only", GSL_EINVAL);
+  const size_t n = interp->size, dim = interp->dim;
+  if (x->size1 != n || x->size2 != dim) GSL_ERROR_NULL("gsl_sinterp_fit_alloc: x must be size x dim", GSL_EBADLEN);
+  if (f->size != n) GSL_ERROR_NULL("gsl_sinterp_fit_alloc: f must have size entries", GSL_EBADLEN);
+  gsl_sinterp_fit_workspace *w = (gsl_sinterp_fit_workspace *)calloc(1, sizeof *w);
+  if (!w) GSL_ERROR_NULL("gsl_sinterp_fit_alloc: out of memory", GSL_ENOMEM);
+  const rbf_state *st = (const rbf_state *)interp->state;
+  w->kind = st->kind; w->krige = st->krige; w->n = n; w->dim = dim;
+  w->chunk = (n + 127) / 128 * 128;
+  if (w->chunk > LOO_CHUNK) w->chunk = LOO_CHUNK;
+  w->n_grid = 9; w->tol = 1e-2; w->max_eval = 40;
+  w->tr_param = (double *)malloc(w->max_eval * sizeof(double));
+  w->tr_score = (double *)malloc(w->max_eval * sizeof(double));
+  double *h = (double *)malloc(n * (dim + 1) * sizeof(double));                  /* [x | f] packed */
+  if (!w->tr_param || !w->tr_score || !h) {
+    free(h); gsl_sinterp_fit_free(w);
+    GSL_ERROR_NULL("gsl_sinterp_fit_alloc: out of memory", GSL_ENOMEM);
+  }
+  for (size_t i = 0; i < n; i++) {
+    for (size_t a = 0; a < dim; a++) h[i * dim + a] = x->data[i * x->tda + a];
+    h[n * dim + i] = f->data[i * f->stride];
+  }
+  if (gsl_sinterp_hip_ctx_create(&w->ctx, interp->devices[0], NULL) != GSL_SUCCESS) {
+    w->ctx = NULL; free(h); gsl_sinterp_fit_free(w);
+    GSL_ERROR_NULL("gsl_sinterp_fit_alloc: no usable HIP device (GPU path has no CPU fallback)", GSL_EFAILED);
+  }
+  int s = gsl_sinterp_hip_malloc(w->ctx, (void **)&w->d_x, (n * (dim + 2) + 4) * sizeof(double));
+  if (!s) s = gsl_sinterp_hip_malloc(w->ctx, (void **)&w->d_phi, n * n * sizeof(double));
+  if (!s) s = gsl_sinterp_hip_h2d(w->ctx, w->d_x, h, n * (dim + 1) * sizeof(double));
+  free(h);
+  if (s) {
+    gsl_error(gsl_sinterp_hip_last_error(w->ctx), __FILE__, __LINE__, s);
+    gsl_sinterp_fit_free(w);
+    return NULL;
+  }
+  w->d_f = w->d_x + n * dim; w->d_w = w->d_f + n; w->d_out = w->d_w + n;
+  return w;
+}
+
+void gsl_sinterp_fit_free(gsl_sinterp_fit_workspace *w)
+{
+  if (!w) return;
+  if (w->ctx) {
+    gsl_sinterp_hip_free(w->ctx, w->d_x); gsl_sinterp_hip_free(w->ctx, w->d_phi);
+    gsl_sinterp_hip_free(w->ctx, w->d_g); gsl_sinterp_hip_free(w->ctx, w->d_work);
+    gsl_sinterp_hip_free(w->ctx, w->d_b); gsl_sinterp_hip_free(w->ctx, w->d_dinv);
+    gsl_sinterp_hip_ctx_destroy(w->ctx);
+  }
+  free(w->tr_param); free(w->tr_score);
+  free(w);
+}
+
+/* what is wrong with (criterion, eps, nugget) for this workspace, or NULL */
+static const char *fit_bad_args(const gsl_sinterp_fit_workspace *w, int criterion, double eps, double nugget)
+{
+  if (criterion != GSL_SINTERP_FIT_LOO && criterion != GSL_SINTERP_FIT_ML) return "unknown criterion";
+  if (!(eps > 0.0) || !isfinite(eps)) return "eps must be finite and > 0";
+  if (!(nugget >= 0.0) || !isfinite(nugget)) return "the nugget must be finite and >= 0";
+  if (!w->krige && nugget != 0.0) return "the nugget must be 0 for a type that is not kriging";
+  return NULL;
+}
+
+/* One evaluation, arguments already checked.  Returns a status WITHOUT calling the error handler (the text of a failure is
+   the context's); a candidate that does not factor gives GSL_SUCCESS and *score = +infinity. */
+static int fit_evaluate(gsl_sinterp_fit_workspace *w, int criterion, double eps, double nugget, double *score)
+{
+  gsl_sinterp_hip_ctx *c = w->ctx;
+  const size_t n = w->n, dim = w->dim;
+  const int loo = criterion == GSL_SINTERP_FIT_LOO;
+  *score = GSL_NAN;
+  int s = GSL_SUCCESS, route = 0;
+  if (loo && !w->d_g) {
+    s = gsl_sinterp_hip_malloc(c, (void **)&w->d_g, n * sizeof(double));
+    if (!s) s = gsl_sinterp_hip_malloc(c, (void **)&w->d_work, gsl_sinterp_hip_chol_inv_diag_work(n, w->chunk) * sizeof(double));
+    if (!s && w->krige) s = gsl_sinterp_hip_malloc(c, (void **)&w->d_b, n * sizeof(double));
+    if (!s && w->krige) s = gsl_sinterp_hip_malloc(c, (void **)&w->d_dinv, ((n + 31) / 32) * 1024 * sizeof(double));
+    if (s) {
+      gsl_sinterp_hip_free(c, w->d_g); gsl_sinterp_hip_free(c, w->d_work); gsl_sinterp_hip_free(c, w->d_b); gsl_sinterp_hip_free(c, w->d_dinv);
+      w->d_g = w->d_work = w->d_b = w->d_dinv = NULL;
+      return s;
+    }
+  }
+  double mean = 0.0, denom = 0.0, out[4] = {0.0, 0.0, 0.0, 0.0};
+  s = gsl_sinterp_hip_d2d_async(c, w->d_w, w->d_f, n * sizeof(double));
+  if (!s) s = w->krige ? gsl_sinterp_hip_krige_solve_fields(c, w->kind, eps, nugget, w->d_x, n, (int)dim, dim, w->d_phi, n, w->d_w, n, 1, &mean, &route)
+                       : gsl_sinterp_hip_rbf_solve_fields(c, w->kind, eps, w->d_x, n, (int)dim, dim, w->d_phi, n, w->d_w, n, 1, &route);
+  if (!s && loo) s = gsl_sinterp_hip_chol_inv_diag(c, n, w->d_phi, n, w->d_g, w->d_work, w->chunk);
+  if (!s && loo && w->krige) s = gsl_sinterp_hip_krige_variance_prepare(c, n, w->d_phi, n, w->d_b, w->d_dinv, &denom);
+  if (s == GSL_EDOM) { *score = INFINITY; return GSL_SUCCESS; }                   /* not positive definite: an expected candidate */
+  if (!s) s = gsl_sinterp_hip_score_reduce(c, n, w->d_phi, n, w->d_f, w->d_w, loo ? w->d_g : NULL, loo && w->krige ? w->d_b : NULL, denom, w->d_out);
+  if (!s) s = gsl_sinterp_hip_d2h(c, out, w->d_out, sizeof out);
+  if (s) return s;
+  const double N = (double)n, s2 = out[1] / N;
+  double v = loo ? out[2] / N : 0.5 * (N * log(6.283185307179586 * s2) + out[0] + N);
+  if (out[3] != 0.0 || !(out[1] > 0.0) || !isfinite(v)) { *score = INFINITY; return GSL_SUCCESS; }
+  *score = v;
+  w->sigma2 = s2; w->have_sigma2 = 1;
+  return GSL_SUCCESS;
+}
+
+int gsl_sinterp_fit_score(gsl_sinterp_fit_workspace *w, int criterion, double eps, double nugget, double *score)
+{
+  if (score) *score = GSL_NAN;
+  if (!w || !score) GSL_ERROR("gsl_sinterp_fit_score: null argument", GSL_EFAULT);
+  const char *bad = fit_bad_args(w, criterion, eps, nugget);
+  if (bad) GSL_ERROR(bad, GSL_EINVAL);
+  HIP_TRY(fit_evaluate(w, criterion, eps, nugget, score), w->ctx);
+  return GSL_SUCCESS;
+}
+
+/* the search of fit_shape (over_nugget = 0: `fixed` is the nugget) and fit_nugget (over_nugget = 1: `fixed` is eps) */
+static int fit_search(gsl_sinterp_fit_workspace *w, int criterion, int over_nugget, double fixed, double lo, double hi, double *best,
+                      double *score_best)
+{
+  if (best) *best = GSL_NAN;
+  if (score_best) *score_best = GSL_NAN;
+  if (!w || !best || !score_best) GSL_ERROR("gsl_sinterp_fit: null argument", GSL_EFAULT);
+  if (over_nugget && !w->krige) GSL_ERROR("gsl_sinterp_fit_nugget: kriging interpolants only", GSL_EINVAL);
+  if (!(lo > 0.0) || !(hi > lo) || !isfinite(hi)) GSL_ERROR("gsl_sinterp_fit: the bracket needs 0 < lo < hi < infinity", GSL_EINVAL);
+  const char *bad = over_nugget ? fit_bad_args(w, criterion, fixed, lo) : fit_bad_args(w, criterion, lo, fixed);
+  if (bad) GSL_ERROR(bad, GSL_EINVAL);
+  w->n_eval = 0;
+  const double tlo = log(lo), thi = log(hi);
+  double p_best = GSL_NAN, s_best = INFINITY, s2_best = GSL_NAN;
+  int status = GSL_SUCCESS;
+  /* one evaluation at t (p != 0: at exactly p): recorded in the trace, the running best kept; +infinity once the budget is spent */
+#define FIT_EVAL(t, p, dst)                                                                       \
+  do {                                                                                            \
+    (dst) = INFINITY;                                                                             \
+    if (!status && w->n_eval < w->max_eval) {                                                     \
+      const double _p = (p) != 0.0 ? (p) : exp(t);                                                \
+      double _v = GSL_NAN;                                                                        \
+      status = over_nugget ? fit_evaluate(w, criterion, fixed, _p, &_v) : fit_evaluate(w, criterion, _p, fixed, &_v); \
+      if (!status) {                                                                              \
+        w->tr_param[w->n_eval] = _p; w->tr_score[w->n_eval] = _v; w->n_eval++;                    \
+        if (_v < s_best) { s_best = _v; p_best = _p; s2_best = w->sigma2; }                                       \
+        (dst) = _v;                                                                               \
+      }                                                                                           \
+    }                                                                                             \
+  } while (0)
+  /* the grid: the first index of the smallest score */
+  size_t k = 0;
+  double g_best = INFINITY;
+  for (size_t j = 0; j < w->n_grid && !status; j++) {
+    const double t = tlo + (thi - tlo) * ((double)j / (double)(w->n_grid - 1));
+    double v;
+    FIT_EVAL(t, j == 0 ? lo : j == w->n_grid - 1 ? hi : 0.0, v);
+    if (v < g_best) { g_best = v; k = j; }
+  }
+  if (!status && isfinite(g_best)) {
+    /* golden section on the two cells around grid point k (one cell at an end) */
+    const size_t ka = k > 0 ? k - 1 : 0, kb = k + 1 < w->n_grid ? k + 1 : k;
+    double a = tlo + (thi - tlo) * ((double)ka / (double)(w->n_grid - 1)), b = tlo + (thi - tlo) * ((double)kb / (double)(w->n_grid - 1));
+    const double r = 0.6180339887498949;               /* (sqrt 5 - 1) / 2 */
+    double cpt = b - r * (b - a), dpt = a + r * (b - a), fc, fd;
+    FIT_EVAL(cpt, 0.0, fc);
+    FIT_EVAL(dpt, 0.0, fd);
+    while (!status && b - a > w->tol && w->n_eval < w->max_eval) {
+      if (fc <= fd) {
+        b = dpt; dpt = cpt; fd = fc; cpt = b - r * (b - a);
+        if (b - a > w->tol) FIT_EVAL(cpt, 0.0, fc);
+      } else {
+        a = cpt; cpt = dpt; fc = fd; dpt = a + r * (b - a);
+        if (b - a > w->tol) FIT_EVAL(dpt, 0.0, fd);
+      }
+    }
+  }
+#undef FIT_EVAL
+  HIP_TRY(status, w->ctx);
+  if (!isfinite(s_best)) GSL_ERROR("gsl_sinterp_fit: no candidate in the bracket has a positive definite matrix", GSL_EDOM);
+  *best = p_best; *score_best = s_best;
+  w->sigma2 = s2_best;                                 /* of the score handed back, not of the last candidate tried */
+  return GSL_SUCCESS;
+}
+
+int gsl_sinterp_fit_shape(gsl_sinterp_fit_workspace *w, int criterion, double nugget, double eps_lo, double eps_hi, double *eps_best,
+                          double *score_best)
+{
+  return fit_search(w, criterion, 0, nugget, eps_lo, eps_hi, eps_best, score_best);
+}
+
+int gsl_sinterp_fit_nugget(gsl_sinterp_fit_workspace *w, int criterion, double eps, double nugget_lo, double nugget_hi,
+                           double *nugget_best, double *score_best)
+{
+  return fit_search(w, criterion, 1, eps, nugget_lo, nugget_hi, nugget_best, score_best);
+}
+
+int gsl_sinterp_fit_set_search(gsl_sinterp_fit_workspace *w, size_t n_grid, double tol, size_t max_eval)
+{
+  /* the numbers first: they can be judged without a workspace */
+  if (n_grid < 3 || !(tol > 0.0) || max_eval < n_grid) GSL_ERROR("gsl_sinterp_fit_set_search: needs n_grid >= 3, tol > 0, max_eval >= n_grid", GSL_EINVAL);
+  if (!w) GSL_ERROR("gsl_sinterp_fit_set_search: null workspace", GSL_EFAULT);
+  if (max_eval != w->max_eval) {
+    double *p = (double *)malloc(max_eval * sizeof(double)), *q = (double *)malloc(max_eval * sizeof(double));
+    if (!p || !q) { free(p); free(q); GSL_ERROR("gsl_sinterp_fit_set_search: out of memory", GSL_ENOMEM); }
+    free(w->tr_param); free(w->tr_score);
+    w->tr_param = p; w->tr_score = q; w->n_eval = 0;     /* the trace of the last search goes with its arrays */
+  }
+  w->n_grid = n_grid; w->tol = tol; w->max_eval = max_eval;
+  return GSL_SUCCESS;
+}
+
+size_t gsl_sinterp_fit_n_eval(const gsl_sinterp_fit_workspace *w) { return w ? w->n_eval : 0; }
+
+int gsl_sinterp_fit_trace(const gsl_sinterp_fit_workspace *w, gsl_vector *param, gsl_vector *score)
+{
+  if (!w || !param || !score) GSL_ERROR("gsl_sinterp_fit_trace: null argument", GSL_EFAULT);
+  if (param->size != w->n_eval || score->size != w->n_eval) GSL_ERROR("gsl_sinterp_fit_trace: the vectors need gsl_sinterp_fit_n_eval entries", GSL_EBADLEN);
+  for (size_t i = 0; i < w->n_eval; i++) {
+    param->data[i * param->stride] = w->tr_param[i];
+    score->data[i * score->stride] = w->tr_score[i];
+  }
+  return GSL_SUCCESS;
+}
+
+int gsl_sinterp_fit_sigma2(const gsl_sinterp_fit_workspace *w, double *s2)
+{
+  if (s2) *s2 = GSL_NAN;
+  if (!w || !s2) GSL_ERROR("gsl_sinterp_fit_sigma2: null argument", GSL_EFAULT);
+  if (!w->have_sigma2) GSL_ERROR("gsl_sinterp_fit_sigma2: no evaluation has returned a finite score yet", GSL_EINVAL);
+  *s2 = w->sigma2;
+  return GSL_SUCCESS;
+}
+
 /* whether variances can be evaluated, as a status (the table of include/gsl_sinterp.h) */
 static int variance_status(const gsl_sinterp *interp)
 {

@@ -355,6 +355,59 @@ int gsl_sinterp_eval_variance_resident(const gsl_sinterp *interp, const double *
 int gsl_sinterp_set_loo(gsl_sinterp *interp, int want);
 int gsl_sinterp_loo_residuals(const gsl_sinterp *interp, gsl_matrix *E);
 int gsl_sinterp_loo_variance(const gsl_sinterp *interp, gsl_vector *v);
+/* Model selection: score a shape parameter eps or a nugget on the data, and fit either by a 1-D search.  GSL's workspace
+   idiom: gsl_sinterp_fit_alloc copies the centres and the response to the (first) device and allocates the N x N matrix
+   ONCE; every evaluation then runs the fill, one Cholesky factorisation with the response riding it and a device-side
+   reduction, and copies 32 bytes back.  The types gsl_sinterp_set_loo accepts (Gaussian, Wendland, Matern 3/2 and 5/2,
+   inverse multiquadric, the three kriging types).  The interpolant only names type, dim, size and device: it needs no
+   init, is not changed, and may be freed before the workspace.
+     GSL_SINTERP_FIT_LOO  (1/N) sum e_i^2, e_i the leave-one-out residuals of gsl_sinterp_set_loo (Rippa; Dubrule for
+                          kriging), from the same factor;
+     GSL_SINTERP_FIT_ML   the negative log-likelihood of a Gaussian process with covariance s2 K, concentrated over the
+                          process variance s2 (and, for kriging, over the constant mean mu): with w = K^-1 f (kriging:
+                          K^-1 (f - mu 1), mu the mean the solve returns; 1^T w = 0, so f.w is the quadratic form there too)
+                          and s2 = f.w / N,   score = 0.5 [N log(2 pi s2) + log|K| + N].
+                          K = Phi + nugget I with the nugget relative to a sill of 1, as everywhere else.  Plain maximum
+                          likelihood, NOT restricted likelihood (REML): the estimate of mu costs no degree of freedom.
+   COST of one evaluation: one fill + one factorisation (N^3 / 3 flops) for ML; about two factorisations for LOO (the
+   diagonal of K^-1 is a second N^3 / 3).  Nothing is allocated or freed on the device after fit_alloc, except that the
+   first LOO evaluation allocates the buffers of the diagonal (2048 x N doubles at most).
+   A CANDIDATE THAT DOES NOT FACTOR IS NOT AN ERROR: when K is not numerically positive definite (or a pivot, a
+   leave-one-out diagonal or f.w comes out non-positive or non-finite) *score = +infinity, the return is GSL_SUCCESS and
+   the error handler is not called; a score is never NaN on success.  The handler is called, with *score = NaN, for a
+   NULL argument (GSL_EFAULT), an unknown criterion, eps not finite or <= 0, a nugget that is negative or, for a
+   non-kriging type, not 0 (GSL_EINVAL), and HIP errors.
+   THE SEARCH (fit_shape over eps, fit_nugget over the nugget) works in t = log(parameter) and is fixed, so that results
+   are reproducible: n_grid points equally spaced in t from lo to hi, both included -- the profile need not be unimodal,
+   hence the grid --; then a golden-section search on the two cells around the FIRST smallest grid value (one cell at an
+   end), until the bracket is no wider than tol in t or max_eval evaluations are spent.  The result is the lowest-scoring
+   point ever evaluated (never worse than the grid's best) and *score_best the value fit_score returns there; nothing is
+   evaluated twice.  Defaults n_grid = 9, tol = 1e-2, max_eval = 40 (gsl_sinterp_fit_set_search; GSL_EINVAL for
+   n_grid < 3, tol not > 0, max_eval < n_grid -- checked before the workspace pointer).  GSL_EINVAL: lo <= 0, hi <= lo or
+   not finite; fit_nugget on a non-kriging type (and nugget_lo > 0 is needed: compare nugget 0 through fit_score);
+   GSL_EDOM, outputs NaN: every candidate scored +infinity.  fit_n_eval / fit_trace: the evaluations of the last search
+   in order (param and score need fit_n_eval entries, GSL_EBADLEN otherwise).  fit_sigma2: s2 = f.w / N of the last
+   finite score handed back -- fit_score's, or the best of a search (GSL_EINVAL before there is one); with the model's
+   sill at 1, s2 times gsl_sinterp_eval_variance_* is the prediction variance in the units of f.
+   fit_alloc: GSL_EFAULT (a NULL argument), GSL_EINVAL (another type), GSL_EBADLEN (x not size x dim, f not size long),
+   GSL_EFAILED / GSL_ENOMEM (no device, no memory), each through the handler with NULL returned.
+   A K-field model is fitted on one response, then gsl_sinterp_set_shape + gsl_sinterp_init_fields.  With a device list
+   the first device does all the work.  Not provided: gradients of the criteria, a simultaneous 2-D search (alternate the
+   two entries), anisotropic length scales, REML, the thin-plate types (no shape parameter). */
+#define GSL_SINTERP_FIT_LOO 0   /* mean squared leave-one-out residual, (1/N) sum e_i^2 (Rippa; Dubrule for kriging)    */
+#define GSL_SINTERP_FIT_ML  1   /* negative concentrated log-likelihood, 0.5 [N log(2 pi s2) + log|K| + N], s2 = f.w / N */
+typedef struct gsl_sinterp_fit_workspace gsl_sinterp_fit_workspace;
+gsl_sinterp_fit_workspace *gsl_sinterp_fit_alloc(const gsl_sinterp *interp, const gsl_matrix *x, const gsl_vector *f);
+void   gsl_sinterp_fit_free(gsl_sinterp_fit_workspace *w);
+int    gsl_sinterp_fit_score(gsl_sinterp_fit_workspace *w, int criterion, double eps, double nugget, double *score);
+int    gsl_sinterp_fit_shape(gsl_sinterp_fit_workspace *w, int criterion, double nugget, double eps_lo, double eps_hi,
+                             double *eps_best, double *score_best);
+int    gsl_sinterp_fit_nugget(gsl_sinterp_fit_workspace *w, int criterion, double eps, double nugget_lo, double nugget_hi,
+                              double *nugget_best, double *score_best);
+int    gsl_sinterp_fit_set_search(gsl_sinterp_fit_workspace *w, size_t n_grid, double tol, size_t max_eval);  /* 9, 1e-2, 40 */
+size_t gsl_sinterp_fit_n_eval(const gsl_sinterp_fit_workspace *w);           /* evaluations of the last search */
+int    gsl_sinterp_fit_trace(const gsl_sinterp_fit_workspace *w, gsl_vector *param, gsl_vector *score);  /* in order of evaluation */
+int    gsl_sinterp_fit_sigma2(const gsl_sinterp_fit_workspace *w, double *s2); /* f.w / N of the last successful score */
 int gsl_sinterp_poly(const gsl_sinterp *interp, gsl_vector *c);    /* c_0 .. c_dim of an initialised gsl_sinterp_rbf_tps_affine interpolant */
 int gsl_sinterp_set_solver(gsl_sinterp *interp, int solver);
 int gsl_sinterp_set_rcond(gsl_sinterp *interp, int want);

@@ -93,6 +93,7 @@ void gsl_sinterp_hip_shard_bounds(size_t m_total, int world, int rank, size_t *f
 /* asynchronous copies on the context's stream + pinned host staging for them */
 int gsl_sinterp_hip_h2d_async(gsl_sinterp_hip_ctx *ctx, void *d_dst, const void *h_src, size_t bytes);
 int gsl_sinterp_hip_d2h_async(gsl_sinterp_hip_ctx *ctx, void *h_dst, const void *d_src, size_t bytes);
+int gsl_sinterp_hip_d2d_async(gsl_sinterp_hip_ctx *ctx, void *d_dst, const void *d_src, size_t bytes);   /* both on the context's device */
 int gsl_sinterp_hip_host_alloc(void **h_ptr, size_t bytes);
 void gsl_sinterp_hip_host_free(void *h_ptr);
 /* copy pipe of one context: an upload and a download stream beside the context's stream, so that the chunks of a host
@@ -379,6 +380,21 @@ int gsl_sinterp_hip_chol_inv_diag(gsl_sinterp_hip_ctx *ctx, size_t n, const doub
    GSL_EINVAL: nf > 64, ldw or lde < n with nf > 0; GSL_EFAULT: a NULL pointer (other than d_b) with work to do. */
 int gsl_sinterp_hip_loo_combine(gsl_sinterp_hip_ctx *ctx, size_t n, size_t nf, const double *d_g, const double *d_b,
                                 double denom, const double *d_w, size_t ldw, double *d_e, size_t lde, double *d_v);
+/* The scalars of the model-selection criteria (gsl_sinterp_fit_score).
+   From a Cholesky factor (lower triangle of d_llt, as routes 1 / 7 leave it), the right-hand side d_f, the solved
+   weights d_w and, optionally, g = diag(K^-1) (gsl_sinterp_hip_chol_inv_diag) and kriging's b = K^-1 1, denom = 1^T b:
+     d_out[0] = sum_i 2 log L_ii            (log|K|; a sum of logs, never the log of a product)
+     d_out[1] = sum_i f_i w_i               (the quadratic form: w = K^-1 f, or K^-1 (f - mu 1) with 1^T w = 0)
+     d_out[2] = sum_i (w_i / diag_i)^2      diag_i = g_i, or g_i - b_i^2 / denom when d_b != NULL; 0 when d_g == NULL
+     d_out[3] = number of i with L_ii not > 0 or not finite, or (d_g != NULL) diag_i not > 0 or not finite
+   One launch, asynchronous on the context's stream.  One workgroup: every thread adds its sites in index order, the 1024
+   partial sums are added in a fixed tree; no atomics, so the four numbers are the same bits from run to run.  Nothing is
+   clamped: a bad site enters the sums as computed (log of a non-positive pivot is -inf or NaN) and is counted in
+   d_out[3], which is always a finite count.  d_b is ignored without d_g.  Only the diagonal of d_llt is read.
+   GSL_EINVAL: lda < n; GSL_EFAULT: a NULL context, or a NULL d_llt / d_f / d_w / d_out with n > 0; n == 0 succeeds and
+   writes four zeros (to a non-NULL d_out). */
+int gsl_sinterp_hip_score_reduce(gsl_sinterp_hip_ctx *ctx, size_t n, const double *d_llt, size_t lda, const double *d_f,
+                                 const double *d_w, const double *d_g, const double *d_b, double denom, double *d_out);
 
 /* Level-3 building block of both factorisations, exposed for tests and roofline
    measurement (role of gsl_blas_dgemm / dsyrk, blas/blas.c:1334,1649):
