@@ -95,7 +95,7 @@ class gsl_sinterp(C.Structure):
                 ("shape", C.c_double), ("init_flags", C.c_int), ("rng", C.c_void_p), ("state", C.c_void_p),
                 ("n_devices", C.c_int), ("devices", C.c_int * 64), ("solver", C.c_int), ("want_rcond", C.c_int),
                 ("rcond", C.c_double), ("route", C.c_int), ("nugget", C.c_double), ("want_variance", C.c_int),
-                ("want_loo", C.c_int)]
+                ("want_loo", C.c_int), ("neighbours", C.c_size_t)]
 
 
 _vp, _i, _sz, _d = C.c_void_p, C.c_int, C.c_size_t, C.c_double
@@ -260,6 +260,13 @@ SIGNATURES = {
     "gsl_sinterp_loo_residuals": (_i, [C.POINTER(gsl_sinterp), _pm]),
     "gsl_sinterp_loo_variance": (_i, [C.POINTER(gsl_sinterp), _pv]),
     "gsl_sinterp_hip_d2d_async": (_i, [_vp, _vp, _vp, _sz]),
+    "gsl_sinterp_hip_knn": (_i, [_vp, _vp, _sz, _i, _sz, _vp, _sz, _sz, _sz, _vp, _vp, C.c_uint64]),
+    "gsl_sinterp_hip_local_krige": (_i, [_vp, _i, _d, _d, _vp, _sz, _i, _sz, _vp, _vp, _sz, _sz, _sz, _vp, _vp, _vp,
+                                         C.POINTER(C.c_size_t), C.c_uint64]),
+    "gsl_sinterp_hip_local_pack": (_i, [_vp, _vp, _sz, _i, _sz, _vp, C.c_uint64]),
+    "gsl_sinterp_hip_local_pack_count": (C.c_uint64, [_vp]),
+    "gsl_sinterp_set_neighbours": (_i, [C.POINTER(gsl_sinterp), _sz]),
+    "gsl_sinterp_eval_local_many": (_i, [C.POINTER(gsl_sinterp), _pm, _pv, _pv, _pi]),
     "gsl_sinterp_hip_score_reduce": (_i, [_vp, _sz, _vp, _sz, _vp, _vp, _vp, _vp, _d, _vp]),
     "gsl_sinterp_fit_alloc": (_vp, [C.POINTER(gsl_sinterp), _pm, _pv]),
     "gsl_sinterp_fit_free": (None, [_vp]),
@@ -614,6 +621,25 @@ class HipContext:
     def krige_variance(self, kind, eps, d_x, n, dim, xtda, d_llt, lda, d_b, d_dinv, denom, d_y, m, ytda, d_var, d_work, chunk):
         return lib().gsl_sinterp_hip_krige_variance(self._h, kind, eps, d_x, n, dim, xtda, d_llt, lda, d_b, d_dinv, denom,
                                                     d_y, m, ytda, d_var, d_work, chunk)
+
+    def knn(self, d_x, n, dim, xtda, d_y, m, ytda, k, d_idx, d_r2=None, model_id=0):
+        """d_idx[m x k] = rows of the k nearest centres of every target, ascending (r2, row); d_r2 optional; returns the status"""
+        return lib().gsl_sinterp_hip_knn(self._h, d_x, n, dim, xtda, d_y, m, ytda, k, d_idx, d_r2, model_id)
+
+    def local_krige(self, kind, eps, nugget, d_x, n, dim, xtda, d_f, d_y, m, ytda, k, d_s=None, d_var=None, d_idx=None, model_id=0):
+        """ordinary kriging on the k nearest centres of every target; each output optional; synchronises;
+        returns (status, failed): GSL_EDOM with `failed` targets NaN where a neighbourhood's matrix has a failed pivot"""
+        failed = C.c_size_t(0)
+        st = lib().gsl_sinterp_hip_local_krige(self._h, kind, eps, nugget, d_x, n, dim, xtda, d_f, d_y, m, ytda, k, d_s, d_var, d_idx,
+                                               C.byref(failed), model_id)
+        return st, failed.value
+
+    def local_pack(self, d_x, n, dim, xtda, d_f=None, model_id=0):
+        return lib().gsl_sinterp_hip_local_pack(self._h, d_x, n, dim, xtda, d_f, model_id)
+
+    def local_pack_count(self):
+        """how often this context has binned a set of centres for knn / local_krige"""
+        return lib().gsl_sinterp_hip_local_pack_count(self._h)
 
     @staticmethod
     def chol_inv_diag_work(n, chunk):
@@ -1014,6 +1040,21 @@ class Sinterp:
 
     def eval_variance_resident(self, d_y, m, ytda, d_var):
         return lib().gsl_sinterp_eval_variance_resident(self._p, d_y, m, ytda, d_var)
+
+    def set_neighbours(self, k):
+        """kriging: k > 0 = the next init takes the local route (kriging on the k nearest centres of every target), 0 = global"""
+        return lib().gsl_sinterp_set_neighbours(self._p, int(k))
+
+    def eval_local_many(self, y, want_s=True, want_var=True, want_idx=True):
+        """(status, s, var, idx) of the local route from one pass; an output that is not wanted is None"""
+        m, k = y.shape[0], int(self._p.contents.neighbours)
+        s = np.full(m, np.nan) if want_s else None
+        v = np.full(m, np.nan) if want_var else None
+        idx = np.full((m, max(k, 1)), -1, dtype=np.int32) if want_idx else None
+        st = lib().gsl_sinterp_eval_local_many(self._p, C.byref(as_matrix(y)), C.byref(as_vector(s)) if want_s else None,
+                                               C.byref(as_vector(v)) if want_var else None,
+                                               idx.ctypes.data_as(_pi) if want_idx else None)
+        return st, s, v, idx
 
     def set_loo(self, want=True):
         """positive definite RBF types and kriging: the next init computes the leave-one-out residuals and variances"""

@@ -39,6 +39,14 @@ struct gsl_sinterp_hip_ctx {
   void *d_cent_f;
   size_t cent_f_bytes;
   CentKey cent_key_f;
+  /* local kriging (local.hip): the centres binned on a uniform grid and gathered into cell order as records
+     {x, f, index}, [256 B head | cell offsets | records]; keyed like d_cent (w = the responses), local_g cells per axis;
+     local_packs counts the packs of this context (gsl_sinterp_hip_local_pack_count) */
+  void *d_local;
+  size_t local_bytes;
+  CentKey local_key;
+  int local_g;
+  unsigned long long local_packs;
   void *d_walk;             /* affine walk records + queue of the barycentric walk (bary.hip), rebuilt per batch */
   size_t walk_bytes;
   hipStream_t side_stream;  /* bary.hip: independent kernels of one evaluation run beside the main stream */
@@ -254,5 +262,6 @@ int sinterp_walkbuf(gsl_sinterp_hip_ctx *ctx, size_t bytes, void **out);
 int sinterp_bbox_keys(gsl_sinterp_hip_ctx *ctx, const double *d_p, size_t n, size_t tda, int dim, unsigned long long *d_box);
 int sinterp_centbuf(gsl_sinterp_hip_ctx *ctx, size_t bytes, void **out);
 int sinterp_centbuf_fields(gsl_sinterp_hip_ctx *ctx, size_t bytes, void **out);
+int sinterp_localbuf(gsl_sinterp_hip_ctx *ctx, size_t bytes, void **out);
 
 #endif

@@ -809,6 +809,10 @@ typedef struct {
   int loo_state;
   size_t loo_nf;
   double *loo_e, *loo_v;
+  /* local kriging (gsl_sinterp_set_neighbours, route 11): the neighbour count and nugget of the last init; 0 = the global
+     model.  d_w then holds the RESPONSES: nothing is solved at init, every target solves its own small system */
+  size_t local_k;
+  double local_nugget;
 } rbf_state;
 
 /* rows of the work matrix per pass of gsl_sinterp_hip_chol_inv_diag ("Leave-one-out") */
@@ -818,6 +822,14 @@ static unsigned long long next_model_id(void)
 {
   static unsigned long long counter = 0;               /* the facade is single-threaded like the reference */
   return ++counter;
+}
+
+/* default shape: Gaussian eps = 2 N^(1/d) (the C-configurations); Wendland: support radius of eight mean
+   spacings of a unit box, eps = N^(1/d) / 8; Matern 3/2, 5/2 and inverse multiquadric: eps = N^(1/d), the length scale
+   1/eps equal to the mean spacing */
+static double rbf_default_eps(int kind, size_t n, size_t dim)
+{
+  return (kind == GSL_SINTERP_RBF_WENDLAND ? 0.125 : kind == GSL_SINTERP_RBF_GAUSSIAN ? 2.0 : 1.0) * pow((double)n, 1.0 / (double)dim);
 }
 
 static void *rbf_alloc_kind(int kind, size_t dim, size_t size)
@@ -959,12 +971,9 @@ static int rbf_init_fields(gsl_sinterp *interp, const gsl_matrix *x, const doubl
   if (s) return s;
   st->nf = 0;                                           /* not initialised until the solve succeeds */
   gsl_sinterp_hip_ctx *c = st->ctx;
-  /* default shape: Gaussian eps = 2 N^(1/d) (the C-configurations); Wendland: support radius of eight mean
-     spacings of a unit box, eps = N^(1/d) / 8; Matern 3/2, 5/2 and inverse multiquadric: eps = N^(1/d), the length scale
-     1/eps equal to the mean spacing */
   st->model_id = next_model_id();                       /* the buffers are about to change */
-  st->eps = interp->shape > 0 ? interp->shape
-            : (st->kind == GSL_SINTERP_RBF_WENDLAND ? 0.125 : st->kind == GSL_SINTERP_RBF_GAUSSIAN ? 2.0 : 1.0) * pow((double)n, 1.0 / (double)dim);
+  st->eps = interp->shape > 0 ? interp->shape : rbf_default_eps(st->kind, n, dim);
+  st->local_k = 0;
 
   double *h_x = (double *)malloc(n * dim * sizeof(double));
   double *h_f = (double *)malloc(n * nf * sizeof(double));
@@ -1040,8 +1049,11 @@ static int rbf_init_fields(gsl_sinterp *interp, const gsl_matrix *x, const doubl
   return GSL_SUCCESS;
 }
 
+static int local_init(gsl_sinterp *interp, const gsl_matrix *x, const gsl_vector *f);
+
 static int rbf_init(gsl_sinterp *interp, const gsl_matrix *x, const gsl_vector *f)
 {
+  if (interp->neighbours > 0) return local_init(interp, x, f);
   return rbf_init_fields(interp, x, f->data, f->stride, 0, 1);
 }
 
@@ -1092,6 +1104,9 @@ static int rbf_prepare_devices(gsl_sinterp *interp, rbf_state *st, size_t nf)
   return GSL_SUCCESS;
 }
 
+static int local_eval_resident(const gsl_sinterp *interp, const double *d_y, size_t m, size_t ytda, double *d_s, double *d_var, int *d_idx);
+static int local_eval_many(const gsl_sinterp *interp, const gsl_matrix *y, gsl_vector *sv, gsl_vector *var, int *idx);
+
 /* the sweep of an RBF-type model on context c (plain, + kriging mean, + affine tail) */
 static int rbf_sweep(const rbf_state *st, gsl_sinterp_hip_ctx *c, const double *d_x, const double *d_w, const double *d_y, size_t m,
                      size_t ytda, double *d_s)
@@ -1110,6 +1125,7 @@ static int rbf_eval_resident(const gsl_sinterp *interp, const double *d_y, size_
   (void)d_leaf;
   const rbf_state *st = (const rbf_state *)interp->state;
   if (!st->d_w) GSL_ERROR("gsl_sinterp_eval: interpolant not initialised", GSL_EINVAL);
+  if (st->local_k) return local_eval_resident(interp, d_y, m, ytda, d_s, NULL, NULL);
   /* resident buffers live on ONE device: member 0 evaluates them (shard resident targets yourself with
      gsl_sinterp_hip_shard_bounds + one interpolant per device, as bench.py does per process) */
   HIP_TRY(rbf_sweep(st, st->ctx, st->d_x, st->d_w, d_y, m, ytda, d_s), st->ctx);
@@ -1137,6 +1153,10 @@ static int rbf_eval_many(const gsl_sinterp *interp, const gsl_matrix *y, gsl_vec
   if (!st->d_w) GSL_ERROR("gsl_sinterp_eval_many: interpolant not initialised", GSL_EINVAL);
   const size_t m = y->size1, dim = st->dim;
   if (m == 0) return GSL_SUCCESS;
+  if (st->local_k) {
+    if (leaf) for (size_t k = 0; k < m; k++) leaf[k] = -1;
+    return local_eval_many(interp, y, sv, NULL, NULL);
+  }
   if (st->ss.grp) {
     rbf_state *mst = (rbf_state *)interp->state;         /* staging buffers are grow-only caches inside the state */
     int sst = shard_eval_many(&mst->ss, dim, y, sv, NULL, &rbf_shard_eval, mst, 0, NULL);
@@ -1151,6 +1171,86 @@ static int rbf_eval_many(const gsl_sinterp *interp, const gsl_matrix *y, gsl_vec
     if (leaf) for (size_t k = 0; k < m; k++) leaf[k] = -1;
   }
   return GSL_SUCCESS;
+}
+
+/* ---- local kriging (gsl_sinterp_set_neighbours; DESIGN.md, "Local kriging") ---- */
+/* init with k > 0: centres and responses go to the (first) device and are binned; nothing is factored */
+static int local_init(gsl_sinterp *interp, const gsl_matrix *x, const gsl_vector *f)
+{
+  rbf_state *st = (rbf_state *)interp->state;
+  const size_t n = st->n, dim = st->dim;
+  rbf_release_variance(st);
+  rbf_release_loo(st);
+  int s = rbf_prepare_devices(interp, st, 1);
+  if (s) return s;
+  st->nf = 0; st->local_k = 0;
+  gsl_sinterp_hip_ctx *c = st->ctx;
+  st->model_id = next_model_id();
+  st->eps = interp->shape > 0 ? interp->shape : rbf_default_eps(st->kind, n, dim);
+  double *h = (double *)malloc(n * (dim + 1) * sizeof(double));
+  if (!h) GSL_ERROR("gsl_sinterp_init: out of memory", GSL_ENOMEM);
+  for (size_t i = 0; i < n; i++) {
+    for (size_t cdim = 0; cdim < dim; cdim++) h[i * dim + cdim] = x->data[i * x->tda + cdim];
+    h[n * dim + i] = f->data[i * f->stride];
+  }
+  s = gsl_sinterp_hip_h2d(c, st->d_x, h, n * (dim + 1) * sizeof(double));        /* one buffer: [centres | responses] */
+  if (!s) s = gsl_sinterp_hip_local_pack(c, st->d_x, n, (int)dim, dim, st->d_w, st->model_id);
+  if (!s) s = gsl_sinterp_hip_sync(c);
+  free(h);
+  HIP_TRY(s, c);
+  memset(st->f_mean, 0, sizeof st->f_mean); memset(st->f_poly, 0, sizeof st->f_poly);
+  st->mean = GSL_NAN;                                   /* every neighbourhood estimates its own */
+  interp->rcond = GSL_NAN; interp->route = 11;
+  st->local_k = interp->neighbours; st->local_nugget = interp->nugget;
+  st->nf = 1;
+  return GSL_SUCCESS;
+}
+
+/* value / variance (clamped at 0) / neighbour indices, each optional, from one pass on member 0 */
+static int local_eval_resident(const gsl_sinterp *interp, const double *d_y, size_t m, size_t ytda, double *d_s, double *d_var, int *d_idx)
+{
+  const rbf_state *st = (const rbf_state *)interp->state;
+  if (m == 0) return GSL_SUCCESS;
+  if (!d_y) GSL_ERROR("gsl_sinterp_eval: null argument", GSL_EFAULT);
+  int s = gsl_sinterp_hip_local_krige(st->ctx, st->kind, st->eps, st->local_nugget, st->d_x, st->n, (int)st->dim, st->dim, st->d_w, d_y, m, ytda,
+                                      st->local_k, d_s, d_var, d_idx, NULL, st->model_id);
+  if ((s == GSL_SUCCESS || s == GSL_EDOM) && d_var)     /* rounding residue where sigma^2 = 0; NaN stays NaN */
+    HIP_TRY(gsl_sinterp_hip_krige_variance_clamp(st->ctx, d_var, m), st->ctx);
+  if (s == GSL_EDOM)
+    GSL_ERROR("gsl_sinterp_eval: local kriging: the covariance matrix of a neighbourhood is not positive definite (NaN at those targets)", GSL_EDOM);
+  HIP_TRY(s, st->ctx);
+  return GSL_SUCCESS;
+}
+
+static int local_eval_many(const gsl_sinterp *interp, const gsl_matrix *y, gsl_vector *sv, gsl_vector *var, int *idx)
+{
+  const rbf_state *st = (const rbf_state *)interp->state;
+  gsl_sinterp_hip_ctx *c = st->ctx;
+  const size_t m = y->size1, dim = st->dim, k = st->local_k;
+  if (m == 0) return GSL_SUCCESS;
+  double *h = (double *)malloc(m * dim * sizeof(double)), *d_y = NULL, *d_s = NULL, *d_v = NULL;
+  int *d_i = NULL;
+  if (!h) GSL_ERROR("gsl_sinterp_eval_many: out of memory", GSL_ENOMEM);
+  for (size_t t = 0; t < m; t++)
+    for (size_t a = 0; a < dim; a++) h[t * dim + a] = y->data[t * y->tda + a];
+  int s = gsl_sinterp_hip_malloc(c, (void **)&d_y, m * dim * sizeof(double));
+  if (!s && sv) s = gsl_sinterp_hip_malloc(c, (void **)&d_s, m * sizeof(double));
+  if (!s && var) s = gsl_sinterp_hip_malloc(c, (void **)&d_v, m * sizeof(double));
+  if (!s && idx) s = gsl_sinterp_hip_malloc(c, (void **)&d_i, m * k * sizeof(int));
+  if (!s) s = gsl_sinterp_hip_h2d(c, d_y, h, m * dim * sizeof(double));
+  int es = GSL_SUCCESS;
+  if (!s) {
+    es = local_eval_resident(interp, d_y, m, dim, d_s, d_v, d_i);
+    if (es != GSL_SUCCESS && es != GSL_EDOM) s = es;    /* EDOM: everything has been stored, NaN where a pivot failed */
+  }
+  if (!s && sv) { s = gsl_sinterp_hip_d2h(c, h, d_s, m * sizeof(double)); if (!s) for (size_t t = 0; t < m; t++) gsl_vector_set(sv, t, h[t]); }
+  if (!s && var) { s = gsl_sinterp_hip_d2h(c, h, d_v, m * sizeof(double)); if (!s) for (size_t t = 0; t < m; t++) gsl_vector_set(var, t, h[t]); }
+  if (!s && idx) s = gsl_sinterp_hip_d2h(c, idx, d_i, m * k * sizeof(int));
+  gsl_sinterp_hip_free(c, d_y); gsl_sinterp_hip_free(c, d_s); gsl_sinterp_hip_free(c, d_v); gsl_sinterp_hip_free(c, d_i);
+  free(h);
+  if (s == es) return es;                               /* already reported */
+  HIP_TRY(s, c);
+  return es;
 }
 
 /* ======================================================================== */
@@ -1343,6 +1443,23 @@ static int is_pd_type(const gsl_sinterp_type *T)
   return T == &gauss_type || T == &wendland_type || T == &matern32_type || T == &matern52_type || T == &imq_type || is_krige_type(T);
 }
 
+/* whether the interpolant is on, or will at the next init be on, the local route (route 11): asked by every entry that
+   needs the global model, before anything touches the device */
+static int is_local(const gsl_sinterp *interp)
+{
+  return is_krige_type(interp->type) && (interp->neighbours > 0 || ((const rbf_state *)interp->state)->local_k > 0);
+}
+
+int gsl_sinterp_set_neighbours(gsl_sinterp *interp, size_t k)
+{
+  if (!interp) GSL_ERROR("gsl_sinterp_set_neighbours: null interpolant", GSL_EFAULT);
+  if (!is_krige_type(interp->type)) GSL_ERROR("gsl_sinterp_set_neighbours: kriging interpolants only", GSL_EINVAL);
+  if (k > GSL_SINTERP_MAX_NEIGHBOURS) GSL_ERROR("gsl_sinterp_set_neighbours: at most 64 neighbours", GSL_EINVAL);
+  if (k > interp->size) GSL_ERROR("gsl_sinterp_set_neighbours: more neighbours than centres", GSL_EINVAL);
+  interp->neighbours = k;
+  return GSL_SUCCESS;
+}
+
 gsl_sinterp *gsl_sinterp_alloc(const gsl_sinterp_type *T, size_t dim, size_t size)
 {
   if (!T) GSL_ERROR_NULL("gsl_sinterp_alloc: null type", GSL_EFAULT);
@@ -1442,6 +1559,7 @@ static int loo_status(const gsl_sinterp *interp)
 {
   if (!is_pd_type(interp->type))
     GSL_ERROR("gsl_sinterp_loo: positive definite RBF (Gaussian, Wendland, Matern, inverse multiquadric) and kriging interpolants only", GSL_EINVAL);
+  if (is_local(interp)) GSL_ERROR("gsl_sinterp_loo: local kriging (gsl_sinterp_set_neighbours) takes a route without a Cholesky factor", GSL_EUNSUP);
   const rbf_state *st = (const rbf_state *)interp->state;
   if (!st->d_w || st->nf == 0) GSL_ERROR("gsl_sinterp_loo: interpolant not initialised", GSL_EINVAL);
   if (st->loo_state == 3)
@@ -1728,6 +1846,7 @@ static int variance_status(const gsl_sinterp *interp)
   if (!is_krige_type(interp->type)) GSL_ERROR("gsl_sinterp_eval_variance: kriging interpolants only", GSL_EINVAL);
   const rbf_state *st = (const rbf_state *)interp->state;
   if (!st->d_w) GSL_ERROR("gsl_sinterp_eval_variance: interpolant not initialised", GSL_EINVAL);
+  if (st->local_k) return GSL_SUCCESS;                  /* the local route keeps no factor and needs none */
   if (st->var_state == 3)
     GSL_ERROR("gsl_sinterp_eval_variance: the interpolant was restored by gsl_sinterp_fread; a checkpoint carries no factor", GSL_EINVAL);
   if (st->var_state == 2)
@@ -1745,6 +1864,7 @@ int gsl_sinterp_eval_variance_resident(const gsl_sinterp *interp, const double *
   rbf_state *st = (rbf_state *)interp->state;           /* the workspace is a grow-only cache inside the state */
   if (m == 0) return GSL_SUCCESS;
   if (!d_y || !d_var) GSL_ERROR("gsl_sinterp_eval_variance: null argument", GSL_EFAULT);
+  if (st->local_k) return local_eval_resident(interp, d_y, m, ytda, NULL, d_var, NULL);
   size_t chunk = (m + 63) / 64 * 64;
   if (chunk > 8192) chunk = 8192;
   const size_t need = gsl_sinterp_hip_krige_variance_work(st->n, chunk);
@@ -1770,6 +1890,7 @@ int gsl_sinterp_eval_variance_many(const gsl_sinterp *interp, const gsl_matrix *
   int vs = variance_status(interp);
   if (vs || m == 0) return vs;
   const rbf_state *st = (const rbf_state *)interp->state;
+  if (st->local_k) return local_eval_many(interp, y, NULL, var, NULL);
   gsl_sinterp_hip_ctx *c = st->ctx;
   double *h = (double *)malloc(m * dim * sizeof(double)), *d_y = NULL, *d_v = NULL;
   if (!h) GSL_ERROR("gsl_sinterp_eval_variance_many: out of memory", GSL_ENOMEM);
@@ -1802,11 +1923,26 @@ int gsl_sinterp_eval_variance_e(const gsl_sinterp *interp, const gsl_vector *y, 
   return st;
 }
 
+int gsl_sinterp_eval_local_many(const gsl_sinterp *interp, const gsl_matrix *y, gsl_vector *s, gsl_vector *var, int *idx)
+{
+  if (!interp || !y) GSL_ERROR("gsl_sinterp_eval_local_many: null argument", GSL_EFAULT);
+  if (!is_krige_type(interp->type)) GSL_ERROR("gsl_sinterp_eval_local_many: kriging interpolants only", GSL_EINVAL);
+  const rbf_state *st = (const rbf_state *)interp->state;
+  if (!st->d_w) GSL_ERROR("gsl_sinterp_eval_local_many: interpolant not initialised", GSL_EINVAL);
+  if (!st->local_k) GSL_ERROR("gsl_sinterp_eval_local_many: initialised without gsl_sinterp_set_neighbours", GSL_EINVAL);
+  if (y->size2 != interp->dim) GSL_ERROR("target matrix must have dim columns", GSL_EBADLEN);
+  if ((s && s->size != y->size1) || (var && var->size != y->size1)) GSL_ERROR("output length must equal the number of targets", GSL_EBADLEN);
+  if (!s && !var && !idx) return GSL_SUCCESS;
+  return local_eval_many(interp, y, s, var, idx);
+}
+
 /* ---- value + gradient (RBF family): dispatch on the type here, no slot in gsl_sinterp_type ---- */
 static int grad_status(const gsl_sinterp *interp)
 {
   if (interp->type == &simplex_type || interp->type == &mesh_type)
     GSL_ERROR("gsl_sinterp_eval_grad: RBF-family interpolants only (the piecewise-linear gradient is constant per leaf)", GSL_EUNSUP);
+  if (is_local(interp))
+    GSL_ERROR("gsl_sinterp_eval_grad: not with gsl_sinterp_set_neighbours (the local predictor is discontinuous where the neighbour set changes)", GSL_EUNSUP);
   return GSL_SUCCESS;
 }
 
@@ -1888,6 +2024,7 @@ static int fields_status(const gsl_sinterp *interp)
 {
   if (interp->type == &simplex_type || interp->type == &mesh_type)
     GSL_ERROR("gsl_sinterp fields: RBF-family interpolants only (several responses per leaf of the linear types: a separate entry)", GSL_EUNSUP);
+  if (is_local(interp)) GSL_ERROR("gsl_sinterp fields: not with gsl_sinterp_set_neighbours (local kriging has one field)", GSL_EUNSUP);
   return GSL_SUCCESS;
 }
 
@@ -2047,6 +2184,7 @@ int gsl_sinterp_mean(const gsl_sinterp *interp, double *mean)
 {
   if (!interp || !mean) GSL_ERROR("gsl_sinterp_mean: null argument", GSL_EFAULT);
   if (!is_krige_type(interp->type)) GSL_ERROR("gsl_sinterp_mean: kriging interpolants only", GSL_EINVAL);
+  if (is_local(interp)) GSL_ERROR("gsl_sinterp_mean: not with gsl_sinterp_set_neighbours (every neighbourhood estimates its own mean)", GSL_EUNSUP);
   const rbf_state *st = (const rbf_state *)interp->state;
   if (!st->d_w) GSL_ERROR("gsl_sinterp_mean: interpolant not initialised", GSL_EINVAL);
   *mean = st->mean;
@@ -2167,6 +2305,7 @@ int gsl_sinterp_get_weights(const gsl_sinterp *interp, gsl_vector *w)
 {
   if (!interp || !w) GSL_ERROR("gsl_sinterp_get_weights: null argument", GSL_EFAULT);
   if (interp->type == &simplex_type) GSL_ERROR("gsl_sinterp_get_weights: not an RBF interpolant", GSL_EINVAL);
+  if (is_local(interp)) GSL_ERROR("gsl_sinterp_get_weights: not with gsl_sinterp_set_neighbours (no global weight vector exists)", GSL_EUNSUP);
   const rbf_state *st = (const rbf_state *)interp->state;
   if (!st->d_w) GSL_ERROR("gsl_sinterp_get_weights: interpolant not initialised", GSL_EINVAL);
   if (w->size != st->n) GSL_ERROR("gsl_sinterp_get_weights: wrong length", GSL_EBADLEN);
@@ -2273,6 +2412,7 @@ static int type_id(const gsl_sinterp_type *T)
 int gsl_sinterp_fwrite(FILE *stream, const gsl_sinterp *interp)
 {
   if (!stream || !interp) GSL_ERROR("gsl_sinterp_fwrite: null argument", GSL_EFAULT);
+  if (is_local(interp)) GSL_ERROR("gsl_sinterp_fwrite: not with gsl_sinterp_set_neighbours (checkpoints hold a solved global model)", GSL_EUNSUP);
   const uint64_t head[3] = {(uint64_t)type_id(interp->type), (uint64_t)interp->dim, (uint64_t)interp->size};
   if (interp->type == &simplex_type) {
     const simplex_state *st = (const simplex_state *)interp->state;
@@ -2330,6 +2470,8 @@ int gsl_sinterp_fwrite(FILE *stream, const gsl_sinterp *interp)
 int gsl_sinterp_fread(FILE *stream, gsl_sinterp *interp)
 {
   if (!stream || !interp) GSL_ERROR("gsl_sinterp_fread: null argument", GSL_EFAULT);
+  if (is_krige_type(interp->type) && interp->neighbours > 0)
+    GSL_ERROR("gsl_sinterp_fread: not with gsl_sinterp_set_neighbours (checkpoints hold a solved global model)", GSL_EUNSUP);
   char magic[8];
   uint64_t head[3];
   double eps;
@@ -2393,7 +2535,7 @@ int gsl_sinterp_fread(FILE *stream, gsl_sinterp *interp)
   rbf_release_variance(st);                             /* a factor kept by an earlier init belongs to another model */
   int s = rbf_prepare_devices(interp, st, 1);
   if (s) { free(h); return s; }
-  st->nf = 1;
+  st->nf = 1; st->local_k = 0;
   st->var_state = 3;                                    /* the checkpoint carries no factor */
   rbf_release_loo(st);
   st->loo_state = 3;                                    /* ... and no leave-one-out data */

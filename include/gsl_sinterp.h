@@ -272,6 +272,7 @@ struct gsl_sinterp_struct {
   double nugget;     /* kriging: added to the diagonal of the covariance matrix (>= 0, default 0) */
   int want_variance; /* kriging: the next init keeps the Cholesky factor for gsl_sinterp_eval_variance_* (default 0) */
   int want_loo;      /* positive definite RBF types (Gaussian / Wendland / Matern / inverse multiquadric) and kriging: the next init computes the leave-one-out residuals and variances (default 0) */
+  size_t neighbours; /* kriging: > 0 = local kriging on that many nearest centres per target (gsl_sinterp_set_neighbours); 0 = the global model (default) */
 };
 
 extern const gsl_sinterp_type *gsl_sinterp_rbf_gaussian;
@@ -333,6 +334,30 @@ int gsl_sinterp_set_variance(gsl_sinterp *interp, int want);            /* the t
 int gsl_sinterp_eval_variance_e(const gsl_sinterp *interp, const gsl_vector *y, double *var);
 int gsl_sinterp_eval_variance_many(const gsl_sinterp *interp, const gsl_matrix *y, gsl_vector *var);
 int gsl_sinterp_eval_variance_resident(const gsl_sinterp *interp, const double *d_y, size_t m, size_t ytda, double *d_var);
+/* Local kriging (a moving neighbourhood) for clouds past the size a dense N x N factorisation holds:
+   gsl_sinterp_set_neighbours(interp, k), 1 <= k <= GSL_SINTERP_MAX_NEIGHBOURS = 64, BEFORE gsl_sinterp_init makes the init
+   upload the centres and the responses and bin them on a grid -- nothing is factored, gsl_sinterp_route is 11 -- and every
+   evaluation solve ordinary kriging on the k nearest centres of each target (exact search; ties go to the smaller row of x):
+   memory O(N + M k), work O(M k^3).  eval_e / _many / _resident / _grid return the local predictor; eval_variance_e / _many /
+   _resident the local variance, clamped at 0, WITHOUT gsl_sinterp_set_variance (no factor is kept);
+   gsl_sinterp_eval_local_many returns value, variance and the neighbour rows (idx: m x k ints, nearest first) from one pass,
+   each output may be NULL.  The formulas and the bit-reproducibility contract: gsl_sinterp_hip_local_krige.
+   A target whose neighbourhood has a covariance matrix that is not positive definite (coincident sites without a nugget)
+   gets NaN in value and variance; every other target is stored and the call returns GSL_EDOM (eval_e: by status, as for a
+   target outside the cage of the linear types).  A target with a NaN coordinate gets NaN and is no error.
+   k = 0 (the default) is the global model: init and every bit as without this call.  Shape, nugget and device are honoured
+   as usual; with a device list the first device evaluates every target.  The fit workspace ignores the setting: fit eps and
+   the nugget on a subsample, then predict on the full cloud with this route.
+   set_neighbours: GSL_EINVAL for another type than the three kriging types, k > 64, k > size.  With k > 0 there is no global
+   weight vector, mean or factor: the gradient entries, init_fields, the eval_fields / field entries, get_weights, mean,
+   fwrite / fread and the leave-one-out accessors return GSL_EUNSUP without touching the device.  eval_local_many: GSL_EINVAL
+   when the interpolant was not initialised with k > 0, GSL_EBADLEN for a size mismatch.
+   Not provided: search by radius or by octant, gradients (the predictor jumps where the neighbour set changes), several
+   fields, simple / universal kriging, sharding over a device group, checkpoints, k > 64. */
+#define GSL_SINTERP_MAX_NEIGHBOURS 64
+int gsl_sinterp_set_neighbours(gsl_sinterp *interp, size_t k);
+int gsl_sinterp_eval_local_many(const gsl_sinterp *interp, const gsl_matrix *y, gsl_vector *s /* or NULL */, gsl_vector *var /* or NULL */,
+                                int *idx /* y->size1 x k, or NULL */);
 /* Leave-one-out cross-validation (Rippa's rule for the positive definite RBF types, Dubrule's for ordinary kriging): how
    good the fit is, and a score for a shape parameter or nugget, without N refits.
        e_i = f_i - s^(-i)(x_i)     the residual at site i of the model built without site i,

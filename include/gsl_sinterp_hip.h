@@ -360,6 +360,40 @@ int gsl_sinterp_hip_krige_variance(gsl_sinterp_hip_ctx *ctx, int kind, double ep
 /* d_v[k] < 0 -> 0 for k < m (NaN stays NaN); asynchronous.  The facade's variance entries apply it. */
 int gsl_sinterp_hip_krige_variance_clamp(gsl_sinterp_hip_ctx *ctx, double *d_v, size_t m);
 
+/* Local ordinary kriging (a moving neighbourhood): every target is kriged on its k <= 64 nearest centres alone -- memory
+   O(N + M k), work O(M k^3), no N x N matrix, so N may be far past what a dense factorisation holds.
+   NEIGHBOUR SET: with r2_j = the FMA chain of the sweeps (r2 = 0; d = y_c - x_jc; r2 = fma(d, d, r2), c < dim), S(y) is the k
+   centres smallest under the key (r2_j, j), in ascending key order.  The search is exact (grid cells in growing rings
+   until a lower bound on every unvisited cell exceeds the k-th key), not approximate and not limited to a ring count.  A
+   target with a NaN coordinate has no neighbours: indices -1, r2 / value / variance NaN, and it is not a failure.
+   Infinite coordinates are not specified.
+   gsl_sinterp_hip_knn: d_idx[t * k + i] = the i-th neighbour of target t (original row of d_x), d_r2 (optional) its r2.
+   gsl_sinterp_hip_local_krige: with K_S = [phi(|x_i - x_j|)] + nugget I = L L^T on S in that order, u = L^-1 k_S,
+   v = L^-1 1, g = L^-1 f_S:   d = v.v,  mu = v.g / d,  s = mu + u.(g - mu v),  sigma^2 = phi(0) - u.u + (1 - v.u)^2 / d.
+   Each of d_s, d_var, d_idx may be NULL.  sigma^2 is NOT clamped (gsl_sinterp_hip_krige_variance_clamp).  The result of a
+   target depends on (model, target, k) alone: the same bits from run to run, alone or in a batch of any size, on any
+   context.  FAILED PIVOTS: a target whose K_S has a pivot that is not > 0 (not above 64 u (phi(0) + nugget): the rounding
+   residue of an exactly singular system has either sign) or not finite gets value and variance NaN; every other target is
+   stored as usual, *h_n_failed (optional) receives the count and the return is GSL_EDOM.  local_krige synchronises (the
+   count is its status); knn is asynchronous on the context's stream.
+   The centres are binned once per model into a cell-ordered copy kept in the context, keyed by model_id as in
+   gsl_sinterp_hip_rbf_eval_model (0 = do not cache); gsl_sinterp_hip_local_pack_count counts the packs of a context.
+   GSL_EINVAL: k < 1, k > 64, k > n, dim outside 1 .. 3, xtda / ytda < dim, a kind that is not positive definite, nugget < 0
+   or not finite, eps <= 0 or not finite -- all checked first; then GSL_EFAULT: a NULL context or a NULL required pointer
+   (d_x, d_f; d_y and, for knn, d_idx when m > 0).  Nothing touches the device before these checks. */
+int gsl_sinterp_hip_knn(gsl_sinterp_hip_ctx *ctx, const double *d_x, size_t n, int dim, size_t xtda, const double *d_y, size_t m,
+                        size_t ytda, size_t k, int *d_idx /* m x k, ascending key, -1 = none */, double *d_r2 /* m x k or NULL */,
+                        unsigned long long model_id);
+int gsl_sinterp_hip_local_krige(gsl_sinterp_hip_ctx *ctx, int kind, double eps, double nugget, const double *d_x, size_t n, int dim,
+                                size_t xtda, const double *d_f, const double *d_y, size_t m, size_t ytda, size_t k,
+                                double *d_s /* or NULL */, double *d_var /* or NULL */, int *d_idx /* or NULL */,
+                                size_t *h_n_failed /* or NULL */, unsigned long long model_id);
+/* bin the centres now (what the first knn / local_krige call on a model does anyway); asynchronous.  The copy is keyed by
+   d_f too: pass the responses local_krige will be called with (knn packs with NULL).  Same checks as above. */
+int gsl_sinterp_hip_local_pack(gsl_sinterp_hip_ctx *ctx, const double *d_x, size_t n, int dim, size_t xtda, const double *d_f,
+                               unsigned long long model_id);
+unsigned long long gsl_sinterp_hip_local_pack_count(const gsl_sinterp_hip_ctx *ctx);
+
 /* Leave-one-out from a Cholesky factor K = L L^T (lower triangle of d_llt, as cholesky_decomp1, factor_solve, rbf_solve
    route 1 and krige_solve route 7 leave it): d_g[i] = (K^-1)_ii = |row i of L^-T|^2, i < n, in N^3 / 3 + O(chunk N^2)
    flops (fp64 MFMA GEMM) -- the recursion of the variance entry started from the identity, with the rows taken `chunk`
