@@ -202,6 +202,8 @@ SIGNATURES = {
     "simplex_tree_device_transport": (C.c_char_p, [_vp]),
     # --- part 2b: imported triangulations
     "simplex_mesh_import": (_vp, [_pm, _pi, _pi, _sz]),
+    "simplex_mesh_import_nd": (_vp, [_pm, _sz, _pi, _pi, _sz]),
+    "simplex_mesh_dim": (_sz, [_vp]),
     "simplex_mesh_from_tree": (_vp, [_pt, _pm]),
     "simplex_mesh_free": (None, [_vp]),
     "simplex_mesh_n_triangles": (_sz, [_vp]),
@@ -210,6 +212,8 @@ SIGNATURES = {
     "simplex_mesh_neighbours": (_pi, [_vp]),
     "simplex_mesh_tree_nodes": (_pi, [_vp]),
     "simplex_mesh_geometry": (None, [_vp, _pd, _pd]),
+    "simplex_mesh_bbox": (None, [_vp, _pd, _pd]),
+    "simplex_mesh_points": (_pd, [_vp]),
     "simplex_mesh_set_convex": (None, [_vp, _i]),
     "simplex_mesh_convex": (_i, [_vp]),
     "simplex_mesh_device_alloc": (_vp, [_vp, _i]),
@@ -225,6 +229,9 @@ SIGNATURES = {
     "simplex_mesh_device_ctx": (_vp, [_vp]),
     "gsl_sinterp_hip_mesh_pack": (_i, [_vp, _i, _vp, _vp, _i, _vp, _pd, _i, _vp, _vp]),
     "gsl_sinterp_hip_mesh_eval": (_i, [_vp, _i, _vp, _vp, _vp, _i, _pd, _i, _vp, _sz, _sz, _vp, _vp, C.POINTER(C.c_longlong)]),
+    "gsl_sinterp_hip_mesh3_pack": (_i, [_vp, _i, _vp, _vp, _i, _vp, _pd, _i, _vp, _vp]),
+    "gsl_sinterp_hip_mesh3_bind": (_i, [_vp, _i, _vp, _i, _vp, _vp]),
+    "gsl_sinterp_hip_mesh3_eval": (_i, [_vp, _i, _vp, _vp, _vp, _i, _pd, _i, _vp, _sz, _sz, _vp, _vp, C.POINTER(C.c_longlong)]),
     # --- part 3
     "gsl_sinterp_alloc": (C.POINTER(gsl_sinterp), [_vp, _sz, _sz]),
     "gsl_sinterp_set_device": (_i, [C.POINTER(gsl_sinterp), _i]),
@@ -872,7 +879,8 @@ class DeviceTree:
 
 
 class SimplexMesh:
-    """An imported triangulation (QHull / CGAL style arrays) or the final triangulation of a SimplexTree."""
+    """An imported triangulation (QHull / CGAL style arrays, triangles in 2-D or tetrahedra in 3-D) or the final
+    triangulation of a SimplexTree."""
 
     def __init__(self, handle, keep=None):
         if not handle:
@@ -882,11 +890,16 @@ class SimplexMesh:
 
     @classmethod
     def from_arrays(cls, points, triangles, neighbours=None):
+        """dim = points.shape[1]: 2 -> simplex_mesh_import, anything else -> simplex_mesh_import_nd (3: tetrahedra)"""
         pts = np.ascontiguousarray(points, dtype=np.float64)
-        tri = np.ascontiguousarray(triangles, dtype=np.int32).reshape(-1, 3)
-        nbr = None if neighbours is None else np.ascontiguousarray(neighbours, dtype=np.int32).reshape(-1, 3)
-        h = lib().simplex_mesh_import(C.byref(as_matrix(pts)), tri.ctypes.data_as(_pi),
-                                      nbr.ctypes.data_as(_pi) if nbr is not None else None, len(tri))
+        dim = pts.shape[1]
+        tri = np.ascontiguousarray(triangles, dtype=np.int32).reshape(-1, dim + 1)
+        nbr = None if neighbours is None else np.ascontiguousarray(neighbours, dtype=np.int32).reshape(-1, dim + 1)
+        pn = nbr.ctypes.data_as(_pi) if nbr is not None else None
+        if dim == 2:
+            h = lib().simplex_mesh_import(C.byref(as_matrix(pts)), tri.ctypes.data_as(_pi), pn, len(tri))
+        else:
+            h = lib().simplex_mesh_import_nd(C.byref(as_matrix(pts)), dim, tri.ctypes.data_as(_pi), pn, len(tri))
         return cls(h)
 
     @classmethod
@@ -897,6 +910,9 @@ class SimplexMesh:
     def n_triangles(self):
         return int(lib().simplex_mesh_n_triangles(self._h))
 
+    def dim(self):
+        return int(lib().simplex_mesh_dim(self._h))
+
     def _ints(self, fn, width):
         p = fn(self._h)
         if not p:
@@ -906,18 +922,29 @@ class SimplexMesh:
             np.ctypeslib.as_array(p, shape=(n,)).copy()
 
     def triangles(self):
-        return self._ints(lib().simplex_mesh_triangles, 3)
+        return self._ints(lib().simplex_mesh_triangles, self.dim() + 1)
 
     def neighbours(self):
-        return self._ints(lib().simplex_mesh_neighbours, 3)
+        return self._ints(lib().simplex_mesh_neighbours, self.dim() + 1)
 
     def tree_nodes(self):
         return self._ints(lib().simplex_mesh_tree_nodes, 1)
 
     def geometry(self):
-        sh, sc = (C.c_double * 2)(), (C.c_double * 2)()
+        d = self.dim()
+        sh, sc = (C.c_double * d)(), (C.c_double * d)()
         lib().simplex_mesh_geometry(self._h, sh, sc)
         return np.array(sh[:]), np.array(sc[:])
+
+    def points(self):
+        n, d = int(lib().simplex_mesh_n_points(self._h)), self.dim()
+        return np.ctypeslib.as_array(lib().simplex_mesh_points(self._h), shape=(n * d,)).reshape(n, d).copy()
+
+    def bbox(self):
+        d = self.dim()
+        lo, hi = (C.c_double * d)(), (C.c_double * d)()
+        lib().simplex_mesh_bbox(self._h, lo, hi)
+        return np.array(lo[:]), np.array(hi[:])
 
     def set_convex(self, convex):
         lib().simplex_mesh_set_convex(self._h, int(convex))
@@ -1159,8 +1186,9 @@ class Sinterp:
         return lib().gsl_sinterp_n_devices(self._p)
 
     def set_triangulation(self, triangles, neighbours=None):
-        tri = np.ascontiguousarray(triangles, dtype=np.int32).reshape(-1, 3)
-        nbr = None if neighbours is None else np.ascontiguousarray(neighbours, dtype=np.int32).reshape(-1, 3)
+        w = int(self._p.contents.dim) + 1                  # ids per simplex: triangles in 2-D, tetrahedra in 3-D
+        tri = np.ascontiguousarray(triangles, dtype=np.int32).reshape(-1, w)
+        nbr = None if neighbours is None else np.ascontiguousarray(neighbours, dtype=np.int32).reshape(-1, w)
         return lib().gsl_sinterp_set_triangulation(self._p, tri.ctypes.data_as(_pi), nbr.ctypes.data_as(_pi) if nbr is not None else None,
                                                    len(tri))
 

@@ -472,24 +472,6 @@ __device__ __forceinline__ WalkRec lds_rec(const char *p)
   return u.r;
 }
 
-/* packed & 1: values is an array of {value, leaf} pairs (16 bytes, one store here and ONE gather per target in the
-   un-sort pass instead of two).  packed & 2 (two-level reorder, sort.hip): leaf_out is not a leaf array but the map
-   from the position in cell order to the position in the coarse order, where the result is stored. */
-__device__ __forceinline__ void store_result(double *__restrict__ values, int *__restrict__ leaf_out, size_t k, double v, int leaf,
-                                             int packed)
-{
-  if (packed & 2) {
-    k = reinterpret_cast<const unsigned *>(leaf_out)[k];
-    leaf_out = NULL;
-  }
-  if (packed & 1) {
-    *reinterpret_cast<double2 *>(values + 2 * k) = make_double2(v, __longlong_as_double((long long)leaf));
-  } else {
-    values[k] = v;
-    if (leaf_out) leaf_out[k] = leaf;
-  }
-}
-
 /* exact coordinates in the located leaf, value and leaf stored (linear_simplex.c:678-711) */
 __device__ __forceinline__ void finish_target(const NodeRec *__restrict__ rec, const LeafRec *__restrict__ tab, int node, double y0,
                                               double y1, double s0, double s1, size_t k, double *__restrict__ values,
@@ -1980,8 +1962,6 @@ __global__ void mesh_seed_kernel(int n_tri, const int *__restrict__ tri, int n_p
 }
 
 #define MESH_SEED_RINGS 8
-#define MESH_GAP 1e-9   /* a target within this much (standardised barycentric units) of a triangle that no triangle contains
-                           under the floating-point closed test is given to the least violating triangle */
 __global__ void mesh_seed_fill_kernel(const int *__restrict__ seed_in, int *__restrict__ seed_out, int G)
 {
   const int c = blockIdx.x * blockDim.x + threadIdx.x;

@@ -258,6 +258,27 @@ int sinterp_sortbuf2(gsl_sinterp_hip_ctx *ctx, size_t bytes, void **out);
 /* exclusive scan of count[0..n) in place, total in count[n]; runsum: n/1024 + 2 entries of scratch (sort.hip) */
 void sinterp_scan_u32(gsl_sinterp_hip_ctx *ctx, unsigned *count, size_t n, unsigned *runsum);
 int sinterp_walkbuf(gsl_sinterp_hip_ctx *ctx, size_t bytes, void **out);
+
+#define MESH_GAP 1e-9   /* imported meshes (bary.hip, mesh3.hip): a target within this much (standardised barycentric units) of a
+                           simplex that no simplex contains under the floating-point closed test is given to the least violating one */
+
+/* packed & 1: values is an array of {value, leaf} pairs (16 bytes, one store here and ONE gather per target in the
+   un-sort pass instead of two).  packed & 2 (two-level reorder, sort.hip): leaf_out is not a leaf array but the map
+   from the position in cell order to the position in the coarse order, where the result is stored. */
+__device__ __forceinline__ void store_result(double *__restrict__ values, int *__restrict__ leaf_out, size_t k, double v, int leaf,
+                                             int packed)
+{
+  if (packed & 2) {
+    k = reinterpret_cast<const unsigned *>(leaf_out)[k];
+    leaf_out = NULL;
+  }
+  if (packed & 1) {
+    *reinterpret_cast<double2 *>(values + 2 * k) = make_double2(v, __longlong_as_double((long long)leaf));
+  } else {
+    values[k] = v;
+    if (leaf_out) leaf_out[k] = leaf;
+  }
+}
 /* sort.hip: bounding box of n points as order-preserving keys, box[2c] = min, box[2c+1] = max (device, 48 bytes) */
 int sinterp_bbox_keys(gsl_sinterp_hip_ctx *ctx, const double *d_p, size_t n, size_t tda, int dim, unsigned long long *d_box);
 int sinterp_centbuf(gsl_sinterp_hip_ctx *ctx, size_t bytes, void **out);

@@ -609,7 +609,8 @@ int simplex_tree_check_device(simplex_tree *tree, gsl_matrix *data, int device, 
 struct simplex_mesh_device {
   gsl_sinterp_hip_ctx *ctx;        /* member 0 */
   int n_tri, n_points, G, convex, n_members;
-  double geom[8];                  /* shift, scale, bounding box */
+  int dim;                         /* 2: triangles (bary.hip), 3: tetrahedra (mesh3.hip) */
+  double geom[12];                 /* shift, scale, bounding box lo, hi: dim entries each */
   void *m_records[SINTERP_MAX_DEVICES], *m_leaftab[SINTERP_MAX_DEVICES];
   int *m_tri[SINTERP_MAX_DEVICES], *m_seed[SINTERP_MAX_DEVICES];
   shard_set ss;                    /* n_members > 1: ss.grp owns the contexts */
@@ -646,12 +647,20 @@ simplex_mesh_device *simplex_mesh_device_alloc_multi(const simplex_mesh *mesh, c
   simplex_mesh_device *dev = (simplex_mesh_device *)calloc(1, sizeof *dev);
   if (!dev) GSL_ERROR_NULL("simplex_mesh_device_alloc: out of memory", GSL_ENOMEM);
   const size_t nt = simplex_mesh_n_triangles(mesh), np = simplex_mesh_n_points(mesh);
+  const size_t d = simplex_mesh_dim(mesh), w = d + 1;
   dev->n_tri = (int)nt; dev->n_points = (int)np; dev->convex = simplex_mesh_convex(mesh); dev->n_members = n_devices;
-  /* about two triangles per seed cell */
-  int G = (int)ceil(sqrt((double)nt / 2.0));
-  dev->G = G < 1 ? 1 : (G > 2048 ? 2048 : G);
-  simplex_mesh_geometry(mesh, dev->geom, dev->geom + 2);
-  simplex_mesh_bbox(mesh, dev->geom + 4, dev->geom + 6);
+  dev->dim = (int)d;
+  if (d == 2) {
+    /* about two triangles per seed cell */
+    int G = (int)ceil(sqrt((double)nt / 2.0));
+    dev->G = G < 1 ? 1 : (G > 2048 ? 2048 : G);
+  } else {
+    /* about four tetrahedra per seed cell; the cap keeps the two G^3 tables at 2 x 160^3 x 4 bytes = 33 MB */
+    int G = (int)ceil(cbrt((double)nt / 4.0));
+    dev->G = G < 1 ? 1 : (G > GSL_SINTERP_MESH3_MAX_GRID ? GSL_SINTERP_MESH3_MAX_GRID : G);
+  }
+  simplex_mesh_geometry(mesh, dev->geom, dev->geom + d);
+  simplex_mesh_bbox(mesh, dev->geom + 2 * d, dev->geom + 3 * d);
   if (n_devices > 1) {
     if (gsl_sinterp_hip_group_create(&dev->ss.grp, devices, n_devices) != GSL_SUCCESS) {
       free(dev);
@@ -663,7 +672,10 @@ simplex_mesh_device *simplex_mesh_device_alloc_multi(const simplex_mesh *mesh, c
     free(dev);
     GSL_ERROR_NULL("simplex_mesh_device_alloc: no usable HIP device (GPU path has no CPU fallback)", GSL_EFAILED);
   }
-  const size_t tb = 3 * nt * sizeof(int), pb = 2 * np * sizeof(double);
+  const size_t tb = w * nt * sizeof(int), pb = d * np * sizeof(double);
+  const size_t rec_bytes = d == 2 ? GSL_SINTERP_TREE_RECORD_BYTES : GSL_SINTERP_MESH3_RECORD_BYTES;
+  const size_t tab_bytes = d == 2 ? GSL_SINTERP_TREE_LEAFTAB_BYTES : GSL_SINTERP_MESH3_TABLE_BYTES;
+  const size_t seed_ints = d == 2 ? 2 * (size_t)dev->G * dev->G : 2 * (size_t)dev->G * dev->G * dev->G + 2;
   int *d_nbr[SINTERP_MAX_DEVICES] = {0};
   double *d_pts[SINTERP_MAX_DEVICES] = {0};
   int st = GSL_SUCCESS;
@@ -672,9 +684,9 @@ simplex_mesh_device *simplex_mesh_device_alloc_multi(const simplex_mesh *mesh, c
     st = gsl_sinterp_hip_malloc(c, (void **)&dev->m_tri[r], tb);
     if (!st) st = gsl_sinterp_hip_malloc(c, (void **)&d_nbr[r], tb);
     if (!st) st = gsl_sinterp_hip_malloc(c, (void **)&d_pts[r], pb);
-    if (!st) st = gsl_sinterp_hip_malloc(c, &dev->m_records[r], nt * GSL_SINTERP_TREE_RECORD_BYTES);
-    if (!st) st = gsl_sinterp_hip_malloc(c, &dev->m_leaftab[r], nt * GSL_SINTERP_TREE_LEAFTAB_BYTES);
-    if (!st) st = gsl_sinterp_hip_malloc(c, (void **)&dev->m_seed[r], 2 * (size_t)dev->G * dev->G * sizeof(int));
+    if (!st) st = gsl_sinterp_hip_malloc(c, &dev->m_records[r], nt * rec_bytes);
+    if (!st) st = gsl_sinterp_hip_malloc(c, &dev->m_leaftab[r], nt * tab_bytes);
+    if (!st) st = gsl_sinterp_hip_malloc(c, (void **)&dev->m_seed[r], seed_ints * sizeof(int));
   }
   if (!st) st = gsl_sinterp_hip_h2d(dev->ctx, dev->m_tri[0], simplex_mesh_triangles(mesh), tb);
   if (!st) st = gsl_sinterp_hip_h2d(dev->ctx, d_nbr[0], simplex_mesh_neighbours(mesh), tb);
@@ -685,8 +697,9 @@ simplex_mesh_device *simplex_mesh_device_alloc_multi(const simplex_mesh *mesh, c
     if (!st) st = gsl_sinterp_hip_group_broadcast(dev->ss.grp, (void *const *)d_pts, pb);
   }
   for (int r = 0; r < n_devices && !st; r++)            /* every member packs its own records and seed grid */
-    st = gsl_sinterp_hip_mesh_pack(mesh_member_ctx(dev, r), dev->n_tri, dev->m_tri[r], d_nbr[r], dev->n_points, d_pts[r], dev->geom, dev->G,
-                                   dev->m_records[r], dev->m_seed[r]);
+    st = (d == 2 ? gsl_sinterp_hip_mesh_pack : gsl_sinterp_hip_mesh3_pack)(mesh_member_ctx(dev, r), dev->n_tri, dev->m_tri[r], d_nbr[r],
+                                                                           dev->n_points, d_pts[r], dev->geom, dev->G, dev->m_records[r],
+                                                                           dev->m_seed[r]);
   for (int r = 0; r < n_devices; r++) {
     gsl_sinterp_hip_ctx *c = mesh_member_ctx(dev, r);
     int s2 = gsl_sinterp_hip_sync(c);
@@ -719,7 +732,8 @@ int simplex_mesh_device_set_response(simplex_mesh_device *dev, const gsl_vector 
   if (!st) st = gsl_sinterp_hip_h2d(dev->ctx, d_r[0], h, rb);
   if (!st && dev->ss.grp) st = gsl_sinterp_hip_group_broadcast(dev->ss.grp, (void *const *)d_r, rb);
   for (int r = 0; r < dev->n_members && !st; r++)
-    st = gsl_sinterp_hip_tree_bind(mesh_member_ctx(dev, r), dev->n_tri, dev->m_tri[r], dev->n_points, d_r[r], dev->m_leaftab[r]);
+    st = (dev->dim == 2 ? gsl_sinterp_hip_tree_bind : gsl_sinterp_hip_mesh3_bind)(mesh_member_ctx(dev, r), dev->n_tri, dev->m_tri[r],
+                                                                                  dev->n_points, d_r[r], dev->m_leaftab[r]);
   for (int r = 0; r < dev->n_members; r++) {
     gsl_sinterp_hip_ctx *c = mesh_member_ctx(dev, r);
     int s2 = gsl_sinterp_hip_sync(c);
@@ -738,8 +752,10 @@ int simplex_mesh_device_eval_resident(simplex_mesh_device *dev, const double *d_
   if (!dev) GSL_ERROR("simplex_mesh_device_eval_resident: null device mirror", GSL_EFAULT);
   if (!dev->response_bound) GSL_ERROR("simplex_mesh_device_eval_resident: no response bound", GSL_EINVAL);
   /* resident buffers live on ONE device: member 0 evaluates them */
-  int st = gsl_sinterp_hip_mesh_eval(dev->ctx, dev->n_tri, dev->m_records[0], dev->m_leaftab[0], dev->m_seed[0], dev->G, dev->geom, dev->convex,
-                                     d_targets, m, ttda, d_values, d_triangle, NULL);
+  if (ttda < (size_t)dev->dim) GSL_ERROR("simplex_mesh_device_eval_resident: target rows shorter than the mesh's dimension", GSL_EBADLEN);
+  int st = (dev->dim == 2 ? gsl_sinterp_hip_mesh_eval : gsl_sinterp_hip_mesh3_eval)(dev->ctx, dev->n_tri, dev->m_records[0], dev->m_leaftab[0],
+                                                                                    dev->m_seed[0], dev->G, dev->geom, dev->convex, d_targets,
+                                                                                    m, ttda, d_values, d_triangle, NULL);
   if (st) GSL_ERROR(gsl_sinterp_hip_last_error(dev->ctx), st);
   return GSL_SUCCESS;
 }
@@ -747,8 +763,10 @@ int simplex_mesh_device_eval_resident(simplex_mesh_device *dev, const double *d_
 static int mesh_shard_eval(void *state, int member, const double *d_y, size_t m, double *d_s, int *d_leaf)
 {
   simplex_mesh_device *dev = (simplex_mesh_device *)state;
-  return gsl_sinterp_hip_mesh_eval(mesh_member_ctx(dev, member), dev->n_tri, dev->m_records[member], dev->m_leaftab[member], dev->m_seed[member],
-                                   dev->G, dev->geom, dev->convex, d_y, m, 2, d_s, d_leaf, (long long *)NULL);
+  return (dev->dim == 2 ? gsl_sinterp_hip_mesh_eval : gsl_sinterp_hip_mesh3_eval)(mesh_member_ctx(dev, member), dev->n_tri, dev->m_records[member],
+                                                                                  dev->m_leaftab[member], dev->m_seed[member], dev->G, dev->geom,
+                                                                                  dev->convex, d_y, m, (size_t)dev->dim, d_s, d_leaf,
+                                                                                  (long long *)NULL);
 }
 static int mesh_chunk_eval(void *state, const double *d_y, size_t m, double *d_s, int *d_leaf) { return mesh_shard_eval(state, 0, d_y, m, d_s, d_leaf); }
 
@@ -756,13 +774,16 @@ int simplex_mesh_device_eval_many(simplex_mesh_device *dev, const gsl_matrix *ta
 {
   if (!dev || !targets || !values) GSL_ERROR("simplex_mesh_device_eval_many: null argument", GSL_EFAULT);
   if (!dev->response_bound) GSL_ERROR("simplex_mesh_device_eval_many: no response bound", GSL_EINVAL);
-  if (targets->size2 != 2) GSL_ERROR("simplex_mesh_device_eval_many: targets must be M x 2", GSL_EBADLEN);
-  const size_t m = targets->size1;
+  if (targets->size2 != (size_t)dev->dim) {
+    if (dev->dim == 2) GSL_ERROR("simplex_mesh_device_eval_many: targets must be M x 2", GSL_EBADLEN);
+    GSL_ERROR("simplex_mesh_device_eval_many: targets must be M x 3 (tetrahedral mesh)", GSL_EBADLEN);
+  }
+  const size_t m = targets->size1, d = (size_t)dev->dim;
   if (values->size != m) GSL_ERROR("simplex_mesh_device_eval_many: values length must equal target rows", GSL_EBADLEN);
   if (m == 0) return GSL_SUCCESS;
   size_t outside_n = 0;
-  int st = dev->ss.grp ? shard_eval_many(&dev->ss, 2, targets, values, triangle, &mesh_shard_eval, dev, 1, &outside_n)
-                       : chunk_eval_many(&dev->cs, dev->ctx, 2, targets, values, triangle, &mesh_chunk_eval, dev, 1, &outside_n);
+  int st = dev->ss.grp ? shard_eval_many(&dev->ss, d, targets, values, triangle, &mesh_shard_eval, dev, 1, &outside_n)
+                       : chunk_eval_many(&dev->cs, dev->ctx, d, targets, values, triangle, &mesh_chunk_eval, dev, 1, &outside_n);
   if (st != GSL_SUCCESS) GSL_ERROR("simplex_mesh_device_eval_many: evaluation failed", st);
   if (outside_n) GSL_ERROR("simplex_mesh_device_eval_many: target(s) outside the triangulation", GSL_EDOM);
   return GSL_SUCCESS;
@@ -1335,8 +1356,8 @@ static int simplex_eval_resident(const gsl_sinterp *interp, const double *d_y, s
 /* imported triangulation type (README:28-31: QHull / CGAL meshes)           */
 /* ======================================================================== */
 typedef struct {
-  size_t n;
-  int *tri, *nbr;            /* the caller's triangulation (gsl_sinterp_set_triangulation), copied */
+  size_t n, dim;             /* dim = 2 (triangles) or 3 (tetrahedra) */
+  int *tri, *nbr;            /* the caller's triangulation (gsl_sinterp_set_triangulation), copied: [(dim + 1) n_tri] */
   size_t n_tri;
   simplex_mesh *mesh;
   simplex_mesh_device *dev;
@@ -1346,9 +1367,9 @@ typedef struct {
 
 static void *mesh_type_alloc(size_t dim, size_t size)
 {
-  if (dim != 2) return NULL;
+  if (dim != 2 && dim != 3) return NULL;
   mesh_state *st = (mesh_state *)calloc(1, sizeof *st);
-  if (st) st->n = size;
+  if (st) { st->n = size; st->dim = dim; }
   return st;
 }
 
@@ -1377,18 +1398,18 @@ static int mesh_type_init(gsl_sinterp *interp, const gsl_matrix *x, const gsl_ve
 {
   mesh_state *st = (mesh_state *)interp->state;
   if (!st->tri) GSL_ERROR("gsl_sinterp_init: no triangulation set (gsl_sinterp_set_triangulation)", GSL_EINVAL);
+  if (st->n < st->dim + 1) GSL_ERROR("gsl_sinterp_init: an imported triangulation needs at least dim + 1 points", GSL_EINVAL);
   simplex_mesh_device_free(st->dev); st->dev = NULL;
   simplex_mesh_free(st->mesh); st->mesh = NULL;
   gsl_matrix_free(st->x); gsl_vector_free(st->f);
-  st->x = gsl_matrix_alloc(st->n, 2);
+  st->x = gsl_matrix_alloc(st->n, st->dim);
   st->f = gsl_vector_alloc(st->n);
   if (!st->x || !st->f) return GSL_ENOMEM;
   for (size_t i = 0; i < st->n; i++) {
-    gsl_matrix_set(st->x, i, 0, x->data[i * x->tda]);
-    gsl_matrix_set(st->x, i, 1, x->data[i * x->tda + 1]);
+    for (size_t j = 0; j < st->dim; j++) gsl_matrix_set(st->x, i, j, x->data[i * x->tda + j]);
     gsl_vector_set(st->f, i, gsl_vector_get(f, i));
   }
-  st->mesh = simplex_mesh_import(st->x, st->tri, st->nbr, st->n_tri);
+  st->mesh = simplex_mesh_import_nd(st->x, st->dim, st->tri, st->nbr, st->n_tri);
   if (!st->mesh) return GSL_EINVAL;
   return mesh_type_mirror(interp, st);
 }
@@ -2230,12 +2251,13 @@ int gsl_sinterp_set_triangulation(gsl_sinterp *interp, const int *triangles, con
 {
   if (!interp || !triangles) GSL_ERROR("gsl_sinterp_set_triangulation: null argument", GSL_EFAULT);
   if (interp->type != &mesh_type) GSL_ERROR("gsl_sinterp_set_triangulation: imported-triangulation interpolants only", GSL_EINVAL);
-  if (n_triangles < 1 || n_triangles > (size_t)INT_MAX / 3) GSL_ERROR("gsl_sinterp_set_triangulation: bad triangle count", GSL_EINVAL);
   mesh_state *st = (mesh_state *)interp->state;
-  int *t = (int *)malloc(3 * n_triangles * sizeof(int)), *nb = neighbours ? (int *)malloc(3 * n_triangles * sizeof(int)) : NULL;
+  const size_t w = st->dim + 1;                          /* ids per simplex */
+  if (n_triangles < 1 || n_triangles > (size_t)INT_MAX / w) GSL_ERROR("gsl_sinterp_set_triangulation: bad triangle count", GSL_EINVAL);
+  int *t = (int *)malloc(w * n_triangles * sizeof(int)), *nb = neighbours ? (int *)malloc(w * n_triangles * sizeof(int)) : NULL;
   if (!t || (neighbours && !nb)) { free(t); free(nb); GSL_ERROR("gsl_sinterp_set_triangulation: out of memory", GSL_ENOMEM); }
-  memcpy(t, triangles, 3 * n_triangles * sizeof(int));
-  if (nb) memcpy(nb, neighbours, 3 * n_triangles * sizeof(int));
+  memcpy(t, triangles, w * n_triangles * sizeof(int));
+  if (nb) memcpy(nb, neighbours, w * n_triangles * sizeof(int));
   free(st->tri); free(st->nbr);
   st->tri = t; st->nbr = nb; st->n_tri = n_triangles;
   return GSL_SUCCESS;
@@ -2507,8 +2529,11 @@ int gsl_sinterp_fread(FILE *stream, gsl_sinterp *interp)
     mesh_state *st = (mesh_state *)interp->state;
     simplex_mesh *mesh = simplex_mesh_fread(stream);
     if (!mesh) return GSL_EFAILED;
-    if (simplex_mesh_n_points(mesh) != st->n) { simplex_mesh_free(mesh); GSL_ERROR("gsl_sinterp_fread: mesh / size mismatch", GSL_EBADLEN); }
-    gsl_matrix *x = gsl_matrix_alloc(st->n, 2);
+    if (simplex_mesh_n_points(mesh) != st->n || simplex_mesh_dim(mesh) != st->dim) {
+      simplex_mesh_free(mesh);
+      GSL_ERROR("gsl_sinterp_fread: mesh / size mismatch", GSL_EBADLEN);
+    }
+    gsl_matrix *x = gsl_matrix_alloc(st->n, st->dim);
     gsl_vector *f = gsl_vector_alloc(st->n);
     int ok = x && f;
     for (size_t i = 0; ok && i < st->n; i++) {
@@ -2516,7 +2541,7 @@ int gsl_sinterp_fread(FILE *stream, gsl_sinterp *interp)
       ok = fread(&fi, sizeof fi, 1, stream) == 1;
       if (ok) {
         gsl_vector_set(f, i, fi);
-        gsl_matrix_set(x, i, 0, simplex_mesh_points(mesh)[2 * i]); gsl_matrix_set(x, i, 1, simplex_mesh_points(mesh)[2 * i + 1]);
+        for (size_t j = 0; j < st->dim; j++) gsl_matrix_set(x, i, j, simplex_mesh_points(mesh)[st->dim * i + j]);
       }
     }
     if (!ok) { simplex_mesh_free(mesh); gsl_matrix_free(x); gsl_vector_free(f); GSL_ERROR("fread failed", GSL_EFAILED); }

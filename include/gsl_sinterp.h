@@ -203,25 +203,40 @@ int simplex_tree_check_device(simplex_tree *tree, gsl_matrix *data, int device, 
 typedef struct simplex_mesh simplex_mesh;
 typedef struct simplex_mesh_device simplex_mesh_device;
 simplex_mesh *simplex_mesh_import(const gsl_matrix *points, const int *triangles, const int *neighbours, size_t n_triangles);
+/* The same import in dim = 2 or 3.  dim = 2 is simplex_mesh_import (same mesh, same checkpoint bytes).  dim = 3: a
+   tetrahedralisation in the same array form, `simplices` [4 n], `neighbours` [4 n] = the tetrahedron across the FACE opposite
+   vertex k, -1 on the hull, or NULL (derived by face matching; a face shared by three tetrahedra is GSL_EINVAL).  Checked
+   like the 2-D import: ids in range, no repeated vertex, no tetrahedron its own neighbour, links mutual across the same
+   face.  Evaluated by csrc/hip/mesh3.hip (grid seed + walk over the face links; flat tetrahedra, which QHull returns for
+   cospherical input, never contain a target).  Any other dim: GSL_EUNIMPL; points->size2 < dim or fewer than dim + 1
+   points: GSL_EINVAL.  simplex_mesh_from_tree stays 2-D, and simplex_mesh_tree_nodes is NULL for a 3-D mesh. */
+simplex_mesh *simplex_mesh_import_nd(const gsl_matrix *points, size_t dim, const int *simplices, const int *neighbours, size_t n_simplices);
 /* the final triangulation of a built tree: its leaves without cage vertices, vertex order, neighbour links and
    standardisation kept, so that evaluation returns the bits of the DAG path wherever the containing leaf is unique */
 simplex_mesh *simplex_mesh_from_tree(simplex_tree *tree, gsl_matrix *data);
 void simplex_mesh_free(simplex_mesh *mesh);
-size_t simplex_mesh_n_triangles(const simplex_mesh *mesh);
+size_t simplex_mesh_dim(const simplex_mesh *mesh);             /* 2 or 3 */
+size_t simplex_mesh_n_triangles(const simplex_mesh *mesh);     /* number of simplices: triangles (dim 2), tetrahedra (dim 3) */
 size_t simplex_mesh_n_points(const simplex_mesh *mesh);
-const int *simplex_mesh_triangles(const simplex_mesh *mesh);   /* [3 n] */
-const int *simplex_mesh_neighbours(const simplex_mesh *mesh);  /* [3 n] */
+const int *simplex_mesh_triangles(const simplex_mesh *mesh);   /* [(dim + 1) n] */
+const int *simplex_mesh_neighbours(const simplex_mesh *mesh);  /* [(dim + 1) n] */
 const int *simplex_mesh_tree_nodes(const simplex_mesh *mesh);  /* [n] DAG node of every triangle (from_tree), else NULL */
-void simplex_mesh_geometry(const simplex_mesh *mesh, double shift[2], double scale[2]);
+/* shift = centre of the points' bounding box, scale = 1 / extent per axis (1 for a zero extent); dim entries are written
+   to each array: 2 for a 2-D mesh, as before, 3 for a 3-D one */
+void simplex_mesh_geometry(const simplex_mesh *mesh, double *shift, double *scale);
 /* convex = 1: a boundary edge in the walking direction proves the target outside (index -1, NaN, GSL_EDOM); 0: such walks
    are resolved by an exhaustive scan (meshes with holes / concave outlines).  simplex_mesh_import decides it from the
    boundary (one closed loop without a reflex turn = convex), simplex_mesh_from_tree exports convex = 1 (the hull of a
-   Delaunay triangulation); simplex_mesh_set_convex overrides, simplex_mesh_convex reads the current setting. */
+   Delaunay triangulation); simplex_mesh_set_convex overrides, simplex_mesh_convex reads the current setting.
+   3-D: decided from the boundary faces -- every boundary edge in exactly two of them, one connected surface, and across
+   every boundary edge the far vertex of the adjacent face on or behind this face's plane (relative tolerance 1e-12);
+   any doubt (a cavity, a dent, a flat boundary tetrahedron whose face cannot be oriented) answers 0. */
 void simplex_mesh_set_convex(simplex_mesh *mesh, int convex);
 int simplex_mesh_convex(const simplex_mesh *mesh);
-const double *simplex_mesh_points(const simplex_mesh *mesh);    /* [2 n_points], packed rows */
-void simplex_mesh_bbox(const simplex_mesh *mesh, double lo[2], double hi[2]);
-/* binary checkpoint of a mesh (gsl_matrix_fwrite conventions); fread re-validates ids and neighbour links */
+const double *simplex_mesh_points(const simplex_mesh *mesh);    /* [dim n_points], packed rows */
+void simplex_mesh_bbox(const simplex_mesh *mesh, double *lo, double *hi);   /* dim entries each */
+/* binary checkpoint of a mesh (gsl_matrix_fwrite conventions); fread re-validates ids and neighbour links.  A 2-D mesh
+   writes the GSLSMSH1 layout; a 3-D mesh writes GSLSMSH2, whose header carries dim; fread accepts both */
 int simplex_mesh_fwrite(FILE *stream, const simplex_mesh *mesh);
 simplex_mesh *simplex_mesh_fread(FILE *stream);
 simplex_mesh_device *simplex_mesh_device_alloc(const simplex_mesh *mesh, int device);
@@ -231,6 +246,7 @@ simplex_mesh_device *simplex_mesh_device_alloc_multi(const simplex_mesh *mesh, c
 int simplex_mesh_device_n_devices(const simplex_mesh_device *dev);
 void simplex_mesh_device_free(simplex_mesh_device *dev);
 int simplex_mesh_device_set_response(simplex_mesh_device *dev, const gsl_vector *response);
+/* targets: M x dim of the mesh (GSL_EBADLEN otherwise); eval_resident: ttda >= dim */
 int simplex_mesh_device_eval_many(simplex_mesh_device *dev, const gsl_matrix *targets, gsl_vector *values, int *triangle);
 int simplex_mesh_device_eval_resident(simplex_mesh_device *dev, const double *d_targets, size_t m, size_t ttda,
                                       double *d_values, int *d_triangle);
@@ -439,8 +455,8 @@ int gsl_sinterp_set_rcond(gsl_sinterp *interp, int want);
 int gsl_sinterp_rcond(const gsl_sinterp *interp, double *rcond);
 int gsl_sinterp_route(const gsl_sinterp *interp);
 int gsl_sinterp_set_tree_options(gsl_sinterp *interp, int init_flags, gsl_rng *rng);
-/* gsl_sinterp_linear_mesh: triangles [3 n] (vertex = row of x), neighbours [3 n] (opposite vertex k, -1 = boundary) or NULL
-   (derived by edge matching); copied, validated by the next gsl_sinterp_init */
+/* gsl_sinterp_linear_mesh (dim 2 or 3): simplices [(dim + 1) n] (vertex = row of x), neighbours [(dim + 1) n] (opposite vertex k,
+   -1 = boundary) or NULL (derived by edge / face matching); copied, validated by the next gsl_sinterp_init */
 int gsl_sinterp_set_triangulation(gsl_sinterp *interp, const int *triangles, const int *neighbours, size_t n_triangles);
 int gsl_sinterp_init(gsl_sinterp *interp, const gsl_matrix *x, const gsl_vector *f);
 const char *gsl_sinterp_name(const gsl_sinterp *interp);

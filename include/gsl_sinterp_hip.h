@@ -147,6 +147,27 @@ int gsl_sinterp_hip_mesh_eval(gsl_sinterp_hip_ctx *ctx, int n_tri, const void *d
                               const int *d_seed, int G, const double *h_geom, int convex, const double *d_targets,
                               size_t m, size_t ttda, double *d_values, int *d_tri, long long *h_n_outside);
 
+/* Imported tetrahedral mesh (csrc/hip/mesh3.hip): the same route one dimension up.  One 128-byte, 128-byte-aligned
+   record per tetrahedron (standardised last vertex, inverse of the standardised 3x3 edge matrix, four neighbour ids, a
+   meta word whose bit 0 marks a flat tetrahedron) and a 32-byte table of the four vertex responses.
+   d_tet / d_nbr [4 n_tet] (vertex ids = rows of d_points; neighbour across the face opposite vertex k, -1 = hull),
+   d_points [3 n_points] in ROW order, h_geom[12] = shift(3), scale(3), bounding box lo(3), hi(3) of the points;
+   G <= GSL_SINTERP_MESH3_MAX_GRID: cells per axis of the seed grid, d_seed: 2 G^3 + 2 ints.  mesh3_bind fills the
+   response table from d_response [n_points] (row order).  mesh3_eval: targets at d_targets + k * ttda, ttda >= 3;
+   d_tet may be NULL; a target outside the mesh gives index -1 and NaN and is counted in *h_n_outside (may be NULL;
+   forces a sync when given) -> GSL_EDOM.  convex = 0: a walk stopped by hull faces is resolved by an exhaustive scan
+   instead of "outside". */
+#define GSL_SINTERP_MESH3_RECORD_BYTES 128
+#define GSL_SINTERP_MESH3_TABLE_BYTES 32
+#define GSL_SINTERP_MESH3_MAX_GRID 160
+int gsl_sinterp_hip_mesh3_pack(gsl_sinterp_hip_ctx *ctx, int n_tet, const int *d_tet, const int *d_nbr, int n_points,
+                               const double *d_points, const double *h_geom, int G, void *d_records, int *d_seed);
+int gsl_sinterp_hip_mesh3_bind(gsl_sinterp_hip_ctx *ctx, int n_tet, const int *d_tet, int n_points, const double *d_response,
+                               void *d_table);
+int gsl_sinterp_hip_mesh3_eval(gsl_sinterp_hip_ctx *ctx, int n_tet, const void *d_records, const void *d_table,
+                               const int *d_seed, int G, const double *h_geom, int convex, const double *d_targets,
+                               size_t m, size_t ttda, double *d_values, int *d_tet, long long *h_n_outside);
+
 /* Device-side integrity checks of a DAG given as raw arrays (same arguments as tree_pack):
    what & 1: _check_leaf_nodes  (interpolation/linear_simplex_integrity_check.c:62-119), one thread per leaf;
    what & 2: _check_delaunay    (:134-160; circumsphere per linear_simplex.c:555-605), leaves x points.
