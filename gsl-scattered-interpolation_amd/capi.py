@@ -19,6 +19,7 @@ FIT_LOO, FIT_ML = 0, 1
 SOLVER_DEFAULT, SOLVER_CHOLESKY2, SOLVER_PCHOLESKY, SOLVER_LU_REFINE = 0, 1, 2, 3
 TREE_DEFAULT, TREE_NOSTANDARDIZE, TREE_ISOSCALE = 0, 1, 2
 TREE_RECORD_BYTES, TREE_LEAFTAB_BYTES = 64, 32
+NATURAL_RECORD_BYTES, NATURAL_STACK = 80, 16          # natural-neighbour records (n_tri + 1 of them); pending-stack default
 
 
 def library_path():
@@ -216,6 +217,7 @@ SIGNATURES = {
     "simplex_mesh_points": (_pd, [_vp]),
     "simplex_mesh_set_convex": (None, [_vp, _i]),
     "simplex_mesh_convex": (_i, [_vp]),
+    "simplex_mesh_delaunay_metric": (_i, [_vp]),
     "simplex_mesh_device_alloc": (_vp, [_vp, _i]),
     "simplex_mesh_device_alloc_multi": (_vp, [_vp, _pi, _i]),
     "simplex_mesh_device_n_devices": (_i, [_vp]),
@@ -227,6 +229,10 @@ SIGNATURES = {
     "simplex_mesh_device_eval_many": (_i, [_vp, _pm, _pv, _pi]),
     "simplex_mesh_device_eval_resident": (_i, [_vp, _vp, _sz, _sz, _vp, _vp]),
     "simplex_mesh_device_ctx": (_vp, [_vp]),
+    "simplex_mesh_device_eval_natural_many": (_i, [_vp, _pm, _pv, _pi]),
+    "simplex_mesh_device_eval_natural_resident": (_i, [_vp, _vp, _sz, _sz, _vp, _vp]),
+    "gsl_sinterp_hip_mesh_natural_pack": (_i, [_vp, _i, _vp, _vp, _i, _vp, _pd, _vp]),
+    "gsl_sinterp_hip_mesh_natural_eval": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _sz, _sz, _i, _vp, C.POINTER(C.c_longlong)]),
     "gsl_sinterp_hip_mesh_pack": (_i, [_vp, _i, _vp, _vp, _i, _vp, _pd, _i, _vp, _vp]),
     "gsl_sinterp_hip_mesh_eval": (_i, [_vp, _i, _vp, _vp, _vp, _i, _pd, _i, _vp, _sz, _sz, _vp, _vp, C.POINTER(C.c_longlong)]),
     "gsl_sinterp_hip_mesh3_pack": (_i, [_vp, _i, _vp, _vp, _i, _vp, _pd, _i, _vp, _vp]),
@@ -324,7 +330,7 @@ SIGNATURES = {
     "gsl_rng_get": (C.c_ulong, [_vp]),
     "gsl_rng_uniform_int": (C.c_ulong, [_vp, C.c_ulong]),
 }
-DATA_SYMBOLS = ["gsl_sinterp_kriging", "gsl_sinterp_linear_mesh", "gsl_sinterp_rbf_gaussian", "gsl_sinterp_rbf_tps", "gsl_sinterp_rbf_tps_affine", "gsl_sinterp_rbf_wendland", "gsl_sinterp_linear_simplex",
+DATA_SYMBOLS = ["gsl_sinterp_kriging", "gsl_sinterp_linear_mesh", "gsl_sinterp_natural_mesh", "gsl_sinterp_natural_simplex", "gsl_sinterp_rbf_gaussian", "gsl_sinterp_rbf_tps", "gsl_sinterp_rbf_tps_affine", "gsl_sinterp_rbf_wendland", "gsl_sinterp_linear_simplex",
                 "gsl_sinterp_rbf_matern32", "gsl_sinterp_rbf_matern52", "gsl_sinterp_rbf_imq", "gsl_sinterp_kriging_matern32", "gsl_sinterp_kriging_matern52",
                 "gsl_rng_mt19937", "gsl_rng_default"]
 
@@ -461,6 +467,19 @@ class HipContext:
 
     def tree_bind(self, n_nodes, d_pidx, n_points, d_response, d_leaftab):
         check(lib().gsl_sinterp_hip_tree_bind(self._h, n_nodes, d_pidx, n_points, d_response, d_leaftab), self._h)
+
+    def mesh_natural_pack(self, n_tri, d_tri, d_nbr, n_points, d_points, metric, d_nnrec):
+        """natural-neighbour records: (n_tri + 1) * NATURAL_RECORD_BYTES bytes at d_nnrec; metric = the per-axis factors"""
+        g = np.ascontiguousarray(metric, dtype=np.float64)
+        check(lib().gsl_sinterp_hip_mesh_natural_pack(self._h, n_tri, d_tri, d_nbr, n_points, d_points, g.ctypes.data_as(_pd), d_nnrec),
+              self._h)
+
+    def mesh_natural_eval(self, n_tri, d_nnrec, d_leaftab, d_located, d_linear_values, d_targets, m, ttda, d_values, depth_cap=0):
+        """the cavity sweep over the triangles gsl_sinterp_hip_mesh_eval located; returns how many targets took the scan"""
+        cnt = C.c_longlong(0)
+        check(lib().gsl_sinterp_hip_mesh_natural_eval(self._h, n_tri, d_nnrec, d_leaftab, d_located, d_linear_values, d_targets, m, ttda,
+                                                      depth_cap, d_values, C.byref(cnt)), self._h)
+        return cnt.value
 
     def bary_eval(self, n_nodes, d_records, d_leaftab, scale, d_targets, m, ttda, d_values, d_leaf=None,
                   count_outside=False):
@@ -952,6 +971,10 @@ class SimplexMesh:
     def convex(self):
         return bool(lib().simplex_mesh_convex(self._h))
 
+    def delaunay_metric(self):
+        """1: Delaunay in the coordinates as given, 2: in the standardised ones, 0: in neither (or a 3-D mesh)"""
+        return int(lib().simplex_mesh_delaunay_metric(self._h))
+
     def device_alloc(self, device=0):
         h = lib().simplex_mesh_device_alloc(self._h, device)
         if not h:
@@ -1002,11 +1025,23 @@ class DeviceMesh:
         st = lib().simplex_mesh_device_eval_many(self._h, C.byref(as_matrix(targets)), C.byref(as_vector(vals)), tri.ctypes.data_as(_pi))
         return st, vals, tri
 
+    def eval_natural_many(self, targets, out=None):
+        """natural-neighbour (Sibson) values on a 2-D Delaunay mesh; same shapes as eval_many"""
+        m = targets.shape[0]
+        vals = np.empty(m, dtype=np.float64) if out is None else out[0]
+        tri = np.empty(m, dtype=np.int32) if out is None else out[1]
+        st = lib().simplex_mesh_device_eval_natural_many(self._h, C.byref(as_matrix(targets)), C.byref(as_vector(vals)),
+                                                         tri.ctypes.data_as(_pi))
+        return st, vals, tri
+
     def n_devices(self):
         return lib().simplex_mesh_device_n_devices(self._h)
 
     def eval_resident(self, d_targets, m, ttda, d_values, d_tri):
         return lib().simplex_mesh_device_eval_resident(self._h, d_targets, m, ttda, d_values, d_tri)
+
+    def eval_natural_resident(self, d_targets, m, ttda, d_values, d_tri):
+        return lib().simplex_mesh_device_eval_natural_resident(self._h, d_targets, m, ttda, d_values, d_tri)
 
     def ctx_handle(self):
         return lib().simplex_mesh_device_ctx(self._h)
@@ -1027,6 +1062,7 @@ class DeviceMesh:
 class Sinterp:
     TYPES = {"gaussian": "gsl_sinterp_rbf_gaussian", "tps": "gsl_sinterp_rbf_tps", "tps_affine": "gsl_sinterp_rbf_tps_affine",
              "wendland": "gsl_sinterp_rbf_wendland", "linear_mesh": "gsl_sinterp_linear_mesh",
+             "natural_mesh": "gsl_sinterp_natural_mesh", "natural_simplex": "gsl_sinterp_natural_simplex",
              "linear_simplex": "gsl_sinterp_linear_simplex", "kriging": "gsl_sinterp_kriging",
              "matern32": "gsl_sinterp_rbf_matern32", "matern52": "gsl_sinterp_rbf_matern52", "imq": "gsl_sinterp_rbf_imq",
              "kriging_matern32": "gsl_sinterp_kriging_matern32", "kriging_matern52": "gsl_sinterp_kriging_matern52"}

@@ -462,6 +462,57 @@ simplex_mesh *simplex_mesh_from_tree(simplex_tree *tree, gsl_matrix *data)
 }
 
 /* ------------------------------------------------------------------------ */
+/* Which metric makes a 2-D mesh Delaunay (natural-neighbour interpolation needs one: csrc/hip/natural.hip walks the
+   triangles whose circumcircle contains the target).  Locally Delaunay in coordinates x_j * s_j: across every interior
+   edge the neighbour's opposite vertex d is not strictly inside the circumcircle of the triangle (a, b, c), in
+   determinant form, relative to d and for the counter-clockwise order:
+       det = cross(a, b) |c|^2 + cross(b, c) |a|^2 + cross(c, a) |b|^2  <=  1e-9 * (the same sum over absolute values).
+   Flat triangles (|orientation| <= 1e-14 * the sum of the squared edge lengths: the rule of natural_pack_kernel) are
+   skipped on either side; cocircular neighbours give det = 0 to rounding, so lattices pass. */
+static int tri_flat(const double p[3][2], double *orient)
+{
+  const double bx = p[1][0] - p[0][0], by = p[1][1] - p[0][1], cx = p[2][0] - p[0][0], cy = p[2][1] - p[0][1];
+  const double ex = p[2][0] - p[1][0], ey = p[2][1] - p[1][1];
+  *orient = bx * cy - by * cx;
+  return !(fabs(*orient) > 1e-14 * ((bx * bx + by * by) + (cx * cx + cy * cy) + (ex * ex + ey * ey)));
+}
+
+static int mesh_locally_delaunay(const simplex_mesh *m, double s0, double s1)
+{
+  for (size_t t = 0; t < m->n_tri; t++) {
+    double p[3][2], q[3][2], orient, qo;
+    for (int i = 0; i < 3; i++) { p[i][0] = m->points[2 * (size_t)m->tri[3 * t + i]] * s0; p[i][1] = m->points[2 * (size_t)m->tri[3 * t + i] + 1] * s1; }
+    if (tri_flat(p, &orient)) continue;
+    for (int k = 0; k < 3; k++) {
+      const int nb = m->nbr[3 * t + k];
+      if (nb < 0 || (size_t)nb < t) continue;               /* every interior edge once; the test is symmetric */
+      int slot = -1;
+      for (int j = 0; j < 3; j++) {
+        if (m->nbr[3 * (size_t)nb + j] == (int)t) slot = j;
+        q[j][0] = m->points[2 * (size_t)m->tri[3 * (size_t)nb + j]] * s0; q[j][1] = m->points[2 * (size_t)m->tri[3 * (size_t)nb + j] + 1] * s1;
+      }
+      if (slot < 0 || tri_flat(q, &qo)) continue;
+      const double sg = orient > 0 ? 1.0 : -1.0;
+      const double ax = p[0][0] - q[slot][0], ay = p[0][1] - q[slot][1], bx = p[1][0] - q[slot][0], by = p[1][1] - q[slot][1];
+      const double cx = p[2][0] - q[slot][0], cy = p[2][1] - q[slot][1];
+      const double a2 = ax * ax + ay * ay, b2 = bx * bx + by * by, c2 = cx * cx + cy * cy;
+      const double det = sg * ((ax * by - ay * bx) * c2 + (bx * cy - by * cx) * a2 + (cx * ay - cy * ax) * b2);
+      const double mag = (fabs(ax * by) + fabs(ay * bx)) * c2 + (fabs(bx * cy) + fabs(by * cx)) * a2 + (fabs(cx * ay) + fabs(cy * ax)) * b2;
+      if (det > 1e-9 * mag) return 0;
+    }
+  }
+  return 1;
+}
+
+int simplex_mesh_delaunay_metric(const simplex_mesh *mesh)
+{
+  if (!mesh || mesh->dim != 2) return 0;
+  if (mesh_locally_delaunay(mesh, 1.0, 1.0)) return 1;
+  if (mesh->scale[0] > 0 && mesh->scale[1] > 0 && mesh_locally_delaunay(mesh, mesh->scale[0], mesh->scale[1])) return 2;
+  return 0;
+}
+
+/* ------------------------------------------------------------------------ */
 /* Binary checkpoint of a mesh (gsl_matrix_fwrite conventions: native byte order, GSL_EFAILED on a short transfer):
      2-D: magic "GSLSMSH1" | n_tri, n_points, has_nodes, convex (int64) | triangles | neighbours | [tree nodes] | points |
           shift, scale, lo, hi;

@@ -616,6 +616,15 @@ struct simplex_mesh_device {
   shard_set ss;                    /* n_members > 1: ss.grp owns the contexts */
   chunk_set cs;                    /* n_members == 1: pipelined host batches */
   int response_bound;
+  /* natural neighbours: nothing is computed, uploaded or kept for them until the first natural evaluation, which asks
+     the (borrowed) mesh for the metric it is Delaunay in (simplex_mesh_delaunay_metric; -1 = not asked yet), uploads its
+     links and points once more and packs nn_rec; nn_leaf: triangle indices of a resident batch whose caller did not ask
+     for them */
+  const simplex_mesh *mesh;
+  int nn_metric;
+  int *nn_leaf;
+  void *nn_rec;
+  size_t nn_leaf_cap;
 };
 
 gsl_sinterp_hip_ctx *simplex_mesh_device_ctx(simplex_mesh_device *dev) { return dev ? dev->ctx : NULL; }
@@ -634,6 +643,9 @@ void simplex_mesh_device_free(simplex_mesh_device *dev)
     if (!c) continue;
     gsl_sinterp_hip_free(c, dev->m_records[r]); gsl_sinterp_hip_free(c, dev->m_leaftab[r]);
     gsl_sinterp_hip_free(c, dev->m_tri[r]); gsl_sinterp_hip_free(c, dev->m_seed[r]);
+  }
+  if (dev->ctx) {
+    gsl_sinterp_hip_free(dev->ctx, dev->nn_rec); gsl_sinterp_hip_free(dev->ctx, dev->nn_leaf);
   }
   if (dev->ss.grp) shard_set_release(&dev->ss);      /* destroys the members' contexts */
   else if (dev->ctx) { chunk_set_release(&dev->cs, dev->ctx); gsl_sinterp_hip_ctx_destroy(dev->ctx); }
@@ -706,6 +718,7 @@ simplex_mesh_device *simplex_mesh_device_alloc_multi(const simplex_mesh *mesh, c
     if (!st) st = s2;
     gsl_sinterp_hip_free(c, d_nbr[r]); gsl_sinterp_hip_free(c, d_pts[r]);
   }
+  dev->mesh = mesh; dev->nn_metric = -1;
   if (st != GSL_SUCCESS) {
     gsl_error(gsl_sinterp_hip_last_error(dev->ctx), __FILE__, __LINE__, st);
     simplex_mesh_device_free(dev);
@@ -786,6 +799,97 @@ int simplex_mesh_device_eval_many(simplex_mesh_device *dev, const gsl_matrix *ta
                        : chunk_eval_many(&dev->cs, dev->ctx, d, targets, values, triangle, &mesh_chunk_eval, dev, 1, &outside_n);
   if (st != GSL_SUCCESS) GSL_ERROR("simplex_mesh_device_eval_many: evaluation failed", st);
   if (outside_n) GSL_ERROR("simplex_mesh_device_eval_many: target(s) outside the triangulation", GSL_EDOM);
+  return GSL_SUCCESS;
+}
+
+/* ---- natural neighbours on the same mirror (csrc/hip/natural.hip) ---- */
+static int natural_status(simplex_mesh_device *dev)
+{
+  if (dev->dim != 2) GSL_ERROR("simplex_mesh_device_eval_natural: 2-D meshes only", GSL_EUNSUP);
+  if (!dev->convex) GSL_ERROR("simplex_mesh_device_eval_natural: the mesh is not convex", GSL_EUNSUP);
+  if (dev->n_members > 1) GSL_ERROR("simplex_mesh_device_eval_natural: one device only (no sharding over a device group)", GSL_EUNSUP);
+  if (dev->nn_metric < 0) dev->nn_metric = simplex_mesh_delaunay_metric(dev->mesh);     /* first use: O(n_tri) on the host */
+  if (dev->nn_metric == 0)
+    GSL_ERROR("simplex_mesh_device_eval_natural: the mesh is not Delaunay, neither as given nor in standardised coordinates", GSL_EINVAL);
+  if (!dev->response_bound) GSL_ERROR("simplex_mesh_device_eval_natural: no response bound", GSL_EINVAL);
+  return GSL_SUCCESS;
+}
+
+/* the natural-neighbour records, packed at the first use from a second upload of the mesh's links and points */
+static int natural_pack_once(simplex_mesh_device *dev)
+{
+  if (dev->nn_rec) return GSL_SUCCESS;
+  gsl_sinterp_hip_ctx *c = dev->ctx;
+  const size_t tb = 3 * (size_t)dev->n_tri * sizeof(int), pb = 2 * (size_t)dev->n_points * sizeof(double);
+  const double one[2] = {1.0, 1.0};
+  int *d_nbr = NULL;
+  double *d_pts = NULL;
+  int st = gsl_sinterp_hip_malloc(c, &dev->nn_rec, ((size_t)dev->n_tri + 1) * GSL_SINTERP_NATURAL_RECORD_BYTES);
+  if (!st) st = gsl_sinterp_hip_malloc(c, (void **)&d_nbr, tb);
+  if (!st) st = gsl_sinterp_hip_malloc(c, (void **)&d_pts, pb);
+  if (!st) st = gsl_sinterp_hip_h2d(c, d_nbr, simplex_mesh_neighbours(dev->mesh), tb);
+  if (!st) st = gsl_sinterp_hip_h2d(c, d_pts, simplex_mesh_points(dev->mesh), pb);
+  if (!st) st = gsl_sinterp_hip_mesh_natural_pack(c, dev->n_tri, dev->m_tri[0], d_nbr, dev->n_points, d_pts,
+                                                  dev->nn_metric == 2 ? dev->geom + 2 : one, dev->nn_rec);
+  int s2 = gsl_sinterp_hip_sync(c);
+  if (!st) st = s2;
+  gsl_sinterp_hip_free(c, d_nbr); gsl_sinterp_hip_free(c, d_pts);
+  if (st) { gsl_sinterp_hip_free(c, dev->nn_rec); dev->nn_rec = NULL; }
+  return st;
+}
+
+/* locate + linear value by the unchanged linear path (batches >= 4096 through its sorted route), then the cavity sweep
+   over the triangle it found; the linear values pass through d_s */
+static int natural_chunk_eval(void *state, const double *d_y, size_t m, double *d_s, int *d_leaf)
+{
+  simplex_mesh_device *dev = (simplex_mesh_device *)state;
+  int st = gsl_sinterp_hip_mesh_eval(dev->ctx, dev->n_tri, dev->m_records[0], dev->m_leaftab[0], dev->m_seed[0], dev->G, dev->geom, dev->convex,
+                                     d_y, m, 2, d_s, d_leaf, (long long *)NULL);
+  if (st) return st;
+  return gsl_sinterp_hip_mesh_natural_eval(dev->ctx, dev->n_tri, dev->nn_rec, dev->m_leaftab[0], d_leaf, d_s, d_y, m, 2, 0, d_s,
+                                           (long long *)NULL);
+}
+
+int simplex_mesh_device_eval_natural_resident(simplex_mesh_device *dev, const double *d_targets, size_t m, size_t ttda,
+                                              double *d_values, int *d_triangle)
+{
+  if (!dev) GSL_ERROR("simplex_mesh_device_eval_natural_resident: null device mirror", GSL_EFAULT);
+  int st = natural_status(dev);
+  if (st) return st;
+  if (ttda < 2) GSL_ERROR("simplex_mesh_device_eval_natural_resident: target rows shorter than the mesh's dimension", GSL_EBADLEN);
+  if (m == 0) return GSL_SUCCESS;
+  st = natural_pack_once(dev);
+  if (!st && !d_triangle) {
+    if (m > dev->nn_leaf_cap) {
+      gsl_sinterp_hip_free(dev->ctx, dev->nn_leaf); dev->nn_leaf = NULL; dev->nn_leaf_cap = 0;
+      st = gsl_sinterp_hip_malloc(dev->ctx, (void **)&dev->nn_leaf, m * sizeof(int));
+      if (!st) dev->nn_leaf_cap = m;
+    }
+    d_triangle = dev->nn_leaf;
+  }
+  if (!st) st = gsl_sinterp_hip_mesh_eval(dev->ctx, dev->n_tri, dev->m_records[0], dev->m_leaftab[0], dev->m_seed[0], dev->G, dev->geom,
+                                          dev->convex, d_targets, m, ttda, d_values, d_triangle, NULL);
+  if (!st) st = gsl_sinterp_hip_mesh_natural_eval(dev->ctx, dev->n_tri, dev->nn_rec, dev->m_leaftab[0], d_triangle, d_values, d_targets, m,
+                                                  ttda, 0, d_values, NULL);
+  if (st) GSL_ERROR(gsl_sinterp_hip_last_error(dev->ctx), st);
+  return GSL_SUCCESS;
+}
+
+int simplex_mesh_device_eval_natural_many(simplex_mesh_device *dev, const gsl_matrix *targets, gsl_vector *values, int *triangle)
+{
+  if (!dev || !targets || !values) GSL_ERROR("simplex_mesh_device_eval_natural_many: null argument", GSL_EFAULT);
+  int st = natural_status(dev);
+  if (st) return st;
+  if (targets->size2 != 2) GSL_ERROR("simplex_mesh_device_eval_natural_many: targets must be M x 2", GSL_EBADLEN);
+  const size_t m = targets->size1;
+  if (values->size != m) GSL_ERROR("simplex_mesh_device_eval_natural_many: values length must equal target rows", GSL_EBADLEN);
+  if (m == 0) return GSL_SUCCESS;
+  st = natural_pack_once(dev);
+  if (st) GSL_ERROR(gsl_sinterp_hip_last_error(dev->ctx), st);
+  size_t outside_n = 0;
+  st = chunk_eval_many(&dev->cs, dev->ctx, 2, targets, values, triangle, &natural_chunk_eval, dev, 1, &outside_n);
+  if (st != GSL_SUCCESS) GSL_ERROR("simplex_mesh_device_eval_natural_many: evaluation failed", st);
+  if (outside_n) GSL_ERROR("simplex_mesh_device_eval_natural_many: target(s) outside the triangulation", GSL_EDOM);
   return GSL_SUCCESS;
 }
 
@@ -1429,6 +1533,84 @@ static int mesh_type_eval_resident(const gsl_sinterp *interp, const double *d_y,
 }
 
 /* ======================================================================== */
+/* natural-neighbour types: a mesh_state whose mesh is imported              */
+/* (natural-mesh) or exported from a host-built tree (natural-simplex)       */
+/* ======================================================================== */
+static void *natural_type_alloc(size_t dim, size_t size)
+{
+  return dim == 2 ? mesh_type_alloc(dim, size) : NULL;
+}
+
+/* what the device entries would refuse at every evaluation is refused once, here */
+static int natural_type_mirror(gsl_sinterp *interp, mesh_state *st)
+{
+  if (interp->n_devices > 1) GSL_ERROR("gsl_sinterp_init: natural-neighbour interpolants run on one device", GSL_EUNSUP);
+  if (!simplex_mesh_convex(st->mesh)) GSL_ERROR("gsl_sinterp_init: natural neighbours need a convex mesh", GSL_EUNSUP);
+  if (simplex_mesh_delaunay_metric(st->mesh) == 0)
+    GSL_ERROR("gsl_sinterp_init: natural neighbours need a Delaunay triangulation (simplex_mesh_delaunay_metric is 0)", GSL_EINVAL);
+  return mesh_type_mirror(interp, st);
+}
+
+static int natural_copy_data(mesh_state *st, const gsl_matrix *x, const gsl_vector *f)
+{
+  simplex_mesh_device_free(st->dev); st->dev = NULL;
+  simplex_mesh_free(st->mesh); st->mesh = NULL;
+  gsl_matrix_free(st->x); gsl_vector_free(st->f);
+  st->x = gsl_matrix_alloc(st->n, 2);
+  st->f = gsl_vector_alloc(st->n);
+  if (!st->x || !st->f) return GSL_ENOMEM;
+  for (size_t i = 0; i < st->n; i++) {
+    for (size_t j = 0; j < 2; j++) gsl_matrix_set(st->x, i, j, x->data[i * x->tda + j]);
+    gsl_vector_set(st->f, i, gsl_vector_get(f, i));
+  }
+  return GSL_SUCCESS;
+}
+
+static int natural_mesh_init(gsl_sinterp *interp, const gsl_matrix *x, const gsl_vector *f)
+{
+  mesh_state *st = (mesh_state *)interp->state;
+  if (!st->tri) GSL_ERROR("gsl_sinterp_init: no triangulation set (gsl_sinterp_set_triangulation)", GSL_EINVAL);
+  if (st->n < 3) GSL_ERROR("gsl_sinterp_init: an imported triangulation needs at least dim + 1 points", GSL_EINVAL);
+  int s = natural_copy_data(st, x, f);
+  if (s) return s;
+  st->mesh = simplex_mesh_import(st->x, st->tri, st->nbr, st->n_tri);
+  if (!st->mesh) return GSL_EINVAL;
+  return natural_type_mirror(interp, st);
+}
+
+/* the tree of gsl_sinterp_linear_simplex (same flags, same generator), exported and dropped: the mesh is all that is kept */
+static int natural_simplex_init(gsl_sinterp *interp, const gsl_matrix *x, const gsl_vector *f)
+{
+  mesh_state *st = (mesh_state *)interp->state;
+  int s = natural_copy_data(st, x, f);
+  if (s) return s;
+  simplex_tree *tree = simplex_tree_alloc(2, (int)st->n);
+  if (!tree) return GSL_ENOMEM;
+  s = simplex_tree_init(tree, st->x, NULL, NULL, interp->init_flags, interp->rng);
+  if (s == GSL_SUCCESS) {
+    st->mesh = simplex_mesh_from_tree(tree, st->x);
+    if (!st->mesh) s = GSL_EINVAL;
+  }
+  simplex_tree_free(tree);
+  if (s != GSL_SUCCESS) return s;
+  return natural_type_mirror(interp, st);
+}
+
+static int natural_type_eval_many(const gsl_sinterp *interp, const gsl_matrix *y, gsl_vector *s, int *leaf)
+{
+  const mesh_state *st = (const mesh_state *)interp->state;
+  if (!st->dev) GSL_ERROR("gsl_sinterp_eval_many: interpolant not initialised", GSL_EINVAL);
+  return simplex_mesh_device_eval_natural_many(st->dev, y, s, leaf);
+}
+
+static int natural_type_eval_resident(const gsl_sinterp *interp, const double *d_y, size_t m, size_t ytda, double *d_s, int *d_leaf)
+{
+  const mesh_state *st = (const mesh_state *)interp->state;
+  if (!st->dev) GSL_ERROR("gsl_sinterp_eval_resident: interpolant not initialised", GSL_EINVAL);
+  return simplex_mesh_device_eval_natural_resident(st->dev, d_y, m, ytda, d_s, d_leaf);
+}
+
+/* ======================================================================== */
 /* type table + generic entry points                                         */
 /* ======================================================================== */
 static const gsl_sinterp_type gauss_type = {"rbf-gaussian", 1, &rbf_gauss_alloc, &rbf_init, &rbf_eval_many, &rbf_eval_resident, &rbf_free};
@@ -1437,6 +1619,13 @@ static const gsl_sinterp_type simplex_type = {"linear-simplex", 3, &simplex_allo
 static const gsl_sinterp_type wendland_type = {"rbf-wendland-c2", 1, &rbf_wendland_alloc, &rbf_init, &rbf_eval_many, &rbf_eval_resident, &rbf_free};
 static const gsl_sinterp_type mesh_type = {"linear-imported-triangulation", 3, &mesh_type_alloc, &mesh_type_init, &mesh_type_eval_many, &mesh_type_eval_resident, &mesh_type_free};
 const gsl_sinterp_type *gsl_sinterp_linear_mesh = &mesh_type;
+static const gsl_sinterp_type natural_mesh_type = {"natural-neighbour-imported-triangulation", 3, &natural_type_alloc, &natural_mesh_init, &natural_type_eval_many, &natural_type_eval_resident, &mesh_type_free};
+static const gsl_sinterp_type natural_simplex_type = {"natural-neighbour-simplex", 3, &natural_type_alloc, &natural_simplex_init, &natural_type_eval_many, &natural_type_eval_resident, &mesh_type_free};
+const gsl_sinterp_type *gsl_sinterp_natural_mesh = &natural_mesh_type;
+const gsl_sinterp_type *gsl_sinterp_natural_simplex = &natural_simplex_type;
+/* the types whose state is a mesh_state, and the natural-neighbour ones among them */
+static int is_natural_type(const gsl_sinterp_type *T) { return T == &natural_mesh_type || T == &natural_simplex_type; }
+static int is_mesh_state_type(const gsl_sinterp_type *T) { return T == &mesh_type || is_natural_type(T); }
 static const gsl_sinterp_type tps_affine_type = {"rbf-thin-plate-spline-affine", 3, &rbf_tps_affine_alloc, &rbf_init, &rbf_eval_many, &rbf_eval_resident, &rbf_free};
 const gsl_sinterp_type *gsl_sinterp_rbf_tps_affine = &tps_affine_type;
 static const gsl_sinterp_type krige_type = {"ordinary-kriging-gaussian", 1, &krige_alloc, &rbf_init, &rbf_eval_many, &rbf_eval_resident, &rbf_free};
@@ -1474,6 +1663,7 @@ static int is_local(const gsl_sinterp *interp)
 int gsl_sinterp_set_neighbours(gsl_sinterp *interp, size_t k)
 {
   if (!interp) GSL_ERROR("gsl_sinterp_set_neighbours: null interpolant", GSL_EFAULT);
+  if (is_natural_type(interp->type)) GSL_ERROR("gsl_sinterp_set_neighbours: not for natural-neighbour interpolants", GSL_EUNSUP);
   if (!is_krige_type(interp->type)) GSL_ERROR("gsl_sinterp_set_neighbours: kriging interpolants only", GSL_EINVAL);
   if (k > GSL_SINTERP_MAX_NEIGHBOURS) GSL_ERROR("gsl_sinterp_set_neighbours: at most 64 neighbours", GSL_EINVAL);
   if (k > interp->size) GSL_ERROR("gsl_sinterp_set_neighbours: more neighbours than centres", GSL_EINVAL);
@@ -1489,6 +1679,8 @@ gsl_sinterp *gsl_sinterp_alloc(const gsl_sinterp_type *T, size_t dim, size_t siz
   if (dim < 1 || dim > 3) GSL_ERROR_NULL("gsl_sinterp_alloc: dim must be 1, 2 or 3", GSL_EINVAL);
   if (T == &simplex_type && dim != 2)
     GSL_ERROR_NULL("gsl_sinterp_alloc: linear-simplex supports dim = 2 only", GSL_EUNIMPL);
+  if (is_natural_type(T) && dim != 2)
+    GSL_ERROR_NULL("gsl_sinterp_alloc: natural-neighbour interpolants support dim = 2 only", GSL_EUNIMPL);
   gsl_sinterp *interp = (gsl_sinterp *)calloc(1, sizeof *interp);
   if (!interp) GSL_ERROR_NULL("failed to allocate space for sinterp struct", GSL_ENOMEM);
   interp->type = T; interp->dim = dim; interp->size = size;
@@ -1578,6 +1770,7 @@ int gsl_sinterp_set_loo(gsl_sinterp *interp, int want)
 /* whether leave-one-out data is held, as a status (the table of include/gsl_sinterp.h) */
 static int loo_status(const gsl_sinterp *interp)
 {
+  if (is_natural_type(interp->type)) GSL_ERROR("gsl_sinterp_loo: not for natural-neighbour interpolants", GSL_EUNSUP);
   if (!is_pd_type(interp->type))
     GSL_ERROR("gsl_sinterp_loo: positive definite RBF (Gaussian, Wendland, Matern, inverse multiquadric) and kriging interpolants only", GSL_EINVAL);
   if (is_local(interp)) GSL_ERROR("gsl_sinterp_loo: local kriging (gsl_sinterp_set_neighbours) takes a route without a Cholesky factor", GSL_EUNSUP);
@@ -1636,6 +1829,7 @@ struct gsl_sinterp_fit_workspace {
 gsl_sinterp_fit_workspace *gsl_sinterp_fit_alloc(const gsl_sinterp *interp, const gsl_matrix *x, const gsl_vector *f)
 {
   if (!interp || !x || !f) GSL_ERROR_NULL("gsl_sinterp_fit_alloc: null argument", GSL_EFAULT);
+  if (is_natural_type(interp->type)) GSL_ERROR_NULL("gsl_sinterp_fit_alloc: not for natural-neighbour interpolants (nothing to fit)", GSL_EUNSUP);
   if (!is_pd_type(interp->type))
     GSL_ERROR_NULL("gsl_sinterp_fit_alloc: positive definite RBF (Gaussian, Wendland, Matern, inverse multiquadric) and kriging interpolants only", GSL_EINVAL);
   const size_t n = interp->size, dim = interp->dim;
@@ -1864,6 +2058,7 @@ int gsl_sinterp_fit_sigma2(const gsl_sinterp_fit_workspace *w, double *s2)
 /* whether variances can be evaluated, as a status (the table of include/gsl_sinterp.h) */
 static int variance_status(const gsl_sinterp *interp)
 {
+  if (is_natural_type(interp->type)) GSL_ERROR("gsl_sinterp_eval_variance: not for natural-neighbour interpolants", GSL_EUNSUP);
   if (!is_krige_type(interp->type)) GSL_ERROR("gsl_sinterp_eval_variance: kriging interpolants only", GSL_EINVAL);
   const rbf_state *st = (const rbf_state *)interp->state;
   if (!st->d_w) GSL_ERROR("gsl_sinterp_eval_variance: interpolant not initialised", GSL_EINVAL);
@@ -1960,6 +2155,7 @@ int gsl_sinterp_eval_local_many(const gsl_sinterp *interp, const gsl_matrix *y, 
 /* ---- value + gradient (RBF family): dispatch on the type here, no slot in gsl_sinterp_type ---- */
 static int grad_status(const gsl_sinterp *interp)
 {
+  if (is_natural_type(interp->type)) GSL_ERROR("gsl_sinterp_eval_grad: not for natural-neighbour interpolants", GSL_EUNSUP);
   if (interp->type == &simplex_type || interp->type == &mesh_type)
     GSL_ERROR("gsl_sinterp_eval_grad: RBF-family interpolants only (the piecewise-linear gradient is constant per leaf)", GSL_EUNSUP);
   if (is_local(interp))
@@ -2043,6 +2239,7 @@ int gsl_sinterp_eval_grad_e(const gsl_sinterp *interp, const gsl_vector *y, doub
 /* ---- several fields on one set of centres (RBF family): dispatch on the type here, no slot in gsl_sinterp_type ---- */
 static int fields_status(const gsl_sinterp *interp)
 {
+  if (is_natural_type(interp->type)) GSL_ERROR("gsl_sinterp fields: not for natural-neighbour interpolants (one response)", GSL_EUNSUP);
   if (interp->type == &simplex_type || interp->type == &mesh_type)
     GSL_ERROR("gsl_sinterp fields: RBF-family interpolants only (several responses per leaf of the linear types: a separate entry)", GSL_EUNSUP);
   if (is_local(interp)) GSL_ERROR("gsl_sinterp fields: not with gsl_sinterp_set_neighbours (local kriging has one field)", GSL_EUNSUP);
@@ -2062,7 +2259,7 @@ int gsl_sinterp_init_fields(gsl_sinterp *interp, const gsl_matrix *x, const gsl_
 
 size_t gsl_sinterp_n_fields(const gsl_sinterp *interp)
 {
-  if (!interp || interp->type == &simplex_type || interp->type == &mesh_type) return 0;
+  if (!interp || interp->type == &simplex_type || is_mesh_state_type(interp->type)) return 0;
   const rbf_state *st = (const rbf_state *)interp->state;
   return st->d_w ? st->nf : 0;
 }
@@ -2250,7 +2447,8 @@ int gsl_sinterp_route(const gsl_sinterp *interp) { return interp ? interp->route
 int gsl_sinterp_set_triangulation(gsl_sinterp *interp, const int *triangles, const int *neighbours, size_t n_triangles)
 {
   if (!interp || !triangles) GSL_ERROR("gsl_sinterp_set_triangulation: null argument", GSL_EFAULT);
-  if (interp->type != &mesh_type) GSL_ERROR("gsl_sinterp_set_triangulation: imported-triangulation interpolants only", GSL_EINVAL);
+  if (interp->type != &mesh_type && interp->type != &natural_mesh_type)
+    GSL_ERROR("gsl_sinterp_set_triangulation: imported-triangulation interpolants only", GSL_EINVAL);
   mesh_state *st = (mesh_state *)interp->state;
   const size_t w = st->dim + 1;                          /* ids per simplex */
   if (n_triangles < 1 || n_triangles > (size_t)INT_MAX / w) GSL_ERROR("gsl_sinterp_set_triangulation: bad triangle count", GSL_EINVAL);
@@ -2356,6 +2554,10 @@ static gsl_sinterp_hip_ctx *interp_ctx0(const gsl_sinterp *interp)
     const simplex_state *st = (const simplex_state *)interp->state;
     return st->dev ? st->dev->ctx : NULL;
   }
+  if (is_natural_type(interp->type)) {
+    const mesh_state *st = (const mesh_state *)interp->state;
+    return st->dev ? st->dev->ctx : NULL;
+  }
   return ((const rbf_state *)interp->state)->ctx;
 }
 
@@ -2393,6 +2595,7 @@ int gsl_sinterp_eval_grid(const gsl_sinterp *interp, const gsl_vector *min, cons
   free(h_s);
   HIP_TRY(st, c);
   if (interp->type == &simplex_type && n_nan) GSL_ERROR("gsl_sinterp_eval_grid: grid node(s) outside the caging simplex", GSL_EDOM);
+  if (is_natural_type(interp->type) && n_nan) GSL_ERROR("gsl_sinterp_eval_grid: grid node(s) outside the triangulation", GSL_EDOM);
   return GSL_SUCCESS;
 }
 
@@ -2428,6 +2631,8 @@ static int type_id(const gsl_sinterp_type *T)
   if (T == &imq_type) return 9;
   if (T == &krige_matern32_type) return 10;
   if (T == &krige_matern52_type) return 11;
+  if (T == &natural_mesh_type) return 12;                 /* 12 / 13: natural neighbours, with the payload of type 6 */
+  if (T == &natural_simplex_type) return 13;
   return T == &gauss_type ? 0 : (T == &tps_type ? 1 : (T == &wendland_type ? 3 : (T == &krige_type ? 4 : (T == &tps_affine_type ? 5 : (T == &mesh_type ? 6 : 2)))));
 }
 
@@ -2452,7 +2657,7 @@ int gsl_sinterp_fwrite(FILE *stream, const gsl_sinterp *interp)
     }
     return GSL_SUCCESS;
   }
-  if (interp->type == &mesh_type) {
+  if (is_mesh_state_type(interp->type)) {
     const mesh_state *st = (const mesh_state *)interp->state;
     if (!st->dev || !st->mesh || !st->x || !st->f) GSL_ERROR("gsl_sinterp_fwrite: interpolant not initialised", GSL_EINVAL);
     const double eps = 0.0;
@@ -2525,7 +2730,7 @@ int gsl_sinterp_fread(FILE *stream, gsl_sinterp *interp)
     interp->init_flags = (int)flags;
     return simplex_mirror(interp, st);                  /* upload + pack + bind: no triangulation */
   }
-  if (interp->type == &mesh_type) {
+  if (is_mesh_state_type(interp->type)) {
     mesh_state *st = (mesh_state *)interp->state;
     simplex_mesh *mesh = simplex_mesh_fread(stream);
     if (!mesh) return GSL_EFAILED;
@@ -2548,7 +2753,8 @@ int gsl_sinterp_fread(FILE *stream, gsl_sinterp *interp)
     simplex_mesh_device_free(st->dev); st->dev = NULL;
     simplex_mesh_free(st->mesh); gsl_matrix_free(st->x); gsl_vector_free(st->f);
     st->mesh = mesh; st->x = x; st->f = f;
-    return mesh_type_mirror(interp, st);                /* upload + pack + bind: nothing is re-imported */
+    /* upload + pack + bind: nothing is re-imported */
+    return is_natural_type(interp->type) ? natural_type_mirror(interp, st) : mesh_type_mirror(interp, st);
   }
   rbf_state *st = (rbf_state *)interp->state;
   const size_t cnt = st->n * (st->dim + 1);

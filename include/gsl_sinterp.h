@@ -234,6 +234,11 @@ void simplex_mesh_geometry(const simplex_mesh *mesh, double *shift, double *scal
 void simplex_mesh_set_convex(simplex_mesh *mesh, int convex);
 int simplex_mesh_convex(const simplex_mesh *mesh);
 const double *simplex_mesh_points(const simplex_mesh *mesh);    /* [dim n_points], packed rows */
+/* The metric in which a 2-D mesh is locally Delaunay (across every interior edge the neighbour's opposite vertex is not
+   inside the circumcircle by more than 1e-9 relative, in determinant form; flat triangles are skipped): 1 = in the
+   coordinates as given (QHull / CGAL output), 2 = in the mesh's standardised coordinates (simplex_mesh_geometry: a mesh
+   exported from a simplex_tree, whose build standardises per axis), 0 = in neither, and for a 3-D mesh.  O(n). */
+int simplex_mesh_delaunay_metric(const simplex_mesh *mesh);
 void simplex_mesh_bbox(const simplex_mesh *mesh, double *lo, double *hi);   /* dim entries each */
 /* binary checkpoint of a mesh (gsl_matrix_fwrite conventions); fread re-validates ids and neighbour links.  A 2-D mesh
    writes the GSLSMSH1 layout; a 3-D mesh writes GSLSMSH2, whose header carries dim; fread accepts both */
@@ -250,6 +255,16 @@ int simplex_mesh_device_set_response(simplex_mesh_device *dev, const gsl_vector 
 int simplex_mesh_device_eval_many(simplex_mesh_device *dev, const gsl_matrix *targets, gsl_vector *values, int *triangle);
 int simplex_mesh_device_eval_resident(simplex_mesh_device *dev, const double *d_targets, size_t m, size_t ttda,
                                       double *d_values, int *d_triangle);
+/* Natural-neighbour (Sibson) interpolation on the same mirror: C1 away from the sites, exact at them, reproduces linear
+   functions, local, no shape parameter and no solve ("Natural neighbours").  Same shapes and status
+   conventions as the two entries above; `triangle` receives the triangle that contains the target.  A target within
+   rounding of the hull takes the piecewise-linear value, the interpolant's limit there.  Nothing is computed or kept for
+   these entries until the first call: it asks the mesh for its metric (O(n) on the host), uploads its links and points
+   once more and packs the natural-neighbour records, so `mesh` must still be alive then (later calls do not need it).  GSL_EINVAL: simplex_mesh_delaunay_metric is 0 (the mesh is not Delaunay);
+   GSL_EUNSUP: a 3-D mesh, a mesh with convex = 0, a device group of more than one member. */
+int simplex_mesh_device_eval_natural_many(simplex_mesh_device *dev, const gsl_matrix *targets, gsl_vector *values, int *triangle);
+int simplex_mesh_device_eval_natural_resident(simplex_mesh_device *dev, const double *d_targets, size_t m, size_t ttda,
+                                              double *d_values, int *d_triangle);
 gsl_sinterp_hip_ctx *simplex_mesh_device_ctx(simplex_mesh_device *dev);
 
 /* ======================================================================== */
@@ -301,6 +316,19 @@ extern const gsl_sinterp_type *gsl_sinterp_linear_simplex;
 /* piecewise-linear interpolation over an IMPORTED triangulation (QHull / CGAL arrays, README:28-31 future list): set the
    triangles with gsl_sinterp_set_triangulation before gsl_sinterp_init(x, f); `leaf` of eval_many = triangle index */
 extern const gsl_sinterp_type *gsl_sinterp_linear_mesh;
+/* natural-neighbour (Sibson) interpolation, dim 2 only: C1 except at the data sites, exact at them, reproduces linear
+   functions, local, no shape parameter and no solve.
+     gsl_sinterp_natural_mesh     over an imported DELAUNAY triangulation, set up like gsl_sinterp_linear_mesh
+                                  (gsl_sinterp_set_triangulation, then init); init gives GSL_EINVAL when
+                                  simplex_mesh_delaunay_metric of the mesh is 0, GSL_EUNSUP when it is not convex;
+     gsl_sinterp_natural_simplex  builds the Delaunay tree on the host exactly as gsl_sinterp_linear_simplex does
+                                  (gsl_sinterp_set_tree_options is honoured), exports it with simplex_mesh_from_tree and
+                                  evaluates on that mesh: no external triangulator is needed.
+   eval_e / eval_many / eval_resident / eval_grid; `leaf` = the triangle of the mesh that contains the target; a target
+   outside the hull gives NaN, -1 and GSL_EDOM.  One device only (a device list of more than one member: GSL_EUNSUP at
+   init).  Gradients, fields, variance, leave-one-out, fit and set_neighbours: GSL_EUNSUP.  Checkpoints: type ids 12 /
+   13 with the mesh payload of gsl_sinterp_linear_mesh. */
+extern const gsl_sinterp_type *gsl_sinterp_natural_mesh, *gsl_sinterp_natural_simplex;
 /* ordinary kriging with a Gaussian covariance exp(-(eps h)^2) and an optional nugget (README:24 future list):
    s(y) = mu + sum_j w_j C(|y - x_j|) with [C + nugget I, 1; 1^T, 0] [w; mu] = [f; 0].  nugget = 0 interpolates the data,
    nugget > 0 smooths (s(x_i) = f_i - nugget w_i); far from the data s -> mu.  gsl_sinterp_set_shape sets eps. */
@@ -455,7 +483,7 @@ int gsl_sinterp_set_rcond(gsl_sinterp *interp, int want);
 int gsl_sinterp_rcond(const gsl_sinterp *interp, double *rcond);
 int gsl_sinterp_route(const gsl_sinterp *interp);
 int gsl_sinterp_set_tree_options(gsl_sinterp *interp, int init_flags, gsl_rng *rng);
-/* gsl_sinterp_linear_mesh (dim 2 or 3): simplices [(dim + 1) n] (vertex = row of x), neighbours [(dim + 1) n] (opposite vertex k,
+/* gsl_sinterp_linear_mesh (dim 2 or 3) and gsl_sinterp_natural_mesh (dim 2): simplices [(dim + 1) n] (vertex = row of x), neighbours [(dim + 1) n] (opposite vertex k,
    -1 = boundary) or NULL (derived by edge / face matching); copied, validated by the next gsl_sinterp_init */
 int gsl_sinterp_set_triangulation(gsl_sinterp *interp, const int *triangles, const int *neighbours, size_t n_triangles);
 int gsl_sinterp_init(gsl_sinterp *interp, const gsl_matrix *x, const gsl_vector *f);

@@ -168,6 +168,27 @@ int gsl_sinterp_hip_mesh3_eval(gsl_sinterp_hip_ctx *ctx, int n_tet, const void *
                                const int *d_seed, int G, const double *h_geom, int convex, const double *d_targets,
                                size_t m, size_t ttda, double *d_values, int *d_tet, long long *h_n_outside);
 
+/* Natural-neighbour (Sibson) interpolation on a 2-D Delaunay mesh (csrc/hip/natural.hip; DESIGN.md 4, "Natural
+   neighbours").  natural_pack: one 80-byte, 16-byte-aligned record per triangle in METRIC coordinates (raw coordinate
+   times h_metric[axis]: {1, 1} for a mesh that is Delaunay as given, the mesh's per-axis scale for one that is Delaunay
+   in standardised coordinates): vertices reordered counter-clockwise with the neighbour slots permuted to match, the
+   circumcentre, a flat flag.  d_nnrec holds n_tri + 1 records; the last one carries the metric.  d_tri / d_nbr /
+   d_points as for gsl_sinterp_hip_mesh_pack.
+   natural_eval: d_located [m] = the triangle of every target and d_linear_values [m] = its piecewise-linear value, both
+   as gsl_sinterp_hip_mesh_eval stored them for the same targets (run it first); d_leaftab = the response table of
+   gsl_sinterp_hip_tree_bind.  d_values may be d_linear_values.  One lane per target walks the cavity; depth_cap = the
+   pending triangles a lane may hold (0 = the default, GSL_SINTERP_NATURAL_STACK, also the maximum); a target that needs
+   more is evaluated by a scan over all triangles, and *h_n_scanned (may be NULL; forces a sync when given) counts
+   those.  A target on a site returns the datum; one within rounding of the hull returns the linear value; d_located
+   < 0 gives NaN. */
+#define GSL_SINTERP_NATURAL_RECORD_BYTES 80
+#define GSL_SINTERP_NATURAL_STACK 16
+int gsl_sinterp_hip_mesh_natural_pack(gsl_sinterp_hip_ctx *ctx, int n_tri, const int *d_tri, const int *d_nbr, int n_points,
+                                      const double *d_points, const double *h_metric, void *d_nnrec);
+int gsl_sinterp_hip_mesh_natural_eval(gsl_sinterp_hip_ctx *ctx, int n_tri, const void *d_nnrec, const void *d_leaftab,
+                                      const int *d_located, const double *d_linear_values, const double *d_targets, size_t m,
+                                      size_t ttda, int depth_cap, double *d_values, long long *h_n_scanned);
+
 /* Device-side integrity checks of a DAG given as raw arrays (same arguments as tree_pack):
    what & 1: _check_leaf_nodes  (interpolation/linear_simplex_integrity_check.c:62-119), one thread per leaf;
    what & 2: _check_delaunay    (:134-160; circumsphere per linear_simplex.c:555-605), leaves x points.
