@@ -817,13 +817,13 @@ extern "C" int gsl_sinterp_hip_tree_pack(gsl_sinterp_hip_ctx *ctx, int n_nodes, 
      built once here; evaluations of these records on this context start their walks from it */
   /* certified leaf walk: seed grid + per-leaf line lists + margin constants (see "Certified leaf walk") */
   ctx->lw_rec = NULL;
-  static const bool no_lw = getenv("GSL_SINTERP_NO_LEAFWALK") && getenv("GSL_SINTERP_NO_LEAFWALK")[0] == '1';
+  const bool no_lw = SINTERP_ENV_ONCE("GSL_SINTERP_NO_LEAFWALK");
   if (!no_lw && n_nodes >= 2048 && n_points >= 3 && d_points) {
     int st = lw_build(ctx, n_nodes, d_type, d_pidx, d_links, n_points, d_points, g, (const NodeRec *)d_records);
     if (st) return st;
   }
   ctx->jump_rec = NULL;
-  static const bool no_jump = getenv("GSL_SINTERP_NO_JUMP") && getenv("GSL_SINTERP_NO_JUMP")[0] == '1';
+  const bool no_jump = SINTERP_ENV_ONCE("GSL_SINTERP_NO_JUMP");
   if (!no_jump && n_nodes >= 2048 && n_points >= 3 && d_points) {
     int G = 32;
     /* cells per node: what stops the descent of a cell is a HISTORIC edge crossing it (flips leave them all over the final
@@ -831,21 +831,21 @@ extern "C" int gsl_sinterp_hip_tree_pack(gsl_sinterp_hip_ctx *ctx, int n_nodes, 
        per step): G = 2048: 1.94 ms, 4096 (40 cells per node, the round-2 rule): 1.67, 8192: 1.57, 16384: 1.61 (the table no
        longer stays in the Infinity Cache).  90 cells per node, at most 8192^2 (256 MB; built coarse-to-fine once per tree, 14.5 ms at C5).
        Developer knobs: GSL_SINTERP_JUMP_GMAX / GSL_SINTERP_JUMP_FACTOR */
-    const int gcap = getenv("GSL_SINTERP_JUMP_GMAX") ? atoi(getenv("GSL_SINTERP_JUMP_GMAX")) : 8192;
+    const int gcap = sinterp_env_int("GSL_SINTERP_JUMP_GMAX", 8192);
     /* with the leaf walk in place the table only starts the exact kernel on the ~1 % of a batch the margin test leaves (and on
        batches below 4096 targets): a quarter of the cells builds in a third of the time (12.8 -> 4 ms at C5), same step time.
        (A sixteenth: 19.6 ms for the whole pack, step unchanged as well; the quarter keeps small batches closer to their leaf.)
        Also measured with the leaf walk: its steps decided with the affine walk records (6 flops a test, no divide) and only the
        final leaf solved exactly -- 1.217 vs 1.228 ms per step, bit-identical; the walk is not bound by the solves, not kept. */
     const bool lw_ok = ctx->lw_rec == d_records && ctx->d_lw_lines != NULL;
-    const double gfac = getenv("GSL_SINTERP_JUMP_FACTOR") ? atof(getenv("GSL_SINTERP_JUMP_FACTOR")) : (lw_ok ? JUMP_CELLS_PER_NODE / 4.0 : (double)JUMP_CELLS_PER_NODE);
+    const double gfac = sinterp_env_double("GSL_SINTERP_JUMP_FACTOR", lw_ok ? JUMP_CELLS_PER_NODE / 4.0 : (double)JUMP_CELLS_PER_NODE);
     while (G < gcap && G < 512 && (double)(2 * G) * (2 * G) <= gfac * (double)n_nodes) G *= 2;
     if (G >= 512) {                                      /* above 512: multiples of 512 (the coarser levels divide by 4) */
       const int want = (int)(sqrt(gfac * (double)n_nodes) / 512.0) * 512;
       G = want < 512 ? 512 : (want > gcap ? gcap : want);
     }
     /* levels of the hierarchical build: ..., G / 16, G / 4, G (the coarser tables live behind the final one) */
-    static const bool flat = getenv("GSL_SINTERP_JUMP_FLAT") && getenv("GSL_SINTERP_JUMP_FLAT")[0] == '1';   /* developer: every cell from the root */
+    const bool flat = SINTERP_ENV_ONCE("GSL_SINTERP_JUMP_FLAT");   /* developer: every cell from the root */
     int lev[8], nlev = 0;
     lev[nlev++] = G;
     if (!flat) while (nlev < 8 && lev[nlev - 1] >= 512) { lev[nlev] = lev[nlev - 1] / 4; nlev++; }
@@ -1572,7 +1572,7 @@ static int lw_build(gsl_sinterp_hip_ctx *ctx, int n_nodes, const int *d_type, co
                      big, big_cap, consts);
   hipLaunchKernelGGL(lw_region_kernel, dim3(512), dim3(256), 0, ctx->stream, n_nodes, d_pidx, n_points, d_points, g, d_records,
                      (const unsigned long long *)own, (const unsigned *)big, lb, relax);
-  if (getenv("GSL_SINTERP_LW_DEBUG") && getenv("GSL_SINTERP_LW_DEBUG")[0] == '1') {
+  if (sinterp_env_flag("GSL_SINTERP_LW_DEBUG")) {
     unsigned np_ = 0;
     HIP_OK(ctx, hipStreamSynchronize(ctx->stream));
     (void)hipMemcpy(&np_, big, sizeof np_, hipMemcpyDeviceToHost);
@@ -1608,7 +1608,7 @@ static int lw_build(gsl_sinterp_hip_ctx *ctx, int n_nodes, const int *d_type, co
   HIP_OK(ctx, hipStreamSynchronize(ctx->stream));
   HIP_OK(ctx, hipMemcpy(hc, consts, 32, hipMemcpyDeviceToHost));
   HIP_OK(ctx, hipMemcpy(&total, off + n_nodes, sizeof total, hipMemcpyDeviceToHost));
-  static const bool dbg = getenv("GSL_SINTERP_LW_DEBUG") && getenv("GSL_SINTERP_LW_DEBUG")[0] == '1';
+  const bool dbg = SINTERP_ENV_ONCE("GSL_SINTERP_LW_DEBUG");
   if (dbg) {
     unsigned nbig = 0;
     (void)hipMemcpy(&nbig, big, sizeof nbig, hipMemcpyDeviceToHost);
@@ -1645,8 +1645,8 @@ static int bary_eval_part(gsl_sinterp_hip_ctx *ctx, int n_nodes, const void *d_r
                           const double *d_targets, size_t m, size_t ttda, double *d_values, int *d_leaf, unsigned long long *d_count,
                           const WalkRec *wrec, char *wsec, size_t m_cap, int slot, bool inner_side)
 {
-  static const bool no_fast = getenv("GSL_SINTERP_NO_FASTDIV") && getenv("GSL_SINTERP_NO_FASTDIV")[0] == '1';
-  const bool will_sort = m >= 4096 && !(getenv("GSL_SINTERP_NO_SORT") && getenv("GSL_SINTERP_NO_SORT")[0] == '1');
+  const bool no_fast = SINTERP_ENV_ONCE("GSL_SINTERP_NO_FASTDIV");
+  const bool will_sort = m >= 4096 && !sinterp_env_flag("GSL_SINTERP_NO_SORT");
   const bool use_walk = wrec != NULL;
   ctx->lw_last = 0;
   const unsigned n_slices = (unsigned)((m + WALK_SLICE - 1) / WALK_SLICE);
@@ -1664,13 +1664,13 @@ static int bary_eval_part(gsl_sinterp_hip_ctx *ctx, int n_nodes, const void *d_r
     wl.y = (double2 *)(wsec + o_y); wl.st = (int4 *)(wsec + o_st); wl.k = (int *)(wsec + o_k); wl.count = (unsigned *)(wsec + o_sc);
     HIP_OK(ctx, hipMemsetAsync(todo_count, 0, 64, ctx->stream));
   }
-  static const bool no_jump = getenv("GSL_SINTERP_NO_JUMP") && getenv("GSL_SINTERP_NO_JUMP")[0] == '1';
+  const bool no_jump = SINTERP_ENV_ONCE("GSL_SINTERP_NO_JUMP");
   const bool have_table = !no_jump && ctx->jump_rec == d_records && ctx->jump_nodes == n_nodes && ctx->d_jumpt;
   sinterp_sorted srt;
   bool sorted = false;
   if (will_sort) {
     /* bin by the data's bounding box when tree_pack kept one for these records: saves the pass over the targets */
-    const int per_cell = getenv("GSL_SINTERP_BARY_PER_CELL") ? atoi(getenv("GSL_SINTERP_BARY_PER_CELL")) : 64;   /* developer */
+    const int per_cell = sinterp_env_int("GSL_SINTERP_BARY_PER_CELL", 64);   /* developer */
     int st = sinterp_sort_reorder(ctx, d_targets, m, ttda, 2, per_cell, &srt, m_cap, slot,
                                   have_table ? (const unsigned long long *)ctx->d_jumpt : (const unsigned long long *)NULL);
     if (st) return st;
@@ -1725,8 +1725,8 @@ static int bary_eval_part(gsl_sinterp_hip_ctx *ctx, int n_nodes, const void *d_r
     const int cus = s_cus[dv];
     int per_cu = s_per_cu[dv];
     int batch = WALK_BATCH;
-    if (getenv("GSL_SINTERP_WALK_WGS_PER_CU")) per_cu = atoi(getenv("GSL_SINTERP_WALK_WGS_PER_CU")) > 0 ? atoi(getenv("GSL_SINTERP_WALK_WGS_PER_CU")) : per_cu;
-    if (getenv("GSL_SINTERP_WALK_BATCH")) batch = atoi(getenv("GSL_SINTERP_WALK_BATCH")) > 0 ? atoi(getenv("GSL_SINTERP_WALK_BATCH")) : batch;
+    if (sinterp_env_int("GSL_SINTERP_WALK_WGS_PER_CU", 0) > 0) per_cu = sinterp_env_int("GSL_SINTERP_WALK_WGS_PER_CU", 0);
+    if (sinterp_env_int("GSL_SINTERP_WALK_BATCH", 0) > 0) batch = sinterp_env_int("GSL_SINTERP_WALK_BATCH", 0);
     size_t wblocks = (size_t)(cus > 0 ? cus : 256) * (size_t)per_cu;
     if (wblocks > n_slices) wblocks = n_slices;
     hipLaunchKernelGGL(bary_walk_kernel, dim3((unsigned)wblocks), dim3(64), 0, ctx->stream, (const WalkRec *)wrec, wl, n_slices,
@@ -1780,7 +1780,7 @@ extern "C" int gsl_sinterp_hip_bary_last_queue(gsl_sinterp_hip_ctx *ctx, unsigne
 static int bary_eval_leafwalk(gsl_sinterp_hip_ctx *ctx, int n_nodes, const void *d_records, const void *d_leaftab, const double *h_scale,
                               const double *d_targets, size_t m, size_t ttda, double *d_values, int *d_leaf, unsigned long long *d_count)
 {
-  static const bool no_jump = getenv("GSL_SINTERP_NO_JUMP") && getenv("GSL_SINTERP_NO_JUMP")[0] == '1';
+  const bool no_jump = SINTERP_ENV_ONCE("GSL_SINTERP_NO_JUMP");
   const bool have_table = !no_jump && ctx->jump_rec == d_records && ctx->jump_nodes == n_nodes && ctx->d_jumpt;
   sinterp_sorted srt;
   int st = sinterp_sort_reorder(ctx, d_targets, m, ttda, 2, 64, &srt, m, -1,
@@ -1796,9 +1796,9 @@ static int bary_eval_leafwalk(gsl_sinterp_hip_ctx *ctx, int n_nodes, const void 
   double *vt = via_map ? srt.res1 : srt.vs;
   int *lt = via_map ? (int *)srt.inv : (int *)NULL;
   const int packed = (d_leaf != NULL ? 1 : 0) | (via_map ? 2 : 0);
-  static const int lw_slices_env = getenv("GSL_SINTERP_LW_SLICES") ? atoi(getenv("GSL_SINTERP_LW_SLICES")) : 0;   /* developer: 1 .. 8 */
+  static const int lw_slices_env = sinterp_env_int("GSL_SINTERP_LW_SLICES", 0);   /* developer: 1 .. 8 */
   const int lw_slices = lw_slices_env >= 1 && lw_slices_env <= LW_SLICES ? lw_slices_env : 1;
-  static const double lwF = getenv("GSL_SINTERP_LW_F") ? atof(getenv("GSL_SINTERP_LW_F")) : 4.0;   /* developer */
+  static const double lwF = sinterp_env_double("GSL_SINTERP_LW_F", 4.0);   /* developer */
   ctx->lw_last = 1;
   LwGrid lg;
   lg.lo0 = ctx->lw_lo[0]; lg.lo1 = ctx->lw_lo[1]; lg.w0 = ctx->lw_w[0]; lg.w1 = ctx->lw_w[1]; lg.G = ctx->lw_Gs;
@@ -1833,12 +1833,12 @@ extern "C" int gsl_sinterp_hip_bary_eval(gsl_sinterp_hip_ctx *ctx, int n_nodes, 
   HIP_OK(ctx, hipMemsetAsync(d_count, 0, sizeof(unsigned long long), ctx->stream));
   /* m >= 4096: the targets are gathered into grid-cell order, swept contiguously, and the results
      un-sorted afterwards (see sinterp_sort_reorder) */
-  static const bool no_fast = getenv("GSL_SINTERP_NO_FASTDIV") && getenv("GSL_SINTERP_NO_FASTDIV")[0] == '1';
-  static const bool no_affine = getenv("GSL_SINTERP_NO_AFFINE_WALK") && getenv("GSL_SINTERP_NO_AFFINE_WALK")[0] == '1';
-  static const bool no_side = getenv("GSL_SINTERP_NO_SIDE_STREAM") && getenv("GSL_SINTERP_NO_SIDE_STREAM")[0] == '1';
-  const bool will_sort = m >= 4096 && !(getenv("GSL_SINTERP_NO_SORT") && getenv("GSL_SINTERP_NO_SORT")[0] == '1');
+  const bool no_fast = SINTERP_ENV_ONCE("GSL_SINTERP_NO_FASTDIV");
+  const bool no_affine = SINTERP_ENV_ONCE("GSL_SINTERP_NO_AFFINE_WALK");
+  const bool no_side = SINTERP_ENV_ONCE("GSL_SINTERP_NO_SIDE_STREAM");
+  const bool will_sort = m >= 4096 && !sinterp_env_flag("GSL_SINTERP_NO_SORT");
   /* batches in cell order on records this context packed: the certified leaf walk (round 4) */
-  static const bool no_lw = getenv("GSL_SINTERP_NO_LEAFWALK") && getenv("GSL_SINTERP_NO_LEAFWALK")[0] == '1';
+  const bool no_lw = SINTERP_ENV_ONCE("GSL_SINTERP_NO_LEAFWALK");
   if (!no_lw && !no_fast && will_sort && m < 0x7fffffffULL && ctx->lw_rec == d_records && ctx->lw_nodes == n_nodes && ctx->d_lw_lines) {
     int st = bary_eval_leafwalk(ctx, n_nodes, d_records, d_leaftab, h_scale, d_targets, m, ttda, d_values, d_leaf, d_count);
     if (st) return st;
@@ -2148,7 +2148,7 @@ extern "C" int gsl_sinterp_hip_mesh_eval(gsl_sinterp_hip_ctx *ctx, int n_tri, co
   mg.lo0 = h_geom[4]; mg.lo1 = h_geom[5]; mg.w0 = (h_geom[6] - h_geom[4]) / G; mg.w1 = (h_geom[7] - h_geom[5]) / G; mg.G = G;
   /* batches of >= 4096 targets: the DAG path's reorder (cell order, two-level from 2^18 targets), results through the
      order's map, un-sorted afterwards.  A result depends on (mesh, target) only: same bits either way. */
-  const bool will_sort = m >= 4096 && !(getenv("GSL_SINTERP_NO_SORT") && getenv("GSL_SINTERP_NO_SORT")[0] == '1');
+  const bool will_sort = m >= 4096 && !sinterp_env_flag("GSL_SINTERP_NO_SORT");
   sinterp_sorted srt;
   if (will_sort) {
     st = sinterp_sort_reorder(ctx, d_targets, m, ttda, 2, 64, &srt, m, -1, (const unsigned long long *)NULL);

@@ -405,13 +405,21 @@ static size_t chol_split(size_t w)
 static int g_chol_riders_last = 0;
 extern "C" int gsl_sinterp_hip_debug_chol_riders(void) { return __atomic_load_n(&g_chol_riders_last, __ATOMIC_RELAXED); }
 
-/* the rider route (DESIGN.md section 6, round 6): the update in front of a leaf factors that leaf's diagonal block on one
-   extra workgroup of its own launch.  Needs the layout in which every leaf is a 128-wide panel written straight into A. */
-static bool chol_rider_applicable(size_t n, const double *d_a, size_t lda)
+/* the 128-wide panel kernels are on (one read of the switch for the whole file) */
+static bool chol_panel128_on(void) { return !SINTERP_ENV_ONCE("GSL_SINTERP_NO_PANEL128"); }
+
+/* every leaf of the recursion is a 128-wide panel written straight into A: no side copy of the diagonal blocks, no
+   write-back launch; the layout the rider and the folded forward substitution need */
+static bool chol_all128(size_t n, const double *d_a, size_t lda)
 {
-  static const bool no_p128 = getenv("GSL_SINTERP_NO_PANEL128") && getenv("GSL_SINTERP_NO_PANEL128")[0] == '1';
-  static const bool no_rider = getenv("GSL_SINTERP_NO_DIAG_RIDER") && getenv("GSL_SINTERP_NO_DIAG_RIDER")[0] == '1';
-  return !no_p128 && !no_rider && n >= 2 * PB && n % PB == 0 && (lda & 1) == 0 && ((((uintptr_t)d_a) & 15) == 0);
+  return chol_panel128_on() && n % PB == 0 && (lda & 1) == 0 && ((((uintptr_t)d_a) & 15) == 0);
+}
+
+/* the rider route (DESIGN.md section 6, round 6): the update in front of a leaf factors that leaf's diagonal block on one
+   extra workgroup of its own launch */
+static bool chol_rider_applicable(bool all128, size_t n)
+{
+  return all128 && !SINTERP_ENV_ONCE("GSL_SINTERP_NO_DIAG_RIDER") && n >= 2 * PB;
 }
 
 /* fb != NULL: nrhs right-hand sides (fb + q * ldf) ride along -- only ever passed when every leaf of the recursion is a
@@ -422,9 +430,8 @@ static int chol_panel(gsl_sinterp_hip_ctx *ctx, double *A, size_t lda, size_t n,
                       double *d_diag, double *fb, size_t ldf, int nrhs, unsigned *d_cnt, bool diag_done)
 {
   int st;
-  static const bool no_p128 = getenv("GSL_SINTERP_NO_PANEL128") && getenv("GSL_SINTERP_NO_PANEL128")[0] == '1';
   double *d_linv = d_diag + ((n + CB - 1) / CB) * (CB * CB);   /* 4 inverted 32x32 blocks */
-  if (w == PB && !no_p128 && (lda & 1) == 0 && ((((uintptr_t)(A + j0 * lda + j0)) & 15) == 0)) {
+  if (w == PB && chol_panel128_on() && (lda & 1) == 0 && ((((uintptr_t)(A + j0 * lda + j0)) & 15) == 0)) {
     const size_t lds_diag = DIAG128_LDS_BYTES;
     { int ast = sinterp_func_lds(ctx, (const void *)chol_diag128_kernel, (int)lds_diag); if (ast) return ast; }
     /* every panel of this factorisation is 128 wide (n a multiple of 128): the blocks are written straight into A and the
@@ -436,7 +443,7 @@ static int chol_panel(gsl_sinterp_hip_ctx *ctx, double *A, size_t lda, size_t n,
     if (below) {
       /* 16 rows per workgroup while that is at most about one workgroup per CU, 64-row strips above
          (developer override: GSL_SINTERP_TRSM_RF = 1, 2, 4 forces the 16 RF-row kernel, 64 the strip kernel) */
-      static const int force_rf = getenv("GSL_SINTERP_TRSM_RF") ? atoi(getenv("GSL_SINTERP_TRSM_RF")) : 0;
+      static const int force_rf = sinterp_env_int("GSL_SINTERP_TRSM_RF", 0);
       int ast = 0;
       if (force_rf == 1 || (!force_rf && below <= 4096)) ast = launch_trsm16<1>(ctx, A, lda, n, j0, d_linv, j0 + PB, fb, ldf, nrhs);
       else if (force_rf == 2) ast = launch_trsm16<2>(ctx, A, lda, n, j0, d_linv, j0 + PB, fb, ldf, nrhs);
@@ -481,11 +488,9 @@ static int chol_panel(gsl_sinterp_hip_ctx *ctx, double *A, size_t lda, size_t n,
 }
 
 /* every leaf of the recursion is a 128-wide panel: the forward substitution can ride along */
-static bool chol_fold_applicable(size_t n, const double *d_a, size_t lda, int nrhs)
+static bool chol_fold_applicable(bool all128, int nrhs)
 {
-  static const bool no_p128 = getenv("GSL_SINTERP_NO_PANEL128") && getenv("GSL_SINTERP_NO_PANEL128")[0] == '1';
-  static const bool no_fold = getenv("GSL_SINTERP_NO_FOLD") && getenv("GSL_SINTERP_NO_FOLD")[0] == '1';
-  return !no_p128 && !no_fold && nrhs >= 1 && nrhs <= TRSV_MAXR && n >= PB && n % PB == 0 && (lda & 1) == 0 && ((((uintptr_t)d_a) & 15) == 0);
+  return all128 && !SINTERP_ENV_ONCE("GSL_SINTERP_NO_FOLD") && nrhs >= 1 && nrhs <= TRSV_MAXR;
 }
 
 
@@ -545,10 +550,11 @@ static int cholesky_decomp1_impl(gsl_sinterp_hip_ctx *ctx, size_t n, double *d_a
   int st = sinterp_workspace(ctx, diag_doubles * sizeof(double) + (n_pan + 4) * sizeof(unsigned), &d_diag);
   if (st) return st;
   unsigned *d_cnt = (unsigned *)((double *)d_diag + diag_doubles);   /* the riders' counters */
-  const bool riders = chol_rider_applicable(n, d_a, lda);
+  const bool all128 = chol_all128(n, d_a, lda);
+  const bool riders = chol_rider_applicable(all128, n);
   st = sinterp_streamk_prepare(ctx);
   if (st) return st;
-  const bool fold = fb != NULL && chol_fold_applicable(n, d_a, lda, nrhs) && ldf >= n;
+  const bool fold = fb != NULL && chol_fold_applicable(all128, nrhs) && ldf >= n;
   if (!fold) { fb = NULL; ldf = 0; nrhs = 0; }
   int replayed = 0;
   /* graph key: the matrix, and the right-hand sides (buffer, stride, count) and input form baked into the kernels */
@@ -567,13 +573,9 @@ static int cholesky_decomp1_impl(gsl_sinterp_hip_ctx *ctx, size_t n, double *d_a
     const unsigned nt = (unsigned)((n + 31) / 32);
     if (!symmetric_input) hipLaunchKernelGGL(tricpy_lower_to_upper_kernel, dim3(nt, nt), dim3(256), 0, ctx->stream, d_a, lda, n);
     st = chol_panel(ctx, d_a, lda, n, 0, n, d_info, (double *)d_diag, fb, ldf, nrhs, riders ? d_cnt : NULL, false);
-    {
-      static const bool no_p128w = getenv("GSL_SINTERP_NO_PANEL128") && getenv("GSL_SINTERP_NO_PANEL128")[0] == '1';
-      const bool all128 = !no_p128w && n % PB == 0 && (lda & 1) == 0 && ((((uintptr_t)d_a) & 15) == 0);
-      if (!all128)
-        hipLaunchKernelGGL(chol_diag_writeback_kernel, dim3((unsigned)nblk), dim3(256), 0, ctx->stream, d_a, lda, n,
-                           (const double *)d_diag);
-    }
+    if (!all128)
+      hipLaunchKernelGGL(chol_diag_writeback_kernel, dim3((unsigned)nblk), dim3(256), 0, ctx->stream, d_a, lda, n,
+                         (const double *)d_diag);
     int st2 = sinterp_capture_end(ctx, saved, 0, gkey);
     if (me != hipSuccess) return sinterp_fail(ctx, ST_EFAILED, "zero info", me, __FILE__, __LINE__);
     if (st) return st;
@@ -1104,7 +1106,7 @@ static int trsv_launches(gsl_sinterp_hip_ctx *ctx, size_t n, const double *T, si
     hipLaunchKernelGGL(tri_inv_kernel, dim3((unsigned)nblk), dim3(64), 0, ctx->stream, T, ldt, n, mode == 2 ? 1 : 0, unit, d_inv);
     LAUNCH_CHECK(ctx);
   }
-  static const bool no_df = getenv("GSL_SINTERP_NO_DATAFLOW_TRSV") && getenv("GSL_SINTERP_NO_DATAFLOW_TRSV")[0] == '1';
+  const bool no_df = SINTERP_ENV_ONCE("GSL_SINTERP_NO_DATAFLOW_TRSV");
   if (use_inv && !no_df && ctx->sk_wgs > 0 && ctx->d_tf && ctx->tf_count >= nblk + 1 && ctx->d_xq) {
     const unsigned G = (unsigned)(nblk < (size_t)ctx->sk_wgs ? nblk : (size_t)ctx->sk_wgs);
     hipLaunchKernelGGL(trsv_dataflow_kernel, dim3(G), dim3(256), 0, ctx->stream, T, ldt, n, (const double *)b, xout, ldb, nrhs, mode,

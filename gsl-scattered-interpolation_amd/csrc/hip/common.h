@@ -6,6 +6,7 @@
 
 #include <hip/hip_runtime.h>
 #include <stdio.h>
+#include <stdlib.h>
 #include <string.h>
 #include "gsl_sinterp_hip.h"
 
@@ -123,6 +124,14 @@ static inline int sinterp_fail(gsl_sinterp_hip_ctx *ctx, int status, const char 
 #define LAUNCH_CHECK(ctx) HIP_OK(ctx, hipGetLastError())
 
 static inline size_t round_up(size_t v, size_t to) { return (v + to - 1) / to * to; }
+
+/* The GSL_SINTERP_* switches.  A flag is on iff its value begins with '1'.  These three read
+   the environment at every call -- for the switches that tests flip inside one process; SINTERP_ENV_ONCE is the flag
+   read once per process, the first time control reaches the site (a static of its own per site). */
+static inline bool sinterp_env_flag(const char *name) { const char *v = getenv(name); return v && v[0] == '1'; }
+static inline int sinterp_env_int(const char *name, int dflt) { const char *v = getenv(name); return v ? atoi(v) : dflt; }
+static inline double sinterp_env_double(const char *name, double dflt) { const char *v = getenv(name); return v ? atof(v) : dflt; }
+#define SINTERP_ENV_ONCE(name) ([] { static const bool on = sinterp_env_flag(name); return on; }())
 
 /* hipFuncAttributeMaxDynamicSharedMemorySize is a PER-DEVICE attribute of a kernel: set it once per
    (kernel, device) pair (a process-wide flag would leave the second device of a process without it) */

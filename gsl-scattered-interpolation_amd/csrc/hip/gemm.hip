@@ -23,10 +23,9 @@
 #include <stdlib.h>
 #include <string.h>
 #include "chol_potrf.h"
+#include "gemm_plan.h"           /* GT_BM / GT_BN / GT_BK, DM_STAGES, SK_*: the tile constants the dispatch rule shares */
 
-#define GT_BM 128
-#define GT_BN 128
-#define GT_BK 16
+static_assert(GEMM_RIDER_LDS == DIAG128_LDS_BYTES + 16, "gemm_plan.h: the rider's LDS image");
 #define GT_LDA (GT_BK + 2)      /* 18 */
 #define GT_LDBN (GT_BN + 16)    /* 144 */
 #define GT_ASZ (GT_BM * GT_LDA) /* 2304 doubles */
@@ -195,8 +194,7 @@ gemm_minus_kernel(GemmArgs g)
    LDS image per stage and operand: 128 rows x 16 doubles, unpadded (a DMA wave-instruction writes
    1 KiB linearly = 8 rows), 16-byte slot index XOR-swizzled with (row>>1)&7 -- applied to the
    per-lane SOURCE address of the DMA and to the fragment read, so the (row = lane&15,
-   k = lane>>4) ds_read_b64 stays bank-conflict free. */
-#define DM_STAGES 3
+   k = lane>>4) ds_read_b64 stays bank-conflict free.  DM_STAGES (gemm_plan.h) is the ring depth. */
 
 __device__ __forceinline__ void dma16(const double *gsrc, double *ldst)
 {
@@ -410,7 +408,6 @@ struct RiderArgs {
   unsigned *counter, *abort_word;
   unsigned need;                /* covering tiles: tile 0 (256x128, 128x128), tiles 0..2 (64x64) */
 };
-#define SK_PRI_SLOTS 32          /* K-slices of priority tiles per launch */
 #define RIDER_MAX_POLLS (1u << 22)   /* x (>= 0.5 us sleep + one L2 miss): seconds, the longest update takes milliseconds */
 
 /* Launched as the LAST workgroup of the update (all owners are resident before it).  One lane polls the panel's counter
@@ -844,8 +841,7 @@ gemm_minus_streamk_kernel(GemmArgs g, StreamK x, RiderArgs rd)
 int sinterp_streamk_prepare(gsl_sinterp_hip_ctx *ctx)
 {
   if (ctx->sk_wgs) return ST_SUCCESS;
-  static const bool off = getenv("GSL_SINTERP_NO_STREAMK") && getenv("GSL_SINTERP_NO_STREAMK")[0] == '1';
-  if (off) return ST_SUCCESS;
+  if (SINTERP_ENV_ONCE("GSL_SINTERP_NO_STREAMK")) return ST_SUCCESS;
   int cus = 0;
   HIP_OK(ctx, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device));
   if (cus <= 0) return ST_SUCCESS;
@@ -929,42 +925,50 @@ gemm_minus_smallk_kernel(GemmArgs g)
     }
 }
 
-/* Tile configurations of the stream-K update (the values of GSL_SINTERP_GEMM_CFG) */
-enum { SK_256 = 0,      /* 256x128, 8 waves of 64x64 */
-       SK_128 = 1,      /* 128x128, 4 waves of 64x64 */
-       SK_64 = 2,       /* 64x64,   4 waves of 32x32 (4-step groups when K allows) */
-       SK_128W8 = 5,    /* 128x128, 8 waves of 64x32 */
-       SK_64W8G = 6 };  /* 64x64,   8 waves of 32x16, 4-step groups */
-static inline int sk_tile(int cfg) { return cfg == SK_128 || cfg == SK_128W8 ? 128 : cfg == SK_256 ? 256 : 64; }
-
-template <int BM, int BN, int WM, int WN, int SS = 1, int ST = DM_STAGES, bool PIPE = false, bool RIDER = false>
-static int launch_sk(gsl_sinterp_hip_ctx *ctx, unsigned G, const GemmArgs &h, const StreamK &x, const RiderArgs &rd = RiderArgs())
-{
-  constexpr int NT = (BM / WM) * (BN / WN) * 64;
-  size_t lds = (size_t)ST * SS * (BM + BN) * GT_BK * sizeof(double);
-  if (RIDER && lds < DIAG128_LDS_BYTES + 16) lds = DIAG128_LDS_BYTES + 16;   /* the rider's potrf128 image + its poll result */
-  { int ast = sinterp_func_lds(ctx, (const void *)gemm_minus_streamk_kernel<BM, BN, WM, WN, SS, ST, PIPE, false, RIDER>, (int)lds); if (ast) return ast; }
-  hipLaunchKernelGGL((gemm_minus_streamk_kernel<BM, BN, WM, WN, SS, ST, PIPE, false, RIDER>), dim3(G + (RIDER ? 1u : 0u)), dim3(NT), lds, ctx->stream, h, x, rd);
-  LAUNCH_CHECK(ctx);
-  return ST_SUCCESS;
-}
-
-/* the dispatch rule, fitted to every update shape of the N = 4096 / 8192 / 16384 recursions (tools/gemm_cfg_sweep.py,
-   DESIGN.md section 3): the 256x128 tile once every CU gets >= 128 of its K-steps, 64x64 tiles while 128-tiles would
-   fill at most 3/4 of the CUs, 128x128 tiles (8 waves) between; always the hybrid split (whole tiles only lost) */
-template <class TilesOf>
-static int sk_rule(bool can256, TilesOf &tiles_of, unsigned steps, unsigned cus)
-{
-  GemmArgs hh;
-  if (can256 && (unsigned long long)tiles_of(SK_256, hh) * steps >= 128ull * cus) return SK_256;
-  if (4ull * tiles_of(SK_128, hh) <= 3ull * cus) return SK_64W8G;
-  return SK_128W8;
-}
-
 /* the N.T stream-K configuration the last gsl_sinterp_hip_gemm_minus call of the process launched: 2 * cfg + (whole
    tiles only), or -1 for any other kernel (tests/test_gpu_gemm_mid.py checks that GSL_SINTERP_GEMM_CFG took effect) */
 static int g_gemm_last_cfg = -1;
 extern "C" int gsl_sinterp_hip_debug_gemm_last_cfg(void) { return __atomic_load_n(&g_gemm_last_cfg, __ATOMIC_RELAXED); }
+
+/* the switches of the dispatch rule: read once per process, except the developer override GSL_SINTERP_GEMM_CFG
+   ("<cfg>" or "<cfg>w", tools/gemm_cfg_sweep.py), which is read at every call */
+static GemmSwitches gemm_switches(void)
+{
+  static const GemmSwitches once = [] {
+    GemmSwitches s = GemmSwitches();
+    s.no_dma = sinterp_env_flag("GSL_SINTERP_NO_DMA_GEMM");
+    s.no_w8 = sinterp_env_flag("GSL_SINTERP_NO_GEMM8");
+    s.rule_r4 = sinterp_env_flag("GSL_SINTERP_GEMM_RULE_R4");
+    s.no_t64 = sinterp_env_flag("GSL_SINTERP_NO_GEMM64");
+    s.no_group = sinterp_env_flag("GSL_SINTERP_NO_GEMM_GROUP");
+    s.no_pipe = sinterp_env_flag("GSL_SINTERP_NO_GEMM_PIPE");
+    s.no_hybrid = sinterp_env_flag("GSL_SINTERP_NO_HYBRID_SK");
+    s.no_kn = sinterp_env_flag("GSL_SINTERP_NO_KN_STREAMK");
+    s.rider_slices = sinterp_env_int("GSL_SINTERP_RIDER_SLICES", 0);
+    return s;
+  }();
+  GemmSwitches s = once;
+  const char *ov = getenv("GSL_SINTERP_GEMM_CFG");
+  s.cfg_override = ov ? atoi(ov) : -1;
+  s.cfg_whole = ov && strchr(ov, 'w') != NULL;
+  return s;
+}
+
+/* attr: what the kernel's dynamic-LDS limit is raised to (0: the launch needs none) */
+template <class Kernel, class... Args>
+static int gemm_launch(gsl_sinterp_hip_ctx *ctx, const GemmPlan &p, int attr, Kernel kernel, const Args &...args)
+{
+  if (attr) { int ast = sinterp_func_lds(ctx, (const void *)kernel, attr); if (ast) return ast; }
+  hipLaunchKernelGGL(kernel, dim3(p.grid), dim3(p.block), p.lds, ctx->stream, args...);
+  LAUNCH_CHECK(ctx);
+  return ST_SUCCESS;
+}
+
+/* one case label per shipped instantiation: (family, cfg, pipe, ride, grouped) */
+static constexpr unsigned plan_key(int family, int cfg = -1, bool pipe = false, bool ride = false, bool grouped = false)
+{
+  return (unsigned)family << 6 | (unsigned)(cfg + 1) << 3 | (pipe ? 4u : 0u) | (ride ? 2u : 0u) | (grouped ? 1u : 0u);
+}
 
 int sinterp_gemm_minus(gsl_sinterp_hip_ctx *ctx, size_t m, size_t n, size_t k, const double *A, size_t lda,
                        const double *B, size_t ldb, int b_is_kn, double *C, size_t ldc, int lower_only,
@@ -972,230 +976,56 @@ int sinterp_gemm_minus(gsl_sinterp_hip_ctx *ctx, size_t m, size_t n, size_t k, c
 {
   if (attached) *attached = 0;
   if (m == 0 || n == 0 || k == 0) return ST_SUCCESS;
-  __atomic_store_n(&g_gemm_last_cfg, -1, __ATOMIC_RELAXED);
+  GemmShape s;
+  s.m = m; s.n = n; s.k = k; s.lower_only = lower_only != 0; s.b_is_kn = b_is_kn != 0;
+  s.ab_aligned = ((lda & 1) == 0) && ((ldb & 1) == 0) && ((((uintptr_t)A) & 15) == 0) && ((((uintptr_t)B) & 15) == 0);
+  s.c_aligned = ((((uintptr_t)C) & 15) == 0) && (ldc & 1) == 0;
+  s.rider_offered = rider && attached;
+  const GemmPlan p = gemm_plan(s, (unsigned)ctx->sk_wgs, gemm_switches());
+
   GemmArgs g;
   g.m = m; g.n = n; g.k = k; g.A = A; g.lda = lda; g.B = B; g.ldb = ldb; g.C = C; g.ldc = ldc;
   g.lower_only = lower_only;
-  g.tiles_m = (int)((m + GT_BM - 1) / GT_BM);
-  g.tiles_n = (int)((n + GT_BN - 1) / GT_BN);
-  if (lower_only && g.tiles_m < g.tiles_n) g.tiles_n = g.tiles_m;   /* columns right of the square part are all above the diagonal */
-  unsigned grid = (unsigned)g.tiles_m * (unsigned)g.tiles_n;
-  if (lower_only) {
-    const unsigned tn_ = (unsigned)g.tiles_n;
-    grid = tn_ * (tn_ + 1) / 2 + ((unsigned)g.tiles_m - tn_) * tn_;
+  g.tiles_m = p.tiles_m; g.tiles_n = p.tiles_n; g.n_active = p.n_active;
+  StreamK x;
+  x.steps = p.steps; x.total = p.total; x.base = p.base; x.rem = p.rem; x.dp_rounds = p.dp_rounds;
+  x.partial = ctx->d_sk_partial; x.flags = ctx->d_sk_flags;
+  x.pri_tiles = p.pri_tiles; x.pri_sl = p.pri_sl; x.pri_nsl = p.pri_nsl; x.pri_base = p.pri_base;
+  RiderArgs rd = RiderArgs();
+  if (p.ride) {
+    rd.info = rider->info; rd.j0 = rider->j0; rd.dinv = rider->dinv; rd.fb = rider->fb; rd.ldf = rider->ldf;
+    rd.nrhs = rider->fb ? rider->nrhs : 0; rd.counter = rider->counter; rd.abort_word = rider->abort_word;
+    rd.need = p.need;
+    *attached = 1;
   }
-  g.n_active = grid;
-  const bool full = (m % GT_BM == 0) && (n % GT_BN == 0) && (k % GT_BK == 0) && ((lda & 1) == 0) && ((ldb & 1) == 0) &&
-                    ((((uintptr_t)A) & 15) == 0) && ((((uintptr_t)B) & 15) == 0);
-  /* skinny small-K update: one round trip */
-  if (!b_is_kn && (n == 32 || n == 64) && k <= 64 && (k % 4) == 0 && k >= 4 && ((lda & 1) == 0) && ((ldb & 1) == 0) &&
-      ((((uintptr_t)A) & 15) == 0) && ((((uintptr_t)B) & 15) == 0)) {
-    const size_t lds = (size_t)(128 + n) * (k + 2) * sizeof(double);
-    if (n == 32) {
-      { int ast = sinterp_func_lds(ctx, (const void *)gemm_minus_smallk_kernel<32>, 160 * 1024); if (ast) return ast; }
-      hipLaunchKernelGGL(gemm_minus_smallk_kernel<32>, dim3((unsigned)g.tiles_m), dim3(256), lds, ctx->stream, g);
-    } else {
-      { int ast = sinterp_func_lds(ctx, (const void *)gemm_minus_smallk_kernel<64>, 160 * 1024); if (ast) return ast; }
-      hipLaunchKernelGGL(gemm_minus_smallk_kernel<64>, dim3((unsigned)g.tiles_m), dim3(256), lds, ctx->stream, g);
-    }
-    LAUNCH_CHECK(ctx);
-    return ST_SUCCESS;
+  __atomic_store_n(&g_gemm_last_cfg, gemm_plan_last_cfg(p), __ATOMIC_RELAXED);
+
+#define STREAMK(...) return gemm_launch(ctx, p, (int)p.lds, gemm_minus_streamk_kernel<__VA_ARGS__>, g, x, rd)
+  switch (plan_key(p.family, p.cfg, p.pipe, p.ride, p.grouped)) {
+    /*                    family      cfg       pipe   ride   grouped          BM   BN   WM  WN SS ST PIPE   BKN    RIDER */
+    case plan_key(GEMM_SK_NT, SK_256,   false):                       STREAMK(256, 128, 64, 64);
+    case plan_key(GEMM_SK_NT, SK_256,   true):                        STREAMK(256, 128, 64, 64, 1, 3, true);
+    case plan_key(GEMM_SK_NT, SK_128,   false):                       STREAMK(128, 128, 64, 64);
+    case plan_key(GEMM_SK_NT, SK_128,   true):                        STREAMK(128, 128, 64, 64, 1, 3, true);
+    case plan_key(GEMM_SK_NT, SK_128W8, false):                       STREAMK(128, 128, 64, 32);
+    case plan_key(GEMM_SK_NT, SK_128W8, true):                        STREAMK(128, 128, 64, 32, 1, 3, true);
+    case plan_key(GEMM_SK_NT, SK_128W8, true,  true):                 STREAMK(128, 128, 64, 32, 1, 3, true,  false, true);
+    case plan_key(GEMM_SK_NT, SK_64W8G, false, false, true):          STREAMK(64,  64,  32, 16, 4, 2);
+    case plan_key(GEMM_SK_NT, SK_64W8G, false, true,  true):          STREAMK(64,  64,  32, 16, 4, 2, false, false, true);
+    case plan_key(GEMM_SK_NT, SK_64,    false, false, false):         STREAMK(64,  64,  32, 32);
+    case plan_key(GEMM_SK_NT, SK_64,    false, false, true):          STREAMK(64,  64,  32, 32, 4, 2);
+    case plan_key(GEMM_SK_KN256, -1,    true):                        STREAMK(256, 128, 64, 64, 1, 3, true,  true);
+    case plan_key(GEMM_SK_KN128, -1,    true):                        STREAMK(128, 128, 64, 64, 1, 3, true,  true);
+    case plan_key(GEMM_SMALLK32): return gemm_launch(ctx, p, 160 * 1024, gemm_minus_smallk_kernel<32>, g);
+    case plan_key(GEMM_SMALLK64): return gemm_launch(ctx, p, 160 * 1024, gemm_minus_smallk_kernel<64>, g);
+    case plan_key(GEMM_DMA256):   return gemm_launch(ctx, p, (int)p.lds, gemm_minus_dma_nt_kernel<4>, g);
+    case plan_key(GEMM_DMA128):   return gemm_launch(ctx, p, (int)p.lds, gemm_minus_dma_nt_kernel<2>, g);
+    case plan_key(GEMM_PLAIN):
+      if (p.b_is_kn) return p.full ? gemm_launch(ctx, p, 0, gemm_minus_kernel<1, true>, g) : gemm_launch(ctx, p, 0, gemm_minus_kernel<1, false>, g);
+      return p.full ? gemm_launch(ctx, p, 0, gemm_minus_kernel<0, true>, g) : gemm_launch(ctx, p, 0, gemm_minus_kernel<0, false>, g);
   }
-  static const bool no_dma = getenv("GSL_SINTERP_NO_DMA_GEMM") && getenv("GSL_SINTERP_NO_DMA_GEMM")[0] == '1';
-  if (full && !b_is_kn && k >= 4 * GT_BK && !no_dma) {
-    static const bool no_w8 = getenv("GSL_SINTERP_NO_GEMM8") && getenv("GSL_SINTERP_NO_GEMM8")[0] == '1';
-    if (ctx->sk_wgs > 0) {
-      /* stream-K: G persistent workgroups share the (tile, K-step) space evenly */
-      StreamK x;
-      x.steps = (unsigned)(k / GT_BK);                   /* groups per tile; rescaled below for the grouped 64x64 variants */
-      x.partial = ctx->d_sk_partial;
-      x.flags = ctx->d_sk_flags;
-      const unsigned cus = (unsigned)ctx->sk_wgs;
-      const bool can256 = !no_w8 && (m % 256 == 0) && (!lower_only || (g.tiles_n % 2) == 0);
-      /* tiles of configuration c (tile shape only; see the table above gemm_minus_streamk_kernel) */
-      auto tiles_of = [&](int c, GemmArgs &hh) -> unsigned {
-        hh = g;
-        if (c == SK_256) {
-          hh.tiles_m = (int)(m / 256);
-          if (!lower_only) return (unsigned)hh.tiles_m * (unsigned)hh.tiles_n;
-          const unsigned fr_ = (unsigned)hh.tiles_n / 2;
-          return 2 * fr_ * (fr_ + 1) / 2 + ((unsigned)hh.tiles_m - fr_) * (unsigned)hh.tiles_n;
-        }
-        const int bt = sk_tile(c);
-        hh.tiles_m = (int)(m / bt); hh.tiles_n = (int)(n / bt);
-        if (lower_only && hh.tiles_m < hh.tiles_n) hh.tiles_n = hh.tiles_m;
-        const unsigned tm_ = (unsigned)hh.tiles_m, tn_ = (unsigned)hh.tiles_n;
-        return lower_only ? tn_ * (tn_ + 1) / 2 + (tm_ - tn_) * tn_ : tm_ * tn_;
-      };
-      static const bool r4_rule = getenv("GSL_SINTERP_GEMM_RULE_R4") && getenv("GSL_SINTERP_GEMM_RULE_R4")[0] == '1';
-      static const bool no_t64 = getenv("GSL_SINTERP_NO_GEMM64") && getenv("GSL_SINTERP_NO_GEMM64")[0] == '1';
-      GemmArgs h;
-      int cfg;
-      bool whole = false;
-      if (r4_rule) {
-        /* round 4: 256x128 when every CU gets >= 16 K-steps of it, 64x64 when 128-tiles fill at most half of the CUs */
-        cfg = SK_128;
-        { GemmArgs h8; const unsigned t8 = tiles_of(SK_256, h8);
-          if (can256 && (unsigned long long)t8 * x.steps >= 16ull * cus) cfg = SK_256; }
-        if (cfg == SK_128 && !no_t64 && 2u * grid <= cus) cfg = SK_64;
-      } else {
-        cfg = sk_rule(can256, tiles_of, x.steps, cus);
-        if (no_t64 && cfg == SK_64W8G) cfg = SK_128W8;
-      }
-      /* developer override (tools/gemm_cfg_sweep.py): "<cfg>" or "<cfg>w" (whole tiles, no K split), where the shape allows it */
-      if (getenv("GSL_SINTERP_GEMM_CFG")) {
-        const char *ov = getenv("GSL_SINTERP_GEMM_CFG");
-        const int want_cfg = atoi(ov);
-        if ((want_cfg == SK_256 && can256) || want_cfg == SK_128 || want_cfg == SK_64 || want_cfg == SK_128W8 || want_cfg == SK_64W8G) {
-          cfg = want_cfg;
-          whole = strchr(ov, 'w') != NULL;
-        }
-      }
-      unsigned tiles = tiles_of(cfg, h);
-      static const bool no_group = getenv("GSL_SINTERP_NO_GEMM_GROUP") && getenv("GSL_SINTERP_NO_GEMM_GROUP")[0] == '1';
-      static const bool no_pipe = getenv("GSL_SINTERP_NO_GEMM_PIPE") && getenv("GSL_SINTERP_NO_GEMM_PIPE")[0] == '1';
-      if (cfg == SK_64W8G && (no_group || (k % (4 * GT_BK)) != 0)) cfg = SK_64;   /* ungrouped 64x64 tiles */
-      const bool grouped = (cfg == SK_64 && !no_group && (k % (4 * GT_BK)) == 0) || cfg == SK_64W8G;
-      if (grouped) x.steps = (unsigned)(k / (4 * GT_BK));
-      static const bool no_hybrid = getenv("GSL_SINTERP_NO_HYBRID_SK") && getenv("GSL_SINTERP_NO_HYBRID_SK")[0] == '1';
-      if (no_hybrid) whole = false;
-      /* the rider rides on the 128x128 and 64x64 8-wave configurations, when the block it factors is covered by the first
-         tiles of the enumeration (lower_only, at least 128 x 128) and a CU can be left to it */
-      const bool ride = rider && attached && lower_only && m >= 128 && n >= 128 && cus >= 2 && !whole &&
-                        ((cfg == SK_128W8 && !no_pipe) || cfg == SK_64W8G) &&
-                        ((((uintptr_t)C) & 15) == 0) && (ldc & 1) == 0;
-      const unsigned cus_g = ride ? cus - 1 : cus;
-      x.pri_tiles = 0; x.pri_sl = 0; x.pri_nsl = 1;
-      x.pri_base = cus;
-      unsigned G;
-      unsigned long long total64;
-      if (whole) {
-        /* whole tiles only: one tile per workgroup and round, the last round partly filled */
-        G = tiles < cus ? tiles : cus;
-        x.dp_rounds = tiles / G;
-        total64 = (unsigned long long)(tiles - x.dp_rounds * G) * x.steps;
-      } else {
-        total64 = (unsigned long long)tiles * x.steps;
-        unsigned long long want = total64 / (grouped ? 4 : 16);   /* >= 16 K-steps (of 16) per workgroup ... */
-        if (want < tiles) want = tiles;                     /* ... but never fewer workgroups than tiles */
-        if (want > cus_g) want = cus_g;
-        G = (unsigned)(want ? want : 1);
-        /* many tiles: all but the last full round (and the remainder) as whole tiles */
-        x.dp_rounds = (!no_hybrid && tiles / G >= 2) ? tiles / G - 1 : 0;
-        total64 = (unsigned long long)(tiles - x.dp_rounds * G) * x.steps;
-      }
-      if (total64 < 0x7fffffffull) {
-        x.total = (unsigned)total64;
-        if (whole) { x.base = x.steps; x.rem = 0; }      /* workgroup w: the w-th remaining tile, if any */
-        else { x.base = x.total / G; x.rem = x.total % G; }
-        RiderArgs rd = RiderArgs();
-        if (ride) {
-          rd.info = rider->info; rd.j0 = rider->j0; rd.dinv = rider->dinv; rd.fb = rider->fb; rd.ldf = rider->ldf;
-          rd.nrhs = rider->fb ? rider->nrhs : 0; rd.counter = rider->counter; rd.abort_word = rider->abort_word;
-          rd.need = cfg == SK_64W8G ? 3u : 1u;
-          if (x.dp_rounds == 0) {
-            /* one round: without a split the covering tiles end when the launch ends.  S slices per tile (the largest
-               divisor of the step count up to the wanted number), every holder keeping at least half of its share
-               for its own range */
-            static const int s_env = getenv("GSL_SINTERP_RIDER_SLICES") ? atoi(getenv("GSL_SINTERP_RIDER_SLICES")) : 0;
-            unsigned S = s_env > 0 ? (unsigned)s_env : 4u;
-            if (S > x.steps) S = x.steps;
-            while (S > 1 && (x.steps % S) != 0) S--;
-            while (S > 1 && (rd.need * S > G || rd.need * S > SK_PRI_SLOTS || 2 * (x.steps / S) > x.base || rd.need >= tiles)) {
-              S--;
-              while (S > 1 && (x.steps % S) != 0) S--;
-            }
-            if (S > 1) {
-              x.pri_tiles = rd.need; x.pri_nsl = S; x.pri_sl = x.steps / S;
-              x.total -= rd.need * x.steps;               /* the space the ranges share; base / rem still count the slices */
-            }
-          }
-          *attached = 1;
-        }
-        __atomic_store_n(&g_gemm_last_cfg, 2 * cfg + (whole ? 1 : 0), __ATOMIC_RELAXED);
-        switch (cfg) {
-          case SK_256:
-            return no_pipe ? launch_sk<256, 128, 64, 64>(ctx, G, h, x) : launch_sk<256, 128, 64, 64, 1, 3, true>(ctx, G, h, x);
-          case SK_128:
-            return no_pipe ? launch_sk<128, 128, 64, 64>(ctx, G, h, x) : launch_sk<128, 128, 64, 64, 1, 3, true>(ctx, G, h, x);
-          case SK_128W8:
-            if (ride) return launch_sk<128, 128, 64, 32, 1, 3, true, true>(ctx, G, h, x, rd);
-            return no_pipe ? launch_sk<128, 128, 64, 32>(ctx, G, h, x) : launch_sk<128, 128, 64, 32, 1, 3, true>(ctx, G, h, x);
-          case SK_64W8G:
-            if (ride) return launch_sk<64, 64, 32, 16, 4, 2, false, true>(ctx, G, h, x, rd);
-            return launch_sk<64, 64, 32, 16, 4, 2>(ctx, G, h, x);
-          default:
-            return grouped ? launch_sk<64, 64, 32, 32, 4, 2>(ctx, G, h, x) : launch_sk<64, 64, 32, 32>(ctx, G, h, x);
-        }
-      }
-    }
-    /* 256x128 tiles (8 waves) when the rows split evenly and there is enough work for every CU */
-    const bool w8 = !no_w8 && (m % 256 == 0) && (!lower_only || (g.tiles_n % 2) == 0) && grid >= 1024;
-    if (w8) {
-      GemmArgs h = g;
-      h.tiles_m = (int)(m / 256);
-      unsigned grid8 = (unsigned)h.tiles_m * (unsigned)h.tiles_n;
-      if (lower_only) {
-        const unsigned fr_ = (unsigned)h.tiles_n / 2;
-        grid8 = 2 * fr_ * (fr_ + 1) / 2 + ((unsigned)h.tiles_m - fr_) * (unsigned)h.tiles_n;
-      }
-      const size_t lds8 = (size_t)DM_STAGES * (256 + 128) * GT_BK * sizeof(double);   /* 144 KiB */
-      { int ast = sinterp_func_lds(ctx, (const void *)gemm_minus_dma_nt_kernel<4>, (int)lds8); if (ast) return ast; }
-      hipLaunchKernelGGL(gemm_minus_dma_nt_kernel<4>, dim3(grid8), dim3(512), lds8, ctx->stream, h);
-      LAUNCH_CHECK(ctx);
-      return ST_SUCCESS;
-    }
-    const size_t lds = (size_t)DM_STAGES * (128 + 128) * GT_BK * sizeof(double);     /* 96 KiB */
-    { int ast = sinterp_func_lds(ctx, (const void *)gemm_minus_dma_nt_kernel<2>, (int)lds); if (ast) return ast; }
-    hipLaunchKernelGGL(gemm_minus_dma_nt_kernel<2>, dim3(grid), dim3(256), lds, ctx->stream, g);
-    LAUNCH_CHECK(ctx);
-    return ST_SUCCESS;
-  }
-  static const bool no_kn = getenv("GSL_SINTERP_NO_KN_STREAMK") && getenv("GSL_SINTERP_NO_KN_STREAMK")[0] == '1';
-  if (b_is_kn && full && !lower_only && !no_dma && !no_kn && ctx->sk_wgs > 0 && k >= 4 * GT_BK) {
-    /* C -= A B with B stored [k][n] (the N.N updates of the LU route): the stream-K DMA pipeline with a [k][n] B image */
-    StreamK x;
-    x.steps = (unsigned)(k / GT_BK);
-    x.partial = ctx->d_sk_partial; x.flags = ctx->d_sk_flags;
-    x.pri_tiles = 0; x.pri_sl = 0; x.pri_nsl = 1; x.pri_base = 0;
-    GemmArgs h = g;
-    unsigned tiles = grid;
-    bool big = false;
-    if ((m % 256) == 0) {
-      const unsigned t8 = (unsigned)(m / 256) * (unsigned)g.tiles_n;
-      if ((unsigned long long)t8 * x.steps >= 16ull * (unsigned)ctx->sk_wgs) { big = true; h.tiles_m = (int)(m / 256); tiles = t8; }
-    }
-    unsigned long long total64 = (unsigned long long)tiles * x.steps;
-    unsigned long long want = total64 / 16;
-    if (want < tiles) want = tiles;
-    if (want > (unsigned long long)ctx->sk_wgs) want = (unsigned long long)ctx->sk_wgs;
-    const unsigned G = (unsigned)(want ? want : 1);
-    x.dp_rounds = (tiles / G >= 2) ? tiles / G - 1 : 0;
-    total64 = (unsigned long long)(tiles - x.dp_rounds * G) * x.steps;
-    if (total64 < 0x7fffffffull) {
-      x.total = (unsigned)total64; x.base = x.total / G; x.rem = x.total % G;
-      if (big) {
-        const size_t lds = (size_t)DM_STAGES * (256 * GT_BK + GT_BK * (128 + 16)) * sizeof(double);      /* 150 KiB */
-        { int ast = sinterp_func_lds(ctx, (const void *)gemm_minus_streamk_kernel<256, 128, 64, 64, 1, 3, true, true>, (int)lds); if (ast) return ast; }
-        hipLaunchKernelGGL((gemm_minus_streamk_kernel<256, 128, 64, 64, 1, 3, true, true>), dim3(G), dim3(512), lds, ctx->stream, h, x, RiderArgs());
-      } else {
-        const size_t lds = (size_t)DM_STAGES * (128 * GT_BK + GT_BK * (128 + 16)) * sizeof(double);
-        { int ast = sinterp_func_lds(ctx, (const void *)gemm_minus_streamk_kernel<128, 128, 64, 64, 1, 3, true, true>, (int)lds); if (ast) return ast; }
-        hipLaunchKernelGGL((gemm_minus_streamk_kernel<128, 128, 64, 64, 1, 3, true, true>), dim3(G), dim3(256), lds, ctx->stream, h, x, RiderArgs());
-      }
-      LAUNCH_CHECK(ctx);
-      return ST_SUCCESS;
-    }
-  }
-  if (b_is_kn) {
-    if (full) hipLaunchKernelGGL((gemm_minus_kernel<1, true>), dim3(grid), dim3(256), 0, ctx->stream, g);
-    else hipLaunchKernelGGL((gemm_minus_kernel<1, false>), dim3(grid), dim3(256), 0, ctx->stream, g);
-  } else {
-    if (full) hipLaunchKernelGGL((gemm_minus_kernel<0, true>), dim3(grid), dim3(256), 0, ctx->stream, g);
-    else hipLaunchKernelGGL((gemm_minus_kernel<0, false>), dim3(grid), dim3(256), 0, ctx->stream, g);
-  }
-  LAUNCH_CHECK(ctx);
-  return ST_SUCCESS;
+#undef STREAMK
+  return sinterp_fail(ctx, ST_EFAILED, "gemm_minus: plan without a kernel", hipSuccess, __FILE__, __LINE__);
 }
 
 extern "C" int gsl_sinterp_hip_gemm_minus(gsl_sinterp_hip_ctx *ctx, size_t m, size_t n, size_t k, const double *d_a,

@@ -117,9 +117,8 @@ extern "C" int gsl_sinterp_hip_group_create(gsl_sinterp_hip_group **out, const i
     if (!st && n > 1) st = gsl_sinterp_hip_ctx_own_stream(g->ctx[i]);   /* devices progress independently */
     if (st) { gsl_sinterp_hip_group_destroy(g); return st; }
   }
-  const char *no = getenv("GSL_SINTERP_NO_RCCL");
-  const char *force1 = getenv("GSL_SINTERP_RCCL_SINGLE");          /* exercise the RCCL binding on a one-GPU box */
-  g->use_rccl = distinct && !(no && no[0] == '1') && (n > 1 || (force1 && force1[0] == '1'));
+  /* GSL_SINTERP_RCCL_SINGLE: exercise the RCCL binding on a one-GPU box */
+  g->use_rccl = distinct && !sinterp_env_flag("GSL_SINTERP_NO_RCCL") && (n > 1 || sinterp_env_flag("GSL_SINTERP_RCCL_SINGLE"));
   if (g->use_rccl) {
     int st = bind_rccl(g);
     if (!st) {

@@ -285,8 +285,7 @@ extern "C" int gsl_sinterp_hip_krige_variance(gsl_sinterp_hip_ctx *ctx, int kind
   if (chunk > ((size_t)1 << 19)) chunk = (size_t)1 << 19;      /* rows / 16 is a grid dimension */
   /* developer switch (tools/krige_variance_time.py): the panel width of the recursion, read once */
   static const size_t panel = [] {
-    const char *e = getenv("GSL_SINTERP_KRIGE_PANEL");
-    const long v = e ? atol(e) : 0;
+    const int v = sinterp_env_int("GSL_SINTERP_KRIGE_PANEL", 0);
     return v >= PB ? (size_t)v / PB * PB : (size_t)PB;
   }();
   int st = sinterp_streamk_prepare(ctx);

@@ -826,7 +826,7 @@ laswp_outside_kernel(double *__restrict__ A, size_t lda, size_t n, size_t pc0, s
 static int trsm_unit_lower(gsl_sinterp_hip_ctx *ctx, double *A, size_t lda, size_t r0, size_t nb, size_t c0, size_t nc)
 {
   if (nb == 0 || nc == 0) return ST_SUCCESS;
-  static const bool no64 = getenv("GSL_SINTERP_NO_TRSM64") && getenv("GSL_SINTERP_NO_TRSM64")[0] == '1';
+  const bool no64 = SINTERP_ENV_ONCE("GSL_SINTERP_NO_TRSM64");
   if (!no64 && nb <= TB64 && nb > TB) {
     hipLaunchKernelGGL(trsm_unit_lower64_kernel, dim3((unsigned)((nc + 63) / 64)), dim3(64), 0, ctx->stream, A, lda,
                        r0, (int)nb, c0, nc);
@@ -854,7 +854,7 @@ static int trsm_unit_lower(gsl_sinterp_hip_ctx *ctx, double *A, size_t lda, size
 /* the cooperative panel kernel applies: buffers in place, aligned rows, at most LC_GMAX workgroups */
 static bool lu_coop_ok(const gsl_sinterp_hip_ctx *ctx, size_t lda, size_t n, size_t j0)
 {
-  static const bool off = getenv("GSL_SINTERP_NO_LU_COOP") && getenv("GSL_SINTERP_NO_LU_COOP")[0] == '1';
+  const bool off = SINTERP_ENV_ONCE("GSL_SINTERP_NO_LU_COOP");
   return !off && ctx->d_lu_coop != NULL && (lda & 1) == 0 && (j0 & 1) == 0 && n - j0 <= (size_t)LC_GMAX * LC_ROWS;
 }
 
@@ -866,7 +866,7 @@ static int lu_panel(gsl_sinterp_hip_ctx *ctx, double *A, size_t lda, size_t n, s
      (<= 1024 rows: its dependent global round trips are few); taller panels go through the
      recursion down to 8-column register-resident panels */
   /* developer override (tools/time_lu.py): tallest panel the single-workgroup block kernel takes */
-  static const size_t block_rows = getenv("GSL_SINTERP_LU_BLOCK_ROWS") ? (size_t)atol(getenv("GSL_SINTERP_LU_BLOCK_ROWS")) : (size_t)BT * 2;
+  static const size_t block_rows = (size_t)sinterp_env_int("GSL_SINTERP_LU_BLOCK_ROWS", BT * 2);
   if (w <= BW && prow <= block_rows && prow <= (size_t)BT * 8) {
     if (prow <= (size_t)BT)
       hipLaunchKernelGGL(lu_block_kernel<1>, dim3(1), dim3(BT), 0, ctx->stream, A, lda, n, j0, (int)w, d_ipiv);
@@ -901,7 +901,7 @@ static int lu_panel(gsl_sinterp_hip_ctx *ctx, double *A, size_t lda, size_t n, s
       /* 512 threads x 8 rows: with 1024 threads the 64 panel registers of 4 rows per thread do not fit the 128-VGPR
          budget of a 16-wave workgroup (scratch on the dependent path), and the per-wave work of a column step
          (reductions, pivot-row exchange, scalar control) is paid by twice as many waves */
-      static const int th = getenv("GSL_SINTERP_LU_BASE_THREADS") ? atoi(getenv("GSL_SINTERP_LU_BASE_THREADS")) : 512;
+      static const int th = sinterp_env_int("GSL_SINTERP_LU_BASE_THREADS", 512);
       if (th == 1024)
         hipLaunchKernelGGL(lu_base_reg_kernel<4>, dim3(1), dim3(LU_THREADS), 0, ctx->stream, A, lda, n, j0, (int)w, d_ipiv);
       else

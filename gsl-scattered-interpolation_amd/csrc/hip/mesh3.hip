@@ -388,7 +388,7 @@ extern "C" int gsl_sinterp_hip_mesh3_eval(gsl_sinterp_hip_ctx *ctx, int n_tet, c
   HIP_OK(ctx, hipMemsetAsync(todo, 0, sizeof(unsigned), ctx->stream));
   /* batches of >= 4096 targets: the 2-D path's reorder (cell order, two-level from 2^18 targets), results through the
      order's map, un-sorted afterwards.  A result depends on (mesh, target) only: same bits either way. */
-  const bool will_sort = m >= 4096 && !(getenv("GSL_SINTERP_NO_SORT") && getenv("GSL_SINTERP_NO_SORT")[0] == '1');
+  const bool will_sort = m >= 4096 && !sinterp_env_flag("GSL_SINTERP_NO_SORT");
   sinterp_sorted srt;
   if (will_sort) {
     st = sinterp_sort_reorder(ctx, d_targets, m, ttda, 3, 64, &srt, m, -1, (const unsigned long long *)NULL);

@@ -28,9 +28,8 @@ template <class F> static auto with_dim_tile(int dim, int ct, F &&f)
 }
 
 /* developer switches: "1" turns the target sort (read at every call) / the tile culling (read once per process) off */
-static bool env_is_1(const char *name) { const char *v = getenv(name); return v && v[0] == '1'; }
-static bool no_sort() { return env_is_1("GSL_SINTERP_NO_SORT"); }
-static bool no_cull() { static const bool off = env_is_1("GSL_SINTERP_NO_CULL"); return off; }
+static bool no_sort() { return sinterp_env_flag("GSL_SINTERP_NO_SORT"); }
+static bool no_cull() { return SINTERP_ENV_ONCE("GSL_SINTERP_NO_CULL"); }
 
 struct RbfTables {
   double exp2_frac[TBL_N];      /* 2^(i/256)                          */

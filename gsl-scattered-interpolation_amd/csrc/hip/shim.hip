@@ -28,10 +28,7 @@ extern "C" int gsl_sinterp_hip_ctx_create(gsl_sinterp_hip_ctx **out, int device,
      caller already enqueued there (hipMemcpy, torch's default stream, ...). */
   ctx->stream = (hipStream_t)stream;
   ctx->owns_stream = 0;
-  {
-    const char *e = getenv("GSL_SINTERP_NO_GRAPH");
-    ctx->use_graphs = !(e && e[0] == '1');
-  }
+  ctx->use_graphs = !sinterp_env_flag("GSL_SINTERP_NO_GRAPH");
   ctx->scratch_bytes = 4096;
   if (hipEventCreate(&ctx->ev0) != hipSuccess || hipEventCreate(&ctx->ev1) != hipSuccess ||
       hipMalloc(&ctx->d_scratch, ctx->scratch_bytes) != hipSuccess) {

@@ -174,8 +174,8 @@ static int rbf_solve_impl(gsl_sinterp_hip_ctx *ctx, int kind, double eps, const 
   /* thin-plate spline: the shift and the row norms need the full matrix; Gaussian: the Cholesky reads the lower
      triangle only, the upper one (the "original kept above the diagonal" of cholesky.c:103) only when asked for */
   const bool spd = kind != GSL_SINTERP_RBF_TPS;        /* every other kind is positive definite (an unknown one fails in the fill) */
-  static const bool no_fused = getenv("GSL_SINTERP_NO_FUSED_SHIFT") && getenv("GSL_SINTERP_NO_FUSED_SHIFT")[0] == '1';
-  const bool force_lu = getenv("GSL_SINTERP_FORCE_LU") && getenv("GSL_SINTERP_FORCE_LU")[0] == '1';
+  const bool no_fused = SINTERP_ENV_ONCE("GSL_SINTERP_NO_FUSED_SHIFT");
+  const bool force_lu = sinterp_env_flag("GSL_SINTERP_FORCE_LU");
   /* thin-plate spline on the SPD route: the matrix is written once, shifted (sinterp_tps_fill_shifted, below) */
   const bool fused = !spd && !no_fused && !force_lu;
   int st = fused ? ST_SUCCESS : sinterp_rbf_fill_ex(ctx, kind, eps, d_x, n, dim, xtda, d_phi, lda, spd && !keep_upper);

@@ -298,7 +298,7 @@ int sinterp_sort_centres(gsl_sinterp_hip_ctx *ctx, const double *d_x, size_t n, 
   launch_cell_scan(ctx, count, ncell, count + ncell + 1);
   hipLaunchKernelGGL(cell_scatter_kernel, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, (const unsigned *)cellid,
                      (const unsigned *)slot, n, (const unsigned *)count, perm);
-  static const bool serial_order = getenv("GSL_SINTERP_SERIAL_CELL_ORDER") && getenv("GSL_SINTERP_SERIAL_CELL_ORDER")[0] == '1';
+  const bool serial_order = SINTERP_ENV_ONCE("GSL_SINTERP_SERIAL_CELL_ORDER");
   if (serial_order) {
     hipLaunchKernelGGL(cell_order_kernel, dim3((unsigned)((ncell + 255) / 256)), dim3(256), 0, ctx->stream, (const unsigned *)count,
                        (unsigned)ncell, perm);
@@ -690,9 +690,8 @@ tl_unsort_staged_kernel(const unsigned *__restrict__ pos1, size_t m, const unsig
 
 static bool sort_two_level(size_t m)
 {
-  const char *e = getenv("GSL_SINTERP_SORT_LEVELS");         /* developer override "1" / "2"; read per call: the tests compare both routes */
-  const bool two = e && (e[0] == '1' || e[0] == '2') ? e[0] == '2' : true;
-  return two && m >= TL_MIN_M;
+  /* developer override "1" / "2" (anything but "1" is the default, two levels); read per call: the tests compare both routes */
+  return !sinterp_env_flag("GSL_SINTERP_SORT_LEVELS") && m >= TL_MIN_M;
 }
 
 bool sinterp_sort_reorder_is_two_level(size_t m) { return sort_two_level(m); }
@@ -730,7 +729,7 @@ static int tl_unsort(gsl_sinterp_hip_ctx *ctx, const sinterp_sorted *s, size_t m
   /* measured at M = 10^7: 8-byte results 85 us staged against ~100 us for the plain gather (three workgroups per CU);
      16-byte {value, leaf} pairs 200 us staged against 130 us (98 KB of LDS: one workgroup per CU, nothing hides the table
      loads and the searches) -- the pairs keep the plain gather.  GSL_SINTERP_UNSORT_GATHER=1 (developer): plain gather always */
-  static const bool unstaged = getenv("GSL_SINTERP_UNSORT_GATHER") && getenv("GSL_SINTERP_UNSORT_GATHER")[0] == '1';
+  const bool unstaged = SINTERP_ENV_ONCE("GSL_SINTERP_UNSORT_GATHER");
   if (unstaged || !s->tl_cnt || ESZ == 2) {
     size_t blocks = (m + 255) / 256;
     if (blocks > 4096) blocks = 4096;
