@@ -13,12 +13,14 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 GSL_SUCCESS, GSL_FAILURE = 0, -1
 GSL_EDOM, GSL_EFAULT, GSL_EINVAL, GSL_EFAILED, GSL_ENOMEM = 1, 3, 4, 5, 8
 GSL_EBADLEN, GSL_ENOTSQR, GSL_EUNSUP, GSL_EUNIMPL = 19, 20, 23, 24
+GSL_EMAXITER = 11
 RBF_GAUSSIAN, RBF_TPS, RBF_WENDLAND = 0, 1, 2
 RBF_MATERN32, RBF_MATERN52, RBF_IMQ = 3, 4, 5
 FIT_LOO, FIT_ML = 0, 1
 SOLVER_DEFAULT, SOLVER_CHOLESKY2, SOLVER_PCHOLESKY, SOLVER_LU_REFINE = 0, 1, 2, 3
 TREE_DEFAULT, TREE_NOSTANDARDIZE, TREE_ISOSCALE = 0, 1, 2
 TREE_RECORD_BYTES, TREE_LEAFTAB_BYTES = 64, 32
+CUBIC_RECORD_BYTES = 160                              # Clough-Tocher records (n_tri of them)
 NATURAL_RECORD_BYTES, NATURAL_STACK = 80, 16          # natural-neighbour records (n_tri + 1 of them); pending-stack default
 
 
@@ -218,6 +220,7 @@ SIGNATURES = {
     "simplex_mesh_set_convex": (None, [_vp, _i]),
     "simplex_mesh_convex": (_i, [_vp]),
     "simplex_mesh_delaunay_metric": (_i, [_vp]),
+    "simplex_mesh_vertex_adjacency": (_i, [_vp, _pi, _pi, _sz, C.POINTER(_sz)]),
     "simplex_mesh_device_alloc": (_vp, [_vp, _i]),
     "simplex_mesh_device_alloc_multi": (_vp, [_vp, _pi, _i]),
     "simplex_mesh_device_n_devices": (_i, [_vp]),
@@ -231,6 +234,14 @@ SIGNATURES = {
     "simplex_mesh_device_ctx": (_vp, [_vp]),
     "simplex_mesh_device_eval_natural_many": (_i, [_vp, _pm, _pv, _pi]),
     "simplex_mesh_device_eval_natural_resident": (_i, [_vp, _vp, _sz, _sz, _vp, _vp]),
+    "simplex_mesh_device_bind_gradients": (_i, [_vp, _pm]),
+    "simplex_mesh_device_set_gradient_options": (_i, [_vp, _d, _sz]),
+    "simplex_mesh_device_gradients": (_i, [_vp, _pm, C.POINTER(_sz), _pd]),
+    "simplex_mesh_device_eval_cubic_many": (_i, [_vp, _pm, _pv, _pm, _pi]),
+    "simplex_mesh_device_eval_cubic_resident": (_i, [_vp, _vp, _sz, _sz, _vp, _vp, _sz, _vp]),
+    "gsl_sinterp_hip_mesh_cubic_gradients": (_i, [_vp, _i, _vp, _vp, _sz, _vp, _vp, _d, _i, _vp, _pi, _pd]),
+    "gsl_sinterp_hip_mesh_cubic_pack": (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
+    "gsl_sinterp_hip_mesh_cubic_eval": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _sz, _sz, _vp, _vp, _sz]),
     "gsl_sinterp_hip_mesh_natural_pack": (_i, [_vp, _i, _vp, _vp, _i, _vp, _pd, _vp]),
     "gsl_sinterp_hip_mesh_natural_eval": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _sz, _sz, _i, _vp, C.POINTER(C.c_longlong)]),
     "gsl_sinterp_hip_mesh_pack": (_i, [_vp, _i, _vp, _vp, _i, _vp, _pd, _i, _vp, _vp]),
@@ -308,6 +319,9 @@ SIGNATURES = {
     "gsl_sinterp_set_device_list": (_i, [C.POINTER(gsl_sinterp), _pi, _i]),
     "gsl_sinterp_n_devices": (_i, [C.POINTER(gsl_sinterp)]),
     "gsl_sinterp_set_tree_options": (_i, [C.POINTER(gsl_sinterp), _i, _vp]),
+    "gsl_sinterp_set_gradients": (_i, [C.POINTER(gsl_sinterp), _pm]),
+    "gsl_sinterp_set_gradient_options": (_i, [C.POINTER(gsl_sinterp), _d, _sz]),
+    "gsl_sinterp_get_gradients": (_i, [C.POINTER(gsl_sinterp), _pm, C.POINTER(_sz), _pd]),
     "gsl_sinterp_init": (_i, [C.POINTER(gsl_sinterp), _pm, _pv]),
     "gsl_sinterp_name": (C.c_char_p, [C.POINTER(gsl_sinterp)]),
     "gsl_sinterp_min_size": (C.c_uint, [C.POINTER(gsl_sinterp)]),
@@ -330,7 +344,7 @@ SIGNATURES = {
     "gsl_rng_get": (C.c_ulong, [_vp]),
     "gsl_rng_uniform_int": (C.c_ulong, [_vp, C.c_ulong]),
 }
-DATA_SYMBOLS = ["gsl_sinterp_kriging", "gsl_sinterp_linear_mesh", "gsl_sinterp_natural_mesh", "gsl_sinterp_natural_simplex", "gsl_sinterp_rbf_gaussian", "gsl_sinterp_rbf_tps", "gsl_sinterp_rbf_tps_affine", "gsl_sinterp_rbf_wendland", "gsl_sinterp_linear_simplex",
+DATA_SYMBOLS = ["gsl_sinterp_kriging", "gsl_sinterp_linear_mesh", "gsl_sinterp_natural_mesh", "gsl_sinterp_natural_simplex", "gsl_sinterp_cubic_mesh", "gsl_sinterp_cubic_simplex", "gsl_sinterp_rbf_gaussian", "gsl_sinterp_rbf_tps", "gsl_sinterp_rbf_tps_affine", "gsl_sinterp_rbf_wendland", "gsl_sinterp_linear_simplex",
                 "gsl_sinterp_rbf_matern32", "gsl_sinterp_rbf_matern52", "gsl_sinterp_rbf_imq", "gsl_sinterp_kriging_matern32", "gsl_sinterp_kriging_matern52",
                 "gsl_rng_mt19937", "gsl_rng_default"]
 
@@ -480,6 +494,24 @@ class HipContext:
         check(lib().gsl_sinterp_hip_mesh_natural_eval(self._h, n_tri, d_nnrec, d_leaftab, d_located, d_linear_values, d_targets, m, ttda,
                                                       depth_cap, d_values, C.byref(cnt)), self._h)
         return cnt.value
+
+    def mesh_cubic_gradients(self, n_points, d_offsets, d_adjacent, n_adjacent, d_points, d_f, d_g, rtol=1e-12, maxiter=1000):
+        """(status, iterations, residual): the Clough-Tocher vertex gradients into d_g [2 n_points]; GSL_EMAXITER is returned, not raised"""
+        it, res = C.c_int(0), C.c_double(0.0)
+        st = lib().gsl_sinterp_hip_mesh_cubic_gradients(self._h, n_points, d_offsets, d_adjacent, n_adjacent, d_points, d_f, rtol, maxiter,
+                                                        d_g, C.byref(it), C.byref(res))
+        if st != GSL_EMAXITER:
+            check(st, self._h)
+        return st, it.value, res.value
+
+    def mesh_cubic_pack(self, n_tri, d_tri, d_nbr, n_points, d_points, d_f, d_g, d_ctrec):
+        """Clough-Tocher records: n_tri * CUBIC_RECORD_BYTES bytes at d_ctrec"""
+        check(lib().gsl_sinterp_hip_mesh_cubic_pack(self._h, n_tri, d_tri, d_nbr, n_points, d_points, d_f, d_g, d_ctrec), self._h)
+
+    def mesh_cubic_eval(self, n_tri, d_ctrec, d_located, d_linear_values, d_targets, m, ttda, d_values, d_grad=None, gtda=2):
+        """the cubic sweep over the triangles gsl_sinterp_hip_mesh_eval located; d_grad = None: values only"""
+        check(lib().gsl_sinterp_hip_mesh_cubic_eval(self._h, n_tri, d_ctrec, d_located, d_linear_values, d_targets, m, ttda, d_values,
+                                                    d_grad, gtda), self._h)
 
     def bary_eval(self, n_nodes, d_records, d_leaftab, scale, d_targets, m, ttda, d_values, d_leaf=None,
                   count_outside=False):
@@ -975,6 +1007,17 @@ class SimplexMesh:
         """1: Delaunay in the coordinates as given, 2: in the standardised ones, 0: in neither (or a 3-D mesh)"""
         return int(lib().simplex_mesh_delaunay_metric(self._h))
 
+    def vertex_adjacency(self):
+        """(offsets [n_points + 1], neighbours): every undirected edge once per endpoint, the neighbours of a vertex ascending"""
+        n_points = len(self.points())
+        off = np.empty(n_points + 1, dtype=np.int32)
+        adj = np.empty(6 * self.n_triangles + 1, dtype=np.int32)
+        cnt = C.c_size_t(0)
+        st = lib().simplex_mesh_vertex_adjacency(self._h, off.ctypes.data_as(_pi), adj.ctypes.data_as(_pi), len(adj), C.byref(cnt))
+        if st != 0:
+            raise GslError(st, "simplex_mesh_vertex_adjacency")
+        return off, adj[:cnt.value].copy()
+
     def device_alloc(self, device=0):
         h = lib().simplex_mesh_device_alloc(self._h, device)
         if not h:
@@ -1034,6 +1077,33 @@ class DeviceMesh:
                                                          tri.ctypes.data_as(_pi))
         return st, vals, tri
 
+    def bind_gradients(self, gradients=None):
+        """Clough-Tocher: the n_points x 2 gradients to interpolate; None = estimate them at the first cubic call"""
+        return lib().simplex_mesh_device_bind_gradients(self._h, C.byref(as_matrix(gradients)) if gradients is not None else None)
+
+    def set_gradient_options(self, rtol, maxiter):
+        return lib().simplex_mesh_device_set_gradient_options(self._h, rtol, maxiter)
+
+    def gradients(self):
+        """(status, g [n_points x 2], iterations, residual) of the gradients in use (estimates them now if still to do)"""
+        g = np.empty((self._mesh.points().shape[0], 2), dtype=np.float64)
+        it, res = C.c_size_t(0), C.c_double(0.0)
+        st = lib().simplex_mesh_device_gradients(self._h, C.byref(as_matrix(g)), C.byref(it), C.byref(res))
+        return st, g, it.value, res.value
+
+    def eval_cubic_many(self, targets, want_grad=False):
+        """(status, values, gradient or None, triangle): Clough-Tocher values (and grad s) on a 2-D mesh"""
+        m = targets.shape[0]
+        vals = np.empty(m, dtype=np.float64)
+        grad = np.empty((m, 2), dtype=np.float64) if want_grad else None
+        tri = np.empty(m, dtype=np.int32)
+        st = lib().simplex_mesh_device_eval_cubic_many(self._h, C.byref(as_matrix(targets)), C.byref(as_vector(vals)),
+                                                       C.byref(as_matrix(grad)) if want_grad else None, tri.ctypes.data_as(_pi))
+        return st, vals, grad, tri
+
+    def eval_cubic_resident(self, d_targets, m, ttda, d_values, d_grad=None, gtda=2, d_tri=None):
+        return lib().simplex_mesh_device_eval_cubic_resident(self._h, d_targets, m, ttda, d_values, d_grad, gtda, d_tri)
+
     def n_devices(self):
         return lib().simplex_mesh_device_n_devices(self._h)
 
@@ -1063,6 +1133,7 @@ class Sinterp:
     TYPES = {"gaussian": "gsl_sinterp_rbf_gaussian", "tps": "gsl_sinterp_rbf_tps", "tps_affine": "gsl_sinterp_rbf_tps_affine",
              "wendland": "gsl_sinterp_rbf_wendland", "linear_mesh": "gsl_sinterp_linear_mesh",
              "natural_mesh": "gsl_sinterp_natural_mesh", "natural_simplex": "gsl_sinterp_natural_simplex",
+             "cubic_mesh": "gsl_sinterp_cubic_mesh", "cubic_simplex": "gsl_sinterp_cubic_simplex",
              "linear_simplex": "gsl_sinterp_linear_simplex", "kriging": "gsl_sinterp_kriging",
              "matern32": "gsl_sinterp_rbf_matern32", "matern52": "gsl_sinterp_rbf_matern52", "imq": "gsl_sinterp_rbf_imq",
              "kriging_matern32": "gsl_sinterp_kriging_matern32", "kriging_matern52": "gsl_sinterp_kriging_matern52"}
@@ -1227,6 +1298,20 @@ class Sinterp:
         nbr = None if neighbours is None else np.ascontiguousarray(neighbours, dtype=np.int32).reshape(-1, w)
         return lib().gsl_sinterp_set_triangulation(self._p, tri.ctypes.data_as(_pi), nbr.ctypes.data_as(_pi) if nbr is not None else None,
                                                    len(tri))
+
+    def set_gradients(self, gradients):
+        """Clough-Tocher types, before init: the size x 2 gradients to interpolate (None: back to the estimate)"""
+        return lib().gsl_sinterp_set_gradients(self._p, C.byref(as_matrix(gradients)) if gradients is not None else None)
+
+    def set_gradient_options(self, rtol, maxiter):
+        return lib().gsl_sinterp_set_gradient_options(self._p, rtol, maxiter)
+
+    def get_gradients(self):
+        """(status, g [size x 2], iterations, residual) after init"""
+        g = np.empty((self._p.contents.size, 2), dtype=np.float64)
+        it, res = C.c_size_t(0), C.c_double(0.0)
+        st = lib().gsl_sinterp_get_gradients(self._p, C.byref(as_matrix(g)), C.byref(it), C.byref(res))
+        return st, g, it.value, res.value
 
     def set_tree_options(self, flags, rng):
         self._rng = rng

@@ -513,6 +513,52 @@ int simplex_mesh_delaunay_metric(const simplex_mesh *mesh)
 }
 
 /* ------------------------------------------------------------------------ */
+/* Vertex -> neighbour CSR of a 2-D mesh (the rows of the gradient system of csrc/hip/cubic.hip): every undirected edge
+   of the triangulation once per endpoint, hull edges included, the neighbours of a vertex ascending.  Every triangle
+   corner files its two edge partners under the vertex (a counting sort by vertex: O(n)); an interior edge is then
+   filed twice per endpoint, so every row (6 entries on average) is sorted by insertion and made unique. */
+int simplex_mesh_vertex_adjacency(const simplex_mesh *mesh, int *offsets, int *neighbours, size_t capacity, size_t *n_entries)
+{
+  if (!mesh || !offsets || !n_entries) GSL_ERROR("simplex_mesh_vertex_adjacency: null argument", GSL_EFAULT);
+  if (mesh->dim != 2) GSL_ERROR("simplex_mesh_vertex_adjacency: 2-D meshes only", GSL_EUNSUP);
+  const size_t np = mesh->n_points, nt = mesh->n_tri;
+  if (6 * nt > (size_t)INT_MAX) GSL_ERROR("simplex_mesh_vertex_adjacency: mesh too large", GSL_EINVAL);
+  int *raw = (int *)malloc((6 * nt + 1) * sizeof(int)), *start = (int *)calloc(np + 1, sizeof(int));
+  if (!raw || !start) { free(raw); free(start); GSL_ERROR("simplex_mesh_vertex_adjacency: out of memory", GSL_ENOMEM); }
+  for (size_t k = 0; k < 3 * nt; k++) start[mesh->tri[k] + 1] += 2;
+  for (size_t i = 0; i < np; i++) start[i + 1] += start[i];
+  for (size_t i = 0; i <= np; i++) offsets[i] = start[i];              /* offsets: the fill cursors for now */
+  for (size_t t = 0; t < nt; t++)
+    for (int a = 0; a < 3; a++) {
+      const int v = mesh->tri[3 * t + a];
+      raw[offsets[v]++] = mesh->tri[3 * t + (a + 1) % 3];
+      raw[offsets[v]++] = mesh->tri[3 * t + (a + 2) % 3];
+    }
+  size_t total = 0;
+  for (size_t i = 0; i < np; i++) {
+    int *row = raw + start[i];
+    const int len = start[i + 1] - start[i];
+    for (int a = 1; a < len; a++) {
+      const int key = row[a];
+      int b = a - 1;
+      for (; b >= 0 && row[b] > key; b--) row[b + 1] = row[b];
+      row[b + 1] = key;
+    }
+    offsets[i] = (int)total;
+    for (int a = 0; a < len; a++) {
+      if (row[a] == (int)i || (a > 0 && row[a] == row[a - 1])) continue;
+      if (neighbours && total < capacity) neighbours[total] = row[a];
+      total++;
+    }
+  }
+  offsets[np] = (int)total;
+  *n_entries = total;
+  free(raw); free(start);
+  if (neighbours && total > capacity) GSL_ERROR("simplex_mesh_vertex_adjacency: neighbour array too short (6 n_triangles always suffices)", GSL_EBADLEN);
+  return GSL_SUCCESS;
+}
+
+/* ------------------------------------------------------------------------ */
 /* Binary checkpoint of a mesh (gsl_matrix_fwrite conventions: native byte order, GSL_EFAILED on a short transfer):
      2-D: magic "GSLSMSH1" | n_tri, n_points, has_nodes, convex (int64) | triangles | neighbours | [tree nodes] | points |
           shift, scale, lo, hi;

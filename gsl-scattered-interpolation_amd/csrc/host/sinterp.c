@@ -625,6 +625,14 @@ struct simplex_mesh_device {
   int *nn_leaf;
   void *nn_rec;
   size_t nn_leaf_cap;
+  /* Clough-Tocher (csrc/hip/cubic.hip), by the same rule: nothing until the first cubic call.  ct_bound: the caller's
+     gradients (host copy, NULL = estimate); ct_g / ct_rec: gradients and records on the device (NULL = still to do);
+     ct_leaf: triangle indices of a resident batch whose caller did not ask for them */
+  double *ct_bound, *ct_g;
+  void *ct_rec;
+  int *ct_leaf;
+  size_t ct_leaf_cap, ct_iters, ct_maxiter;
+  double ct_rtol, ct_resid;
 };
 
 gsl_sinterp_hip_ctx *simplex_mesh_device_ctx(simplex_mesh_device *dev) { return dev ? dev->ctx : NULL; }
@@ -646,7 +654,9 @@ void simplex_mesh_device_free(simplex_mesh_device *dev)
   }
   if (dev->ctx) {
     gsl_sinterp_hip_free(dev->ctx, dev->nn_rec); gsl_sinterp_hip_free(dev->ctx, dev->nn_leaf);
+    gsl_sinterp_hip_free(dev->ctx, dev->ct_g); gsl_sinterp_hip_free(dev->ctx, dev->ct_rec); gsl_sinterp_hip_free(dev->ctx, dev->ct_leaf);
   }
+  free(dev->ct_bound);
   if (dev->ss.grp) shard_set_release(&dev->ss);      /* destroys the members' contexts */
   else if (dev->ctx) { chunk_set_release(&dev->cs, dev->ctx); gsl_sinterp_hip_ctx_destroy(dev->ctx); }
   free(dev);
@@ -719,6 +729,7 @@ simplex_mesh_device *simplex_mesh_device_alloc_multi(const simplex_mesh *mesh, c
     gsl_sinterp_hip_free(c, d_nbr[r]); gsl_sinterp_hip_free(c, d_pts[r]);
   }
   dev->mesh = mesh; dev->nn_metric = -1;
+  dev->ct_rtol = 1e-12; dev->ct_maxiter = 1000;
   if (st != GSL_SUCCESS) {
     gsl_error(gsl_sinterp_hip_last_error(dev->ctx), __FILE__, __LINE__, st);
     simplex_mesh_device_free(dev);
@@ -730,6 +741,14 @@ simplex_mesh_device *simplex_mesh_device_alloc_multi(const simplex_mesh *mesh, c
 simplex_mesh_device *simplex_mesh_device_alloc(const simplex_mesh *mesh, int device)
 {
   return simplex_mesh_device_alloc_multi(mesh, &device, 1);
+}
+
+/* forget the Clough-Tocher gradients and records (and, with `bound`, the caller's gradients) */
+static void cubic_drop(simplex_mesh_device *dev, int bound)
+{
+  if (dev->ctx) { gsl_sinterp_hip_free(dev->ctx, dev->ct_g); gsl_sinterp_hip_free(dev->ctx, dev->ct_rec); }
+  dev->ct_g = NULL; dev->ct_rec = NULL; dev->ct_iters = 0; dev->ct_resid = 0.0;
+  if (bound) { free(dev->ct_bound); dev->ct_bound = NULL; }
 }
 
 int simplex_mesh_device_set_response(simplex_mesh_device *dev, const gsl_vector *response)
@@ -756,6 +775,7 @@ int simplex_mesh_device_set_response(simplex_mesh_device *dev, const gsl_vector 
   free(h);
   if (st) GSL_ERROR(gsl_sinterp_hip_last_error(dev->ctx), st);
   dev->response_bound = 1;
+  cubic_drop(dev, 1);                                   /* gradients and records belong to the response */
   return GSL_SUCCESS;
 }
 
@@ -890,6 +910,222 @@ int simplex_mesh_device_eval_natural_many(simplex_mesh_device *dev, const gsl_ma
   st = chunk_eval_many(&dev->cs, dev->ctx, 2, targets, values, triangle, &natural_chunk_eval, dev, 1, &outside_n);
   if (st != GSL_SUCCESS) GSL_ERROR("simplex_mesh_device_eval_natural_many: evaluation failed", st);
   if (outside_n) GSL_ERROR("simplex_mesh_device_eval_natural_many: target(s) outside the triangulation", GSL_EDOM);
+  return GSL_SUCCESS;
+}
+
+/* ---- Clough-Tocher on the same mirror (csrc/hip/cubic.hip) ---- */
+static int cubic_status(simplex_mesh_device *dev)
+{
+  if (dev->dim != 2) GSL_ERROR("simplex_mesh_device cubic: 2-D meshes only", GSL_EUNSUP);
+  if (dev->n_members > 1) GSL_ERROR("simplex_mesh_device cubic: one device only (no sharding over a device group)", GSL_EUNSUP);
+  if (!dev->response_bound) GSL_ERROR("simplex_mesh_device cubic: no response bound", GSL_EINVAL);
+  return GSL_SUCCESS;
+}
+
+int simplex_mesh_device_bind_gradients(simplex_mesh_device *dev, const gsl_matrix *gradients)
+{
+  if (!dev) GSL_ERROR("simplex_mesh_device_bind_gradients: null device mirror", GSL_EFAULT);
+  if (dev->dim != 2) GSL_ERROR("simplex_mesh_device_bind_gradients: 2-D meshes only", GSL_EUNSUP);
+  if (gradients && (gradients->size1 != (size_t)dev->n_points || gradients->size2 != 2))
+    GSL_ERROR("simplex_mesh_device_bind_gradients: gradients must be (number of points) x 2", GSL_EBADLEN);
+  double *h = NULL;
+  if (gradients) {
+    h = (double *)malloc(2 * (size_t)dev->n_points * sizeof(double));
+    if (!h) GSL_ERROR("simplex_mesh_device_bind_gradients: out of memory", GSL_ENOMEM);
+    for (size_t i = 0; i < (size_t)dev->n_points; i++) {
+      h[2 * i] = gradients->data[i * gradients->tda]; h[2 * i + 1] = gradients->data[i * gradients->tda + 1];
+    }
+  }
+  cubic_drop(dev, 1);
+  dev->ct_bound = h;
+  return GSL_SUCCESS;
+}
+
+int simplex_mesh_device_set_gradient_options(simplex_mesh_device *dev, double rtol, size_t maxiter)
+{
+  if (!dev) GSL_ERROR("simplex_mesh_device_set_gradient_options: null device mirror", GSL_EFAULT);
+  if (!(rtol > 0.0 && rtol < 1.0) || maxiter < 1 || maxiter > (size_t)INT_MAX)
+    GSL_ERROR("simplex_mesh_device_set_gradient_options: need 0 < rtol < 1 and maxiter >= 1", GSL_EINVAL);
+  dev->ct_rtol = rtol; dev->ct_maxiter = maxiter;
+  return GSL_SUCCESS;
+}
+
+/* gradients (bound or estimated) and records, at the first use.  The per-vertex data come back from the response
+   table the linear path keeps (vertex i of triangle t = entry i of row t); a vertex of no triangle has no datum
+   there and needs none. */
+static int cubic_prepare(simplex_mesh_device *dev)
+{
+  if (dev->ct_rec) return GSL_SUCCESS;
+  gsl_sinterp_hip_ctx *c = dev->ctx;
+  const size_t nt = (size_t)dev->n_tri, np = (size_t)dev->n_points;
+  const size_t tb = 3 * nt * sizeof(int), pb = 2 * np * sizeof(double);
+  const int *tri = simplex_mesh_triangles(dev->mesh);
+  int *d_nbr = NULL, *d_off = NULL, *d_adj = NULL, *h_off = NULL, *h_adj = NULL;
+  double *d_pts = NULL, *d_f = NULL;
+  double *h_tab = (double *)malloc(nt * GSL_SINTERP_TREE_LEAFTAB_BYTES), *h_f = (double *)calloc(np, sizeof(double));
+  size_t n_adj = 0;
+  int st = (h_tab && h_f) ? GSL_SUCCESS : GSL_ENOMEM, solve = GSL_SUCCESS;
+  if (!st) st = gsl_sinterp_hip_sync(c);
+  if (!st) st = gsl_sinterp_hip_d2h(c, h_tab, dev->m_leaftab[0], nt * GSL_SINTERP_TREE_LEAFTAB_BYTES);
+  if (!st)
+    for (size_t t = 0; t < nt; t++)
+      for (int i = 0; i < 3; i++) h_f[tri[3 * t + i]] = h_tab[4 * t + i];
+  if (!st) st = gsl_sinterp_hip_malloc(c, (void **)&d_nbr, tb);
+  if (!st) st = gsl_sinterp_hip_malloc(c, (void **)&d_pts, pb);
+  if (!st) st = gsl_sinterp_hip_malloc(c, (void **)&d_f, np * sizeof(double));
+  if (!st && !dev->ct_g) st = gsl_sinterp_hip_malloc(c, (void **)&dev->ct_g, pb);
+  if (!st) st = gsl_sinterp_hip_h2d(c, d_nbr, simplex_mesh_neighbours(dev->mesh), tb);
+  if (!st) st = gsl_sinterp_hip_h2d(c, d_pts, simplex_mesh_points(dev->mesh), pb);
+  if (!st) st = gsl_sinterp_hip_h2d(c, d_f, h_f, np * sizeof(double));
+  if (!st && dev->ct_bound) {
+    st = gsl_sinterp_hip_h2d(c, dev->ct_g, dev->ct_bound, pb);
+    dev->ct_iters = 0; dev->ct_resid = 0.0;
+  } else if (!st) {
+    h_off = (int *)malloc((np + 1) * sizeof(int)); h_adj = (int *)malloc((6 * nt + 1) * sizeof(int));
+    if (!h_off || !h_adj) st = GSL_ENOMEM;
+    if (!st) st = simplex_mesh_vertex_adjacency(dev->mesh, h_off, h_adj, 6 * nt, &n_adj);
+    if (!st) st = gsl_sinterp_hip_malloc(c, (void **)&d_off, (np + 1) * sizeof(int));
+    if (!st) st = gsl_sinterp_hip_malloc(c, (void **)&d_adj, (n_adj + 1) * sizeof(int));
+    if (!st) st = gsl_sinterp_hip_h2d(c, d_off, h_off, (np + 1) * sizeof(int));
+    if (!st && n_adj) st = gsl_sinterp_hip_h2d(c, d_adj, h_adj, n_adj * sizeof(int));
+    if (!st) {
+      int iters = 0;
+      solve = gsl_sinterp_hip_mesh_cubic_gradients(c, dev->n_points, d_off, d_adj, n_adj, d_pts, d_f, dev->ct_rtol, (int)dev->ct_maxiter,
+                                                   dev->ct_g, &iters, &dev->ct_resid);
+      dev->ct_iters = (size_t)iters;
+      if (solve != GSL_SUCCESS && solve != GSL_EMAXITER) st = solve;
+    }
+  }
+  if (!st) st = gsl_sinterp_hip_malloc(c, &dev->ct_rec, nt * GSL_SINTERP_CUBIC_RECORD_BYTES);
+  if (!st) st = gsl_sinterp_hip_mesh_cubic_pack(c, dev->n_tri, dev->m_tri[0], d_nbr, dev->n_points, d_pts, d_f, dev->ct_g, dev->ct_rec);
+  int s2 = gsl_sinterp_hip_sync(c);
+  if (!st) st = s2;
+  gsl_sinterp_hip_free(c, d_nbr); gsl_sinterp_hip_free(c, d_pts); gsl_sinterp_hip_free(c, d_f);
+  gsl_sinterp_hip_free(c, d_off); gsl_sinterp_hip_free(c, d_adj);
+  free(h_tab); free(h_f); free(h_off); free(h_adj);
+  if (st) {
+    const size_t it = dev->ct_iters;
+    const double rs = dev->ct_resid;
+    cubic_drop(dev, 0);
+    dev->ct_iters = it; dev->ct_resid = rs;
+    GSL_ERROR(gsl_sinterp_hip_last_error(c), st);
+  }
+  /* maxiter reached: the gradients of the last iterate and their records stay usable; the caller hears about it once */
+  if (solve == GSL_EMAXITER) GSL_ERROR("simplex_mesh_device cubic: the gradient estimate reached maxiter before rtol", GSL_EMAXITER);
+  return GSL_SUCCESS;
+}
+
+int simplex_mesh_device_gradients(simplex_mesh_device *dev, gsl_matrix *gradients, size_t *iterations, double *residual)
+{
+  if (!dev) GSL_ERROR("simplex_mesh_device_gradients: null device mirror", GSL_EFAULT);
+  int st = cubic_status(dev);
+  if (st) return st;
+  if (gradients && (gradients->size1 != (size_t)dev->n_points || gradients->size2 != 2))
+    GSL_ERROR("simplex_mesh_device_gradients: gradients must be (number of points) x 2", GSL_EBADLEN);
+  const int ps = cubic_prepare(dev);
+  if (iterations) *iterations = dev->ct_iters;
+  if (residual) *residual = dev->ct_resid;
+  if (ps != GSL_SUCCESS && ps != GSL_EMAXITER) return ps;
+  if (gradients) {
+    const size_t np = (size_t)dev->n_points;
+    double *h = (double *)malloc(2 * np * sizeof(double));
+    if (!h) GSL_ERROR("simplex_mesh_device_gradients: out of memory", GSL_ENOMEM);
+    st = gsl_sinterp_hip_d2h(dev->ctx, h, dev->ct_g, 2 * np * sizeof(double));
+    if (!st)
+      for (size_t i = 0; i < np; i++) { gradients->data[i * gradients->tda] = h[2 * i]; gradients->data[i * gradients->tda + 1] = h[2 * i + 1]; }
+    free(h);
+    if (st) GSL_ERROR(gsl_sinterp_hip_last_error(dev->ctx), st);
+  }
+  return ps;
+}
+
+/* locate + linear value by the unchanged linear path (batches >= 4096 through its sorted route), then the cubic sweep
+   over the triangle it found; the linear values pass through d_values */
+int simplex_mesh_device_eval_cubic_resident(simplex_mesh_device *dev, const double *d_targets, size_t m, size_t ttda, double *d_values,
+                                            double *d_gradient, size_t gtda, int *d_triangle)
+{
+  if (!dev) GSL_ERROR("simplex_mesh_device_eval_cubic_resident: null device mirror", GSL_EFAULT);
+  int st = cubic_status(dev);
+  if (st) return st;
+  if (m > 0 && (!d_targets || !d_values)) GSL_ERROR("simplex_mesh_device_eval_cubic_resident: null argument", GSL_EFAULT);
+  if (ttda < 2) GSL_ERROR("simplex_mesh_device_eval_cubic_resident: target rows shorter than the mesh's dimension", GSL_EBADLEN);
+  if (d_gradient && gtda < 2) GSL_ERROR("simplex_mesh_device_eval_cubic_resident: gradient rows shorter than the mesh's dimension", GSL_EBADLEN);
+  if (m == 0) return GSL_SUCCESS;
+  st = cubic_prepare(dev);
+  if (st == GSL_EMAXITER && dev->ct_rec) st = GSL_SUCCESS;          /* reported by the call that estimated */
+  if (st) return st;
+  if (!d_triangle) {
+    if (m > dev->ct_leaf_cap) {
+      gsl_sinterp_hip_free(dev->ctx, dev->ct_leaf); dev->ct_leaf = NULL; dev->ct_leaf_cap = 0;
+      st = gsl_sinterp_hip_malloc(dev->ctx, (void **)&dev->ct_leaf, m * sizeof(int));
+      if (!st) dev->ct_leaf_cap = m;
+    }
+    d_triangle = dev->ct_leaf;
+  }
+  if (!st) st = gsl_sinterp_hip_mesh_eval(dev->ctx, dev->n_tri, dev->m_records[0], dev->m_leaftab[0], dev->m_seed[0], dev->G, dev->geom,
+                                          dev->convex, d_targets, m, ttda, d_values, d_triangle, NULL);
+  if (!st) st = gsl_sinterp_hip_mesh_cubic_eval(dev->ctx, dev->n_tri, dev->ct_rec, d_triangle, d_values, d_targets, m, ttda, d_values,
+                                                d_gradient, gtda);
+  if (st) GSL_ERROR(gsl_sinterp_hip_last_error(dev->ctx), st);
+  return GSL_SUCCESS;
+}
+
+static int cubic_chunk_eval(void *state, const double *d_y, size_t m, double *d_s, int *d_leaf)
+{
+  simplex_mesh_device *dev = (simplex_mesh_device *)state;
+  int st = gsl_sinterp_hip_mesh_eval(dev->ctx, dev->n_tri, dev->m_records[0], dev->m_leaftab[0], dev->m_seed[0], dev->G, dev->geom, dev->convex,
+                                     d_y, m, 2, d_s, d_leaf, (long long *)NULL);
+  if (st) return st;
+  return gsl_sinterp_hip_mesh_cubic_eval(dev->ctx, dev->n_tri, dev->ct_rec, d_leaf, d_s, d_y, m, 2, d_s, (double *)NULL, 0);
+}
+
+/* host batches.  Values only: the chunk pipe of the linear entries.  With gradients: one staging buffer on either side,
+   [targets m x 2 | values m | gradient m x 2 | triangle m] */
+int simplex_mesh_device_eval_cubic_many(simplex_mesh_device *dev, const gsl_matrix *targets, gsl_vector *values, gsl_matrix *gradient,
+                                        int *triangle)
+{
+  if (!dev || !targets || !values) GSL_ERROR("simplex_mesh_device_eval_cubic_many: null argument", GSL_EFAULT);
+  int st = cubic_status(dev);
+  if (st) return st;
+  if (targets->size2 != 2) GSL_ERROR("simplex_mesh_device_eval_cubic_many: targets must be M x 2", GSL_EBADLEN);
+  const size_t m = targets->size1;
+  if (values->size != m) GSL_ERROR("simplex_mesh_device_eval_cubic_many: values length must equal target rows", GSL_EBADLEN);
+  if (gradient && (gradient->size1 != m || gradient->size2 != 2))
+    GSL_ERROR("simplex_mesh_device_eval_cubic_many: gradient must be M x 2", GSL_EBADLEN);
+  if (m == 0) return GSL_SUCCESS;
+  gsl_sinterp_hip_ctx *c = dev->ctx;
+  if (!gradient) {
+    st = cubic_prepare(dev);
+    if (st == GSL_EMAXITER && dev->ct_rec) st = GSL_SUCCESS;          /* reported by the call that estimated */
+    if (st) return st;
+    size_t neg = 0;
+    st = chunk_eval_many(&dev->cs, c, 2, targets, values, triangle, &cubic_chunk_eval, dev, 1, &neg);
+    if (st != GSL_SUCCESS) GSL_ERROR("simplex_mesh_device_eval_cubic_many: evaluation failed", st);
+    if (neg) GSL_ERROR("simplex_mesh_device_eval_cubic_many: target(s) outside the triangulation", GSL_EDOM);
+    return GSL_SUCCESS;
+  }
+  const size_t nd = 5 * m, bytes = nd * sizeof(double) + m * sizeof(int);
+  double *h = (double *)malloc(bytes), *d = NULL;
+  if (!h) GSL_ERROR("simplex_mesh_device_eval_cubic_many: out of memory", GSL_ENOMEM);
+  for (size_t k = 0; k < m; k++) { h[2 * k] = targets->data[k * targets->tda]; h[2 * k + 1] = targets->data[k * targets->tda + 1]; }
+  st = gsl_sinterp_hip_malloc(c, (void **)&d, bytes);
+  if (!st) st = gsl_sinterp_hip_h2d(c, d, h, 2 * m * sizeof(double));
+  int es = GSL_SUCCESS;
+  long long outside_n = 0;
+  int *d_tri = (int *)(d + nd);
+  if (!st) es = simplex_mesh_device_eval_cubic_resident(dev, d, m, 2, d + 2 * m, d + 3 * m, 2, d_tri);
+  if (!st && !es) st = gsl_sinterp_hip_count_negative(c, d_tri, m, &outside_n);
+  if (!st && !es) st = gsl_sinterp_hip_d2h(c, h, d + 2 * m, bytes - 2 * m * sizeof(double));
+  if (!st && !es) {
+    for (size_t k = 0; k < m; k++) values->data[k * values->stride] = h[k];
+    for (size_t k = 0; k < m; k++) { gradient->data[k * gradient->tda] = h[m + 2 * k]; gradient->data[k * gradient->tda + 1] = h[m + 2 * k + 1]; }
+    if (triangle) memcpy(triangle, h + 3 * m, m * sizeof(int));
+  }
+  gsl_sinterp_hip_free(c, d);
+  free(h);
+  if (st) GSL_ERROR(gsl_sinterp_hip_last_error(c), st);
+  if (es) return es;
+  if (outside_n) GSL_ERROR("simplex_mesh_device_eval_cubic_many: target(s) outside the triangulation", GSL_EDOM);
   return GSL_SUCCESS;
 }
 
@@ -1467,6 +1703,11 @@ typedef struct {
   simplex_mesh_device *dev;
   gsl_matrix *x;             /* private copies (checkpoints) */
   gsl_vector *f;
+  /* the Clough-Tocher types only: g_set = the caller's gradients (gsl_sinterp_set_gradients; NULL = estimate), g = the
+     gradients in use after init / fread, the stopping rule of the estimate (0 = the mirror's defaults) and what it took */
+  gsl_matrix *g_set, *g;
+  double g_rtol, g_resid;
+  size_t g_maxiter, g_iters;
 } mesh_state;
 
 static void *mesh_type_alloc(size_t dim, size_t size)
@@ -1485,6 +1726,8 @@ static void mesh_type_free(void *vstate)
   simplex_mesh_free(st->mesh);
   gsl_matrix_free(st->x);
   gsl_vector_free(st->f);
+  if (st->g_set) gsl_matrix_free(st->g_set);
+  if (st->g) gsl_matrix_free(st->g);
   free(st->tri); free(st->nbr);
   free(st);
 }
@@ -1611,6 +1854,69 @@ static int natural_type_eval_resident(const gsl_sinterp *interp, const double *d
 }
 
 /* ======================================================================== */
+/* Clough-Tocher types: the same mesh_state, plus the gradients at the sites */
+/* ======================================================================== */
+/* mirror, then the gradients: `known` (the caller's, or a checkpoint's) or the estimate, which runs here so that
+   gsl_sinterp_get_gradients and a GSL_EMAXITER verdict belong to init */
+static int cubic_type_mirror(gsl_sinterp *interp, mesh_state *st, const gsl_matrix *known)
+{
+  if (interp->n_devices > 1) GSL_ERROR("gsl_sinterp_init: Clough-Tocher interpolants run on one device", GSL_EUNSUP);
+  int s = mesh_type_mirror(interp, st);
+  if (s) return s;
+  if (st->g_rtol > 0.0) s = simplex_mesh_device_set_gradient_options(st->dev, st->g_rtol, st->g_maxiter);
+  if (!s) s = simplex_mesh_device_bind_gradients(st->dev, known);
+  if (s) return s;
+  if (st->g) gsl_matrix_free(st->g);
+  st->g = gsl_matrix_alloc(st->n, 2);
+  if (!st->g) return GSL_ENOMEM;
+  return simplex_mesh_device_gradients(st->dev, st->g, &st->g_iters, &st->g_resid);
+}
+
+static int cubic_mesh_init(gsl_sinterp *interp, const gsl_matrix *x, const gsl_vector *f)
+{
+  mesh_state *st = (mesh_state *)interp->state;
+  if (!st->tri) GSL_ERROR("gsl_sinterp_init: no triangulation set (gsl_sinterp_set_triangulation)", GSL_EINVAL);
+  if (st->n < 3) GSL_ERROR("gsl_sinterp_init: an imported triangulation needs at least dim + 1 points", GSL_EINVAL);
+  int s = natural_copy_data(st, x, f);
+  if (s) return s;
+  st->mesh = simplex_mesh_import(st->x, st->tri, st->nbr, st->n_tri);
+  if (!st->mesh) return GSL_EINVAL;
+  return cubic_type_mirror(interp, st, st->g_set);
+}
+
+/* the tree of gsl_sinterp_natural_simplex, exported and dropped */
+static int cubic_simplex_init(gsl_sinterp *interp, const gsl_matrix *x, const gsl_vector *f)
+{
+  mesh_state *st = (mesh_state *)interp->state;
+  int s = natural_copy_data(st, x, f);
+  if (s) return s;
+  simplex_tree *tree = simplex_tree_alloc(2, (int)st->n);
+  if (!tree) return GSL_ENOMEM;
+  s = simplex_tree_init(tree, st->x, NULL, NULL, interp->init_flags, interp->rng);
+  if (s == GSL_SUCCESS) {
+    st->mesh = simplex_mesh_from_tree(tree, st->x);
+    if (!st->mesh) s = GSL_EINVAL;
+  }
+  simplex_tree_free(tree);
+  if (s != GSL_SUCCESS) return s;
+  return cubic_type_mirror(interp, st, st->g_set);
+}
+
+static int cubic_type_eval_many(const gsl_sinterp *interp, const gsl_matrix *y, gsl_vector *s, int *leaf)
+{
+  const mesh_state *st = (const mesh_state *)interp->state;
+  if (!st->dev) GSL_ERROR("gsl_sinterp_eval_many: interpolant not initialised", GSL_EINVAL);
+  return simplex_mesh_device_eval_cubic_many(st->dev, y, s, NULL, leaf);
+}
+
+static int cubic_type_eval_resident(const gsl_sinterp *interp, const double *d_y, size_t m, size_t ytda, double *d_s, int *d_leaf)
+{
+  const mesh_state *st = (const mesh_state *)interp->state;
+  if (!st->dev) GSL_ERROR("gsl_sinterp_eval_resident: interpolant not initialised", GSL_EINVAL);
+  return simplex_mesh_device_eval_cubic_resident(st->dev, d_y, m, ytda, d_s, NULL, 0, d_leaf);
+}
+
+/* ======================================================================== */
 /* type table + generic entry points                                         */
 /* ======================================================================== */
 static const gsl_sinterp_type gauss_type = {"rbf-gaussian", 1, &rbf_gauss_alloc, &rbf_init, &rbf_eval_many, &rbf_eval_resident, &rbf_free};
@@ -1625,7 +1931,14 @@ const gsl_sinterp_type *gsl_sinterp_natural_mesh = &natural_mesh_type;
 const gsl_sinterp_type *gsl_sinterp_natural_simplex = &natural_simplex_type;
 /* the types whose state is a mesh_state, and the natural-neighbour ones among them */
 static int is_natural_type(const gsl_sinterp_type *T) { return T == &natural_mesh_type || T == &natural_simplex_type; }
-static int is_mesh_state_type(const gsl_sinterp_type *T) { return T == &mesh_type || is_natural_type(T); }
+static const gsl_sinterp_type cubic_mesh_type = {"clough-tocher-imported-triangulation", 3, &natural_type_alloc, &cubic_mesh_init, &cubic_type_eval_many, &cubic_type_eval_resident, &mesh_type_free};
+static const gsl_sinterp_type cubic_simplex_type = {"clough-tocher-simplex", 3, &natural_type_alloc, &cubic_simplex_init, &cubic_type_eval_many, &cubic_type_eval_resident, &mesh_type_free};
+const gsl_sinterp_type *gsl_sinterp_cubic_mesh = &cubic_mesh_type;
+const gsl_sinterp_type *gsl_sinterp_cubic_simplex = &cubic_simplex_type;
+static int is_cubic_type(const gsl_sinterp_type *T) { return T == &cubic_mesh_type || T == &cubic_simplex_type; }
+/* the 2-D mesh types beyond the linear one: what the natural-neighbour types refuse, the Clough-Tocher types refuse too */
+static int is_mesh2_type(const gsl_sinterp_type *T) { return is_natural_type(T) || is_cubic_type(T); }
+static int is_mesh_state_type(const gsl_sinterp_type *T) { return T == &mesh_type || is_mesh2_type(T); }
 static const gsl_sinterp_type tps_affine_type = {"rbf-thin-plate-spline-affine", 3, &rbf_tps_affine_alloc, &rbf_init, &rbf_eval_many, &rbf_eval_resident, &rbf_free};
 const gsl_sinterp_type *gsl_sinterp_rbf_tps_affine = &tps_affine_type;
 static const gsl_sinterp_type krige_type = {"ordinary-kriging-gaussian", 1, &krige_alloc, &rbf_init, &rbf_eval_many, &rbf_eval_resident, &rbf_free};
@@ -1664,6 +1977,7 @@ int gsl_sinterp_set_neighbours(gsl_sinterp *interp, size_t k)
 {
   if (!interp) GSL_ERROR("gsl_sinterp_set_neighbours: null interpolant", GSL_EFAULT);
   if (is_natural_type(interp->type)) GSL_ERROR("gsl_sinterp_set_neighbours: not for natural-neighbour interpolants", GSL_EUNSUP);
+  if (is_cubic_type(interp->type)) GSL_ERROR("gsl_sinterp_set_neighbours: not for Clough-Tocher interpolants", GSL_EUNSUP);
   if (!is_krige_type(interp->type)) GSL_ERROR("gsl_sinterp_set_neighbours: kriging interpolants only", GSL_EINVAL);
   if (k > GSL_SINTERP_MAX_NEIGHBOURS) GSL_ERROR("gsl_sinterp_set_neighbours: at most 64 neighbours", GSL_EINVAL);
   if (k > interp->size) GSL_ERROR("gsl_sinterp_set_neighbours: more neighbours than centres", GSL_EINVAL);
@@ -1681,6 +1995,8 @@ gsl_sinterp *gsl_sinterp_alloc(const gsl_sinterp_type *T, size_t dim, size_t siz
     GSL_ERROR_NULL("gsl_sinterp_alloc: linear-simplex supports dim = 2 only", GSL_EUNIMPL);
   if (is_natural_type(T) && dim != 2)
     GSL_ERROR_NULL("gsl_sinterp_alloc: natural-neighbour interpolants support dim = 2 only", GSL_EUNIMPL);
+  if (is_cubic_type(T) && dim != 2)
+    GSL_ERROR_NULL("gsl_sinterp_alloc: Clough-Tocher interpolants support dim = 2 only", GSL_EUNIMPL);
   gsl_sinterp *interp = (gsl_sinterp *)calloc(1, sizeof *interp);
   if (!interp) GSL_ERROR_NULL("failed to allocate space for sinterp struct", GSL_ENOMEM);
   interp->type = T; interp->dim = dim; interp->size = size;
@@ -1771,6 +2087,7 @@ int gsl_sinterp_set_loo(gsl_sinterp *interp, int want)
 static int loo_status(const gsl_sinterp *interp)
 {
   if (is_natural_type(interp->type)) GSL_ERROR("gsl_sinterp_loo: not for natural-neighbour interpolants", GSL_EUNSUP);
+  if (is_cubic_type(interp->type)) GSL_ERROR("gsl_sinterp_loo: not for Clough-Tocher interpolants", GSL_EUNSUP);
   if (!is_pd_type(interp->type))
     GSL_ERROR("gsl_sinterp_loo: positive definite RBF (Gaussian, Wendland, Matern, inverse multiquadric) and kriging interpolants only", GSL_EINVAL);
   if (is_local(interp)) GSL_ERROR("gsl_sinterp_loo: local kriging (gsl_sinterp_set_neighbours) takes a route without a Cholesky factor", GSL_EUNSUP);
@@ -1830,6 +2147,7 @@ gsl_sinterp_fit_workspace *gsl_sinterp_fit_alloc(const gsl_sinterp *interp, cons
 {
   if (!interp || !x || !f) GSL_ERROR_NULL("gsl_sinterp_fit_alloc: null argument", GSL_EFAULT);
   if (is_natural_type(interp->type)) GSL_ERROR_NULL("gsl_sinterp_fit_alloc: not for natural-neighbour interpolants (nothing to fit)", GSL_EUNSUP);
+  if (is_cubic_type(interp->type)) GSL_ERROR_NULL("gsl_sinterp_fit_alloc: not for Clough-Tocher interpolants (nothing to fit)", GSL_EUNSUP);
   if (!is_pd_type(interp->type))
     GSL_ERROR_NULL("gsl_sinterp_fit_alloc: positive definite RBF (Gaussian, Wendland, Matern, inverse multiquadric) and kriging interpolants only", GSL_EINVAL);
   const size_t n = interp->size, dim = interp->dim;
@@ -2059,6 +2377,7 @@ int gsl_sinterp_fit_sigma2(const gsl_sinterp_fit_workspace *w, double *s2)
 static int variance_status(const gsl_sinterp *interp)
 {
   if (is_natural_type(interp->type)) GSL_ERROR("gsl_sinterp_eval_variance: not for natural-neighbour interpolants", GSL_EUNSUP);
+  if (is_cubic_type(interp->type)) GSL_ERROR("gsl_sinterp_eval_variance: not for Clough-Tocher interpolants", GSL_EUNSUP);
   if (!is_krige_type(interp->type)) GSL_ERROR("gsl_sinterp_eval_variance: kriging interpolants only", GSL_EINVAL);
   const rbf_state *st = (const rbf_state *)interp->state;
   if (!st->d_w) GSL_ERROR("gsl_sinterp_eval_variance: interpolant not initialised", GSL_EINVAL);
@@ -2156,6 +2475,7 @@ int gsl_sinterp_eval_local_many(const gsl_sinterp *interp, const gsl_matrix *y, 
 static int grad_status(const gsl_sinterp *interp)
 {
   if (is_natural_type(interp->type)) GSL_ERROR("gsl_sinterp_eval_grad: not for natural-neighbour interpolants", GSL_EUNSUP);
+  if (is_cubic_type(interp->type)) return GSL_SUCCESS;     /* the one mesh type with a continuous gradient */
   if (interp->type == &simplex_type || interp->type == &mesh_type)
     GSL_ERROR("gsl_sinterp_eval_grad: RBF-family interpolants only (the piecewise-linear gradient is constant per leaf)", GSL_EUNSUP);
   if (is_local(interp))
@@ -2170,6 +2490,13 @@ int gsl_sinterp_eval_grad_resident(const gsl_sinterp *interp, const double *d_y,
   if (m > 0 && (!d_y || !d_g)) GSL_ERROR("gsl_sinterp_eval_grad_resident: null argument", GSL_EFAULT);
   int gs = grad_status(interp);
   if (gs) return gs;
+  if (is_cubic_type(interp->type)) {
+    const mesh_state *ms = (const mesh_state *)interp->state;
+    if (!ms->dev) GSL_ERROR("gsl_sinterp_eval_grad: interpolant not initialised", GSL_EINVAL);
+    if (m > 0 && !d_s) GSL_ERROR("gsl_sinterp_eval_grad_resident: Clough-Tocher interpolants need d_s (the locate step writes through it)", GSL_EFAULT);
+    if (gtda < 2) GSL_ERROR("gsl_sinterp_eval_grad_resident: gradient rows shorter than dim", GSL_EINVAL);
+    return simplex_mesh_device_eval_cubic_resident(ms->dev, d_y, m, ytda, d_s, d_g, gtda, NULL);
+  }
   const rbf_state *st = (const rbf_state *)interp->state;
   if (!st->d_w) GSL_ERROR("gsl_sinterp_eval_grad: interpolant not initialised", GSL_EINVAL);
   /* the tail: the affine polynomial, or kriging's constant mean; member 0 evaluates every target (as
@@ -2190,6 +2517,17 @@ int gsl_sinterp_eval_grad_many(const gsl_sinterp *interp, const gsl_matrix *y, g
   if (y->size2 != dim) GSL_ERROR("target matrix must have dim columns", GSL_EBADLEN);
   if (g->size1 != m || g->size2 != dim) GSL_ERROR("gradient matrix must be (number of targets) x dim", GSL_EBADLEN);
   if (sv && sv->size != m) GSL_ERROR("output length must equal the number of targets", GSL_EBADLEN);
+  if (is_cubic_type(interp->type)) {
+    const mesh_state *ms = (const mesh_state *)interp->state;
+    if (!ms->dev) GSL_ERROR("gsl_sinterp_eval_grad: interpolant not initialised", GSL_EINVAL);
+    if (sv) return simplex_mesh_device_eval_cubic_many(ms->dev, y, sv, g, NULL);
+    if (m == 0) return GSL_SUCCESS;
+    gsl_vector *tmp = gsl_vector_alloc(m);                  /* a gradient-only call: the values are dropped */
+    if (!tmp) GSL_ERROR("gsl_sinterp_eval_grad_many: out of memory", GSL_ENOMEM);
+    const int cs = simplex_mesh_device_eval_cubic_many(ms->dev, y, tmp, g, NULL);
+    gsl_vector_free(tmp);
+    return cs;
+  }
   const rbf_state *st = (const rbf_state *)interp->state;
   if (!st->d_w) GSL_ERROR("gsl_sinterp_eval_grad: interpolant not initialised", GSL_EINVAL);
   if (m == 0) return GSL_SUCCESS;
@@ -2240,6 +2578,7 @@ int gsl_sinterp_eval_grad_e(const gsl_sinterp *interp, const gsl_vector *y, doub
 static int fields_status(const gsl_sinterp *interp)
 {
   if (is_natural_type(interp->type)) GSL_ERROR("gsl_sinterp fields: not for natural-neighbour interpolants (one response)", GSL_EUNSUP);
+  if (is_cubic_type(interp->type)) GSL_ERROR("gsl_sinterp fields: not for Clough-Tocher interpolants (one response)", GSL_EUNSUP);
   if (interp->type == &simplex_type || interp->type == &mesh_type)
     GSL_ERROR("gsl_sinterp fields: RBF-family interpolants only (several responses per leaf of the linear types: a separate entry)", GSL_EUNSUP);
   if (is_local(interp)) GSL_ERROR("gsl_sinterp fields: not with gsl_sinterp_set_neighbours (local kriging has one field)", GSL_EUNSUP);
@@ -2447,7 +2786,7 @@ int gsl_sinterp_route(const gsl_sinterp *interp) { return interp ? interp->route
 int gsl_sinterp_set_triangulation(gsl_sinterp *interp, const int *triangles, const int *neighbours, size_t n_triangles)
 {
   if (!interp || !triangles) GSL_ERROR("gsl_sinterp_set_triangulation: null argument", GSL_EFAULT);
-  if (interp->type != &mesh_type && interp->type != &natural_mesh_type)
+  if (interp->type != &mesh_type && interp->type != &natural_mesh_type && interp->type != &cubic_mesh_type)
     GSL_ERROR("gsl_sinterp_set_triangulation: imported-triangulation interpolants only", GSL_EINVAL);
   mesh_state *st = (mesh_state *)interp->state;
   const size_t w = st->dim + 1;                          /* ids per simplex */
@@ -2458,6 +2797,53 @@ int gsl_sinterp_set_triangulation(gsl_sinterp *interp, const int *triangles, con
   if (nb) memcpy(nb, neighbours, w * n_triangles * sizeof(int));
   free(st->tri); free(st->nbr);
   st->tri = t; st->nbr = nb; st->n_tri = n_triangles;
+  return GSL_SUCCESS;
+}
+
+/* ---- the gradients of the Clough-Tocher types ---- */
+int gsl_sinterp_set_gradients(gsl_sinterp *interp, const gsl_matrix *gradients)
+{
+  if (!interp) GSL_ERROR("gsl_sinterp_set_gradients: null interpolant", GSL_EFAULT);
+  if (!is_cubic_type(interp->type)) GSL_ERROR("gsl_sinterp_set_gradients: Clough-Tocher interpolants only", GSL_EINVAL);
+  mesh_state *st = (mesh_state *)interp->state;
+  if (gradients && (gradients->size1 != st->n || gradients->size2 != 2))
+    GSL_ERROR("gsl_sinterp_set_gradients: gradients must be size x 2", GSL_EBADLEN);
+  gsl_matrix *copy = NULL;
+  if (gradients) {
+    copy = gsl_matrix_alloc(st->n, 2);
+    if (!copy) GSL_ERROR("gsl_sinterp_set_gradients: out of memory", GSL_ENOMEM);
+    for (size_t i = 0; i < st->n; i++)
+      for (size_t j = 0; j < 2; j++) gsl_matrix_set(copy, i, j, gradients->data[i * gradients->tda + j]);
+  }
+  if (st->g_set) gsl_matrix_free(st->g_set);
+  st->g_set = copy;
+  return GSL_SUCCESS;
+}
+
+int gsl_sinterp_set_gradient_options(gsl_sinterp *interp, double rtol, size_t maxiter)
+{
+  if (!interp) GSL_ERROR("gsl_sinterp_set_gradient_options: null interpolant", GSL_EFAULT);
+  if (!is_cubic_type(interp->type)) GSL_ERROR("gsl_sinterp_set_gradient_options: Clough-Tocher interpolants only", GSL_EINVAL);
+  if (!(rtol > 0.0 && rtol < 1.0) || maxiter < 1 || maxiter > (size_t)INT_MAX)
+    GSL_ERROR("gsl_sinterp_set_gradient_options: need 0 < rtol < 1 and maxiter >= 1", GSL_EINVAL);
+  mesh_state *st = (mesh_state *)interp->state;
+  st->g_rtol = rtol; st->g_maxiter = maxiter;
+  return GSL_SUCCESS;
+}
+
+int gsl_sinterp_get_gradients(const gsl_sinterp *interp, gsl_matrix *gradients, size_t *iterations, double *residual)
+{
+  if (!interp) GSL_ERROR("gsl_sinterp_get_gradients: null interpolant", GSL_EFAULT);
+  if (!is_cubic_type(interp->type)) GSL_ERROR("gsl_sinterp_get_gradients: Clough-Tocher interpolants only", GSL_EINVAL);
+  const mesh_state *st = (const mesh_state *)interp->state;
+  if (!st->dev || !st->g) GSL_ERROR("gsl_sinterp_get_gradients: interpolant not initialised", GSL_EINVAL);
+  if (gradients && (gradients->size1 != st->n || gradients->size2 != 2))
+    GSL_ERROR("gsl_sinterp_get_gradients: gradients must be size x 2", GSL_EBADLEN);
+  if (gradients)
+    for (size_t i = 0; i < st->n; i++)
+      for (size_t j = 0; j < 2; j++) gradients->data[i * gradients->tda + j] = gsl_matrix_get(st->g, i, j);
+  if (iterations) *iterations = st->g_iters;
+  if (residual) *residual = st->g_resid;
   return GSL_SUCCESS;
 }
 
@@ -2554,7 +2940,7 @@ static gsl_sinterp_hip_ctx *interp_ctx0(const gsl_sinterp *interp)
     const simplex_state *st = (const simplex_state *)interp->state;
     return st->dev ? st->dev->ctx : NULL;
   }
-  if (is_natural_type(interp->type)) {
+  if (is_mesh2_type(interp->type)) {
     const mesh_state *st = (const mesh_state *)interp->state;
     return st->dev ? st->dev->ctx : NULL;
   }
@@ -2595,7 +2981,7 @@ int gsl_sinterp_eval_grid(const gsl_sinterp *interp, const gsl_vector *min, cons
   free(h_s);
   HIP_TRY(st, c);
   if (interp->type == &simplex_type && n_nan) GSL_ERROR("gsl_sinterp_eval_grid: grid node(s) outside the caging simplex", GSL_EDOM);
-  if (is_natural_type(interp->type) && n_nan) GSL_ERROR("gsl_sinterp_eval_grid: grid node(s) outside the triangulation", GSL_EDOM);
+  if (is_mesh2_type(interp->type) && n_nan) GSL_ERROR("gsl_sinterp_eval_grid: grid node(s) outside the triangulation", GSL_EDOM);
   return GSL_SUCCESS;
 }
 
@@ -2633,6 +3019,8 @@ static int type_id(const gsl_sinterp_type *T)
   if (T == &krige_matern52_type) return 11;
   if (T == &natural_mesh_type) return 12;                 /* 12 / 13: natural neighbours, with the payload of type 6 */
   if (T == &natural_simplex_type) return 13;
+  if (T == &cubic_mesh_type) return 14;                   /* 14 / 15: Clough-Tocher, the payload of type 6 + the 2 N gradients */
+  if (T == &cubic_simplex_type) return 15;
   return T == &gauss_type ? 0 : (T == &tps_type ? 1 : (T == &wendland_type ? 3 : (T == &krige_type ? 4 : (T == &tps_affine_type ? 5 : (T == &mesh_type ? 6 : 2)))));
 }
 
@@ -2670,6 +3058,13 @@ int gsl_sinterp_fwrite(FILE *stream, const gsl_sinterp *interp)
     for (size_t i = 0; i < st->n; i++) {
       const double fi = gsl_vector_get(st->f, i);
       if (fwrite(&fi, sizeof fi, 1, stream) != 1) GSL_ERROR("fwrite failed", GSL_EFAILED);
+    }
+    if (is_cubic_type(interp->type)) {
+      if (!st->g) GSL_ERROR("gsl_sinterp_fwrite: interpolant not initialised", GSL_EINVAL);
+      for (size_t i = 0; i < st->n; i++) {
+        const double gi[2] = {gsl_matrix_get(st->g, i, 0), gsl_matrix_get(st->g, i, 1)};
+        if (fwrite(gi, sizeof(double), 2, stream) != 2) GSL_ERROR("fwrite failed", GSL_EFAILED);
+      }
     }
     return GSL_SUCCESS;
   }
@@ -2749,10 +3144,25 @@ int gsl_sinterp_fread(FILE *stream, gsl_sinterp *interp)
         for (size_t j = 0; j < st->dim; j++) gsl_matrix_set(x, i, j, simplex_mesh_points(mesh)[st->dim * i + j]);
       }
     }
-    if (!ok) { simplex_mesh_free(mesh); gsl_matrix_free(x); gsl_vector_free(f); GSL_ERROR("fread failed", GSL_EFAILED); }
+    gsl_matrix *g = NULL;                                /* Clough-Tocher: the gradients follow the response */
+    if (ok && is_cubic_type(interp->type)) {
+      g = gsl_matrix_alloc(st->n, 2);
+      ok = g != NULL;
+      for (size_t i = 0; ok && i < st->n; i++) ok = fread(g->data + i * g->tda, sizeof(double), 2, stream) == 2;
+    }
+    if (!ok) {
+      simplex_mesh_free(mesh); gsl_matrix_free(x); gsl_vector_free(f);
+      if (g) gsl_matrix_free(g);
+      GSL_ERROR("fread failed", GSL_EFAILED);
+    }
     simplex_mesh_device_free(st->dev); st->dev = NULL;
     simplex_mesh_free(st->mesh); gsl_matrix_free(st->x); gsl_vector_free(st->f);
     st->mesh = mesh; st->x = x; st->f = f;
+    if (is_cubic_type(interp->type)) {                   /* the stored gradients are bound: nothing is estimated again */
+      const int s = cubic_type_mirror(interp, st, g);
+      gsl_matrix_free(g);
+      return s;
+    }
     /* upload + pack + bind: nothing is re-imported */
     return is_natural_type(interp->type) ? natural_type_mirror(interp, st) : mesh_type_mirror(interp, st);
   }

@@ -239,6 +239,11 @@ const double *simplex_mesh_points(const simplex_mesh *mesh);    /* [dim n_points
    coordinates as given (QHull / CGAL output), 2 = in the mesh's standardised coordinates (simplex_mesh_geometry: a mesh
    exported from a simplex_tree, whose build standardises per axis), 0 = in neither, and for a 3-D mesh.  O(n). */
 int simplex_mesh_delaunay_metric(const simplex_mesh *mesh);
+/* Vertex -> neighbour CSR of a 2-D mesh: every undirected edge of the triangulation once per endpoint (hull edges
+   included), the neighbours of a vertex ascending.  offsets [n_points + 1] is always filled and *n_entries receives
+   offsets[n_points]; neighbours (may be NULL: count only) receives the entries when capacity >= *n_entries, otherwise
+   GSL_EBADLEN (6 n_triangles always suffices).  Host, O(n).  GSL_EUNSUP for a 3-D mesh. */
+int simplex_mesh_vertex_adjacency(const simplex_mesh *mesh, int *offsets, int *neighbours, size_t capacity, size_t *n_entries);
 void simplex_mesh_bbox(const simplex_mesh *mesh, double *lo, double *hi);   /* dim entries each */
 /* binary checkpoint of a mesh (gsl_matrix_fwrite conventions); fread re-validates ids and neighbour links.  A 2-D mesh
    writes the GSLSMSH1 layout; a 3-D mesh writes GSLSMSH2, whose header carries dim; fread accepts both */
@@ -265,6 +270,29 @@ int simplex_mesh_device_eval_resident(simplex_mesh_device *dev, const double *d_
 int simplex_mesh_device_eval_natural_many(simplex_mesh_device *dev, const gsl_matrix *targets, gsl_vector *values, int *triangle);
 int simplex_mesh_device_eval_natural_resident(simplex_mesh_device *dev, const double *d_targets, size_t m, size_t ttda,
                                               double *d_values, int *d_triangle);
+/* Clough-Tocher C1 piecewise-cubic interpolation on the same mirror, with gradients ("Clough-Tocher";
+   csrc/hip/cubic.hip): interpolates the data and the vertex gradients, C1 everywhere, reproduces quadratics when the
+   gradients are exact.  Needs no Delaunay property and no convexity: any 2-D mesh qualifies.
+     bind_gradients   gradients [n_points x 2] to interpolate, or NULL = estimate them (the global estimator of scipy's
+                      CloughTocher2DInterpolator, solved on the device by preconditioned conjugate gradients to the
+                      options below; defaults rtol = 1e-12, maxiter = 1000).  Drops what an earlier binding computed.
+                      simplex_mesh_device_set_response drops the gradients and the records as well.
+     gradients        the gradients in use [n_points x 2] (estimates them now if that is still to do), the iterations
+                      the estimate took (0 for bound gradients) and its relative residual; any output may be NULL.
+                      GSL_EMAXITER: maxiter was reached before rtol; count and residual are still returned.
+     eval_cubic_*     shapes and statuses of the linear entries; gradient (may be NULL) receives grad s in raw
+                      coordinates, M x 2 (resident: row k at d_gradient + k * gtda, gtda >= 2); the value bits do not
+                      depend on it.  A target outside gives NaN in the value and the gradient, triangle -1, GSL_EDOM.
+   Nothing is computed, uploaded or kept for these entries until the first call of gradients / eval_cubic_*: it reads
+   the mesh (adjacency, links, points), so `mesh` must still be alive then.  GSL_EUNSUP: a 3-D mesh, a device group
+   of more than one member. */
+int simplex_mesh_device_bind_gradients(simplex_mesh_device *dev, const gsl_matrix *gradients);
+int simplex_mesh_device_set_gradient_options(simplex_mesh_device *dev, double rtol, size_t maxiter);
+int simplex_mesh_device_gradients(simplex_mesh_device *dev, gsl_matrix *gradients, size_t *iterations, double *residual);
+int simplex_mesh_device_eval_cubic_many(simplex_mesh_device *dev, const gsl_matrix *targets, gsl_vector *values, gsl_matrix *gradient,
+                                        int *triangle);
+int simplex_mesh_device_eval_cubic_resident(simplex_mesh_device *dev, const double *d_targets, size_t m, size_t ttda, double *d_values,
+                                            double *d_gradient, size_t gtda, int *d_triangle);
 gsl_sinterp_hip_ctx *simplex_mesh_device_ctx(simplex_mesh_device *dev);
 
 /* ======================================================================== */
@@ -329,6 +357,20 @@ extern const gsl_sinterp_type *gsl_sinterp_linear_mesh;
    init).  Gradients, fields, variance, leave-one-out, fit and set_neighbours: GSL_EUNSUP.  Checkpoints: type ids 12 /
    13 with the mesh payload of gsl_sinterp_linear_mesh. */
 extern const gsl_sinterp_type *gsl_sinterp_natural_mesh, *gsl_sinterp_natural_simplex;
+/* Clough-Tocher C1 piecewise-cubic interpolation, dim 2 only (scipy's CloughTocher2DInterpolator, griddata's "cubic"):
+   interpolates the data and a gradient at every site, C1 everywhere -- the mesh method whose gradient is continuous.
+     gsl_sinterp_cubic_mesh     over an imported triangulation, set up like gsl_sinterp_linear_mesh
+                                (gsl_sinterp_set_triangulation, then init); no Delaunay property, no convexity needed;
+     gsl_sinterp_cubic_simplex  builds the tree on the host as gsl_sinterp_natural_simplex does and evaluates on the
+                                exported mesh.
+   The gradients at the sites are estimated at init (gsl_sinterp_set_gradient_options; GSL_EMAXITER from init when the
+   solve did not reach rtol) unless gsl_sinterp_set_gradients gave them; gsl_sinterp_get_gradients reads them back.
+   eval_e / eval_many / eval_resident / eval_grid and gsl_sinterp_eval_grad_e / _many / _resident; `leaf` = the triangle
+   that contains the target; a target outside the triangulation gives NaN (value and gradient), -1 and GSL_EDOM.  One
+   device only (GSL_EUNSUP at init otherwise).  Fields, variance, leave-one-out, fit and set_neighbours: GSL_EUNSUP.
+   Checkpoints: type ids 14 / 15, the mesh payload of gsl_sinterp_linear_mesh followed by the 2 N gradients; a restored
+   interpolant does not estimate again. */
+extern const gsl_sinterp_type *gsl_sinterp_cubic_mesh, *gsl_sinterp_cubic_simplex;
 /* ordinary kriging with a Gaussian covariance exp(-(eps h)^2) and an optional nugget (README:24 future list):
    s(y) = mu + sum_j w_j C(|y - x_j|) with [C + nugget I, 1; 1^T, 0] [w; mu] = [f; 0].  nugget = 0 interpolates the data,
    nugget > 0 smooths (s(x_i) = f_i - nugget w_i); far from the data s -> mu.  gsl_sinterp_set_shape sets eps. */
@@ -483,9 +525,18 @@ int gsl_sinterp_set_rcond(gsl_sinterp *interp, int want);
 int gsl_sinterp_rcond(const gsl_sinterp *interp, double *rcond);
 int gsl_sinterp_route(const gsl_sinterp *interp);
 int gsl_sinterp_set_tree_options(gsl_sinterp *interp, int init_flags, gsl_rng *rng);
-/* gsl_sinterp_linear_mesh (dim 2 or 3) and gsl_sinterp_natural_mesh (dim 2): simplices [(dim + 1) n] (vertex = row of x), neighbours [(dim + 1) n] (opposite vertex k,
+/* gsl_sinterp_linear_mesh (dim 2 or 3), gsl_sinterp_natural_mesh and gsl_sinterp_cubic_mesh (dim 2): simplices [(dim + 1) n] (vertex = row of x), neighbours [(dim + 1) n] (opposite vertex k,
    -1 = boundary) or NULL (derived by edge / face matching); copied, validated by the next gsl_sinterp_init */
 int gsl_sinterp_set_triangulation(gsl_sinterp *interp, const int *triangles, const int *neighbours, size_t n_triangles);
+/* gsl_sinterp_cubic_mesh / _simplex (every other type: GSL_EINVAL).  set_gradients, before init: the N x 2 gradients
+   to interpolate instead of the estimate (copied; GSL_EBADLEN for another shape; NULL returns to the estimate).
+   set_gradient_options, before init: the stopping rule of the estimate, |r| / |b| <= rtol or maxiter iterations
+   (defaults 1e-12, 1000; 0 < rtol < 1 and maxiter >= 1, otherwise GSL_EINVAL).  get_gradients, after init: the
+   gradients in use (N x 2, may be NULL), the iterations the estimate took (0 for given or restored gradients) and its
+   relative residual (either may be NULL). */
+int gsl_sinterp_set_gradients(gsl_sinterp *interp, const gsl_matrix *gradients);
+int gsl_sinterp_set_gradient_options(gsl_sinterp *interp, double rtol, size_t maxiter);
+int gsl_sinterp_get_gradients(const gsl_sinterp *interp, gsl_matrix *gradients, size_t *iterations, double *residual);
 int gsl_sinterp_init(gsl_sinterp *interp, const gsl_matrix *x, const gsl_vector *f);
 const char *gsl_sinterp_name(const gsl_sinterp *interp);
 unsigned int gsl_sinterp_min_size(const gsl_sinterp *interp);
@@ -507,7 +558,11 @@ int gsl_sinterp_eval_resident(const gsl_sinterp *interp, const double *d_y, size
    != y->size1; GSL_EINVAL: not initialised (or gtda < dim).  An interpolant restored by gsl_sinterp_fread evaluates
    gradients: centres, weights, mean and polynomial are all a gradient needs.  With a device list the first device
    evaluates every target, as gsl_sinterp_eval_resident and the variance entries do: gradient batches are not sharded
-   over the group, and eval_grad_many copies through plain (not pinned, not pipelined) staging. */
+   over the group, and eval_grad_many copies through plain (not pinned, not pipelined) staging.
+   gsl_sinterp_cubic_mesh / _simplex: the analytic gradient of the Clough-Tocher cubic in the micro-triangle of the
+   target, continuous across every edge; same shapes; a target outside the triangulation gets NaN and GSL_EDOM (many / e;
+   the resident entry does not read back).  d_s == NULL in the resident entry is GSL_EFAULT for these two types (the
+   locate step passes its values through it). */
 int gsl_sinterp_eval_grad_e(const gsl_sinterp *interp, const gsl_vector *y, double *s, gsl_vector *g);
 int gsl_sinterp_eval_grad_many(const gsl_sinterp *interp, const gsl_matrix *y, gsl_vector *s /* may be NULL */, gsl_matrix *g);
 int gsl_sinterp_eval_grad_resident(const gsl_sinterp *interp, const double *d_y, size_t m, size_t ytda,

@@ -189,6 +189,34 @@ int gsl_sinterp_hip_mesh_natural_eval(gsl_sinterp_hip_ctx *ctx, int n_tri, const
                                       const int *d_located, const double *d_linear_values, const double *d_targets, size_t m,
                                       size_t ttda, int depth_cap, double *d_values, long long *h_n_scanned);
 
+/* Clough-Tocher C1 piecewise-cubic interpolation on a 2-D mesh, with gradients (csrc/hip/cubic.hip; DESIGN.md 4,
+   "Clough-Tocher").  No Delaunay property and no convexity is needed.
+   cubic_gradients: the global estimate of grad f at the vertices (Nielson / Renka, scipy's CloughTocher2DInterpolator):
+   the SPD system over the undirected mesh edges, solved by conjugate gradients preconditioned with the inverse 2x2
+   diagonal blocks.  The CSR d_offsets [n_points + 1] / d_adjacent [n_adjacent] lists every undirected edge once per
+   endpoint (simplex_mesh_vertex_adjacency); entries out of range, self-edges and edges of length 0 are skipped; a
+   vertex without two non-collinear edges gets g = 0 and is left out.  d_g [2 n_points] receives the gradients.  The
+   solve stops at |r| / |b| <= rtol or after maxiter iterations; *h_iterations / *h_residual (may be NULL) receive the
+   count and the achieved relative residual in either case; GSL_EMAXITER (11) when rtol was not met.  Synchronises.
+   The dot products are reduced in a fixed order: the same input gives the same bits.
+   cubic_pack: one 160-byte, 16-byte-aligned record per triangle: the barycentric map (raw coordinates) and the 12
+   independent Bezier ordinates; d_f [n_points], d_g [2 n_points]; d_tri / d_nbr / d_points as for
+   gsl_sinterp_hip_mesh_pack.  d_ctrec holds n_tri records.
+   cubic_eval: d_located [m] = the triangle of every target and d_linear_values [m] = its piecewise-linear value, both
+   as gsl_sinterp_hip_mesh_eval stored them for the same targets (run it first); d_values may be d_linear_values.
+   d_grad (may be NULL) receives the gradient in raw coordinates, row k at d_grad + k * gtda, gtda >= 2; the value bits
+   do not depend on it.  d_located < 0 gives NaN in the value and the gradient; a flat triangle gives the linear value
+   and the gradient of the plane through its data (NaN when there is none). */
+#define GSL_SINTERP_CUBIC_RECORD_BYTES 160
+int gsl_sinterp_hip_mesh_cubic_gradients(gsl_sinterp_hip_ctx *ctx, int n_points, const int *d_offsets, const int *d_adjacent,
+                                         size_t n_adjacent, const double *d_points, const double *d_f, double rtol, int maxiter,
+                                         double *d_g, int *h_iterations, double *h_residual);
+int gsl_sinterp_hip_mesh_cubic_pack(gsl_sinterp_hip_ctx *ctx, int n_tri, const int *d_tri, const int *d_nbr, int n_points,
+                                    const double *d_points, const double *d_f, const double *d_g, void *d_ctrec);
+int gsl_sinterp_hip_mesh_cubic_eval(gsl_sinterp_hip_ctx *ctx, int n_tri, const void *d_ctrec, const int *d_located,
+                                    const double *d_linear_values, const double *d_targets, size_t m, size_t ttda,
+                                    double *d_values, double *d_grad, size_t gtda);
+
 /* Device-side integrity checks of a DAG given as raw arrays (same arguments as tree_pack):
    what & 1: _check_leaf_nodes  (interpolation/linear_simplex_integrity_check.c:62-119), one thread per leaf;
    what & 2: _check_delaunay    (:134-160; circumsphere per linear_simplex.c:555-605), leaves x points.
