@@ -197,12 +197,11 @@ static int chunk_eval_many(chunk_set *cs, gsl_sinterp_hip_ctx *c, size_t dim, co
   /* Dense caller buffers go over PCIe as they are: measured on the MI355X box (tools/pcie_probe), the runtime moves
      pageable memory at 38 GB/s (H2D) / 56 GB/s (D2H) against 30 / 22 GB/s for a single-threaded memcpy into / out of pinned
      staging -- which would then still have to be copied.  Strided matrices / vectors are repacked through pinned staging. */
-  const int y_direct = y->tda == dim, s_direct = sv->stride == 1, l_direct = want_leaf && leaf != NULL;
-  const int l_down = want_leaf && leaf != NULL;          /* the indices only travel when the caller asked for them */
+  const int y_direct = y->tda == dim, s_direct = sv->stride == 1;
+  const int l_down = want_leaf && leaf != NULL;          /* the indices only travel when the caller asked for them, straight into leaf */
   int st = GSL_SUCCESS;
   if (!cs->pipe) st = gsl_sinterp_hip_pipe_create(c, &cs->pipe);
-  const size_t b_y = y_direct ? 0 : m * dim * sizeof(double), b_s = s_direct ? 0 : m * sizeof(double),
-               b_l = 0, need = b_y + b_s + b_l;
+  const size_t b_y = y_direct ? 0 : m * dim * sizeof(double), b_s = s_direct ? 0 : m * sizeof(double), need = b_y + b_s;
   if (!st && need > cs->h_bytes) {
     gsl_sinterp_hip_host_free(cs->h_stage);
     cs->h_stage = NULL; cs->h_bytes = 0;
@@ -220,7 +219,6 @@ static int chunk_eval_many(chunk_set *cs, gsl_sinterp_hip_ctx *c, size_t dim, co
   if (st) { gsl_error(gsl_sinterp_hip_last_error(c), __FILE__, __LINE__, st); return st; }
   double *h_y = y_direct ? y->data : (double *)cs->h_stage;
   double *h_s = s_direct ? sv->data : (double *)((char *)cs->h_stage + b_y);
-  int *h_l = l_direct ? leaf : NULL;
   size_t nch = m / CHUNK_MIN;
   if (nch < 1) nch = 1;
   if (nch > CHUNK_MAX_N) nch = CHUNK_MAX_N;
@@ -242,7 +240,7 @@ static int chunk_eval_many(chunk_set *cs, gsl_sinterp_hip_ctx *c, size_t dim, co
     if (!st && cnt) st = gsl_sinterp_hip_pipe_mark(cs->pipe, &mark);         /* "sweep of this chunk done" */
     if (!st && pc) {
       st = gsl_sinterp_hip_pipe_download(cs->pipe, pmark, h_s + pf, cs->d_s + pf, pc * sizeof(double));
-      if (!st && l_down) st = gsl_sinterp_hip_pipe_download(cs->pipe, pmark, h_l + pf, cs->d_leaf + pf, pc * sizeof(int));
+      if (!st && l_down) st = gsl_sinterp_hip_pipe_download(cs->pipe, pmark, leaf + pf, cs->d_leaf + pf, pc * sizeof(int));
     }
     pf = first; pc = cnt; pmark = mark;
   }
@@ -255,6 +253,78 @@ static int chunk_eval_many(chunk_set *cs, gsl_sinterp_hip_ctx *c, size_t dim, co
   if (!s_direct) for (size_t k = 0; k < m; k++) sv->data[k * sv->stride] = h_s[k];
   if (n_neg) *n_neg = (size_t)neg;
   return GSL_SUCCESS;
+}
+
+/* ======================================================================== */
+/* host batches on ONE device, in one shot: every `_many` entry that is not   */
+/* on the chunk pipe (variance, gradient, fields, local kriging, cubic + grad) */
+/* ======================================================================== */
+/* host_stage_begin repacks the m x dim targets (tda honoured) into pageable memory and uploads them, with room behind
+   them for every output of the list; the caller runs its resident entry on hs.d_y and out[i].d; host_stage_end downloads
+   each output (straight into a dense destination, through the staging buffer and a scatter into a strided one) and
+   frees everything, whatever happened in between.  Allocation per call and
+   synchronous copies: these entries are not the throughput path (that is chunk_eval_many). */
+typedef struct {
+  size_t cols;          /* entries per target, m x cols dense on the device; 0 = not asked for: no room, no download */
+  int is_int;           /* the doubles of a list come first (alignment) */
+  double *dst;          /* doubles: entry (t, q) goes to dst[t * pitch + q] -- a gsl_vector's stride, a gsl_matrix's tda */
+  size_t pitch;
+  int *idst;            /* ints: m x cols dense; NULL = wanted on the device only */
+  void *d;              /* set by host_stage_begin */
+} stage_out;
+#define STAGE_VECTOR(v) {(v) ? 1 : 0, 0, (v) ? (v)->data : NULL, (v) ? (v)->stride : 0, NULL, NULL}
+#define STAGE_MATRIX(g) {(g)->size2, 0, (g)->data, (g)->tda, NULL, NULL}
+#define STAGE_INTS(p, cols) {(cols), 1, NULL, 0, (p), NULL}
+
+typedef struct {
+  gsl_sinterp_hip_ctx *c;
+  size_t m, in_bytes, out_bytes;
+  double *h, *d_y;      /* h == NULL after host_stage_begin: out of host memory */
+  stage_out *out;
+  int n_out;
+} host_stage;
+
+static int host_stage_begin(host_stage *hs, gsl_sinterp_hip_ctx *c, const gsl_matrix *y, size_t dim, stage_out *out, int n_out)
+{
+  const size_t m = y->size1;
+  memset(hs, 0, sizeof *hs);
+  hs->c = c; hs->m = m; hs->out = out; hs->n_out = n_out; hs->in_bytes = m * dim * sizeof(double);
+  size_t h_bytes = hs->in_bytes;                        /* the targets, later any one strided output */
+  for (int i = 0; i < n_out; i++) {
+    const size_t b = m * out[i].cols * (out[i].is_int ? sizeof(int) : sizeof(double));
+    hs->out_bytes += b;
+    if (!out[i].is_int && out[i].pitch != out[i].cols && b > h_bytes) h_bytes = b;
+  }
+  hs->h = (double *)malloc(h_bytes);
+  if (!hs->h) return GSL_ENOMEM;
+  for (size_t t = 0; t < m; t++)
+    for (size_t a = 0; a < dim; a++) hs->h[t * dim + a] = y->data[t * y->tda + a];
+  int s = gsl_sinterp_hip_malloc(c, (void **)&hs->d_y, hs->in_bytes + hs->out_bytes);
+  if (s) return s;
+  char *p = (char *)hs->d_y + hs->in_bytes;
+  for (int i = 0; i < n_out; i++)
+    if (out[i].cols) { out[i].d = p; p += m * out[i].cols * (out[i].is_int ? sizeof(int) : sizeof(double)); }
+  return gsl_sinterp_hip_h2d(c, hs->d_y, hs->h, hs->in_bytes);
+}
+
+/* st: what happened so far (nothing is downloaded after a failure, nor without `download`); returns st, or the copy's */
+static int host_stage_end(host_stage *hs, int st, int download)
+{
+  for (int i = 0; i < hs->n_out && !st && download; i++) {
+    const stage_out *o = &hs->out[i];
+    const size_t cnt = hs->m * o->cols;
+    if (!cnt || (o->is_int && !o->idst)) continue;
+    if (o->is_int) st = gsl_sinterp_hip_d2h(hs->c, o->idst, o->d, cnt * sizeof(int));
+    else if (o->pitch == o->cols) st = gsl_sinterp_hip_d2h(hs->c, o->dst, o->d, cnt * sizeof(double));      /* dense: in place */
+    else {
+      st = gsl_sinterp_hip_d2h(hs->c, hs->h, o->d, cnt * sizeof(double));
+      for (size_t t = 0; t < hs->m && !st; t++)
+        for (size_t q = 0; q < o->cols; q++) o->dst[t * o->pitch + q] = hs->h[t * o->cols + q];
+    }
+  }
+  gsl_sinterp_hip_free(hs->c, hs->d_y);
+  free(hs->h);
+  return st;
 }
 
 /* ======================================================================== */
@@ -618,21 +688,19 @@ struct simplex_mesh_device {
   int response_bound;
   /* natural neighbours: nothing is computed, uploaded or kept for them until the first natural evaluation, which asks
      the (borrowed) mesh for the metric it is Delaunay in (simplex_mesh_delaunay_metric; -1 = not asked yet), uploads its
-     links and points once more and packs nn_rec; nn_leaf: triangle indices of a resident batch whose caller did not ask
-     for them */
+     links and points once more and packs nn_rec */
   const simplex_mesh *mesh;
   int nn_metric;
-  int *nn_leaf;
   void *nn_rec;
-  size_t nn_leaf_cap;
   /* Clough-Tocher (csrc/hip/cubic.hip), by the same rule: nothing until the first cubic call.  ct_bound: the caller's
-     gradients (host copy, NULL = estimate); ct_g / ct_rec: gradients and records on the device (NULL = still to do);
-     ct_leaf: triangle indices of a resident batch whose caller did not ask for them */
+     gradients (host copy, NULL = estimate); ct_g / ct_rec: gradients and records on the device (NULL = still to do) */
   double *ct_bound, *ct_g;
   void *ct_rec;
-  int *ct_leaf;
-  size_t ct_leaf_cap, ct_iters, ct_maxiter;
+  size_t ct_iters, ct_maxiter;
   double ct_rtol, ct_resid;
+  /* grow-only: the triangle indices of a resident natural / cubic batch whose caller did not ask for them */
+  int *sw_leaf;
+  size_t sw_leaf_cap;
 };
 
 gsl_sinterp_hip_ctx *simplex_mesh_device_ctx(simplex_mesh_device *dev) { return dev ? dev->ctx : NULL; }
@@ -653,8 +721,8 @@ void simplex_mesh_device_free(simplex_mesh_device *dev)
     gsl_sinterp_hip_free(c, dev->m_tri[r]); gsl_sinterp_hip_free(c, dev->m_seed[r]);
   }
   if (dev->ctx) {
-    gsl_sinterp_hip_free(dev->ctx, dev->nn_rec); gsl_sinterp_hip_free(dev->ctx, dev->nn_leaf);
-    gsl_sinterp_hip_free(dev->ctx, dev->ct_g); gsl_sinterp_hip_free(dev->ctx, dev->ct_rec); gsl_sinterp_hip_free(dev->ctx, dev->ct_leaf);
+    gsl_sinterp_hip_free(dev->ctx, dev->nn_rec); gsl_sinterp_hip_free(dev->ctx, dev->sw_leaf);
+    gsl_sinterp_hip_free(dev->ctx, dev->ct_g); gsl_sinterp_hip_free(dev->ctx, dev->ct_rec);
   }
   free(dev->ct_bound);
   if (dev->ss.grp) shard_set_release(&dev->ss);      /* destroys the members' contexts */
@@ -858,16 +926,44 @@ static int natural_pack_once(simplex_mesh_device *dev)
   return st;
 }
 
-/* locate + linear value by the unchanged linear path (batches >= 4096 through its sorted route), then the cavity sweep
-   over the triangle it found; the linear values pass through d_s */
+/* The natural-neighbour and Clough-Tocher entries, resident and chunked: locate + linear value by the unchanged linear
+   path (batches >= 4096 through its sorted route), then the method's sweep (cubic = 0: the cavity sweep, 1: the cubic
+   one, d_g its optional gradient) over the triangle found; the linear values pass through d_s.  Nothing is read back. */
+static int mesh_locate_sweep(simplex_mesh_device *dev, int cubic, const double *d_y, size_t m, size_t ytda, double *d_s, double *d_g,
+                             size_t gtda, int *d_leaf)
+{
+  int st = gsl_sinterp_hip_mesh_eval(dev->ctx, dev->n_tri, dev->m_records[0], dev->m_leaftab[0], dev->m_seed[0], dev->G, dev->geom, dev->convex,
+                                     d_y, m, ytda, d_s, d_leaf, (long long *)NULL);
+  if (st) return st;
+  if (cubic) return gsl_sinterp_hip_mesh_cubic_eval(dev->ctx, dev->n_tri, dev->ct_rec, d_leaf, d_s, d_y, m, ytda, d_s, d_g, gtda);
+  return gsl_sinterp_hip_mesh_natural_eval(dev->ctx, dev->n_tri, dev->nn_rec, dev->m_leaftab[0], d_leaf, d_s, d_y, m, ytda, 0, d_s,
+                                           (long long *)NULL);
+}
 static int natural_chunk_eval(void *state, const double *d_y, size_t m, double *d_s, int *d_leaf)
 {
-  simplex_mesh_device *dev = (simplex_mesh_device *)state;
-  int st = gsl_sinterp_hip_mesh_eval(dev->ctx, dev->n_tri, dev->m_records[0], dev->m_leaftab[0], dev->m_seed[0], dev->G, dev->geom, dev->convex,
-                                     d_y, m, 2, d_s, d_leaf, (long long *)NULL);
-  if (st) return st;
-  return gsl_sinterp_hip_mesh_natural_eval(dev->ctx, dev->n_tri, dev->nn_rec, dev->m_leaftab[0], d_leaf, d_s, d_y, m, 2, 0, d_s,
-                                           (long long *)NULL);
+  return mesh_locate_sweep((simplex_mesh_device *)state, 0, d_y, m, 2, d_s, NULL, 0, d_leaf);
+}
+static int cubic_chunk_eval(void *state, const double *d_y, size_t m, double *d_s, int *d_leaf)
+{
+  return mesh_locate_sweep((simplex_mesh_device *)state, 1, d_y, m, 2, d_s, NULL, 0, d_leaf);
+}
+
+/* a resident batch: the sweep needs the triangle indices also when the caller does not */
+static int mesh_sweep_resident(simplex_mesh_device *dev, int cubic, const double *d_y, size_t m, size_t ytda, double *d_s, double *d_g,
+                               size_t gtda, int *d_leaf)
+{
+  int st = GSL_SUCCESS;
+  if (!d_leaf) {
+    if (m > dev->sw_leaf_cap) {
+      gsl_sinterp_hip_free(dev->ctx, dev->sw_leaf); dev->sw_leaf = NULL; dev->sw_leaf_cap = 0;
+      st = gsl_sinterp_hip_malloc(dev->ctx, (void **)&dev->sw_leaf, m * sizeof(int));
+      if (!st) dev->sw_leaf_cap = m;
+    }
+    d_leaf = dev->sw_leaf;
+  }
+  if (!st) st = mesh_locate_sweep(dev, cubic, d_y, m, ytda, d_s, d_g, gtda, d_leaf);
+  if (st) GSL_ERROR(gsl_sinterp_hip_last_error(dev->ctx), st);
+  return GSL_SUCCESS;
 }
 
 int simplex_mesh_device_eval_natural_resident(simplex_mesh_device *dev, const double *d_targets, size_t m, size_t ttda,
@@ -879,20 +975,8 @@ int simplex_mesh_device_eval_natural_resident(simplex_mesh_device *dev, const do
   if (ttda < 2) GSL_ERROR("simplex_mesh_device_eval_natural_resident: target rows shorter than the mesh's dimension", GSL_EBADLEN);
   if (m == 0) return GSL_SUCCESS;
   st = natural_pack_once(dev);
-  if (!st && !d_triangle) {
-    if (m > dev->nn_leaf_cap) {
-      gsl_sinterp_hip_free(dev->ctx, dev->nn_leaf); dev->nn_leaf = NULL; dev->nn_leaf_cap = 0;
-      st = gsl_sinterp_hip_malloc(dev->ctx, (void **)&dev->nn_leaf, m * sizeof(int));
-      if (!st) dev->nn_leaf_cap = m;
-    }
-    d_triangle = dev->nn_leaf;
-  }
-  if (!st) st = gsl_sinterp_hip_mesh_eval(dev->ctx, dev->n_tri, dev->m_records[0], dev->m_leaftab[0], dev->m_seed[0], dev->G, dev->geom,
-                                          dev->convex, d_targets, m, ttda, d_values, d_triangle, NULL);
-  if (!st) st = gsl_sinterp_hip_mesh_natural_eval(dev->ctx, dev->n_tri, dev->nn_rec, dev->m_leaftab[0], d_triangle, d_values, d_targets, m,
-                                                  ttda, 0, d_values, NULL);
   if (st) GSL_ERROR(gsl_sinterp_hip_last_error(dev->ctx), st);
-  return GSL_SUCCESS;
+  return mesh_sweep_resident(dev, 0, d_targets, m, ttda, d_values, NULL, 0, d_triangle);
 }
 
 int simplex_mesh_device_eval_natural_many(simplex_mesh_device *dev, const gsl_matrix *targets, gsl_vector *values, int *triangle)
@@ -1054,33 +1138,10 @@ int simplex_mesh_device_eval_cubic_resident(simplex_mesh_device *dev, const doub
   st = cubic_prepare(dev);
   if (st == GSL_EMAXITER && dev->ct_rec) st = GSL_SUCCESS;          /* reported by the call that estimated */
   if (st) return st;
-  if (!d_triangle) {
-    if (m > dev->ct_leaf_cap) {
-      gsl_sinterp_hip_free(dev->ctx, dev->ct_leaf); dev->ct_leaf = NULL; dev->ct_leaf_cap = 0;
-      st = gsl_sinterp_hip_malloc(dev->ctx, (void **)&dev->ct_leaf, m * sizeof(int));
-      if (!st) dev->ct_leaf_cap = m;
-    }
-    d_triangle = dev->ct_leaf;
-  }
-  if (!st) st = gsl_sinterp_hip_mesh_eval(dev->ctx, dev->n_tri, dev->m_records[0], dev->m_leaftab[0], dev->m_seed[0], dev->G, dev->geom,
-                                          dev->convex, d_targets, m, ttda, d_values, d_triangle, NULL);
-  if (!st) st = gsl_sinterp_hip_mesh_cubic_eval(dev->ctx, dev->n_tri, dev->ct_rec, d_triangle, d_values, d_targets, m, ttda, d_values,
-                                                d_gradient, gtda);
-  if (st) GSL_ERROR(gsl_sinterp_hip_last_error(dev->ctx), st);
-  return GSL_SUCCESS;
+  return mesh_sweep_resident(dev, 1, d_targets, m, ttda, d_values, d_gradient, gtda, d_triangle);
 }
 
-static int cubic_chunk_eval(void *state, const double *d_y, size_t m, double *d_s, int *d_leaf)
-{
-  simplex_mesh_device *dev = (simplex_mesh_device *)state;
-  int st = gsl_sinterp_hip_mesh_eval(dev->ctx, dev->n_tri, dev->m_records[0], dev->m_leaftab[0], dev->m_seed[0], dev->G, dev->geom, dev->convex,
-                                     d_y, m, 2, d_s, d_leaf, (long long *)NULL);
-  if (st) return st;
-  return gsl_sinterp_hip_mesh_cubic_eval(dev->ctx, dev->n_tri, dev->ct_rec, d_leaf, d_s, d_y, m, 2, d_s, (double *)NULL, 0);
-}
-
-/* host batches.  Values only: the chunk pipe of the linear entries.  With gradients: one staging buffer on either side,
-   [targets m x 2 | values m | gradient m x 2 | triangle m] */
+/* host batches.  Values only: the chunk pipe of the linear entries.  With gradients: one shot through host_stage */
 int simplex_mesh_device_eval_cubic_many(simplex_mesh_device *dev, const gsl_matrix *targets, gsl_vector *values, gsl_matrix *gradient,
                                         int *triangle)
 {
@@ -1104,29 +1165,46 @@ int simplex_mesh_device_eval_cubic_many(simplex_mesh_device *dev, const gsl_matr
     if (neg) GSL_ERROR("simplex_mesh_device_eval_cubic_many: target(s) outside the triangulation", GSL_EDOM);
     return GSL_SUCCESS;
   }
-  const size_t nd = 5 * m, bytes = nd * sizeof(double) + m * sizeof(int);
-  double *h = (double *)malloc(bytes), *d = NULL;
-  if (!h) GSL_ERROR("simplex_mesh_device_eval_cubic_many: out of memory", GSL_ENOMEM);
-  for (size_t k = 0; k < m; k++) { h[2 * k] = targets->data[k * targets->tda]; h[2 * k + 1] = targets->data[k * targets->tda + 1]; }
-  st = gsl_sinterp_hip_malloc(c, (void **)&d, bytes);
-  if (!st) st = gsl_sinterp_hip_h2d(c, d, h, 2 * m * sizeof(double));
+  stage_out out[3] = {STAGE_VECTOR(values), STAGE_MATRIX(gradient), STAGE_INTS(triangle, 1)};
+  host_stage hs;
+  st = host_stage_begin(&hs, c, targets, 2, out, 3);
+  if (!hs.h) GSL_ERROR("simplex_mesh_device_eval_cubic_many: out of memory", GSL_ENOMEM);
   int es = GSL_SUCCESS;
   long long outside_n = 0;
-  int *d_tri = (int *)(d + nd);
-  if (!st) es = simplex_mesh_device_eval_cubic_resident(dev, d, m, 2, d + 2 * m, d + 3 * m, 2, d_tri);
-  if (!st && !es) st = gsl_sinterp_hip_count_negative(c, d_tri, m, &outside_n);
-  if (!st && !es) st = gsl_sinterp_hip_d2h(c, h, d + 2 * m, bytes - 2 * m * sizeof(double));
-  if (!st && !es) {
-    for (size_t k = 0; k < m; k++) values->data[k * values->stride] = h[k];
-    for (size_t k = 0; k < m; k++) { gradient->data[k * gradient->tda] = h[m + 2 * k]; gradient->data[k * gradient->tda + 1] = h[m + 2 * k + 1]; }
-    if (triangle) memcpy(triangle, h + 3 * m, m * sizeof(int));
-  }
-  gsl_sinterp_hip_free(c, d);
-  free(h);
+  if (!st) es = simplex_mesh_device_eval_cubic_resident(dev, hs.d_y, m, 2, (double *)out[0].d, (double *)out[1].d, 2, (int *)out[2].d);
+  if (!st && !es) st = gsl_sinterp_hip_count_negative(c, (const int *)out[2].d, m, &outside_n);
+  st = host_stage_end(&hs, st, !es);
   if (st) GSL_ERROR(gsl_sinterp_hip_last_error(c), st);
   if (es) return es;
   if (outside_n) GSL_ERROR("simplex_mesh_device_eval_cubic_many: target(s) outside the triangulation", GSL_EDOM);
   return GSL_SUCCESS;
+}
+
+/* ======================================================================== */
+/* what a type is: one row of type_table (below, with the generic entries)    */
+/* ======================================================================== */
+enum { FAM_RBF, FAM_TREE, FAM_MESH };                   /* the struct behind gsl_sinterp.state: rbf_state, simplex_state, mesh_state */
+enum { MESH_LINEAR, MESH_NATURAL, MESH_CUBIC };
+typedef struct {
+  gsl_sinterp_type pub;       /* first member: the extern gsl_sinterp_* pointers point here */
+  int id;                     /* the type id of a GSLSINT1 checkpoint: never renumbered */
+  int family;
+  int kind, krige, affine, pd;/* FAM_RBF: the kernel, ordinary kriging (covariance + estimated mean), the affine tail, positive
+                                 definite kernel (Cholesky routes 1 / 7, hence leave-one-out and the fit) */
+  int method, imported;       /* FAM_MESH: the interpolant on the triangles; the mesh is imported (gsl_sinterp_set_triangulation)
+                                 or exported from a host-built tree */
+  const char *noun;           /* natural and cubic types: what their refusals call them */
+} type_desc;
+static const type_desc *desc_of(const gsl_sinterp_type *T);     /* the row of T, NULL for a type that is not in the table */
+
+/* "<...> natural-neighbour <...>" / "<...> Clough-Tocher <...>": the refusals the two 2-D mesh methods share.  fmt has one
+   %s; the facade is single-threaded, the handler reads the text before it returns */
+static int noun_error(const type_desc *d, const char *fmt, int status)
+{
+  static char reason[192];
+  snprintf(reason, sizeof reason, fmt, d->noun);
+  gsl_error(reason, __FILE__, __LINE__, status);
+  return status;
 }
 
 /* ======================================================================== */
@@ -1193,34 +1271,16 @@ static double rbf_default_eps(int kind, size_t n, size_t dim)
   return (kind == GSL_SINTERP_RBF_WENDLAND ? 0.125 : kind == GSL_SINTERP_RBF_GAUSSIAN ? 2.0 : 1.0) * pow((double)n, 1.0 / (double)dim);
 }
 
-static void *rbf_alloc_kind(int kind, size_t dim, size_t size)
+/* kind / krige / affine come from the type's row of the table: gsl_sinterp_alloc fills them in */
+static void *rbf_alloc(size_t dim, size_t size)
 {
   rbf_state *st = (rbf_state *)calloc(1, sizeof *st);
-  if (!st) return NULL;
-  st->kind = kind; st->n = size; st->dim = dim;
+  if (st) { st->n = size; st->dim = dim; }
   return st;
 }
-static void *rbf_gauss_alloc(size_t dim, size_t size) { return rbf_alloc_kind(GSL_SINTERP_RBF_GAUSSIAN, dim, size); }
-static void *rbf_tps_alloc(size_t dim, size_t size) { return rbf_alloc_kind(GSL_SINTERP_RBF_TPS, dim, size); }
-static void *rbf_wendland_alloc(size_t dim, size_t size) { return rbf_alloc_kind(GSL_SINTERP_RBF_WENDLAND, dim, size); }
-static void *rbf_matern32_alloc(size_t dim, size_t size) { return rbf_alloc_kind(GSL_SINTERP_RBF_MATERN32, dim, size); }
-static void *rbf_matern52_alloc(size_t dim, size_t size) { return rbf_alloc_kind(GSL_SINTERP_RBF_MATERN52, dim, size); }
-static void *rbf_imq_alloc(size_t dim, size_t size) { return rbf_alloc_kind(GSL_SINTERP_RBF_IMQ, dim, size); }
-static void *rbf_tps_affine_alloc(size_t dim, size_t size)
-{
-  rbf_state *st = (rbf_state *)rbf_alloc_kind(GSL_SINTERP_RBF_TPS, dim, size);
-  if (st) st->affine = 1;
-  return st;
-}
-static void *krige_alloc_kind(int kind, size_t dim, size_t size)
-{
-  rbf_state *st = (rbf_state *)rbf_alloc_kind(kind, dim, size);                          /* the kernel is the covariance */
-  if (st) st->krige = 1;
-  return st;
-}
-static void *krige_alloc(size_t dim, size_t size) { return krige_alloc_kind(GSL_SINTERP_RBF_GAUSSIAN, dim, size); }
-static void *krige_matern32_alloc(size_t dim, size_t size) { return krige_alloc_kind(GSL_SINTERP_RBF_MATERN32, dim, size); }
-static void *krige_matern52_alloc(size_t dim, size_t size) { return krige_alloc_kind(GSL_SINTERP_RBF_MATERN52, dim, size); }
+
+/* one accessor per state family (defined with the type table): NULL when the interpolant's type is of another family */
+static rbf_state *rbf_of(const gsl_sinterp *interp);
 
 /* the kept factor and everything derived from it (member 0's context must still be alive) */
 static void rbf_release_variance(rbf_state *st)
@@ -1323,7 +1383,7 @@ static int rbf_solve_column(gsl_sinterp *interp, rbf_state *st, double *d_phi, s
 /* f(i, q) = fdata[i * frow + q * fcol], nf fields: gsl_sinterp_init (nf = 1) and gsl_sinterp_init_fields */
 static int rbf_init_fields(gsl_sinterp *interp, const gsl_matrix *x, const double *fdata, size_t frow, size_t fcol, size_t nf)
 {
-  rbf_state *st = (rbf_state *)interp->state;
+  rbf_state *st = rbf_of(interp);
   const size_t n = st->n, dim = st->dim;
   const int nd = interp->n_devices > 1 ? interp->n_devices : 1;
   rbf_release_variance(st);                             /* the factor of the previous model, if one was kept */
@@ -1484,7 +1544,7 @@ static int rbf_eval_resident(const gsl_sinterp *interp, const double *d_y, size_
                              double *d_s, int *d_leaf)
 {
   (void)d_leaf;
-  const rbf_state *st = (const rbf_state *)interp->state;
+  const rbf_state *st = rbf_of(interp);
   if (!st->d_w) GSL_ERROR("gsl_sinterp_eval: interpolant not initialised", GSL_EINVAL);
   if (st->local_k) return local_eval_resident(interp, d_y, m, ytda, d_s, NULL, NULL);
   /* resident buffers live on ONE device: member 0 evaluates them (shard resident targets yourself with
@@ -1510,7 +1570,7 @@ static int rbf_chunk_eval(void *state, const double *d_y, size_t m, double *d_s,
 
 static int rbf_eval_many(const gsl_sinterp *interp, const gsl_matrix *y, gsl_vector *sv, int *leaf)
 {
-  const rbf_state *st = (const rbf_state *)interp->state;
+  rbf_state *st = rbf_of(interp);                       /* not const: the staging buffers are grow-only caches inside the state */
   if (!st->d_w) GSL_ERROR("gsl_sinterp_eval_many: interpolant not initialised", GSL_EINVAL);
   const size_t m = y->size1, dim = st->dim;
   if (m == 0) return GSL_SUCCESS;
@@ -1519,18 +1579,13 @@ static int rbf_eval_many(const gsl_sinterp *interp, const gsl_matrix *y, gsl_vec
     return local_eval_many(interp, y, sv, NULL, NULL);
   }
   if (st->ss.grp) {
-    rbf_state *mst = (rbf_state *)interp->state;         /* staging buffers are grow-only caches inside the state */
-    int sst = shard_eval_many(&mst->ss, dim, y, sv, NULL, &rbf_shard_eval, mst, 0, NULL);
+    int sst = shard_eval_many(&st->ss, dim, y, sv, NULL, &rbf_shard_eval, st, 0, NULL);
     if (sst != GSL_SUCCESS) GSL_ERROR("gsl_sinterp_eval_many: sharded evaluation failed", sst);
-    if (leaf) for (size_t k = 0; k < m; k++) leaf[k] = -1;
-    return GSL_SUCCESS;
-  }
-  {
-    rbf_state *mst = (rbf_state *)interp->state;           /* staging buffers are grow-only caches inside the state */
-    int s = chunk_eval_many(&mst->cs, st->ctx, dim, y, sv, NULL, &rbf_chunk_eval, mst, 0, NULL);
+  } else {
+    int s = chunk_eval_many(&st->cs, st->ctx, dim, y, sv, NULL, &rbf_chunk_eval, st, 0, NULL);
     if (s != GSL_SUCCESS) GSL_ERROR("gsl_sinterp_eval_many: evaluation failed", s);
-    if (leaf) for (size_t k = 0; k < m; k++) leaf[k] = -1;
   }
+  if (leaf) for (size_t k = 0; k < m; k++) leaf[k] = -1;
   return GSL_SUCCESS;
 }
 
@@ -1538,7 +1593,7 @@ static int rbf_eval_many(const gsl_sinterp *interp, const gsl_matrix *y, gsl_vec
 /* init with k > 0: centres and responses go to the (first) device and are binned; nothing is factored */
 static int local_init(gsl_sinterp *interp, const gsl_matrix *x, const gsl_vector *f)
 {
-  rbf_state *st = (rbf_state *)interp->state;
+  rbf_state *st = rbf_of(interp);
   const size_t n = st->n, dim = st->dim;
   rbf_release_variance(st);
   rbf_release_loo(st);
@@ -1570,7 +1625,7 @@ static int local_init(gsl_sinterp *interp, const gsl_matrix *x, const gsl_vector
 /* value / variance (clamped at 0) / neighbour indices, each optional, from one pass on member 0 */
 static int local_eval_resident(const gsl_sinterp *interp, const double *d_y, size_t m, size_t ytda, double *d_s, double *d_var, int *d_idx)
 {
-  const rbf_state *st = (const rbf_state *)interp->state;
+  const rbf_state *st = rbf_of(interp);
   if (m == 0) return GSL_SUCCESS;
   if (!d_y) GSL_ERROR("gsl_sinterp_eval: null argument", GSL_EFAULT);
   int s = gsl_sinterp_hip_local_krige(st->ctx, st->kind, st->eps, st->local_nugget, st->d_x, st->n, (int)st->dim, st->dim, st->d_w, d_y, m, ytda,
@@ -1585,33 +1640,19 @@ static int local_eval_resident(const gsl_sinterp *interp, const double *d_y, siz
 
 static int local_eval_many(const gsl_sinterp *interp, const gsl_matrix *y, gsl_vector *sv, gsl_vector *var, int *idx)
 {
-  const rbf_state *st = (const rbf_state *)interp->state;
+  const rbf_state *st = rbf_of(interp);
   gsl_sinterp_hip_ctx *c = st->ctx;
   const size_t m = y->size1, dim = st->dim, k = st->local_k;
   if (m == 0) return GSL_SUCCESS;
-  double *h = (double *)malloc(m * dim * sizeof(double)), *d_y = NULL, *d_s = NULL, *d_v = NULL;
-  int *d_i = NULL;
-  if (!h) GSL_ERROR("gsl_sinterp_eval_many: out of memory", GSL_ENOMEM);
-  for (size_t t = 0; t < m; t++)
-    for (size_t a = 0; a < dim; a++) h[t * dim + a] = y->data[t * y->tda + a];
-  int s = gsl_sinterp_hip_malloc(c, (void **)&d_y, m * dim * sizeof(double));
-  if (!s && sv) s = gsl_sinterp_hip_malloc(c, (void **)&d_s, m * sizeof(double));
-  if (!s && var) s = gsl_sinterp_hip_malloc(c, (void **)&d_v, m * sizeof(double));
-  if (!s && idx) s = gsl_sinterp_hip_malloc(c, (void **)&d_i, m * k * sizeof(int));
-  if (!s) s = gsl_sinterp_hip_h2d(c, d_y, h, m * dim * sizeof(double));
-  int es = GSL_SUCCESS;
-  if (!s) {
-    es = local_eval_resident(interp, d_y, m, dim, d_s, d_v, d_i);
-    if (es != GSL_SUCCESS && es != GSL_EDOM) s = es;    /* EDOM: everything has been stored, NaN where a pivot failed */
-  }
-  if (!s && sv) { s = gsl_sinterp_hip_d2h(c, h, d_s, m * sizeof(double)); if (!s) for (size_t t = 0; t < m; t++) gsl_vector_set(sv, t, h[t]); }
-  if (!s && var) { s = gsl_sinterp_hip_d2h(c, h, d_v, m * sizeof(double)); if (!s) for (size_t t = 0; t < m; t++) gsl_vector_set(var, t, h[t]); }
-  if (!s && idx) s = gsl_sinterp_hip_d2h(c, idx, d_i, m * k * sizeof(int));
-  gsl_sinterp_hip_free(c, d_y); gsl_sinterp_hip_free(c, d_s); gsl_sinterp_hip_free(c, d_v); gsl_sinterp_hip_free(c, d_i);
-  free(h);
-  if (s == es) return es;                               /* already reported */
+  stage_out out[3] = {STAGE_VECTOR(sv), STAGE_VECTOR(var), STAGE_INTS(idx, idx ? k : 0)};
+  host_stage hs;
+  int s = host_stage_begin(&hs, c, y, dim, out, 3), es = GSL_SUCCESS;
+  if (!hs.h) GSL_ERROR("gsl_sinterp_eval_many: out of memory", GSL_ENOMEM);
+  if (!s) es = local_eval_resident(interp, hs.d_y, m, dim, (double *)out[0].d, (double *)out[1].d, (int *)out[2].d);
+  /* EDOM: everything has been stored, NaN where a pivot failed */
+  s = host_stage_end(&hs, s, es == GSL_SUCCESS || es == GSL_EDOM);
   HIP_TRY(s, c);
-  return es;
+  return es;                                            /* reported by the resident entry */
 }
 
 /* ======================================================================== */
@@ -1624,6 +1665,7 @@ typedef struct {
   gsl_matrix *x; /* private copy of the centres: the tree keeps pointers into it */
   gsl_vector *f; /* private copy of the response (checkpoints) */
 } simplex_state;
+static simplex_state *tree_of(const gsl_sinterp *interp);
 
 static void *simplex_alloc(size_t dim, size_t size)
 {
@@ -1656,7 +1698,7 @@ static int simplex_mirror(gsl_sinterp *interp, simplex_state *st)
 
 static int simplex_init(gsl_sinterp *interp, const gsl_matrix *x, const gsl_vector *f)
 {
-  simplex_state *st = (simplex_state *)interp->state;
+  simplex_state *st = tree_of(interp);
   simplex_tree_device_free(st->dev); st->dev = NULL;
   simplex_tree_free(st->tree); st->tree = NULL;
   gsl_matrix_free(st->x);
@@ -1679,7 +1721,7 @@ static int simplex_init(gsl_sinterp *interp, const gsl_matrix *x, const gsl_vect
 
 static int simplex_eval_many(const gsl_sinterp *interp, const gsl_matrix *y, gsl_vector *s, int *leaf)
 {
-  const simplex_state *st = (const simplex_state *)interp->state;
+  const simplex_state *st = tree_of(interp);
   if (!st->dev) GSL_ERROR("gsl_sinterp_eval_many: interpolant not initialised", GSL_EINVAL);
   return simplex_tree_device_eval_many(st->dev, y, s, leaf);
 }
@@ -1687,13 +1729,15 @@ static int simplex_eval_many(const gsl_sinterp *interp, const gsl_matrix *y, gsl
 static int simplex_eval_resident(const gsl_sinterp *interp, const double *d_y, size_t m, size_t ytda,
                                  double *d_s, int *d_leaf)
 {
-  const simplex_state *st = (const simplex_state *)interp->state;
+  const simplex_state *st = tree_of(interp);
   if (!st->dev) GSL_ERROR("gsl_sinterp_eval_resident: interpolant not initialised", GSL_EINVAL);
   return simplex_tree_device_eval_resident(st->dev, d_y, m, ytda, d_s, d_leaf);
 }
 
 /* ======================================================================== */
-/* imported triangulation type (README:28-31: QHull / CGAL meshes)           */
+/* the mesh-state types: linear, natural-neighbour or Clough-Tocher on a      */
+/* mesh that is imported (README:28-31: QHull / CGAL meshes) or exported     */
+/* from a host-built tree                                                    */
 /* ======================================================================== */
 typedef struct {
   size_t n, dim;             /* dim = 2 (triangles) or 3 (tetrahedra) */
@@ -1710,9 +1754,11 @@ typedef struct {
   size_t g_maxiter, g_iters;
 } mesh_state;
 
+static mesh_state *mesh_of(const gsl_sinterp *interp);
+
 static void *mesh_type_alloc(size_t dim, size_t size)
 {
-  if (dim != 2 && dim != 3) return NULL;
+  if (dim != 2 && dim != 3) return NULL;                /* the natural and cubic types: dim = 2 only, refused by gsl_sinterp_alloc */
   mesh_state *st = (mesh_state *)calloc(1, sizeof *st);
   if (st) { st->n = size; st->dim = dim; }
   return st;
@@ -1732,20 +1778,42 @@ static void mesh_type_free(void *vstate)
   free(st);
 }
 
-static int mesh_type_mirror(gsl_sinterp *interp, mesh_state *st)
+/* Mirror st->mesh on the interpolant's device(s) and bind st->f: the last step of init and of gsl_sinterp_fread.  What
+   the device entries of a method would refuse at every evaluation is refused once, here.  Clough-Tocher: then the
+   gradients, `known` (the caller's, or a checkpoint's) or the estimate, which runs here so that
+   gsl_sinterp_get_gradients and a GSL_EMAXITER verdict belong to init. */
+static int mesh_type_mirror(gsl_sinterp *interp, mesh_state *st, const gsl_matrix *known)
 {
+  const type_desc *d = desc_of(interp->type);
+  if (d->noun && interp->n_devices > 1) return noun_error(d, "gsl_sinterp_init: %s interpolants run on one device", GSL_EUNSUP);
+  if (d->method == MESH_NATURAL) {
+    if (!simplex_mesh_convex(st->mesh)) GSL_ERROR("gsl_sinterp_init: natural neighbours need a convex mesh", GSL_EUNSUP);
+    if (simplex_mesh_delaunay_metric(st->mesh) == 0)
+      GSL_ERROR("gsl_sinterp_init: natural neighbours need a Delaunay triangulation (simplex_mesh_delaunay_metric is 0)", GSL_EINVAL);
+  }
   simplex_mesh_device_free(st->dev);
   st->dev = interp->n_devices > 1 ? simplex_mesh_device_alloc_multi(st->mesh, interp->devices, interp->n_devices)
                                   : simplex_mesh_device_alloc(st->mesh, interp->device);
   if (!st->dev) return GSL_EFAILED;
-  return simplex_mesh_device_set_response(st->dev, st->f);
+  int s = simplex_mesh_device_set_response(st->dev, st->f);
+  if (s || d->method != MESH_CUBIC) return s;
+  if (st->g_rtol > 0.0) s = simplex_mesh_device_set_gradient_options(st->dev, st->g_rtol, st->g_maxiter);
+  if (!s) s = simplex_mesh_device_bind_gradients(st->dev, known);
+  if (s) return s;
+  if (st->g) gsl_matrix_free(st->g);
+  st->g = gsl_matrix_alloc(st->n, 2);
+  if (!st->g) return GSL_ENOMEM;
+  return simplex_mesh_device_gradients(st->dev, st->g, &st->g_iters, &st->g_resid);
 }
 
+/* every mesh-state type: checks, private copies of the data, the mesh (imported, or the tree of gsl_sinterp_linear_simplex --
+   same flags, same generator -- exported and dropped: the mesh is all that is kept), the mirror */
 static int mesh_type_init(gsl_sinterp *interp, const gsl_matrix *x, const gsl_vector *f)
 {
-  mesh_state *st = (mesh_state *)interp->state;
-  if (!st->tri) GSL_ERROR("gsl_sinterp_init: no triangulation set (gsl_sinterp_set_triangulation)", GSL_EINVAL);
-  if (st->n < st->dim + 1) GSL_ERROR("gsl_sinterp_init: an imported triangulation needs at least dim + 1 points", GSL_EINVAL);
+  mesh_state *st = mesh_of(interp);
+  const int imported = desc_of(interp->type)->imported;
+  if (imported && !st->tri) GSL_ERROR("gsl_sinterp_init: no triangulation set (gsl_sinterp_set_triangulation)", GSL_EINVAL);
+  if (imported && st->n < st->dim + 1) GSL_ERROR("gsl_sinterp_init: an imported triangulation needs at least dim + 1 points", GSL_EINVAL);
   simplex_mesh_device_free(st->dev); st->dev = NULL;
   simplex_mesh_free(st->mesh); st->mesh = NULL;
   gsl_matrix_free(st->x); gsl_vector_free(st->f);
@@ -1756,229 +1824,115 @@ static int mesh_type_init(gsl_sinterp *interp, const gsl_matrix *x, const gsl_ve
     for (size_t j = 0; j < st->dim; j++) gsl_matrix_set(st->x, i, j, x->data[i * x->tda + j]);
     gsl_vector_set(st->f, i, gsl_vector_get(f, i));
   }
-  st->mesh = simplex_mesh_import_nd(st->x, st->dim, st->tri, st->nbr, st->n_tri);
+  if (imported) {
+    st->mesh = simplex_mesh_import_nd(st->x, st->dim, st->tri, st->nbr, st->n_tri);
+  } else {
+    simplex_tree *tree = simplex_tree_alloc(2, (int)st->n);
+    if (!tree) return GSL_ENOMEM;
+    int s = simplex_tree_init(tree, st->x, NULL, NULL, interp->init_flags, interp->rng);
+    if (s == GSL_SUCCESS) st->mesh = simplex_mesh_from_tree(tree, st->x);
+    simplex_tree_free(tree);
+    if (s != GSL_SUCCESS) return s;
+  }
   if (!st->mesh) return GSL_EINVAL;
-  return mesh_type_mirror(interp, st);
+  return mesh_type_mirror(interp, st, st->g_set);
 }
 
 static int mesh_type_eval_many(const gsl_sinterp *interp, const gsl_matrix *y, gsl_vector *s, int *leaf)
 {
-  const mesh_state *st = (const mesh_state *)interp->state;
+  const mesh_state *st = mesh_of(interp);
   if (!st->dev) GSL_ERROR("gsl_sinterp_eval_many: interpolant not initialised", GSL_EINVAL);
-  return simplex_mesh_device_eval_many(st->dev, y, s, leaf);
+  switch (desc_of(interp->type)->method) {
+    case MESH_NATURAL: return simplex_mesh_device_eval_natural_many(st->dev, y, s, leaf);
+    case MESH_CUBIC: return simplex_mesh_device_eval_cubic_many(st->dev, y, s, NULL, leaf);
+    default: return simplex_mesh_device_eval_many(st->dev, y, s, leaf);
+  }
 }
 
 static int mesh_type_eval_resident(const gsl_sinterp *interp, const double *d_y, size_t m, size_t ytda, double *d_s, int *d_leaf)
 {
-  const mesh_state *st = (const mesh_state *)interp->state;
+  const mesh_state *st = mesh_of(interp);
   if (!st->dev) GSL_ERROR("gsl_sinterp_eval_resident: interpolant not initialised", GSL_EINVAL);
-  return simplex_mesh_device_eval_resident(st->dev, d_y, m, ytda, d_s, d_leaf);
-}
-
-/* ======================================================================== */
-/* natural-neighbour types: a mesh_state whose mesh is imported              */
-/* (natural-mesh) or exported from a host-built tree (natural-simplex)       */
-/* ======================================================================== */
-static void *natural_type_alloc(size_t dim, size_t size)
-{
-  return dim == 2 ? mesh_type_alloc(dim, size) : NULL;
-}
-
-/* what the device entries would refuse at every evaluation is refused once, here */
-static int natural_type_mirror(gsl_sinterp *interp, mesh_state *st)
-{
-  if (interp->n_devices > 1) GSL_ERROR("gsl_sinterp_init: natural-neighbour interpolants run on one device", GSL_EUNSUP);
-  if (!simplex_mesh_convex(st->mesh)) GSL_ERROR("gsl_sinterp_init: natural neighbours need a convex mesh", GSL_EUNSUP);
-  if (simplex_mesh_delaunay_metric(st->mesh) == 0)
-    GSL_ERROR("gsl_sinterp_init: natural neighbours need a Delaunay triangulation (simplex_mesh_delaunay_metric is 0)", GSL_EINVAL);
-  return mesh_type_mirror(interp, st);
-}
-
-static int natural_copy_data(mesh_state *st, const gsl_matrix *x, const gsl_vector *f)
-{
-  simplex_mesh_device_free(st->dev); st->dev = NULL;
-  simplex_mesh_free(st->mesh); st->mesh = NULL;
-  gsl_matrix_free(st->x); gsl_vector_free(st->f);
-  st->x = gsl_matrix_alloc(st->n, 2);
-  st->f = gsl_vector_alloc(st->n);
-  if (!st->x || !st->f) return GSL_ENOMEM;
-  for (size_t i = 0; i < st->n; i++) {
-    for (size_t j = 0; j < 2; j++) gsl_matrix_set(st->x, i, j, x->data[i * x->tda + j]);
-    gsl_vector_set(st->f, i, gsl_vector_get(f, i));
+  switch (desc_of(interp->type)->method) {
+    case MESH_NATURAL: return simplex_mesh_device_eval_natural_resident(st->dev, d_y, m, ytda, d_s, d_leaf);
+    case MESH_CUBIC: return simplex_mesh_device_eval_cubic_resident(st->dev, d_y, m, ytda, d_s, NULL, 0, d_leaf);
+    default: return simplex_mesh_device_eval_resident(st->dev, d_y, m, ytda, d_s, d_leaf);
   }
-  return GSL_SUCCESS;
-}
-
-static int natural_mesh_init(gsl_sinterp *interp, const gsl_matrix *x, const gsl_vector *f)
-{
-  mesh_state *st = (mesh_state *)interp->state;
-  if (!st->tri) GSL_ERROR("gsl_sinterp_init: no triangulation set (gsl_sinterp_set_triangulation)", GSL_EINVAL);
-  if (st->n < 3) GSL_ERROR("gsl_sinterp_init: an imported triangulation needs at least dim + 1 points", GSL_EINVAL);
-  int s = natural_copy_data(st, x, f);
-  if (s) return s;
-  st->mesh = simplex_mesh_import(st->x, st->tri, st->nbr, st->n_tri);
-  if (!st->mesh) return GSL_EINVAL;
-  return natural_type_mirror(interp, st);
-}
-
-/* the tree of gsl_sinterp_linear_simplex (same flags, same generator), exported and dropped: the mesh is all that is kept */
-static int natural_simplex_init(gsl_sinterp *interp, const gsl_matrix *x, const gsl_vector *f)
-{
-  mesh_state *st = (mesh_state *)interp->state;
-  int s = natural_copy_data(st, x, f);
-  if (s) return s;
-  simplex_tree *tree = simplex_tree_alloc(2, (int)st->n);
-  if (!tree) return GSL_ENOMEM;
-  s = simplex_tree_init(tree, st->x, NULL, NULL, interp->init_flags, interp->rng);
-  if (s == GSL_SUCCESS) {
-    st->mesh = simplex_mesh_from_tree(tree, st->x);
-    if (!st->mesh) s = GSL_EINVAL;
-  }
-  simplex_tree_free(tree);
-  if (s != GSL_SUCCESS) return s;
-  return natural_type_mirror(interp, st);
-}
-
-static int natural_type_eval_many(const gsl_sinterp *interp, const gsl_matrix *y, gsl_vector *s, int *leaf)
-{
-  const mesh_state *st = (const mesh_state *)interp->state;
-  if (!st->dev) GSL_ERROR("gsl_sinterp_eval_many: interpolant not initialised", GSL_EINVAL);
-  return simplex_mesh_device_eval_natural_many(st->dev, y, s, leaf);
-}
-
-static int natural_type_eval_resident(const gsl_sinterp *interp, const double *d_y, size_t m, size_t ytda, double *d_s, int *d_leaf)
-{
-  const mesh_state *st = (const mesh_state *)interp->state;
-  if (!st->dev) GSL_ERROR("gsl_sinterp_eval_resident: interpolant not initialised", GSL_EINVAL);
-  return simplex_mesh_device_eval_natural_resident(st->dev, d_y, m, ytda, d_s, d_leaf);
-}
-
-/* ======================================================================== */
-/* Clough-Tocher types: the same mesh_state, plus the gradients at the sites */
-/* ======================================================================== */
-/* mirror, then the gradients: `known` (the caller's, or a checkpoint's) or the estimate, which runs here so that
-   gsl_sinterp_get_gradients and a GSL_EMAXITER verdict belong to init */
-static int cubic_type_mirror(gsl_sinterp *interp, mesh_state *st, const gsl_matrix *known)
-{
-  if (interp->n_devices > 1) GSL_ERROR("gsl_sinterp_init: Clough-Tocher interpolants run on one device", GSL_EUNSUP);
-  int s = mesh_type_mirror(interp, st);
-  if (s) return s;
-  if (st->g_rtol > 0.0) s = simplex_mesh_device_set_gradient_options(st->dev, st->g_rtol, st->g_maxiter);
-  if (!s) s = simplex_mesh_device_bind_gradients(st->dev, known);
-  if (s) return s;
-  if (st->g) gsl_matrix_free(st->g);
-  st->g = gsl_matrix_alloc(st->n, 2);
-  if (!st->g) return GSL_ENOMEM;
-  return simplex_mesh_device_gradients(st->dev, st->g, &st->g_iters, &st->g_resid);
-}
-
-static int cubic_mesh_init(gsl_sinterp *interp, const gsl_matrix *x, const gsl_vector *f)
-{
-  mesh_state *st = (mesh_state *)interp->state;
-  if (!st->tri) GSL_ERROR("gsl_sinterp_init: no triangulation set (gsl_sinterp_set_triangulation)", GSL_EINVAL);
-  if (st->n < 3) GSL_ERROR("gsl_sinterp_init: an imported triangulation needs at least dim + 1 points", GSL_EINVAL);
-  int s = natural_copy_data(st, x, f);
-  if (s) return s;
-  st->mesh = simplex_mesh_import(st->x, st->tri, st->nbr, st->n_tri);
-  if (!st->mesh) return GSL_EINVAL;
-  return cubic_type_mirror(interp, st, st->g_set);
-}
-
-/* the tree of gsl_sinterp_natural_simplex, exported and dropped */
-static int cubic_simplex_init(gsl_sinterp *interp, const gsl_matrix *x, const gsl_vector *f)
-{
-  mesh_state *st = (mesh_state *)interp->state;
-  int s = natural_copy_data(st, x, f);
-  if (s) return s;
-  simplex_tree *tree = simplex_tree_alloc(2, (int)st->n);
-  if (!tree) return GSL_ENOMEM;
-  s = simplex_tree_init(tree, st->x, NULL, NULL, interp->init_flags, interp->rng);
-  if (s == GSL_SUCCESS) {
-    st->mesh = simplex_mesh_from_tree(tree, st->x);
-    if (!st->mesh) s = GSL_EINVAL;
-  }
-  simplex_tree_free(tree);
-  if (s != GSL_SUCCESS) return s;
-  return cubic_type_mirror(interp, st, st->g_set);
-}
-
-static int cubic_type_eval_many(const gsl_sinterp *interp, const gsl_matrix *y, gsl_vector *s, int *leaf)
-{
-  const mesh_state *st = (const mesh_state *)interp->state;
-  if (!st->dev) GSL_ERROR("gsl_sinterp_eval_many: interpolant not initialised", GSL_EINVAL);
-  return simplex_mesh_device_eval_cubic_many(st->dev, y, s, NULL, leaf);
-}
-
-static int cubic_type_eval_resident(const gsl_sinterp *interp, const double *d_y, size_t m, size_t ytda, double *d_s, int *d_leaf)
-{
-  const mesh_state *st = (const mesh_state *)interp->state;
-  if (!st->dev) GSL_ERROR("gsl_sinterp_eval_resident: interpolant not initialised", GSL_EINVAL);
-  return simplex_mesh_device_eval_cubic_resident(st->dev, d_y, m, ytda, d_s, NULL, 0, d_leaf);
 }
 
 /* ======================================================================== */
 /* type table + generic entry points                                         */
 /* ======================================================================== */
-static const gsl_sinterp_type gauss_type = {"rbf-gaussian", 1, &rbf_gauss_alloc, &rbf_init, &rbf_eval_many, &rbf_eval_resident, &rbf_free};
-static const gsl_sinterp_type tps_type = {"rbf-thin-plate-spline", 1, &rbf_tps_alloc, &rbf_init, &rbf_eval_many, &rbf_eval_resident, &rbf_free};
-static const gsl_sinterp_type simplex_type = {"linear-simplex", 3, &simplex_alloc, &simplex_init, &simplex_eval_many, &simplex_eval_resident, &simplex_free};
-static const gsl_sinterp_type wendland_type = {"rbf-wendland-c2", 1, &rbf_wendland_alloc, &rbf_init, &rbf_eval_many, &rbf_eval_resident, &rbf_free};
-static const gsl_sinterp_type mesh_type = {"linear-imported-triangulation", 3, &mesh_type_alloc, &mesh_type_init, &mesh_type_eval_many, &mesh_type_eval_resident, &mesh_type_free};
-const gsl_sinterp_type *gsl_sinterp_linear_mesh = &mesh_type;
-static const gsl_sinterp_type natural_mesh_type = {"natural-neighbour-imported-triangulation", 3, &natural_type_alloc, &natural_mesh_init, &natural_type_eval_many, &natural_type_eval_resident, &mesh_type_free};
-static const gsl_sinterp_type natural_simplex_type = {"natural-neighbour-simplex", 3, &natural_type_alloc, &natural_simplex_init, &natural_type_eval_many, &natural_type_eval_resident, &mesh_type_free};
-const gsl_sinterp_type *gsl_sinterp_natural_mesh = &natural_mesh_type;
-const gsl_sinterp_type *gsl_sinterp_natural_simplex = &natural_simplex_type;
-/* the types whose state is a mesh_state, and the natural-neighbour ones among them */
-static int is_natural_type(const gsl_sinterp_type *T) { return T == &natural_mesh_type || T == &natural_simplex_type; }
-static const gsl_sinterp_type cubic_mesh_type = {"clough-tocher-imported-triangulation", 3, &natural_type_alloc, &cubic_mesh_init, &cubic_type_eval_many, &cubic_type_eval_resident, &mesh_type_free};
-static const gsl_sinterp_type cubic_simplex_type = {"clough-tocher-simplex", 3, &natural_type_alloc, &cubic_simplex_init, &cubic_type_eval_many, &cubic_type_eval_resident, &mesh_type_free};
-const gsl_sinterp_type *gsl_sinterp_cubic_mesh = &cubic_mesh_type;
-const gsl_sinterp_type *gsl_sinterp_cubic_simplex = &cubic_simplex_type;
-static int is_cubic_type(const gsl_sinterp_type *T) { return T == &cubic_mesh_type || T == &cubic_simplex_type; }
-/* the 2-D mesh types beyond the linear one: what the natural-neighbour types refuse, the Clough-Tocher types refuse too */
-static int is_mesh2_type(const gsl_sinterp_type *T) { return is_natural_type(T) || is_cubic_type(T); }
-static int is_mesh_state_type(const gsl_sinterp_type *T) { return T == &mesh_type || is_mesh2_type(T); }
-static const gsl_sinterp_type tps_affine_type = {"rbf-thin-plate-spline-affine", 3, &rbf_tps_affine_alloc, &rbf_init, &rbf_eval_many, &rbf_eval_resident, &rbf_free};
-const gsl_sinterp_type *gsl_sinterp_rbf_tps_affine = &tps_affine_type;
-static const gsl_sinterp_type krige_type = {"ordinary-kriging-gaussian", 1, &krige_alloc, &rbf_init, &rbf_eval_many, &rbf_eval_resident, &rbf_free};
-const gsl_sinterp_type *gsl_sinterp_kriging = &krige_type;
-static const gsl_sinterp_type matern32_type = {"rbf-matern-3/2", 1, &rbf_matern32_alloc, &rbf_init, &rbf_eval_many, &rbf_eval_resident, &rbf_free};
-static const gsl_sinterp_type matern52_type = {"rbf-matern-5/2", 1, &rbf_matern52_alloc, &rbf_init, &rbf_eval_many, &rbf_eval_resident, &rbf_free};
-static const gsl_sinterp_type imq_type = {"rbf-inverse-multiquadric", 1, &rbf_imq_alloc, &rbf_init, &rbf_eval_many, &rbf_eval_resident, &rbf_free};
-static const gsl_sinterp_type krige_matern32_type = {"ordinary-kriging-matern-3/2", 1, &krige_matern32_alloc, &rbf_init, &rbf_eval_many, &rbf_eval_resident, &rbf_free};
-static const gsl_sinterp_type krige_matern52_type = {"ordinary-kriging-matern-5/2", 1, &krige_matern52_alloc, &rbf_init, &rbf_eval_many, &rbf_eval_resident, &rbf_free};
-const gsl_sinterp_type *gsl_sinterp_rbf_matern32 = &matern32_type;
-const gsl_sinterp_type *gsl_sinterp_rbf_matern52 = &matern52_type;
-const gsl_sinterp_type *gsl_sinterp_rbf_imq = &imq_type;
-const gsl_sinterp_type *gsl_sinterp_kriging_matern32 = &krige_matern32_type;
-const gsl_sinterp_type *gsl_sinterp_kriging_matern52 = &krige_matern52_type;
-const gsl_sinterp_type *gsl_sinterp_rbf_wendland = &wendland_type;
-const gsl_sinterp_type *gsl_sinterp_rbf_gaussian = &gauss_type;
-const gsl_sinterp_type *gsl_sinterp_rbf_tps = &tps_type;
-const gsl_sinterp_type *gsl_sinterp_linear_simplex = &simplex_type;
+#define RBF_ROW(name, min_size, id, kind, krige, affine, pd)                                                       \
+  {{name, min_size, &rbf_alloc, &rbf_init, &rbf_eval_many, &rbf_eval_resident, &rbf_free}, id, FAM_RBF, kind, krige, affine, pd, 0, 0, NULL}
+#define MESH_ROW(name, id, method, imported, noun)                                                                 \
+  {{name, 3, &mesh_type_alloc, &mesh_type_init, &mesh_type_eval_many, &mesh_type_eval_resident, &mesh_type_free}, id, FAM_MESH, 0, 0, 0, 0, \
+   method, imported, noun}
+/* one row per type, in the order of the checkpoint ids.  The checkpoints of 12 / 13 have the payload of 6, those of
+   14 / 15 the same + the 2 N gradients */
+static const type_desc type_table[] = {
+  RBF_ROW("rbf-gaussian", 1, 0, GSL_SINTERP_RBF_GAUSSIAN, 0, 0, 1),
+  RBF_ROW("rbf-thin-plate-spline", 1, 1, GSL_SINTERP_RBF_TPS, 0, 0, 0),
+  {{"linear-simplex", 3, &simplex_alloc, &simplex_init, &simplex_eval_many, &simplex_eval_resident, &simplex_free}, 2, FAM_TREE, 0, 0, 0, 0, 0, 0, NULL},
+  RBF_ROW("rbf-wendland-c2", 1, 3, GSL_SINTERP_RBF_WENDLAND, 0, 0, 1),
+  RBF_ROW("ordinary-kriging-gaussian", 1, 4, GSL_SINTERP_RBF_GAUSSIAN, 1, 0, 1),
+  RBF_ROW("rbf-thin-plate-spline-affine", 3, 5, GSL_SINTERP_RBF_TPS, 0, 1, 0),
+  MESH_ROW("linear-imported-triangulation", 6, MESH_LINEAR, 1, NULL),
+  RBF_ROW("rbf-matern-3/2", 1, 7, GSL_SINTERP_RBF_MATERN32, 0, 0, 1),
+  RBF_ROW("rbf-matern-5/2", 1, 8, GSL_SINTERP_RBF_MATERN52, 0, 0, 1),
+  RBF_ROW("rbf-inverse-multiquadric", 1, 9, GSL_SINTERP_RBF_IMQ, 0, 0, 1),
+  RBF_ROW("ordinary-kriging-matern-3/2", 1, 10, GSL_SINTERP_RBF_MATERN32, 1, 0, 1),
+  RBF_ROW("ordinary-kriging-matern-5/2", 1, 11, GSL_SINTERP_RBF_MATERN52, 1, 0, 1),
+  MESH_ROW("natural-neighbour-imported-triangulation", 12, MESH_NATURAL, 1, "natural-neighbour"),
+  MESH_ROW("natural-neighbour-simplex", 13, MESH_NATURAL, 0, "natural-neighbour"),
+  MESH_ROW("clough-tocher-imported-triangulation", 14, MESH_CUBIC, 1, "Clough-Tocher"),
+  MESH_ROW("clough-tocher-simplex", 15, MESH_CUBIC, 0, "Clough-Tocher"),
+};
+#define N_TYPES (sizeof type_table / sizeof type_table[0])
+const gsl_sinterp_type *gsl_sinterp_rbf_gaussian = &type_table[0].pub;
+const gsl_sinterp_type *gsl_sinterp_rbf_tps = &type_table[1].pub;
+const gsl_sinterp_type *gsl_sinterp_linear_simplex = &type_table[2].pub;
+const gsl_sinterp_type *gsl_sinterp_rbf_wendland = &type_table[3].pub;
+const gsl_sinterp_type *gsl_sinterp_kriging = &type_table[4].pub;
+const gsl_sinterp_type *gsl_sinterp_rbf_tps_affine = &type_table[5].pub;
+const gsl_sinterp_type *gsl_sinterp_linear_mesh = &type_table[6].pub;
+const gsl_sinterp_type *gsl_sinterp_rbf_matern32 = &type_table[7].pub;
+const gsl_sinterp_type *gsl_sinterp_rbf_matern52 = &type_table[8].pub;
+const gsl_sinterp_type *gsl_sinterp_rbf_imq = &type_table[9].pub;
+const gsl_sinterp_type *gsl_sinterp_kriging_matern32 = &type_table[10].pub;
+const gsl_sinterp_type *gsl_sinterp_kriging_matern52 = &type_table[11].pub;
+const gsl_sinterp_type *gsl_sinterp_natural_mesh = &type_table[12].pub;
+const gsl_sinterp_type *gsl_sinterp_natural_simplex = &type_table[13].pub;
+const gsl_sinterp_type *gsl_sinterp_cubic_mesh = &type_table[14].pub;
+const gsl_sinterp_type *gsl_sinterp_cubic_simplex = &type_table[15].pub;
 
-/* the kriging types (a covariance + the estimated mean), and the types on a positive definite kernel: Cholesky routes
-   1 / 7, hence leave-one-out */
-static int is_krige_type(const gsl_sinterp_type *T) { return T == &krige_type || T == &krige_matern32_type || T == &krige_matern52_type; }
-static int is_pd_type(const gsl_sinterp_type *T)
+static const type_desc *desc_of(const gsl_sinterp_type *T)
 {
-  return T == &gauss_type || T == &wendland_type || T == &matern32_type || T == &matern52_type || T == &imq_type || is_krige_type(T);
+  for (size_t i = 0; i < N_TYPES; i++)
+    if (T == &type_table[i].pub) return &type_table[i];
+  return NULL;
 }
+
+/* the state as its family's struct; NULL for an interpolant of another family.  gsl_sinterp_alloc admits the rows of the
+   table only, so desc_of(interp->type) is never NULL */
+static rbf_state *rbf_of(const gsl_sinterp *interp) { return desc_of(interp->type)->family == FAM_RBF ? (rbf_state *)interp->state : NULL; }
+static simplex_state *tree_of(const gsl_sinterp *interp) { return desc_of(interp->type)->family == FAM_TREE ? (simplex_state *)interp->state : NULL; }
+static mesh_state *mesh_of(const gsl_sinterp *interp) { return desc_of(interp->type)->family == FAM_MESH ? (mesh_state *)interp->state : NULL; }
+static int mesh_method(const gsl_sinterp *interp, int method) { return mesh_of(interp) && desc_of(interp->type)->method == method; }
 
 /* whether the interpolant is on, or will at the next init be on, the local route (route 11): asked by every entry that
    needs the global model, before anything touches the device */
 static int is_local(const gsl_sinterp *interp)
 {
-  return is_krige_type(interp->type) && (interp->neighbours > 0 || ((const rbf_state *)interp->state)->local_k > 0);
+  return desc_of(interp->type)->krige && (interp->neighbours > 0 || rbf_of(interp)->local_k > 0);
 }
 
 int gsl_sinterp_set_neighbours(gsl_sinterp *interp, size_t k)
 {
   if (!interp) GSL_ERROR("gsl_sinterp_set_neighbours: null interpolant", GSL_EFAULT);
-  if (is_natural_type(interp->type)) GSL_ERROR("gsl_sinterp_set_neighbours: not for natural-neighbour interpolants", GSL_EUNSUP);
-  if (is_cubic_type(interp->type)) GSL_ERROR("gsl_sinterp_set_neighbours: not for Clough-Tocher interpolants", GSL_EUNSUP);
-  if (!is_krige_type(interp->type)) GSL_ERROR("gsl_sinterp_set_neighbours: kriging interpolants only", GSL_EINVAL);
+  const type_desc *d = desc_of(interp->type);
+  if (d->noun) return noun_error(d, "gsl_sinterp_set_neighbours: not for %s interpolants", GSL_EUNSUP);
+  if (!d->krige) GSL_ERROR("gsl_sinterp_set_neighbours: kriging interpolants only", GSL_EINVAL);
   if (k > GSL_SINTERP_MAX_NEIGHBOURS) GSL_ERROR("gsl_sinterp_set_neighbours: at most 64 neighbours", GSL_EINVAL);
   if (k > interp->size) GSL_ERROR("gsl_sinterp_set_neighbours: more neighbours than centres", GSL_EINVAL);
   interp->neighbours = k;
@@ -1988,15 +1942,17 @@ int gsl_sinterp_set_neighbours(gsl_sinterp *interp, size_t k)
 gsl_sinterp *gsl_sinterp_alloc(const gsl_sinterp_type *T, size_t dim, size_t size)
 {
   if (!T) GSL_ERROR_NULL("gsl_sinterp_alloc: null type", GSL_EFAULT);
+  const type_desc *d = desc_of(T);
+  if (!d) GSL_ERROR_NULL("gsl_sinterp_alloc: not one of the gsl_sinterp types", GSL_EINVAL);
   if (size < T->min_size)
     GSL_ERROR_NULL("insufficient number of points for interpolation type", GSL_EINVAL);
   if (dim < 1 || dim > 3) GSL_ERROR_NULL("gsl_sinterp_alloc: dim must be 1, 2 or 3", GSL_EINVAL);
-  if (T == &simplex_type && dim != 2)
+  if (d->family == FAM_TREE && dim != 2)
     GSL_ERROR_NULL("gsl_sinterp_alloc: linear-simplex supports dim = 2 only", GSL_EUNIMPL);
-  if (is_natural_type(T) && dim != 2)
-    GSL_ERROR_NULL("gsl_sinterp_alloc: natural-neighbour interpolants support dim = 2 only", GSL_EUNIMPL);
-  if (is_cubic_type(T) && dim != 2)
-    GSL_ERROR_NULL("gsl_sinterp_alloc: Clough-Tocher interpolants support dim = 2 only", GSL_EUNIMPL);
+  if (d->noun && dim != 2) {
+    noun_error(d, "gsl_sinterp_alloc: %s interpolants support dim = 2 only", GSL_EUNIMPL);
+    return NULL;
+  }
   gsl_sinterp *interp = (gsl_sinterp *)calloc(1, sizeof *interp);
   if (!interp) GSL_ERROR_NULL("failed to allocate space for sinterp struct", GSL_ENOMEM);
   interp->type = T; interp->dim = dim; interp->size = size;
@@ -2013,6 +1969,8 @@ gsl_sinterp *gsl_sinterp_alloc(const gsl_sinterp_type *T, size_t dim, size_t siz
     free(interp);
     GSL_ERROR_NULL("failed to allocate space for sinterp state", GSL_ENOMEM);
   }
+  rbf_state *st = rbf_of(interp);
+  if (st) { st->kind = d->kind; st->krige = d->krige; st->affine = d->affine; }
   return interp;
 }
 
@@ -2060,7 +2018,7 @@ int gsl_sinterp_set_shape(gsl_sinterp *interp, double eps)
 int gsl_sinterp_set_nugget(gsl_sinterp *interp, double nugget)
 {
   if (!interp) GSL_ERROR("gsl_sinterp_set_nugget: null interpolant", GSL_EFAULT);
-  if (!is_krige_type(interp->type)) GSL_ERROR("gsl_sinterp_set_nugget: kriging interpolants only", GSL_EINVAL);
+  if (!desc_of(interp->type)->krige) GSL_ERROR("gsl_sinterp_set_nugget: kriging interpolants only", GSL_EINVAL);
   if (!(nugget >= 0.0)) GSL_ERROR("gsl_sinterp_set_nugget: the nugget must be >= 0", GSL_EDOM);
   interp->nugget = nugget;
   return GSL_SUCCESS;
@@ -2069,7 +2027,7 @@ int gsl_sinterp_set_nugget(gsl_sinterp *interp, double nugget)
 int gsl_sinterp_set_variance(gsl_sinterp *interp, int want)
 {
   if (!interp) GSL_ERROR("gsl_sinterp_set_variance: null interpolant", GSL_EFAULT);
-  if (!is_krige_type(interp->type)) GSL_ERROR("gsl_sinterp_set_variance: kriging interpolants only", GSL_EINVAL);
+  if (!desc_of(interp->type)->krige) GSL_ERROR("gsl_sinterp_set_variance: kriging interpolants only", GSL_EINVAL);
   interp->want_variance = want != 0;
   return GSL_SUCCESS;
 }
@@ -2077,7 +2035,7 @@ int gsl_sinterp_set_variance(gsl_sinterp *interp, int want)
 int gsl_sinterp_set_loo(gsl_sinterp *interp, int want)
 {
   if (!interp) GSL_ERROR("gsl_sinterp_set_loo: null interpolant", GSL_EFAULT);
-  if (!is_pd_type(interp->type))
+  if (!desc_of(interp->type)->pd)
     GSL_ERROR("gsl_sinterp_set_loo: positive definite RBF (Gaussian, Wendland, Matern, inverse multiquadric) and kriging interpolants only", GSL_EINVAL);
   interp->want_loo = want != 0;
   return GSL_SUCCESS;
@@ -2086,12 +2044,12 @@ int gsl_sinterp_set_loo(gsl_sinterp *interp, int want)
 /* whether leave-one-out data is held, as a status (the table of include/gsl_sinterp.h) */
 static int loo_status(const gsl_sinterp *interp)
 {
-  if (is_natural_type(interp->type)) GSL_ERROR("gsl_sinterp_loo: not for natural-neighbour interpolants", GSL_EUNSUP);
-  if (is_cubic_type(interp->type)) GSL_ERROR("gsl_sinterp_loo: not for Clough-Tocher interpolants", GSL_EUNSUP);
-  if (!is_pd_type(interp->type))
+  const type_desc *d = desc_of(interp->type);
+  if (d->noun) return noun_error(d, "gsl_sinterp_loo: not for %s interpolants", GSL_EUNSUP);
+  if (!d->pd)
     GSL_ERROR("gsl_sinterp_loo: positive definite RBF (Gaussian, Wendland, Matern, inverse multiquadric) and kriging interpolants only", GSL_EINVAL);
   if (is_local(interp)) GSL_ERROR("gsl_sinterp_loo: local kriging (gsl_sinterp_set_neighbours) takes a route without a Cholesky factor", GSL_EUNSUP);
-  const rbf_state *st = (const rbf_state *)interp->state;
+  const rbf_state *st = rbf_of(interp);
   if (!st->d_w || st->nf == 0) GSL_ERROR("gsl_sinterp_loo: interpolant not initialised", GSL_EINVAL);
   if (st->loo_state == 3)
     GSL_ERROR("gsl_sinterp_loo: the interpolant was restored by gsl_sinterp_fread; a checkpoint carries no leave-one-out data", GSL_EINVAL);
@@ -2107,7 +2065,7 @@ int gsl_sinterp_loo_residuals(const gsl_sinterp *interp, gsl_matrix *E)
   if (!interp || !E) GSL_ERROR("gsl_sinterp_loo_residuals: null argument", GSL_EFAULT);
   int ls = loo_status(interp);
   if (ls) return ls;
-  const rbf_state *st = (const rbf_state *)interp->state;
+  const rbf_state *st = rbf_of(interp);
   if (E->size1 != st->n || E->size2 != st->loo_nf) GSL_ERROR("gsl_sinterp_loo_residuals: E must be size x fields", GSL_EBADLEN);
   for (size_t i = 0; i < st->n; i++)
     for (size_t q = 0; q < st->loo_nf; q++) E->data[i * E->tda + q] = st->loo_e[q * st->n + i];
@@ -2119,7 +2077,7 @@ int gsl_sinterp_loo_variance(const gsl_sinterp *interp, gsl_vector *v)
   if (!interp || !v) GSL_ERROR("gsl_sinterp_loo_variance: null argument", GSL_EFAULT);
   int ls = loo_status(interp);
   if (ls) return ls;
-  const rbf_state *st = (const rbf_state *)interp->state;
+  const rbf_state *st = rbf_of(interp);
   if (v->size != st->n) GSL_ERROR("gsl_sinterp_loo_variance: wrong length", GSL_EBADLEN);
   for (size_t i = 0; i < st->n; i++) gsl_vector_set(v, i, st->loo_v[i]);
   return GSL_SUCCESS;
@@ -2146,16 +2104,19 @@ struct gsl_sinterp_fit_workspace {
 gsl_sinterp_fit_workspace *gsl_sinterp_fit_alloc(const gsl_sinterp *interp, const gsl_matrix *x, const gsl_vector *f)
 {
   if (!interp || !x || !f) GSL_ERROR_NULL("gsl_sinterp_fit_alloc: null argument", GSL_EFAULT);
-  if (is_natural_type(interp->type)) GSL_ERROR_NULL("gsl_sinterp_fit_alloc: not for natural-neighbour interpolants (nothing to fit)", GSL_EUNSUP);
-  if (is_cubic_type(interp->type)) GSL_ERROR_NULL("gsl_sinterp_fit_alloc: not for Clough-Tocher interpolants (nothing to fit)", GSL_EUNSUP);
-  if (!is_pd_type(interp->type))
+  const type_desc *d = desc_of(interp->type);
+  if (d->noun) {
+    noun_error(d, "gsl_sinterp_fit_alloc: not for %s interpolants (nothing to fit)", GSL_EUNSUP);
+    return NULL;
+  }
+  if (!d->pd)
     GSL_ERROR_NULL("gsl_sinterp_fit_alloc: positive definite RBF (Gaussian, Wendland, Matern, inverse multiquadric) and kriging interpolants only", GSL_EINVAL);
   const size_t n = interp->size, dim = interp->dim;
   if (x->size1 != n || x->size2 != dim) GSL_ERROR_NULL("gsl_sinterp_fit_alloc: x must be size x dim", GSL_EBADLEN);
   if (f->size != n) GSL_ERROR_NULL("gsl_sinterp_fit_alloc: f must have size entries", GSL_EBADLEN);
   gsl_sinterp_fit_workspace *w = (gsl_sinterp_fit_workspace *)calloc(1, sizeof *w);
   if (!w) GSL_ERROR_NULL("gsl_sinterp_fit_alloc: out of memory", GSL_ENOMEM);
-  const rbf_state *st = (const rbf_state *)interp->state;
+  const rbf_state *st = rbf_of(interp);
   w->kind = st->kind; w->krige = st->krige; w->n = n; w->dim = dim;
   w->chunk = (n + 127) / 128 * 128;
   if (w->chunk > LOO_CHUNK) w->chunk = LOO_CHUNK;
@@ -2376,10 +2337,10 @@ int gsl_sinterp_fit_sigma2(const gsl_sinterp_fit_workspace *w, double *s2)
 /* whether variances can be evaluated, as a status (the table of include/gsl_sinterp.h) */
 static int variance_status(const gsl_sinterp *interp)
 {
-  if (is_natural_type(interp->type)) GSL_ERROR("gsl_sinterp_eval_variance: not for natural-neighbour interpolants", GSL_EUNSUP);
-  if (is_cubic_type(interp->type)) GSL_ERROR("gsl_sinterp_eval_variance: not for Clough-Tocher interpolants", GSL_EUNSUP);
-  if (!is_krige_type(interp->type)) GSL_ERROR("gsl_sinterp_eval_variance: kriging interpolants only", GSL_EINVAL);
-  const rbf_state *st = (const rbf_state *)interp->state;
+  const type_desc *d = desc_of(interp->type);
+  if (d->noun) return noun_error(d, "gsl_sinterp_eval_variance: not for %s interpolants", GSL_EUNSUP);
+  if (!d->krige) GSL_ERROR("gsl_sinterp_eval_variance: kriging interpolants only", GSL_EINVAL);
+  const rbf_state *st = rbf_of(interp);
   if (!st->d_w) GSL_ERROR("gsl_sinterp_eval_variance: interpolant not initialised", GSL_EINVAL);
   if (st->local_k) return GSL_SUCCESS;                  /* the local route keeps no factor and needs none */
   if (st->var_state == 3)
@@ -2396,7 +2357,7 @@ int gsl_sinterp_eval_variance_resident(const gsl_sinterp *interp, const double *
   if (!interp) GSL_ERROR("gsl_sinterp_eval_variance: null interpolant", GSL_EFAULT);
   int vs = variance_status(interp);
   if (vs) return vs;
-  rbf_state *st = (rbf_state *)interp->state;           /* the workspace is a grow-only cache inside the state */
+  rbf_state *st = rbf_of(interp);           /* the workspace is a grow-only cache inside the state */
   if (m == 0) return GSL_SUCCESS;
   if (!d_y || !d_var) GSL_ERROR("gsl_sinterp_eval_variance: null argument", GSL_EFAULT);
   if (st->local_k) return local_eval_resident(interp, d_y, m, ytda, NULL, d_var, NULL);
@@ -2424,22 +2385,15 @@ int gsl_sinterp_eval_variance_many(const gsl_sinterp *interp, const gsl_matrix *
   const size_t m = y->size1, dim = interp->dim;
   int vs = variance_status(interp);
   if (vs || m == 0) return vs;
-  const rbf_state *st = (const rbf_state *)interp->state;
+  const rbf_state *st = rbf_of(interp);
   if (st->local_k) return local_eval_many(interp, y, NULL, var, NULL);
   gsl_sinterp_hip_ctx *c = st->ctx;
-  double *h = (double *)malloc(m * dim * sizeof(double)), *d_y = NULL, *d_v = NULL;
-  if (!h) GSL_ERROR("gsl_sinterp_eval_variance_many: out of memory", GSL_ENOMEM);
-  for (size_t k = 0; k < m; k++)
-    for (size_t a = 0; a < dim; a++) h[k * dim + a] = y->data[k * y->tda + a];
-  int s = gsl_sinterp_hip_malloc(c, (void **)&d_y, m * dim * sizeof(double));
-  if (!s) s = gsl_sinterp_hip_malloc(c, (void **)&d_v, m * sizeof(double));
-  if (!s) s = gsl_sinterp_hip_h2d(c, d_y, h, m * dim * sizeof(double));
-  int es = GSL_SUCCESS;
-  if (!s) es = gsl_sinterp_eval_variance_resident(interp, d_y, m, dim, d_v);
-  if (!s && !es) s = gsl_sinterp_hip_d2h(c, h, d_v, m * sizeof(double));
-  if (!s && !es) for (size_t k = 0; k < m; k++) gsl_vector_set(var, k, h[k]);
-  gsl_sinterp_hip_free(c, d_y); gsl_sinterp_hip_free(c, d_v);
-  free(h);
+  stage_out out[1] = {STAGE_VECTOR(var)};
+  host_stage hs;
+  int s = host_stage_begin(&hs, c, y, dim, out, 1), es = GSL_SUCCESS;
+  if (!hs.h) GSL_ERROR("gsl_sinterp_eval_variance_many: out of memory", GSL_ENOMEM);
+  if (!s) es = gsl_sinterp_eval_variance_resident(interp, hs.d_y, m, dim, (double *)out[0].d);
+  s = host_stage_end(&hs, s, !es);
   HIP_TRY(s, c);
   return es;
 }
@@ -2461,8 +2415,8 @@ int gsl_sinterp_eval_variance_e(const gsl_sinterp *interp, const gsl_vector *y, 
 int gsl_sinterp_eval_local_many(const gsl_sinterp *interp, const gsl_matrix *y, gsl_vector *s, gsl_vector *var, int *idx)
 {
   if (!interp || !y) GSL_ERROR("gsl_sinterp_eval_local_many: null argument", GSL_EFAULT);
-  if (!is_krige_type(interp->type)) GSL_ERROR("gsl_sinterp_eval_local_many: kriging interpolants only", GSL_EINVAL);
-  const rbf_state *st = (const rbf_state *)interp->state;
+  if (!desc_of(interp->type)->krige) GSL_ERROR("gsl_sinterp_eval_local_many: kriging interpolants only", GSL_EINVAL);
+  const rbf_state *st = rbf_of(interp);
   if (!st->d_w) GSL_ERROR("gsl_sinterp_eval_local_many: interpolant not initialised", GSL_EINVAL);
   if (!st->local_k) GSL_ERROR("gsl_sinterp_eval_local_many: initialised without gsl_sinterp_set_neighbours", GSL_EINVAL);
   if (y->size2 != interp->dim) GSL_ERROR("target matrix must have dim columns", GSL_EBADLEN);
@@ -2474,9 +2428,9 @@ int gsl_sinterp_eval_local_many(const gsl_sinterp *interp, const gsl_matrix *y, 
 /* ---- value + gradient (RBF family): dispatch on the type here, no slot in gsl_sinterp_type ---- */
 static int grad_status(const gsl_sinterp *interp)
 {
-  if (is_natural_type(interp->type)) GSL_ERROR("gsl_sinterp_eval_grad: not for natural-neighbour interpolants", GSL_EUNSUP);
-  if (is_cubic_type(interp->type)) return GSL_SUCCESS;     /* the one mesh type with a continuous gradient */
-  if (interp->type == &simplex_type || interp->type == &mesh_type)
+  if (mesh_method(interp, MESH_NATURAL)) GSL_ERROR("gsl_sinterp_eval_grad: not for natural-neighbour interpolants", GSL_EUNSUP);
+  if (mesh_method(interp, MESH_CUBIC)) return GSL_SUCCESS;     /* the one mesh method with a continuous gradient */
+  if (!rbf_of(interp))
     GSL_ERROR("gsl_sinterp_eval_grad: RBF-family interpolants only (the piecewise-linear gradient is constant per leaf)", GSL_EUNSUP);
   if (is_local(interp))
     GSL_ERROR("gsl_sinterp_eval_grad: not with gsl_sinterp_set_neighbours (the local predictor is discontinuous where the neighbour set changes)", GSL_EUNSUP);
@@ -2490,14 +2444,14 @@ int gsl_sinterp_eval_grad_resident(const gsl_sinterp *interp, const double *d_y,
   if (m > 0 && (!d_y || !d_g)) GSL_ERROR("gsl_sinterp_eval_grad_resident: null argument", GSL_EFAULT);
   int gs = grad_status(interp);
   if (gs) return gs;
-  if (is_cubic_type(interp->type)) {
-    const mesh_state *ms = (const mesh_state *)interp->state;
+  const mesh_state *ms = mesh_of(interp);                /* Clough-Tocher: grad_status let no other mesh type through */
+  if (ms) {
     if (!ms->dev) GSL_ERROR("gsl_sinterp_eval_grad: interpolant not initialised", GSL_EINVAL);
     if (m > 0 && !d_s) GSL_ERROR("gsl_sinterp_eval_grad_resident: Clough-Tocher interpolants need d_s (the locate step writes through it)", GSL_EFAULT);
     if (gtda < 2) GSL_ERROR("gsl_sinterp_eval_grad_resident: gradient rows shorter than dim", GSL_EINVAL);
     return simplex_mesh_device_eval_cubic_resident(ms->dev, d_y, m, ytda, d_s, d_g, gtda, NULL);
   }
-  const rbf_state *st = (const rbf_state *)interp->state;
+  const rbf_state *st = rbf_of(interp);
   if (!st->d_w) GSL_ERROR("gsl_sinterp_eval_grad: interpolant not initialised", GSL_EINVAL);
   /* the tail: the affine polynomial, or kriging's constant mean; member 0 evaluates every target (as
      gsl_sinterp_eval_resident does) */
@@ -2517,8 +2471,8 @@ int gsl_sinterp_eval_grad_many(const gsl_sinterp *interp, const gsl_matrix *y, g
   if (y->size2 != dim) GSL_ERROR("target matrix must have dim columns", GSL_EBADLEN);
   if (g->size1 != m || g->size2 != dim) GSL_ERROR("gradient matrix must be (number of targets) x dim", GSL_EBADLEN);
   if (sv && sv->size != m) GSL_ERROR("output length must equal the number of targets", GSL_EBADLEN);
-  if (is_cubic_type(interp->type)) {
-    const mesh_state *ms = (const mesh_state *)interp->state;
+  const mesh_state *ms = mesh_of(interp);                /* Clough-Tocher: grad_status let no other mesh type through */
+  if (ms) {
     if (!ms->dev) GSL_ERROR("gsl_sinterp_eval_grad: interpolant not initialised", GSL_EINVAL);
     if (sv) return simplex_mesh_device_eval_cubic_many(ms->dev, y, sv, g, NULL);
     if (m == 0) return GSL_SUCCESS;
@@ -2528,28 +2482,16 @@ int gsl_sinterp_eval_grad_many(const gsl_sinterp *interp, const gsl_matrix *y, g
     gsl_vector_free(tmp);
     return cs;
   }
-  const rbf_state *st = (const rbf_state *)interp->state;
+  const rbf_state *st = rbf_of(interp);
   if (!st->d_w) GSL_ERROR("gsl_sinterp_eval_grad: interpolant not initialised", GSL_EINVAL);
   if (m == 0) return GSL_SUCCESS;
   gsl_sinterp_hip_ctx *c = st->ctx;
-  /* one staging buffer on either side: [targets m x dim | gradient m x dim | values m] */
-  double *h = (double *)malloc(m * (2 * dim + 1) * sizeof(double)), *d = NULL;
-  if (!h) GSL_ERROR("gsl_sinterp_eval_grad_many: out of memory", GSL_ENOMEM);
-  for (size_t k = 0; k < m; k++)
-    for (size_t a = 0; a < dim; a++) h[k * dim + a] = y->data[k * y->tda + a];
-  int s = gsl_sinterp_hip_malloc(c, (void **)&d, m * (2 * dim + 1) * sizeof(double));
-  if (!s) s = gsl_sinterp_hip_h2d(c, d, h, m * dim * sizeof(double));
-  int es = GSL_SUCCESS;
-  double *d_g = d + m * dim, *d_s = sv ? d_g + m * dim : NULL;
-  if (!s) es = gsl_sinterp_eval_grad_resident(interp, d, m, dim, d_s, d_g, dim);
-  if (!s && !es) s = gsl_sinterp_hip_d2h(c, h, d_g, m * (dim + (sv ? 1 : 0)) * sizeof(double));
-  if (!s && !es) {
-    for (size_t k = 0; k < m; k++)
-      for (size_t a = 0; a < dim; a++) g->data[k * g->tda + a] = h[k * dim + a];
-    if (sv) for (size_t k = 0; k < m; k++) gsl_vector_set(sv, k, h[m * dim + k]);
-  }
-  gsl_sinterp_hip_free(c, d);
-  free(h);
+  stage_out out[2] = {STAGE_MATRIX(g), STAGE_VECTOR(sv)};     /* no sv: no room for values, nothing downloaded for them */
+  host_stage hs;
+  int s = host_stage_begin(&hs, c, y, dim, out, 2), es = GSL_SUCCESS;
+  if (!hs.h) GSL_ERROR("gsl_sinterp_eval_grad_many: out of memory", GSL_ENOMEM);
+  if (!s) es = gsl_sinterp_eval_grad_resident(interp, hs.d_y, m, dim, (double *)out[1].d, (double *)out[0].d, dim);
+  s = host_stage_end(&hs, s, !es);
   HIP_TRY(s, c);
   return es;
 }
@@ -2577,9 +2519,9 @@ int gsl_sinterp_eval_grad_e(const gsl_sinterp *interp, const gsl_vector *y, doub
 /* ---- several fields on one set of centres (RBF family): dispatch on the type here, no slot in gsl_sinterp_type ---- */
 static int fields_status(const gsl_sinterp *interp)
 {
-  if (is_natural_type(interp->type)) GSL_ERROR("gsl_sinterp fields: not for natural-neighbour interpolants (one response)", GSL_EUNSUP);
-  if (is_cubic_type(interp->type)) GSL_ERROR("gsl_sinterp fields: not for Clough-Tocher interpolants (one response)", GSL_EUNSUP);
-  if (interp->type == &simplex_type || interp->type == &mesh_type)
+  const type_desc *d = desc_of(interp->type);
+  if (d->noun) return noun_error(d, "gsl_sinterp fields: not for %s interpolants (one response)", GSL_EUNSUP);
+  if (d->family != FAM_RBF)
     GSL_ERROR("gsl_sinterp fields: RBF-family interpolants only (several responses per leaf of the linear types: a separate entry)", GSL_EUNSUP);
   if (is_local(interp)) GSL_ERROR("gsl_sinterp fields: not with gsl_sinterp_set_neighbours (local kriging has one field)", GSL_EUNSUP);
   return GSL_SUCCESS;
@@ -2598,9 +2540,8 @@ int gsl_sinterp_init_fields(gsl_sinterp *interp, const gsl_matrix *x, const gsl_
 
 size_t gsl_sinterp_n_fields(const gsl_sinterp *interp)
 {
-  if (!interp || interp->type == &simplex_type || is_mesh_state_type(interp->type)) return 0;
-  const rbf_state *st = (const rbf_state *)interp->state;
-  return st->d_w ? st->nf : 0;
+  const rbf_state *st = interp ? rbf_of(interp) : NULL;
+  return st && st->d_w ? st->nf : 0;
 }
 
 int gsl_sinterp_eval_fields_resident(const gsl_sinterp *interp, const double *d_y, size_t m, size_t ytda, double *d_s, size_t stda)
@@ -2609,7 +2550,7 @@ int gsl_sinterp_eval_fields_resident(const gsl_sinterp *interp, const double *d_
   if (m > 0 && (!d_y || !d_s)) GSL_ERROR("gsl_sinterp_eval_fields_resident: null argument", GSL_EFAULT);
   int fs = fields_status(interp);
   if (fs) return fs;
-  const rbf_state *st = (const rbf_state *)interp->state;
+  const rbf_state *st = rbf_of(interp);
   if (!st->d_w || st->nf == 0) GSL_ERROR("gsl_sinterp_eval_fields: interpolant not initialised", GSL_EINVAL);
   if (stda < st->nf) GSL_ERROR("gsl_sinterp_eval_fields_resident: row pitch below the number of fields", GSL_EINVAL);
   /* the tails: the affine polynomials, or kriging's constant means; member 0 evaluates every target (as the gradient and
@@ -2631,28 +2572,18 @@ int gsl_sinterp_eval_fields_many(const gsl_sinterp *interp, const gsl_matrix *y,
   const size_t m = y->size1, dim = interp->dim;
   if (y->size2 != dim) GSL_ERROR("target matrix must have dim columns", GSL_EBADLEN);
   if (S->size1 != m) GSL_ERROR("output matrix must have one row per target", GSL_EBADLEN);
-  const rbf_state *st = (const rbf_state *)interp->state;
+  const rbf_state *st = rbf_of(interp);
   if (!st->d_w || st->nf == 0) GSL_ERROR("gsl_sinterp_eval_fields: interpolant not initialised", GSL_EINVAL);
   const size_t K = st->nf;
   if (S->size2 != K) GSL_ERROR("output matrix must have one column per field", GSL_EBADLEN);
   if (m == 0) return GSL_SUCCESS;
   gsl_sinterp_hip_ctx *c = st->ctx;
-  /* one staging buffer on either side: [targets m x dim | values m x K] */
-  double *h = (double *)malloc(m * (dim + K) * sizeof(double)), *d = NULL;
-  if (!h) GSL_ERROR("gsl_sinterp_eval_fields_many: out of memory", GSL_ENOMEM);
-  for (size_t k = 0; k < m; k++)
-    for (size_t a = 0; a < dim; a++) h[k * dim + a] = y->data[k * y->tda + a];
-  int s = gsl_sinterp_hip_malloc(c, (void **)&d, m * (dim + K) * sizeof(double));
-  if (!s) s = gsl_sinterp_hip_h2d(c, d, h, m * dim * sizeof(double));
-  int es = GSL_SUCCESS;
-  double *d_s = d + m * dim;
-  if (!s) es = gsl_sinterp_eval_fields_resident(interp, d, m, dim, d_s, K);
-  if (!s && !es) s = gsl_sinterp_hip_d2h(c, h, d_s, m * K * sizeof(double));
-  if (!s && !es)
-    for (size_t k = 0; k < m; k++)
-      for (size_t q = 0; q < K; q++) S->data[k * S->tda + q] = h[k * K + q];
-  gsl_sinterp_hip_free(c, d);
-  free(h);
+  stage_out out[1] = {STAGE_MATRIX(S)};
+  host_stage hs;
+  int s = host_stage_begin(&hs, c, y, dim, out, 1), es = GSL_SUCCESS;
+  if (!hs.h) GSL_ERROR("gsl_sinterp_eval_fields_many: out of memory", GSL_ENOMEM);
+  if (!s) es = gsl_sinterp_eval_fields_resident(interp, hs.d_y, m, dim, (double *)out[0].d, K);
+  s = host_stage_end(&hs, s, !es);
   HIP_TRY(s, c);
   return es;
 }
@@ -2681,7 +2612,7 @@ static const rbf_state *field_state(const gsl_sinterp *interp, size_t q, int *st
 {
   *status = fields_status(interp);
   if (*status) return NULL;
-  const rbf_state *st = (const rbf_state *)interp->state;
+  const rbf_state *st = rbf_of(interp);
   if (!st->d_w || st->nf == 0) { *status = GSL_EINVAL; gsl_error("gsl_sinterp fields: interpolant not initialised", __FILE__, __LINE__, GSL_EINVAL); return NULL; }
   if (q >= st->nf) { *status = GSL_EBADLEN; gsl_error("gsl_sinterp fields: no such field", __FILE__, __LINE__, GSL_EBADLEN); return NULL; }
   return st;
@@ -2709,7 +2640,7 @@ int gsl_sinterp_field_mean(const gsl_sinterp *interp, size_t q, double *mean)
   int status;
   const rbf_state *st = field_state(interp, q, &status);
   if (!st) return status;
-  if (!is_krige_type(interp->type)) GSL_ERROR("gsl_sinterp_field_mean: kriging interpolants only", GSL_EINVAL);
+  if (!st->krige) GSL_ERROR("gsl_sinterp_field_mean: kriging interpolants only", GSL_EINVAL);
   *mean = st->f_mean[q];
   return GSL_SUCCESS;
 }
@@ -2720,7 +2651,7 @@ int gsl_sinterp_field_poly(const gsl_sinterp *interp, size_t q, gsl_vector *c)
   int status;
   const rbf_state *st = field_state(interp, q, &status);
   if (!st) return status;
-  if (interp->type != &tps_affine_type) GSL_ERROR("gsl_sinterp_field_poly: affine thin-plate-spline interpolants only", GSL_EINVAL);
+  if (!st->affine) GSL_ERROR("gsl_sinterp_field_poly: affine thin-plate-spline interpolants only", GSL_EINVAL);
   if (c->size != st->dim + 1) GSL_ERROR("gsl_sinterp_field_poly: vector length must be dim + 1", GSL_EBADLEN);
   for (size_t a = 0; a <= st->dim; a++) gsl_vector_set(c, a, st->f_poly[q][a]);
   return GSL_SUCCESS;
@@ -2729,8 +2660,8 @@ int gsl_sinterp_field_poly(const gsl_sinterp *interp, size_t q, gsl_vector *c)
 int gsl_sinterp_poly(const gsl_sinterp *interp, gsl_vector *c)
 {
   if (!interp || !c) GSL_ERROR("gsl_sinterp_poly: null argument", GSL_EFAULT);
-  if (interp->type != &tps_affine_type) GSL_ERROR("gsl_sinterp_poly: affine thin-plate-spline interpolants only", GSL_EINVAL);
-  const rbf_state *st = (const rbf_state *)interp->state;
+  if (!desc_of(interp->type)->affine) GSL_ERROR("gsl_sinterp_poly: affine thin-plate-spline interpolants only", GSL_EINVAL);
+  const rbf_state *st = rbf_of(interp);
   if (!st->d_w) GSL_ERROR("gsl_sinterp_poly: interpolant not initialised", GSL_EINVAL);
   if (c->size != st->dim + 1) GSL_ERROR("gsl_sinterp_poly: vector length must be dim + 1", GSL_EBADLEN);
   for (size_t a = 0; a <= st->dim; a++) gsl_vector_set(c, a, st->poly[a]);
@@ -2740,9 +2671,9 @@ int gsl_sinterp_poly(const gsl_sinterp *interp, gsl_vector *c)
 int gsl_sinterp_mean(const gsl_sinterp *interp, double *mean)
 {
   if (!interp || !mean) GSL_ERROR("gsl_sinterp_mean: null argument", GSL_EFAULT);
-  if (!is_krige_type(interp->type)) GSL_ERROR("gsl_sinterp_mean: kriging interpolants only", GSL_EINVAL);
+  if (!desc_of(interp->type)->krige) GSL_ERROR("gsl_sinterp_mean: kriging interpolants only", GSL_EINVAL);
   if (is_local(interp)) GSL_ERROR("gsl_sinterp_mean: not with gsl_sinterp_set_neighbours (every neighbourhood estimates its own mean)", GSL_EUNSUP);
-  const rbf_state *st = (const rbf_state *)interp->state;
+  const rbf_state *st = rbf_of(interp);
   if (!st->d_w) GSL_ERROR("gsl_sinterp_mean: interpolant not initialised", GSL_EINVAL);
   *mean = st->mean;
   return GSL_SUCCESS;
@@ -2753,12 +2684,13 @@ int gsl_sinterp_set_solver(gsl_sinterp *interp, int solver)
   if (!interp) GSL_ERROR("gsl_sinterp_set_solver: null interpolant", GSL_EFAULT);
   if (solver < GSL_SINTERP_SOLVER_DEFAULT || solver > GSL_SINTERP_SOLVER_LU_REFINE)
     GSL_ERROR("gsl_sinterp_set_solver: unknown solver", GSL_EINVAL);
-  if (interp->type == &simplex_type) GSL_ERROR("gsl_sinterp_set_solver: not an RBF interpolant", GSL_EINVAL);
+  const type_desc *d = desc_of(interp->type);
+  if (d->family != FAM_RBF) GSL_ERROR("gsl_sinterp_set_solver: not an RBF interpolant", GSL_EINVAL);
   /* kriging and the affine thin-plate spline solve saddle systems on routes of their own (7 / 8, 9 / 10): accepting a
      solver here and ignoring it at init would be a silent no-op */
-  if ((is_krige_type(interp->type) || interp->type == &tps_affine_type) && solver != GSL_SINTERP_SOLVER_DEFAULT)
+  if ((d->krige || d->affine) && solver != GSL_SINTERP_SOLVER_DEFAULT)
     GSL_ERROR("gsl_sinterp_set_solver: kriging / affine thin-plate-spline interpolants choose their own route", GSL_EINVAL);
-  if (interp->type == &tps_type && (solver == GSL_SINTERP_SOLVER_CHOLESKY2 || solver == GSL_SINTERP_SOLVER_PCHOLESKY))
+  if (d->kind == GSL_SINTERP_RBF_TPS && (solver == GSL_SINTERP_SOLVER_CHOLESKY2 || solver == GSL_SINTERP_SOLVER_PCHOLESKY))
     GSL_ERROR("gsl_sinterp_set_solver: the thin-plate-spline matrix is indefinite (zero diagonal): no Cholesky-type solver", GSL_EINVAL);
   interp->solver = solver;
   return GSL_SUCCESS;
@@ -2767,7 +2699,7 @@ int gsl_sinterp_set_solver(gsl_sinterp *interp, int solver)
 int gsl_sinterp_set_rcond(gsl_sinterp *interp, int want)
 {
   if (!interp) GSL_ERROR("gsl_sinterp_set_rcond: null interpolant", GSL_EFAULT);
-  if (want && (is_krige_type(interp->type) || interp->type == &tps_affine_type))
+  if (want && (desc_of(interp->type)->krige || desc_of(interp->type)->affine))
     GSL_ERROR("gsl_sinterp_set_rcond: no condition estimate on the kriging / affine thin-plate-spline routes", GSL_EINVAL);
   interp->want_rcond = want != 0;
   return GSL_SUCCESS;
@@ -2786,9 +2718,8 @@ int gsl_sinterp_route(const gsl_sinterp *interp) { return interp ? interp->route
 int gsl_sinterp_set_triangulation(gsl_sinterp *interp, const int *triangles, const int *neighbours, size_t n_triangles)
 {
   if (!interp || !triangles) GSL_ERROR("gsl_sinterp_set_triangulation: null argument", GSL_EFAULT);
-  if (interp->type != &mesh_type && interp->type != &natural_mesh_type && interp->type != &cubic_mesh_type)
-    GSL_ERROR("gsl_sinterp_set_triangulation: imported-triangulation interpolants only", GSL_EINVAL);
-  mesh_state *st = (mesh_state *)interp->state;
+  mesh_state *st = mesh_of(interp);
+  if (!st || !desc_of(interp->type)->imported) GSL_ERROR("gsl_sinterp_set_triangulation: imported-triangulation interpolants only", GSL_EINVAL);
   const size_t w = st->dim + 1;                          /* ids per simplex */
   if (n_triangles < 1 || n_triangles > (size_t)INT_MAX / w) GSL_ERROR("gsl_sinterp_set_triangulation: bad triangle count", GSL_EINVAL);
   int *t = (int *)malloc(w * n_triangles * sizeof(int)), *nb = neighbours ? (int *)malloc(w * n_triangles * sizeof(int)) : NULL;
@@ -2804,8 +2735,8 @@ int gsl_sinterp_set_triangulation(gsl_sinterp *interp, const int *triangles, con
 int gsl_sinterp_set_gradients(gsl_sinterp *interp, const gsl_matrix *gradients)
 {
   if (!interp) GSL_ERROR("gsl_sinterp_set_gradients: null interpolant", GSL_EFAULT);
-  if (!is_cubic_type(interp->type)) GSL_ERROR("gsl_sinterp_set_gradients: Clough-Tocher interpolants only", GSL_EINVAL);
-  mesh_state *st = (mesh_state *)interp->state;
+  if (!mesh_method(interp, MESH_CUBIC)) GSL_ERROR("gsl_sinterp_set_gradients: Clough-Tocher interpolants only", GSL_EINVAL);
+  mesh_state *st = mesh_of(interp);
   if (gradients && (gradients->size1 != st->n || gradients->size2 != 2))
     GSL_ERROR("gsl_sinterp_set_gradients: gradients must be size x 2", GSL_EBADLEN);
   gsl_matrix *copy = NULL;
@@ -2823,10 +2754,10 @@ int gsl_sinterp_set_gradients(gsl_sinterp *interp, const gsl_matrix *gradients)
 int gsl_sinterp_set_gradient_options(gsl_sinterp *interp, double rtol, size_t maxiter)
 {
   if (!interp) GSL_ERROR("gsl_sinterp_set_gradient_options: null interpolant", GSL_EFAULT);
-  if (!is_cubic_type(interp->type)) GSL_ERROR("gsl_sinterp_set_gradient_options: Clough-Tocher interpolants only", GSL_EINVAL);
+  if (!mesh_method(interp, MESH_CUBIC)) GSL_ERROR("gsl_sinterp_set_gradient_options: Clough-Tocher interpolants only", GSL_EINVAL);
   if (!(rtol > 0.0 && rtol < 1.0) || maxiter < 1 || maxiter > (size_t)INT_MAX)
     GSL_ERROR("gsl_sinterp_set_gradient_options: need 0 < rtol < 1 and maxiter >= 1", GSL_EINVAL);
-  mesh_state *st = (mesh_state *)interp->state;
+  mesh_state *st = mesh_of(interp);
   st->g_rtol = rtol; st->g_maxiter = maxiter;
   return GSL_SUCCESS;
 }
@@ -2834,8 +2765,8 @@ int gsl_sinterp_set_gradient_options(gsl_sinterp *interp, double rtol, size_t ma
 int gsl_sinterp_get_gradients(const gsl_sinterp *interp, gsl_matrix *gradients, size_t *iterations, double *residual)
 {
   if (!interp) GSL_ERROR("gsl_sinterp_get_gradients: null interpolant", GSL_EFAULT);
-  if (!is_cubic_type(interp->type)) GSL_ERROR("gsl_sinterp_get_gradients: Clough-Tocher interpolants only", GSL_EINVAL);
-  const mesh_state *st = (const mesh_state *)interp->state;
+  if (!mesh_method(interp, MESH_CUBIC)) GSL_ERROR("gsl_sinterp_get_gradients: Clough-Tocher interpolants only", GSL_EINVAL);
+  const mesh_state *st = mesh_of(interp);
   if (!st->dev || !st->g) GSL_ERROR("gsl_sinterp_get_gradients: interpolant not initialised", GSL_EINVAL);
   if (gradients && (gradients->size1 != st->n || gradients->size2 != 2))
     GSL_ERROR("gsl_sinterp_get_gradients: gradients must be size x 2", GSL_EBADLEN);
@@ -2910,9 +2841,9 @@ double gsl_sinterp_eval(const gsl_sinterp *interp, const gsl_vector *y)
 int gsl_sinterp_get_weights(const gsl_sinterp *interp, gsl_vector *w)
 {
   if (!interp || !w) GSL_ERROR("gsl_sinterp_get_weights: null argument", GSL_EFAULT);
-  if (interp->type == &simplex_type) GSL_ERROR("gsl_sinterp_get_weights: not an RBF interpolant", GSL_EINVAL);
+  const rbf_state *st = rbf_of(interp);
+  if (!st) GSL_ERROR("gsl_sinterp_get_weights: not an RBF interpolant", GSL_EINVAL);
   if (is_local(interp)) GSL_ERROR("gsl_sinterp_get_weights: not with gsl_sinterp_set_neighbours (no global weight vector exists)", GSL_EUNSUP);
-  const rbf_state *st = (const rbf_state *)interp->state;
   if (!st->d_w) GSL_ERROR("gsl_sinterp_get_weights: interpolant not initialised", GSL_EINVAL);
   if (w->size != st->n) GSL_ERROR("gsl_sinterp_get_weights: wrong length", GSL_EBADLEN);
   double *h = (double *)malloc(st->n * sizeof(double));
@@ -2936,15 +2867,11 @@ void gsl_sinterp_free(gsl_sinterp *interp)
 /* ======================================================================== */
 static gsl_sinterp_hip_ctx *interp_ctx0(const gsl_sinterp *interp)
 {
-  if (interp->type == &simplex_type) {
-    const simplex_state *st = (const simplex_state *)interp->state;
-    return st->dev ? st->dev->ctx : NULL;
-  }
-  if (is_mesh2_type(interp->type)) {
-    const mesh_state *st = (const mesh_state *)interp->state;
-    return st->dev ? st->dev->ctx : NULL;
-  }
-  return ((const rbf_state *)interp->state)->ctx;
+  const simplex_state *ts = tree_of(interp);
+  const mesh_state *ms = mesh_of(interp);
+  if (ts) return ts->dev ? ts->dev->ctx : NULL;
+  if (ms) return ms->dev ? ms->dev->ctx : NULL;
+  return rbf_of(interp)->ctx;
 }
 
 int gsl_sinterp_eval_grid(const gsl_sinterp *interp, const gsl_vector *min, const gsl_vector *max, gsl_matrix *grid)
@@ -2980,8 +2907,8 @@ int gsl_sinterp_eval_grid(const gsl_sinterp *interp, const gsl_vector *min, cons
   gsl_sinterp_hip_free(c, d_y); gsl_sinterp_hip_free(c, d_s);
   free(h_s);
   HIP_TRY(st, c);
-  if (interp->type == &simplex_type && n_nan) GSL_ERROR("gsl_sinterp_eval_grid: grid node(s) outside the caging simplex", GSL_EDOM);
-  if (is_mesh2_type(interp->type) && n_nan) GSL_ERROR("gsl_sinterp_eval_grid: grid node(s) outside the triangulation", GSL_EDOM);
+  if (tree_of(interp) && n_nan) GSL_ERROR("gsl_sinterp_eval_grid: grid node(s) outside the caging simplex", GSL_EDOM);
+  if (mesh_of(interp) && n_nan) GSL_ERROR("gsl_sinterp_eval_grid: grid node(s) outside the triangulation", GSL_EDOM);
   return GSL_SUCCESS;
 }
 
@@ -3009,34 +2936,22 @@ int gsl_sinterp_fprintf_grid(FILE *stream, const gsl_vector *min, const gsl_vect
 /* ======================================================================== */
 static const char INTERP_MAGIC[8] = {'G', 'S', 'L', 'S', 'I', 'N', 'T', '1'};
 
-static int type_id(const gsl_sinterp_type *T)
+/* 1 when the whole header went out */
+static int header_fwrite(FILE *stream, const gsl_sinterp *interp, double eps, int64_t flags)
 {
-  /* 7 .. 11: the Matern / inverse multiquadric types; the ids and the GSLSINT1 layout of the older types are unchanged */
-  if (T == &matern32_type) return 7;
-  if (T == &matern52_type) return 8;
-  if (T == &imq_type) return 9;
-  if (T == &krige_matern32_type) return 10;
-  if (T == &krige_matern52_type) return 11;
-  if (T == &natural_mesh_type) return 12;                 /* 12 / 13: natural neighbours, with the payload of type 6 */
-  if (T == &natural_simplex_type) return 13;
-  if (T == &cubic_mesh_type) return 14;                   /* 14 / 15: Clough-Tocher, the payload of type 6 + the 2 N gradients */
-  if (T == &cubic_simplex_type) return 15;
-  return T == &gauss_type ? 0 : (T == &tps_type ? 1 : (T == &wendland_type ? 3 : (T == &krige_type ? 4 : (T == &tps_affine_type ? 5 : (T == &mesh_type ? 6 : 2)))));
+  const uint64_t head[3] = {(uint64_t)desc_of(interp->type)->id, (uint64_t)interp->dim, (uint64_t)interp->size};
+  return fwrite(INTERP_MAGIC, 1, 8, stream) == 8 && fwrite(head, sizeof head[0], 3, stream) == 3 &&
+         fwrite(&eps, sizeof eps, 1, stream) == 1 && fwrite(&flags, sizeof flags, 1, stream) == 1;
 }
 
 int gsl_sinterp_fwrite(FILE *stream, const gsl_sinterp *interp)
 {
   if (!stream || !interp) GSL_ERROR("gsl_sinterp_fwrite: null argument", GSL_EFAULT);
   if (is_local(interp)) GSL_ERROR("gsl_sinterp_fwrite: not with gsl_sinterp_set_neighbours (checkpoints hold a solved global model)", GSL_EUNSUP);
-  const uint64_t head[3] = {(uint64_t)type_id(interp->type), (uint64_t)interp->dim, (uint64_t)interp->size};
-  if (interp->type == &simplex_type) {
-    const simplex_state *st = (const simplex_state *)interp->state;
+  if (tree_of(interp)) {
+    const simplex_state *st = tree_of(interp);
     if (!st->dev || !st->tree || !st->x || !st->f) GSL_ERROR("gsl_sinterp_fwrite: interpolant not initialised", GSL_EINVAL);
-    const double eps = 0.0;
-    const int64_t flags = interp->init_flags;
-    if (fwrite(INTERP_MAGIC, 1, 8, stream) != 8 || fwrite(head, sizeof head[0], 3, stream) != 3 ||
-        fwrite(&eps, sizeof eps, 1, stream) != 1 || fwrite(&flags, sizeof flags, 1, stream) != 1)
-      GSL_ERROR("fwrite failed", GSL_EFAILED);
+    if (!header_fwrite(stream, interp, 0.0, interp->init_flags)) GSL_ERROR("fwrite failed", GSL_EFAILED);
     int s = simplex_tree_fwrite(stream, st->tree);
     if (s) return s;
     for (size_t i = 0; i < st->n; i++) {
@@ -3045,21 +2960,17 @@ int gsl_sinterp_fwrite(FILE *stream, const gsl_sinterp *interp)
     }
     return GSL_SUCCESS;
   }
-  if (is_mesh_state_type(interp->type)) {
-    const mesh_state *st = (const mesh_state *)interp->state;
+  if (mesh_of(interp)) {
+    const mesh_state *st = mesh_of(interp);
     if (!st->dev || !st->mesh || !st->x || !st->f) GSL_ERROR("gsl_sinterp_fwrite: interpolant not initialised", GSL_EINVAL);
-    const double eps = 0.0;
-    const int64_t flags = 0;
-    if (fwrite(INTERP_MAGIC, 1, 8, stream) != 8 || fwrite(head, sizeof head[0], 3, stream) != 3 ||
-        fwrite(&eps, sizeof eps, 1, stream) != 1 || fwrite(&flags, sizeof flags, 1, stream) != 1)
-      GSL_ERROR("fwrite failed", GSL_EFAILED);
+    if (!header_fwrite(stream, interp, 0.0, 0)) GSL_ERROR("fwrite failed", GSL_EFAILED);
     int s = simplex_mesh_fwrite(stream, st->mesh);
     if (s) return s;
     for (size_t i = 0; i < st->n; i++) {
       const double fi = gsl_vector_get(st->f, i);
       if (fwrite(&fi, sizeof fi, 1, stream) != 1) GSL_ERROR("fwrite failed", GSL_EFAILED);
     }
-    if (is_cubic_type(interp->type)) {
+    if (mesh_method(interp, MESH_CUBIC)) {
       if (!st->g) GSL_ERROR("gsl_sinterp_fwrite: interpolant not initialised", GSL_EINVAL);
       for (size_t i = 0; i < st->n; i++) {
         const double gi[2] = {gsl_matrix_get(st->g, i, 0), gsl_matrix_get(st->g, i, 1)};
@@ -3068,7 +2979,7 @@ int gsl_sinterp_fwrite(FILE *stream, const gsl_sinterp *interp)
     }
     return GSL_SUCCESS;
   }
-  const rbf_state *st = (const rbf_state *)interp->state;
+  const rbf_state *st = rbf_of(interp);
   if (!st->d_w) GSL_ERROR("gsl_sinterp_fwrite: interpolant not initialised", GSL_EINVAL);
   if (st->nf > 1) GSL_ERROR("gsl_sinterp_fwrite: the GSLSINT1 format holds one weight vector (interpolant with several fields)", GSL_EUNSUP);
   const size_t cnt = st->n * (st->dim + 1);
@@ -3077,9 +2988,7 @@ int gsl_sinterp_fwrite(FILE *stream, const gsl_sinterp *interp)
   int s = gsl_sinterp_hip_d2h(st->ctx, h, st->d_x, cnt * sizeof(double));      /* the model buffer: [centres | weights] */
   int64_t flags = 0;
   if (st->krige) memcpy(&flags, &st->mean, sizeof flags);                       /* kriging: the word carries the mean's bits */
-  if (!s && (fwrite(INTERP_MAGIC, 1, 8, stream) != 8 || fwrite(head, sizeof head[0], 3, stream) != 3 ||
-             fwrite(&st->eps, sizeof st->eps, 1, stream) != 1 || fwrite(&flags, sizeof flags, 1, stream) != 1 ||
-             fwrite(h, sizeof(double), cnt, stream) != cnt ||
+  if (!s && (!header_fwrite(stream, interp, st->eps, flags) || fwrite(h, sizeof(double), cnt, stream) != cnt ||
              (st->affine && fwrite(st->poly, sizeof(double), 4, stream) != 4))) {      /* affine tail: c_0 .. c_3 behind the weights */
     free(h);
     GSL_ERROR("fwrite failed", GSL_EFAILED);
@@ -3092,7 +3001,7 @@ int gsl_sinterp_fwrite(FILE *stream, const gsl_sinterp *interp)
 int gsl_sinterp_fread(FILE *stream, gsl_sinterp *interp)
 {
   if (!stream || !interp) GSL_ERROR("gsl_sinterp_fread: null argument", GSL_EFAULT);
-  if (is_krige_type(interp->type) && interp->neighbours > 0)
+  if (desc_of(interp->type)->krige && interp->neighbours > 0)
     GSL_ERROR("gsl_sinterp_fread: not with gsl_sinterp_set_neighbours (checkpoints hold a solved global model)", GSL_EUNSUP);
   char magic[8];
   uint64_t head[3];
@@ -3103,10 +3012,10 @@ int gsl_sinterp_fread(FILE *stream, gsl_sinterp *interp)
   if (fread(head, sizeof head[0], 3, stream) != 3 || fread(&eps, sizeof eps, 1, stream) != 1 ||
       fread(&flags, sizeof flags, 1, stream) != 1)
     GSL_ERROR("fread failed", GSL_EFAILED);
-  if (head[0] != (uint64_t)type_id(interp->type) || head[1] != interp->dim || head[2] != interp->size)
+  if (head[0] != (uint64_t)desc_of(interp->type)->id || head[1] != interp->dim || head[2] != interp->size)
     GSL_ERROR("gsl_sinterp_fread: checkpoint does not match the type / dim / size of the interpolant", GSL_EBADLEN);
-  if (interp->type == &simplex_type) {
-    simplex_state *st = (simplex_state *)interp->state;
+  if (tree_of(interp)) {
+    simplex_state *st = tree_of(interp);
     simplex_tree *tree = simplex_tree_fread(stream);
     if (!tree) return GSL_EFAILED;
     if ((size_t)tree->n_points != st->n) { simplex_tree_free(tree); GSL_ERROR("gsl_sinterp_fread: tree / size mismatch", GSL_EBADLEN); }
@@ -3125,8 +3034,8 @@ int gsl_sinterp_fread(FILE *stream, gsl_sinterp *interp)
     interp->init_flags = (int)flags;
     return simplex_mirror(interp, st);                  /* upload + pack + bind: no triangulation */
   }
-  if (is_mesh_state_type(interp->type)) {
-    mesh_state *st = (mesh_state *)interp->state;
+  if (mesh_of(interp)) {
+    mesh_state *st = mesh_of(interp);
     simplex_mesh *mesh = simplex_mesh_fread(stream);
     if (!mesh) return GSL_EFAILED;
     if (simplex_mesh_n_points(mesh) != st->n || simplex_mesh_dim(mesh) != st->dim) {
@@ -3145,7 +3054,7 @@ int gsl_sinterp_fread(FILE *stream, gsl_sinterp *interp)
       }
     }
     gsl_matrix *g = NULL;                                /* Clough-Tocher: the gradients follow the response */
-    if (ok && is_cubic_type(interp->type)) {
+    if (ok && mesh_method(interp, MESH_CUBIC)) {
       g = gsl_matrix_alloc(st->n, 2);
       ok = g != NULL;
       for (size_t i = 0; ok && i < st->n; i++) ok = fread(g->data + i * g->tda, sizeof(double), 2, stream) == 2;
@@ -3158,15 +3067,12 @@ int gsl_sinterp_fread(FILE *stream, gsl_sinterp *interp)
     simplex_mesh_device_free(st->dev); st->dev = NULL;
     simplex_mesh_free(st->mesh); gsl_matrix_free(st->x); gsl_vector_free(st->f);
     st->mesh = mesh; st->x = x; st->f = f;
-    if (is_cubic_type(interp->type)) {                   /* the stored gradients are bound: nothing is estimated again */
-      const int s = cubic_type_mirror(interp, st, g);
-      gsl_matrix_free(g);
-      return s;
-    }
-    /* upload + pack + bind: nothing is re-imported */
-    return is_natural_type(interp->type) ? natural_type_mirror(interp, st) : mesh_type_mirror(interp, st);
+    /* upload + pack + bind: nothing is re-imported; the stored gradients are bound: nothing is estimated again */
+    const int s = mesh_type_mirror(interp, st, g);
+    if (g) gsl_matrix_free(g);
+    return s;
   }
-  rbf_state *st = (rbf_state *)interp->state;
+  rbf_state *st = rbf_of(interp);
   const size_t cnt = st->n * (st->dim + 1);
   double *h = (double *)malloc(cnt * sizeof(double));
   if (!h) GSL_ERROR("gsl_sinterp_fread: out of memory", GSL_ENOMEM);
