@@ -290,6 +290,14 @@ SIGNATURES = {
     "gsl_sinterp_hip_local_pack": (_i, [_vp, _vp, _sz, _i, _sz, _vp, C.c_uint64]),
     "gsl_sinterp_hip_local_pack_count": (C.c_uint64, [_vp]),
     "gsl_sinterp_set_neighbours": (_i, [C.POINTER(gsl_sinterp), _sz]),
+    "gsl_sinterp_hip_shepard_fit": (_i, [_vp, _vp, _sz, _i, _sz, _vp, _sz, _sz, _vp, _vp, _vp, C.POINTER(C.c_size_t)]),
+    "gsl_sinterp_hip_shepard_eval": (_i, [_vp, _vp, _sz, _i, _sz, _vp, _vp, _vp, _vp, _vp, _sz, _sz, _vp, _vp, _sz, _vp,
+                                          C.POINTER(C.c_size_t), C.c_uint64]),
+    "gsl_sinterp_hip_shepard_pack_count": (C.c_uint64, [_vp]),
+    "gsl_sinterp_hip_shepard_fit_count": (C.c_uint64, [_vp]),
+    "gsl_sinterp_set_shepard": (_i, [C.POINTER(gsl_sinterp), _sz, _sz]),
+    "gsl_sinterp_shepard_stats": (_i, [C.POINTER(gsl_sinterp), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), _pd]),
+    "gsl_sinterp_shepard_ctx": (_vp, [C.POINTER(gsl_sinterp)]),
     "gsl_sinterp_eval_local_many": (_i, [C.POINTER(gsl_sinterp), _pm, _pv, _pv, _pi]),
     "gsl_sinterp_hip_score_reduce": (_i, [_vp, _sz, _vp, _sz, _vp, _vp, _vp, _vp, _d, _vp]),
     "gsl_sinterp_fit_alloc": (_vp, [C.POINTER(gsl_sinterp), _pm, _pv]),
@@ -344,7 +352,7 @@ SIGNATURES = {
     "gsl_rng_get": (C.c_ulong, [_vp]),
     "gsl_rng_uniform_int": (C.c_ulong, [_vp, C.c_ulong]),
 }
-DATA_SYMBOLS = ["gsl_sinterp_kriging", "gsl_sinterp_linear_mesh", "gsl_sinterp_natural_mesh", "gsl_sinterp_natural_simplex", "gsl_sinterp_cubic_mesh", "gsl_sinterp_cubic_simplex", "gsl_sinterp_rbf_gaussian", "gsl_sinterp_rbf_tps", "gsl_sinterp_rbf_tps_affine", "gsl_sinterp_rbf_wendland", "gsl_sinterp_linear_simplex",
+DATA_SYMBOLS = ["gsl_sinterp_kriging", "gsl_sinterp_linear_mesh", "gsl_sinterp_natural_mesh", "gsl_sinterp_natural_simplex", "gsl_sinterp_cubic_mesh", "gsl_sinterp_cubic_simplex", "gsl_sinterp_shepard", "gsl_sinterp_rbf_gaussian", "gsl_sinterp_rbf_tps", "gsl_sinterp_rbf_tps_affine", "gsl_sinterp_rbf_wendland", "gsl_sinterp_linear_simplex",
                 "gsl_sinterp_rbf_matern32", "gsl_sinterp_rbf_matern52", "gsl_sinterp_rbf_imq", "gsl_sinterp_kriging_matern32", "gsl_sinterp_kriging_matern52",
                 "gsl_rng_mt19937", "gsl_rng_default"]
 
@@ -698,6 +706,28 @@ class HipContext:
     def local_pack_count(self):
         """how often this context has binned a set of centres for knn / local_krige"""
         return lib().gsl_sinterp_hip_local_pack_count(self._h)
+
+    def shepard_fit(self, d_x, n, dim, xtda, d_f, nq, nw, d_rq, d_rw, d_coef):
+        """modified Shepard: radii and the n x nc nodal coefficients; synchronises; returns (status, (linear fallbacks,
+        constant fallbacks, coincident nodes)): GSL_EDOM when a node has a coincident site"""
+        counts = (C.c_size_t * 3)(0, 0, 0)
+        st = lib().gsl_sinterp_hip_shepard_fit(self._h, d_x, n, dim, xtda, d_f, nq, nw, d_rq, d_rw, d_coef, counts)
+        return st, tuple(int(v) for v in counts)
+
+    def shepard_eval(self, d_x, n, dim, xtda, d_f, d_rq, d_rw, d_coef, d_y, m, ytda, d_s=None, d_g=None, gtda=0, d_leaf=None, model_id=0):
+        """modified Shepard sweep; each output optional; synchronises; returns (status, outside): GSL_EDOM with `outside`
+        targets NaN / -1 where no node's radius covers the target"""
+        outside = C.c_size_t(0)
+        st = lib().gsl_sinterp_hip_shepard_eval(self._h, d_x, n, dim, xtda, d_f, d_rq, d_rw, d_coef, d_y, m, ytda, d_s, d_g, gtda, d_leaf,
+                                                C.byref(outside), model_id)
+        return st, outside.value
+
+    def shepard_pack_count(self):
+        """how often this context has packed a modified Shepard model for evaluation"""
+        return lib().gsl_sinterp_hip_shepard_pack_count(self._h)
+
+    def shepard_fit_count(self):
+        return lib().gsl_sinterp_hip_shepard_fit_count(self._h)
 
     @staticmethod
     def chol_inv_diag_work(n, chunk):
@@ -1138,8 +1168,10 @@ class Sinterp:
              "matern32": "gsl_sinterp_rbf_matern32", "matern52": "gsl_sinterp_rbf_matern52", "imq": "gsl_sinterp_rbf_imq",
              "kriging_matern32": "gsl_sinterp_kriging_matern32", "kriging_matern52": "gsl_sinterp_kriging_matern52"}
 
+    MORE_TYPES = {"shepard": "gsl_sinterp_shepard"}    # consulted after TYPES
+
     def __init__(self, kind, dim, size, device=0):
-        self._p = lib().gsl_sinterp_alloc(_ptr(self.TYPES[kind]), dim, size)
+        self._p = lib().gsl_sinterp_alloc(_ptr(self.TYPES[kind] if kind in self.TYPES else self.MORE_TYPES[kind]), dim, size)
         if not self._p:
             raise GslError(GSL_EINVAL, "gsl_sinterp_alloc")
         lib().gsl_sinterp_set_device(self._p, device)
@@ -1189,6 +1221,21 @@ class Sinterp:
                                                C.byref(as_vector(v)) if want_var else None,
                                                idx.ctypes.data_as(_pi) if want_idx else None)
         return st, s, v, idx
+
+    def set_shepard(self, nq=0, nw=0):
+        """modified Shepard, before init: neighbours behind the fit radius and the weight radius; 0 = Renka's defaults"""
+        return lib().gsl_sinterp_set_shepard(self._p, int(nq), int(nw))
+
+    def shepard_stats(self):
+        """(status, linear fallbacks, constant fallbacks, largest radius of influence) after init"""
+        nl, ncst, rw = C.c_size_t(0), C.c_size_t(0), C.c_double(float("nan"))
+        st = lib().gsl_sinterp_shepard_stats(self._p, C.byref(nl), C.byref(ncst), C.byref(rw))
+        return st, nl.value, ncst.value, rw.value
+
+    def shepard_counters(self):
+        """(fits, packs) of the interpolant's device context; (0, 0) before the first init"""
+        h = lib().gsl_sinterp_shepard_ctx(self._p)
+        return int(lib().gsl_sinterp_hip_shepard_fit_count(h)), int(lib().gsl_sinterp_hip_shepard_pack_count(h))
 
     def set_loo(self, want=True):
         """positive definite RBF types and kriging: the next init computes the leave-one-out residuals and variances"""
@@ -1308,7 +1355,7 @@ class Sinterp:
 
     def get_gradients(self):
         """(status, g [size x 2], iterations, residual) after init"""
-        g = np.empty((self._p.contents.size, 2), dtype=np.float64)
+        g = np.empty((self._p.contents.size, self._p.contents.dim if self.name() == "modified-quadratic-shepard" else 2), dtype=np.float64)
         it, res = C.c_size_t(0), C.c_double(0.0)
         st = lib().gsl_sinterp_get_gradients(self._p, C.byref(as_matrix(g)), C.byref(it), C.byref(res))
         return st, g, it.value, res.value

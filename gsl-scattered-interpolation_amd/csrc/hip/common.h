@@ -88,6 +88,14 @@ struct gsl_sinterp_hip_ctx {
   int jump_nodes, jump_G;
   int excl_depth;           /* nesting of sinterp_exclusive_begin/end */
   char err[512];
+  /* modified Shepard (shepard.hip): the nodes binned on the grid of local.hip and gathered into cell order, rows ascending
+     inside a cell, [256 B head | cell offsets | cell boxes | rows | records]; keyed like d_local (x = the centres, w = the
+     coefficients), shep_g cells per axis; shep_packs / shep_fits count the packs and the fits of this context */
+  void *d_shep;
+  size_t shep_bytes;
+  CentKey shep_key;
+  int shep_g;
+  unsigned long long shep_packs, shep_fits;
 };
 
 /* Graph helpers (shim.hip).  A key is up to GRAPH_KEY_WORDS - 1 argument words (unused words 0); the helpers append
@@ -293,5 +301,6 @@ int sinterp_bbox_keys(gsl_sinterp_hip_ctx *ctx, const double *d_p, size_t n, siz
 int sinterp_centbuf(gsl_sinterp_hip_ctx *ctx, size_t bytes, void **out);
 int sinterp_centbuf_fields(gsl_sinterp_hip_ctx *ctx, size_t bytes, void **out);
 int sinterp_localbuf(gsl_sinterp_hip_ctx *ctx, size_t bytes, void **out);
+int sinterp_shepbuf(gsl_sinterp_hip_ctx *ctx, size_t bytes, void **out);
 
 #endif

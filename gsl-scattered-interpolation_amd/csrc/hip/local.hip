@@ -38,20 +38,10 @@
 #include "chol_potrf.h"
 #include "rbf_phi.h"
 
+#include "local_grid.h"           /* LkGrid, lk_axis_cell, lk_cell, lk_grid_size, LK_SORT_MIN: shared with shepard.hip */
+
 #define LK_HEAD 256               /* bytes: LkGrid | box keys at 64 | failure counter at 128 */
 #define LK_NONE 0x7fffffff        /* index of an empty list entry: (inf, LK_NONE) is above every real key */
-#define LK_SORT_MIN 4096          /* batches of at least this many targets are processed in cell order */
-
-struct LkGrid { double lo[3], hi[3]; };
-
-/* cell index of coordinate v on an axis of g cells over [lo, hi]; non-decreasing in v; NaN and a degenerate axis -> 0 */
-__host__ __device__ __forceinline__ int lk_axis_cell(double v, double lo, double hi, int g)
-{
-  const double f = hi > lo ? (v - lo) / (hi - lo) : 0.0;
-  const double t = f * (double)g;
-  if (!(t > 0.0)) return 0;
-  return t >= (double)(g - 1) ? g - 1 : (int)t;
-}
 
 __global__ void lk_head_kernel(const unsigned long long *__restrict__ box, int dim, LkGrid *__restrict__ out)
 {
@@ -64,15 +54,6 @@ __global__ void lk_head_kernel(const unsigned long long *__restrict__ box, int d
     v = __longlong_as_double((long long)u);
   }
   if (threadIdx.x & 1) out->hi[c] = v; else out->lo[c] = v;
-}
-
-template <int DIM>
-__device__ __forceinline__ size_t lk_cell(const LkGrid &G, int g, const double (&v)[DIM])
-{
-  size_t cell = 0;
-#pragma unroll
-  for (int c = DIM - 1; c >= 0; c--) cell = cell * (size_t)g + (size_t)lk_axis_cell(v[c], G.lo[c], G.hi[c], g);
-  return cell;
 }
 
 /* one atomic per centre: the returned count is the centre's slot inside its cell */
@@ -370,14 +351,6 @@ struct lk_model {
   unsigned *n_failed;
   int g;
 };
-
-static int lk_grid_size(size_t n, int dim)
-{
-  const double cells = (double)n / 8.0;            /* ~8 centres per cell: a 3^dim block holds k = 64 in 2-D at the first ring */
-  int g = (int)floor(pow(cells < 1.0 ? 1.0 : cells, 1.0 / dim));
-  const int gmax = dim == 1 ? (1 << 20) : (dim == 2 ? 1024 : 100);
-  return g < 1 ? 1 : (g > gmax ? gmax : g);
-}
 
 /* the packed centres of the local route, cached per model like the culled sweep's (cull_pack in rbf.hip): reused when the
    caller vouches for the model (model_id != 0) and every word of the key matches */

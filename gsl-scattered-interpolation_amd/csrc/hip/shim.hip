@@ -70,6 +70,7 @@ extern "C" void gsl_sinterp_hip_ctx_destroy(gsl_sinterp_hip_ctx *ctx)
   if (ctx->d_cent) (void)hipFree(ctx->d_cent);
   if (ctx->d_cent_f) (void)hipFree(ctx->d_cent_f);
   if (ctx->d_local) (void)hipFree(ctx->d_local);
+  if (ctx->d_shep) (void)hipFree(ctx->d_shep);
   if (ctx->d_walk) (void)hipFree(ctx->d_walk);
   for (int i = 0; i < 4; i++) if (ctx->side_ev[i]) (void)hipEventDestroy(ctx->side_ev[i]);
   if (ctx->side_stream) (void)hipStreamDestroy(ctx->side_stream);
@@ -340,6 +341,7 @@ int sinterp_walkbuf(gsl_sinterp_hip_ctx *ctx, size_t bytes, void **out) { return
 int sinterp_centbuf(gsl_sinterp_hip_ctx *ctx, size_t bytes, void **out) { return grow_buf(ctx, &ctx->d_cent, &ctx->cent_bytes, bytes, out); }
 int sinterp_centbuf_fields(gsl_sinterp_hip_ctx *ctx, size_t bytes, void **out) { return grow_buf(ctx, &ctx->d_cent_f, &ctx->cent_f_bytes, bytes, out); }
 int sinterp_localbuf(gsl_sinterp_hip_ctx *ctx, size_t bytes, void **out) { return grow_buf(ctx, &ctx->d_local, &ctx->local_bytes, bytes, out); }
+int sinterp_shepbuf(gsl_sinterp_hip_ctx *ctx, size_t bytes, void **out) { return grow_buf(ctx, &ctx->d_shep, &ctx->shep_bytes, bytes, out); }
 
 /* u(k) = (splitmix64(seed ^ k) >> 11) * 2^-53, out[i] = offset + span * u(first + i)
    (same generator as oracle/oracle_synth.c so CPU and GPU see

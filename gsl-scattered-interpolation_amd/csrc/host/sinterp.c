@@ -1183,7 +1183,7 @@ int simplex_mesh_device_eval_cubic_many(simplex_mesh_device *dev, const gsl_matr
 /* ======================================================================== */
 /* what a type is: one row of type_table (below, with the generic entries)    */
 /* ======================================================================== */
-enum { FAM_RBF, FAM_TREE, FAM_MESH };                   /* the struct behind gsl_sinterp.state: rbf_state, simplex_state, mesh_state */
+enum { FAM_RBF, FAM_TREE, FAM_MESH, FAM_SHEPARD };      /* the struct behind gsl_sinterp.state: rbf_state, simplex_state, mesh_state, shepard_state */
 enum { MESH_LINEAR, MESH_NATURAL, MESH_CUBIC };
 typedef struct {
   gsl_sinterp_type pub;       /* first member: the extern gsl_sinterp_* pointers point here */
@@ -1193,7 +1193,7 @@ typedef struct {
                                  definite kernel (Cholesky routes 1 / 7, hence leave-one-out and the fit) */
   int method, imported;       /* FAM_MESH: the interpolant on the triangles; the mesh is imported (gsl_sinterp_set_triangulation)
                                  or exported from a host-built tree */
-  const char *noun;           /* natural and cubic types: what their refusals call them */
+  const char *noun;           /* natural, cubic and Shepard types: what their refusals call them */
 } type_desc;
 static const type_desc *desc_of(const gsl_sinterp_type *T);     /* the row of T, NULL for a type that is not in the table */
 
@@ -1861,6 +1861,139 @@ static int mesh_type_eval_resident(const gsl_sinterp *interp, const double *d_y,
 }
 
 /* ======================================================================== */
+/* modified quadratic Shepard (csrc/hip/shepard.hip; DESIGN.md 4, "Modified    */
+/* Shepard"): the fit at init, one sweep per evaluation, one device           */
+/* ======================================================================== */
+typedef struct {
+  size_t n, dim, nc;         /* nc = 5 (dim 2) or 9 (dim 3) coefficients per node */
+  size_t nq_set, nw_set;     /* gsl_sinterp_set_shepard; 0 = the default of the dimension */
+  size_t nq, nw;             /* of the model held */
+  gsl_sinterp_hip_ctx *ctx;
+  double *d_model;           /* one buffer: [x n dim | f n | Rq n | Rw n | c n nc] */
+  int ready;                 /* a model is held (init or fread succeeded) */
+  unsigned long long model_id;
+  size_t n_linear, n_constant;
+  double rw_max;
+} shepard_state;
+static shepard_state *shepard_of(const gsl_sinterp *interp);
+
+static double *shep_f(const shepard_state *st) { return st->d_model + st->n * st->dim; }
+static double *shep_rq(const shepard_state *st) { return shep_f(st) + st->n; }
+static double *shep_rw(const shepard_state *st) { return shep_rq(st) + st->n; }
+static double *shep_coef(const shepard_state *st) { return shep_rw(st) + st->n; }
+static size_t shep_model_doubles(const shepard_state *st) { return st->n * (st->dim + 3 + st->nc); }
+
+static void *shepard_alloc(size_t dim, size_t size)
+{
+  if (dim != 2 && dim != 3) return NULL;                /* refused by gsl_sinterp_alloc */
+  shepard_state *st = (shepard_state *)calloc(1, sizeof *st);
+  if (st) { st->n = size; st->dim = dim; st->nc = dim == 2 ? 5 : 9; }
+  return st;
+}
+
+static void shepard_free(void *vstate)
+{
+  shepard_state *st = (shepard_state *)vstate;
+  if (!st) return;
+  if (st->ctx) {
+    gsl_sinterp_hip_free(st->ctx, st->d_model);
+    gsl_sinterp_hip_ctx_destroy(st->ctx);
+  }
+  free(st);
+}
+
+/* the context on the interpolant's device and the model buffer; the model held so far is dropped */
+static int shepard_prepare(gsl_sinterp *interp, shepard_state *st)
+{
+  st->ready = 0;
+  if (interp->n_devices > 1) GSL_ERROR("gsl_sinterp_init: modified Shepard interpolants run on one device", GSL_EUNSUP);
+  if (st->ctx && gsl_sinterp_hip_ctx_device(st->ctx) != interp->device) {
+    gsl_sinterp_hip_free(st->ctx, st->d_model);
+    gsl_sinterp_hip_ctx_destroy(st->ctx);
+    st->ctx = NULL; st->d_model = NULL;
+  }
+  if (!st->ctx && gsl_sinterp_hip_ctx_create(&st->ctx, interp->device, NULL) != GSL_SUCCESS) {
+    st->ctx = NULL;
+    GSL_ERROR("gsl_sinterp_init: no usable HIP device (GPU path has no CPU fallback)", GSL_EFAILED);
+  }
+  if (!st->d_model) HIP_TRY(gsl_sinterp_hip_malloc(st->ctx, (void **)&st->d_model, shep_model_doubles(st) * sizeof(double)), st->ctx);
+  st->model_id = next_model_id();                       /* the buffer is about to change */
+  return GSL_SUCCESS;
+}
+
+static int shepard_init(gsl_sinterp *interp, const gsl_matrix *x, const gsl_vector *f)
+{
+  shepard_state *st = shepard_of(interp);
+  const size_t n = st->n, dim = st->dim;
+  const size_t nq = st->nq_set ? st->nq_set : (dim == 2 ? 13 : 17), nw = st->nw_set ? st->nw_set : (dim == 2 ? 19 : 32);   /* Renka's defaults */
+  if (n < (nq > nw ? nq : nw) + 2) GSL_ERROR("gsl_sinterp_init: modified Shepard needs size >= max(nq, nw) + 2", GSL_EINVAL);
+  int s = shepard_prepare(interp, st);
+  if (s) return s;
+  gsl_sinterp_hip_ctx *c = st->ctx;
+  double *h = (double *)malloc(n * (dim + 1) * sizeof(double));
+  if (!h) GSL_ERROR("gsl_sinterp_init: out of memory", GSL_ENOMEM);
+  for (size_t i = 0; i < n; i++) {
+    for (size_t a = 0; a < dim; a++) h[i * dim + a] = x->data[i * x->tda + a];
+    h[n * dim + i] = f->data[i * f->stride];
+  }
+  size_t counts[3] = {0, 0, 0};
+  s = gsl_sinterp_hip_h2d(c, st->d_model, h, n * (dim + 1) * sizeof(double));
+  if (!s) s = gsl_sinterp_hip_shepard_fit(c, st->d_model, n, (int)dim, dim, shep_f(st), nq, nw, shep_rq(st), shep_rw(st), shep_coef(st), counts);
+  if (!s) s = gsl_sinterp_hip_d2h(c, h, shep_rw(st), n * sizeof(double));
+  double big = 0.0;
+  if (!s) for (size_t i = 0; i < n; i++) if (h[i] > big) big = h[i];
+  free(h);
+  if (s == GSL_EDOM) GSL_ERROR("gsl_sinterp_init: coincident sites (modified Shepard weights are undefined at distance 0)", GSL_EDOM);
+  HIP_TRY(s, c);
+  st->nq = nq; st->nw = nw; st->n_linear = counts[0]; st->n_constant = counts[1]; st->rw_max = big;
+  st->ready = 1;
+  return GSL_SUCCESS;
+}
+
+/* value / gradient / leaf, each optional, from one sweep; uncovered targets are the status */
+static int shepard_sweep(const shepard_state *st, const double *d_y, size_t m, size_t ytda, double *d_s, double *d_g, size_t gtda, int *d_leaf)
+{
+  size_t outside = 0;
+  int s = gsl_sinterp_hip_shepard_eval(st->ctx, st->d_model, st->n, (int)st->dim, st->dim, shep_f(st), shep_rq(st), shep_rw(st), shep_coef(st),
+                                       d_y, m, ytda, d_s, d_g, gtda, d_leaf, &outside, st->model_id);
+  if (s == GSL_EDOM) GSL_ERROR("gsl_sinterp_eval: target(s) outside every node's radius of influence (NaN there)", GSL_EDOM);
+  HIP_TRY(s, st->ctx);
+  return GSL_SUCCESS;
+}
+
+static int shepard_eval_resident(const gsl_sinterp *interp, const double *d_y, size_t m, size_t ytda, double *d_s, int *d_leaf)
+{
+  const shepard_state *st = shepard_of(interp);
+  if (!st->ready) GSL_ERROR("gsl_sinterp_eval_resident: interpolant not initialised", GSL_EINVAL);
+  if (m == 0) return GSL_SUCCESS;
+  if (!d_y || !d_s) GSL_ERROR("gsl_sinterp_eval_resident: null argument", GSL_EFAULT);
+  if (ytda < st->dim) GSL_ERROR("gsl_sinterp_eval_resident: target rows shorter than dim", GSL_EBADLEN);
+  return shepard_sweep(st, d_y, m, ytda, d_s, NULL, 0, d_leaf);
+}
+
+/* host batch: values (or NULL), gradient (or NULL), leaf (or NULL) through plain staging */
+static int shepard_eval_host(const shepard_state *st, const gsl_matrix *y, gsl_vector *sv, gsl_matrix *g, int *leaf)
+{
+  const size_t m = y->size1, dim = st->dim;
+  if (m == 0) return GSL_SUCCESS;
+  stage_out out[3] = {STAGE_VECTOR(sv), {g ? dim : 0, 0, g ? g->data : NULL, g ? g->tda : 0, NULL, NULL}, STAGE_INTS(leaf, leaf ? 1 : 0)};
+  host_stage hs;
+  int s = host_stage_begin(&hs, st->ctx, y, dim, out, 3), es = GSL_SUCCESS;
+  if (!hs.h) GSL_ERROR("gsl_sinterp_eval_many: out of memory", GSL_ENOMEM);
+  if (!s) es = shepard_sweep(st, hs.d_y, m, dim, (double *)out[0].d, (double *)out[1].d, dim, (int *)out[2].d);
+  s = host_stage_end(&hs, s, es == GSL_SUCCESS || es == GSL_EDOM);     /* EDOM: everything has been stored, NaN where uncovered */
+  HIP_TRY(s, st->ctx);
+  return es;                                            /* reported by shepard_sweep */
+}
+
+static int shepard_eval_many(const gsl_sinterp *interp, const gsl_matrix *y, gsl_vector *s, int *leaf)
+{
+  const shepard_state *st = shepard_of(interp);
+  if (!st->ready) GSL_ERROR("gsl_sinterp_eval_many: interpolant not initialised", GSL_EINVAL);
+  return shepard_eval_host(st, y, s, NULL, leaf);
+}
+
+/* ======================================================================== */
 /* type table + generic entry points                                         */
 /* ======================================================================== */
 #define RBF_ROW(name, min_size, id, kind, krige, affine, pd)                                                       \
@@ -1869,7 +2002,7 @@ static int mesh_type_eval_resident(const gsl_sinterp *interp, const double *d_y,
   {{name, 3, &mesh_type_alloc, &mesh_type_init, &mesh_type_eval_many, &mesh_type_eval_resident, &mesh_type_free}, id, FAM_MESH, 0, 0, 0, 0, \
    method, imported, noun}
 /* one row per type, in the order of the checkpoint ids.  The checkpoints of 12 / 13 have the payload of 6, those of
-   14 / 15 the same + the 2 N gradients */
+   14 / 15 the same + the 2 N gradients; 16 has a payload of its own (gsl_sinterp_fwrite) */
 static const type_desc type_table[] = {
   RBF_ROW("rbf-gaussian", 1, 0, GSL_SINTERP_RBF_GAUSSIAN, 0, 0, 1),
   RBF_ROW("rbf-thin-plate-spline", 1, 1, GSL_SINTERP_RBF_TPS, 0, 0, 0),
@@ -1887,6 +2020,8 @@ static const type_desc type_table[] = {
   MESH_ROW("natural-neighbour-simplex", 13, MESH_NATURAL, 0, "natural-neighbour"),
   MESH_ROW("clough-tocher-imported-triangulation", 14, MESH_CUBIC, 1, "Clough-Tocher"),
   MESH_ROW("clough-tocher-simplex", 15, MESH_CUBIC, 0, "Clough-Tocher"),
+  {{"modified-quadratic-shepard", 7, &shepard_alloc, &shepard_init, &shepard_eval_many, &shepard_eval_resident, &shepard_free}, 16, FAM_SHEPARD,
+   0, 0, 0, 0, 0, 0, "modified Shepard"},
 };
 #define N_TYPES (sizeof type_table / sizeof type_table[0])
 const gsl_sinterp_type *gsl_sinterp_rbf_gaussian = &type_table[0].pub;
@@ -1905,6 +2040,7 @@ const gsl_sinterp_type *gsl_sinterp_natural_mesh = &type_table[12].pub;
 const gsl_sinterp_type *gsl_sinterp_natural_simplex = &type_table[13].pub;
 const gsl_sinterp_type *gsl_sinterp_cubic_mesh = &type_table[14].pub;
 const gsl_sinterp_type *gsl_sinterp_cubic_simplex = &type_table[15].pub;
+const gsl_sinterp_type *gsl_sinterp_shepard = &type_table[16].pub;
 
 static const type_desc *desc_of(const gsl_sinterp_type *T)
 {
@@ -1918,6 +2054,7 @@ static const type_desc *desc_of(const gsl_sinterp_type *T)
 static rbf_state *rbf_of(const gsl_sinterp *interp) { return desc_of(interp->type)->family == FAM_RBF ? (rbf_state *)interp->state : NULL; }
 static simplex_state *tree_of(const gsl_sinterp *interp) { return desc_of(interp->type)->family == FAM_TREE ? (simplex_state *)interp->state : NULL; }
 static mesh_state *mesh_of(const gsl_sinterp *interp) { return desc_of(interp->type)->family == FAM_MESH ? (mesh_state *)interp->state : NULL; }
+static shepard_state *shepard_of(const gsl_sinterp *interp) { return desc_of(interp->type)->family == FAM_SHEPARD ? (shepard_state *)interp->state : NULL; }
 static int mesh_method(const gsl_sinterp *interp, int method) { return mesh_of(interp) && desc_of(interp->type)->method == method; }
 
 /* whether the interpolant is on, or will at the next init be on, the local route (route 11): asked by every entry that
@@ -1946,10 +2083,12 @@ gsl_sinterp *gsl_sinterp_alloc(const gsl_sinterp_type *T, size_t dim, size_t siz
   if (!d) GSL_ERROR_NULL("gsl_sinterp_alloc: not one of the gsl_sinterp types", GSL_EINVAL);
   if (size < T->min_size)
     GSL_ERROR_NULL("insufficient number of points for interpolation type", GSL_EINVAL);
+  if (d->family == FAM_SHEPARD && dim != 2 && dim != 3)
+    GSL_ERROR_NULL("gsl_sinterp_alloc: modified Shepard interpolants support dim = 2 and 3 only", GSL_EUNIMPL);
   if (dim < 1 || dim > 3) GSL_ERROR_NULL("gsl_sinterp_alloc: dim must be 1, 2 or 3", GSL_EINVAL);
   if (d->family == FAM_TREE && dim != 2)
     GSL_ERROR_NULL("gsl_sinterp_alloc: linear-simplex supports dim = 2 only", GSL_EUNIMPL);
-  if (d->noun && dim != 2) {
+  if (d->family == FAM_MESH && d->noun && dim != 2) {
     noun_error(d, "gsl_sinterp_alloc: %s interpolants support dim = 2 only", GSL_EUNIMPL);
     return NULL;
   }
@@ -2430,6 +2569,7 @@ static int grad_status(const gsl_sinterp *interp)
 {
   if (mesh_method(interp, MESH_NATURAL)) GSL_ERROR("gsl_sinterp_eval_grad: not for natural-neighbour interpolants", GSL_EUNSUP);
   if (mesh_method(interp, MESH_CUBIC)) return GSL_SUCCESS;     /* the one mesh method with a continuous gradient */
+  if (shepard_of(interp)) return GSL_SUCCESS;
   if (!rbf_of(interp))
     GSL_ERROR("gsl_sinterp_eval_grad: RBF-family interpolants only (the piecewise-linear gradient is constant per leaf)", GSL_EUNSUP);
   if (is_local(interp))
@@ -2450,6 +2590,12 @@ int gsl_sinterp_eval_grad_resident(const gsl_sinterp *interp, const double *d_y,
     if (m > 0 && !d_s) GSL_ERROR("gsl_sinterp_eval_grad_resident: Clough-Tocher interpolants need d_s (the locate step writes through it)", GSL_EFAULT);
     if (gtda < 2) GSL_ERROR("gsl_sinterp_eval_grad_resident: gradient rows shorter than dim", GSL_EINVAL);
     return simplex_mesh_device_eval_cubic_resident(ms->dev, d_y, m, ytda, d_s, d_g, gtda, NULL);
+  }
+  const shepard_state *sh = shepard_of(interp);
+  if (sh) {
+    if (!sh->ready) GSL_ERROR("gsl_sinterp_eval_grad: interpolant not initialised", GSL_EINVAL);
+    if (ytda < sh->dim || gtda < sh->dim) GSL_ERROR("gsl_sinterp_eval_grad_resident: target or gradient rows shorter than dim", GSL_EINVAL);
+    return m == 0 ? GSL_SUCCESS : shepard_sweep(sh, d_y, m, ytda, d_s, d_g, gtda, NULL);
   }
   const rbf_state *st = rbf_of(interp);
   if (!st->d_w) GSL_ERROR("gsl_sinterp_eval_grad: interpolant not initialised", GSL_EINVAL);
@@ -2481,6 +2627,11 @@ int gsl_sinterp_eval_grad_many(const gsl_sinterp *interp, const gsl_matrix *y, g
     const int cs = simplex_mesh_device_eval_cubic_many(ms->dev, y, tmp, g, NULL);
     gsl_vector_free(tmp);
     return cs;
+  }
+  const shepard_state *sh = shepard_of(interp);
+  if (sh) {
+    if (!sh->ready) GSL_ERROR("gsl_sinterp_eval_grad: interpolant not initialised", GSL_EINVAL);
+    return shepard_eval_host(sh, y, sv, g, NULL);
   }
   const rbf_state *st = rbf_of(interp);
   if (!st->d_w) GSL_ERROR("gsl_sinterp_eval_grad: interpolant not initialised", GSL_EINVAL);
@@ -2731,6 +2882,59 @@ int gsl_sinterp_set_triangulation(gsl_sinterp *interp, const int *triangles, con
   return GSL_SUCCESS;
 }
 
+/* ---- modified Shepard: settings, statistics, nodal gradients ---- */
+int gsl_sinterp_set_shepard(gsl_sinterp *interp, size_t nq, size_t nw)
+{
+  if (!interp) GSL_ERROR("gsl_sinterp_set_shepard: null interpolant", GSL_EFAULT);
+  shepard_state *st = shepard_of(interp);
+  if (!st) GSL_ERROR("gsl_sinterp_set_shepard: modified Shepard interpolants only", GSL_EINVAL);
+  if (nq != 0 && (nq < st->nc || nq > GSL_SINTERP_MAX_NEIGHBOURS - 2))
+    GSL_ERROR("gsl_sinterp_set_shepard: nq must be 0 (default) or between the number of monomials (5 in 2-D, 9 in 3-D) and 62", GSL_EINVAL);
+  if (nw > GSL_SINTERP_MAX_NEIGHBOURS - 2) GSL_ERROR("gsl_sinterp_set_shepard: nw must be 0 (default) or between 1 and 62", GSL_EINVAL);
+  st->nq_set = nq; st->nw_set = nw;
+  return GSL_SUCCESS;
+}
+
+int gsl_sinterp_shepard_stats(const gsl_sinterp *interp, size_t *n_linear, size_t *n_constant, double *rw_max)
+{
+  if (!interp) GSL_ERROR("gsl_sinterp_shepard_stats: null interpolant", GSL_EFAULT);
+  const shepard_state *st = shepard_of(interp);
+  if (!st) GSL_ERROR("gsl_sinterp_shepard_stats: modified Shepard interpolants only", GSL_EINVAL);
+  if (!st->ready) GSL_ERROR("gsl_sinterp_shepard_stats: interpolant not initialised", GSL_EINVAL);
+  if (n_linear) *n_linear = st->n_linear;
+  if (n_constant) *n_constant = st->n_constant;
+  if (rw_max) *rw_max = st->rw_max;
+  return GSL_SUCCESS;
+}
+
+gsl_sinterp_hip_ctx *gsl_sinterp_shepard_ctx(const gsl_sinterp *interp)
+{
+  const shepard_state *st = interp ? shepard_of(interp) : NULL;
+  return st ? st->ctx : NULL;
+}
+
+/* the nodal gradients grad Q_i(x_i) = (linear coefficients) / Rq_i, read back from the model */
+static int shepard_get_gradients(const shepard_state *st, gsl_matrix *gradients, size_t *iterations, double *residual)
+{
+  if (!st->ready) GSL_ERROR("gsl_sinterp_get_gradients: interpolant not initialised", GSL_EINVAL);
+  if (gradients && (gradients->size1 != st->n || gradients->size2 != st->dim))
+    GSL_ERROR("gsl_sinterp_get_gradients: gradients must be size x dim", GSL_EBADLEN);
+  if (gradients) {
+    const size_t n = st->n, nc = st->nc;
+    double *h = (double *)malloc(n * (nc + 2) * sizeof(double));      /* [Rq | Rw | c], contiguous in the model */
+    if (!h) GSL_ERROR("gsl_sinterp_get_gradients: out of memory", GSL_ENOMEM);
+    int s = gsl_sinterp_hip_d2h(st->ctx, h, shep_rq(st), n * (nc + 2) * sizeof(double));
+    if (!s)
+      for (size_t i = 0; i < n; i++)
+        for (size_t a = 0; a < st->dim; a++) gradients->data[i * gradients->tda + a] = h[2 * n + i * nc + a] * (1.0 / h[i]);
+    free(h);
+    HIP_TRY(s, st->ctx);
+  }
+  if (iterations) *iterations = 0;
+  if (residual) *residual = 0.0;
+  return GSL_SUCCESS;
+}
+
 /* ---- the gradients of the Clough-Tocher types ---- */
 int gsl_sinterp_set_gradients(gsl_sinterp *interp, const gsl_matrix *gradients)
 {
@@ -2765,6 +2969,7 @@ int gsl_sinterp_set_gradient_options(gsl_sinterp *interp, double rtol, size_t ma
 int gsl_sinterp_get_gradients(const gsl_sinterp *interp, gsl_matrix *gradients, size_t *iterations, double *residual)
 {
   if (!interp) GSL_ERROR("gsl_sinterp_get_gradients: null interpolant", GSL_EFAULT);
+  if (shepard_of(interp)) return shepard_get_gradients(shepard_of(interp), gradients, iterations, residual);
   if (!mesh_method(interp, MESH_CUBIC)) GSL_ERROR("gsl_sinterp_get_gradients: Clough-Tocher interpolants only", GSL_EINVAL);
   const mesh_state *st = mesh_of(interp);
   if (!st->dev || !st->g) GSL_ERROR("gsl_sinterp_get_gradients: interpolant not initialised", GSL_EINVAL);
@@ -2871,6 +3076,7 @@ static gsl_sinterp_hip_ctx *interp_ctx0(const gsl_sinterp *interp)
   const mesh_state *ms = mesh_of(interp);
   if (ts) return ts->dev ? ts->dev->ctx : NULL;
   if (ms) return ms->dev ? ms->dev->ctx : NULL;
+  if (shepard_of(interp)) return shepard_of(interp)->ready ? shepard_of(interp)->ctx : NULL;
   return rbf_of(interp)->ctx;
 }
 
@@ -2909,6 +3115,7 @@ int gsl_sinterp_eval_grid(const gsl_sinterp *interp, const gsl_vector *min, cons
   HIP_TRY(st, c);
   if (tree_of(interp) && n_nan) GSL_ERROR("gsl_sinterp_eval_grid: grid node(s) outside the caging simplex", GSL_EDOM);
   if (mesh_of(interp) && n_nan) GSL_ERROR("gsl_sinterp_eval_grid: grid node(s) outside the triangulation", GSL_EDOM);
+  if (shepard_of(interp) && n_nan) GSL_ERROR("gsl_sinterp_eval_grid: grid node(s) outside every node's radius of influence", GSL_EDOM);
   return GSL_SUCCESS;
 }
 
@@ -2977,6 +3184,23 @@ int gsl_sinterp_fwrite(FILE *stream, const gsl_sinterp *interp)
         if (fwrite(gi, sizeof(double), 2, stream) != 2) GSL_ERROR("fwrite failed", GSL_EFAILED);
       }
     }
+    return GSL_SUCCESS;
+  }
+  if (shepard_of(interp)) {
+    /* payload: nq | nw | linear fallbacks | constant fallbacks (uint64 each) | the model buffer [x | f | Rq | Rw | c] */
+    const shepard_state *st = shepard_of(interp);
+    if (!st->ready) GSL_ERROR("gsl_sinterp_fwrite: interpolant not initialised", GSL_EINVAL);
+    const size_t cnt = shep_model_doubles(st);
+    const uint64_t par[4] = {(uint64_t)st->nq, (uint64_t)st->nw, (uint64_t)st->n_linear, (uint64_t)st->n_constant};
+    double *h = (double *)malloc(cnt * sizeof(double));
+    if (!h) GSL_ERROR("gsl_sinterp_fwrite: out of memory", GSL_ENOMEM);
+    int s = gsl_sinterp_hip_d2h(st->ctx, h, st->d_model, cnt * sizeof(double));
+    if (!s && (!header_fwrite(stream, interp, 0.0, 0) || fwrite(par, sizeof par[0], 4, stream) != 4 || fwrite(h, sizeof(double), cnt, stream) != cnt)) {
+      free(h);
+      GSL_ERROR("fwrite failed", GSL_EFAILED);
+    }
+    free(h);
+    HIP_TRY(s, st->ctx);
     return GSL_SUCCESS;
   }
   const rbf_state *st = rbf_of(interp);
@@ -3071,6 +3295,30 @@ int gsl_sinterp_fread(FILE *stream, gsl_sinterp *interp)
     const int s = mesh_type_mirror(interp, st, g);
     if (g) gsl_matrix_free(g);
     return s;
+  }
+  if (shepard_of(interp)) {
+    shepard_state *st = shepard_of(interp);
+    const size_t cnt = shep_model_doubles(st), n = st->n;
+    uint64_t par[4];
+    double *h = (double *)malloc(cnt * sizeof(double));
+    if (!h) GSL_ERROR("gsl_sinterp_fread: out of memory", GSL_ENOMEM);
+    if (fread(par, sizeof par[0], 4, stream) != 4 || fread(h, sizeof(double), cnt, stream) != cnt) { free(h); GSL_ERROR("fread failed", GSL_EFAILED); }
+    if (par[0] < st->nc || par[0] > GSL_SINTERP_MAX_NEIGHBOURS - 2 || par[1] < 1 || par[1] > GSL_SINTERP_MAX_NEIGHBOURS - 2) {
+      free(h);
+      GSL_ERROR("gsl_sinterp_fread: corrupt modified Shepard checkpoint", GSL_EFAILED);
+    }
+    int s = shepard_prepare(interp, st);
+    if (s) { free(h); return s; }
+    s = gsl_sinterp_hip_h2d(st->ctx, st->d_model, h, cnt * sizeof(double));
+    if (!s) s = gsl_sinterp_hip_sync(st->ctx);
+    double big = 0.0;
+    const double *h_rw = h + n * (st->dim + 2);
+    for (size_t i = 0; i < n; i++) if (h_rw[i] > big) big = h_rw[i];
+    free(h);
+    HIP_TRY(s, st->ctx);
+    st->nq = (size_t)par[0]; st->nw = (size_t)par[1]; st->n_linear = (size_t)par[2]; st->n_constant = (size_t)par[3]; st->rw_max = big;
+    st->ready = 1;
+    return GSL_SUCCESS;                                 /* nothing was searched or fitted */
   }
   rbf_state *st = rbf_of(interp);
   const size_t cnt = st->n * (st->dim + 1);

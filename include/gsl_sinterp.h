@@ -371,6 +371,32 @@ extern const gsl_sinterp_type *gsl_sinterp_natural_mesh, *gsl_sinterp_natural_si
    Checkpoints: type ids 14 / 15, the mesh payload of gsl_sinterp_linear_mesh followed by the 2 N gradients; a restored
    interpolant does not estimate again. */
 extern const gsl_sinterp_type *gsl_sinterp_cubic_mesh, *gsl_sinterp_cubic_simplex;
+/* Modified quadratic Shepard interpolation ("modified-quadratic-shepard"; Renka's QSHEP2D / QSHEP3D, ACM TOMS 660 / 661),
+   dim 2 or 3 (any other dim: GSL_EUNIMPL at alloc): the smooth interpolant for clouds past the size a dense solve holds and
+   for 3-D clouds without a mesh.  C1 everywhere, exact at the data, reproduces quadratics, local, O(N) memory, no solve, no
+   triangulation, no shape parameter, analytic gradient.  The method and its reproducibility contract:
+   gsl_sinterp_hip_shepard_fit / _eval (gsl_sinterp_hip.h).
+     gsl_sinterp_set_shepard(interp, nq, nw), before init: the number of neighbours behind the radius of the nodal fits and
+       of the evaluation weights; 0 = the default, Renka's 13 / 19 in 2-D and 17 / 32 in 3-D.  GSL_EINVAL: another type, nq
+       below the number of monomials (5 / 9) or above 62, nw above 62.  gsl_sinterp_init: GSL_EINVAL when size <
+       max(nq, nw) + 2; GSL_EDOM when two sites coincide (the interpolant stays uninitialised).  Init searches the
+       neighbours and fits every node on the device; nothing is solved globally.
+     eval_e / eval_many / eval_resident / eval_grid (dim 2) and gsl_sinterp_eval_grad_e / _many / _resident; `leaf` = the number
+       of nodes whose weight is positive at the target (1 at a site).  A target no node's radius covers gives NaN (value and
+       gradient), -1 and GSL_EDOM after every other target has been stored; a NaN coordinate gives NaN and is no error.
+     gsl_sinterp_get_gradients: the N x dim nodal gradients, iterations 0, residual 0.
+     gsl_sinterp_shepard_stats: how many nodes fell back to a linear and to a constant nodal function (rank-deficient
+       neighbourhoods: collinear or coplanar sites) and the largest radius of influence; each output may be NULL.
+     gsl_sinterp_shepard_ctx: the device context of the interpolant (NULL before the first init), for the counters
+       gsl_sinterp_hip_shepard_fit_count / _pack_count.
+   One device only (a device list of more than one member: GSL_EUNSUP at init).  Fields, variance, leave-one-out, fit,
+   set_neighbours: GSL_EUNSUP; set_solver, get_weights, mean, poly: GSL_EINVAL.  Checkpoints: type id 16 -- nq, nw, the
+   fallback counts, centres, responses, radii and coefficients; a restored interpolant does not search or fit again and
+   evaluates to the same bits. */
+extern const gsl_sinterp_type *gsl_sinterp_shepard;
+int gsl_sinterp_set_shepard(gsl_sinterp *interp, size_t nq, size_t nw);
+int gsl_sinterp_shepard_stats(const gsl_sinterp *interp, size_t *n_linear, size_t *n_constant, double *rw_max);
+gsl_sinterp_hip_ctx *gsl_sinterp_shepard_ctx(const gsl_sinterp *interp);
 /* ordinary kriging with a Gaussian covariance exp(-(eps h)^2) and an optional nugget (README:24 future list):
    s(y) = mu + sum_j w_j C(|y - x_j|) with [C + nugget I, 1; 1^T, 0] [w; mu] = [f; 0].  nugget = 0 interpolates the data,
    nugget > 0 smooths (s(x_i) = f_i - nugget w_i); far from the data s -> mu.  gsl_sinterp_set_shape sets eps. */
@@ -533,7 +559,8 @@ int gsl_sinterp_set_triangulation(gsl_sinterp *interp, const int *triangles, con
    set_gradient_options, before init: the stopping rule of the estimate, |r| / |b| <= rtol or maxiter iterations
    (defaults 1e-12, 1000; 0 < rtol < 1 and maxiter >= 1, otherwise GSL_EINVAL).  get_gradients, after init: the
    gradients in use (N x 2, may be NULL), the iterations the estimate took (0 for given or restored gradients) and its
-   relative residual (either may be NULL). */
+   relative residual (either may be NULL).  get_gradients also serves gsl_sinterp_shepard: the N x dim nodal gradients,
+   iterations 0, residual 0. */
 int gsl_sinterp_set_gradients(gsl_sinterp *interp, const gsl_matrix *gradients);
 int gsl_sinterp_set_gradient_options(gsl_sinterp *interp, double rtol, size_t maxiter);
 int gsl_sinterp_get_gradients(const gsl_sinterp *interp, gsl_matrix *gradients, size_t *iterations, double *residual);
@@ -562,7 +589,9 @@ int gsl_sinterp_eval_resident(const gsl_sinterp *interp, const double *d_y, size
    gsl_sinterp_cubic_mesh / _simplex: the analytic gradient of the Clough-Tocher cubic in the micro-triangle of the
    target, continuous across every edge; same shapes; a target outside the triangulation gets NaN and GSL_EDOM (many / e;
    the resident entry does not read back).  d_s == NULL in the resident entry is GSL_EFAULT for these two types (the
-   locate step passes its values through it). */
+   locate step passes its values through it).
+   gsl_sinterp_shepard: the analytic gradient of the modified Shepard interpolant, continuous everywhere; same shapes, d_s
+   may be NULL; a target no node covers gets NaN and GSL_EDOM (all three entries: the sweep reports its count). */
 int gsl_sinterp_eval_grad_e(const gsl_sinterp *interp, const gsl_vector *y, double *s, gsl_vector *g);
 int gsl_sinterp_eval_grad_many(const gsl_sinterp *interp, const gsl_matrix *y, gsl_vector *s /* may be NULL */, gsl_matrix *g);
 int gsl_sinterp_eval_grad_resident(const gsl_sinterp *interp, const double *d_y, size_t m, size_t ytda,

@@ -464,6 +464,49 @@ int gsl_sinterp_hip_local_pack(gsl_sinterp_hip_ctx *ctx, const double *d_x, size
                                unsigned long long model_id);
 unsigned long long gsl_sinterp_hip_local_pack_count(const gsl_sinterp_hip_ctx *ctx);
 
+/* Modified quadratic Shepard interpolation (Renka, ACM TOMS 660 / 661; Franke & Nielson 1980) in dim 2 or 3: C1, exact at the
+   data, reproduces quadratics, local, O(N) memory, no solve, no mesh, no shape parameter, analytic gradient.
+   With r2 the FMA chain of the sweeps, r = sqrt(r2), and integer parameters nq, nw:
+     Rq_i, Rw_i   the distance from x_i to its (nq + 1)-th, (nw + 1)-th nearest OTHER site.  Only sites STRICTLY inside a radius
+                  carry weight (a site on it has weight 0, so no result depends on how the search breaks a distance tie; on a
+                  lattice fewer than nq sites may then take part).
+     Q_i(y)       = f_i + c_i . m((y - x_i) / Rq_i), m(u) = the dim linear monomials u_0 .. u_{dim-1}, then u_a u_b for a <= b
+                  in row-major order: nc = 5 (dim 2) or 9 (dim 3) coefficients per node.
+     c_i          minimises sum_j omega_ij^2 (Q_i(x_j) - f_j)^2 over j != i with r_ij < Rq_i, omega_ij = (Rq_i - r_ij) / (Rq_i r_ij):
+                  Householder QR of the weighted matrix, its columns scaled to unit 2-norm first (a zero column is deficient),
+                  in that column order without pivoting, no normal equations.  RANK RULE, rho(k) = min |R_jj| / max |R_jj| over
+                  j < k: rho(nc) >= GSL_SQRT_DBL_EPSILON: the quadratic fit; otherwise rho(dim) >= GSL_SQRT_DBL_EPSILON: the linear
+                  fit on the first dim columns, quadratic coefficients 0; otherwise c_i = 0.
+     W_i(y)       = ((Rw_i - r_i)_+ / (Rw_i r_i))^2,  s(y) = sum W_i Q_i / sum W_i,
+                  grad s = sum (W_i grad Q_i + (Q_i - s) grad W_i) / sum W_i in raw coordinates.
+   gsl_sinterp_hip_shepard_fit: d_rq[n], d_rw[n], d_coef[n x nc] from the sites d_x (n x dim, pitch xtda) and responses d_f.
+   The neighbours come from gsl_sinterp_hip_knn with the sites as targets and k = max(nq, nw) + 2 (neighbour 0 is the node
+   itself, hence nq, nw <= 62), in chunks of nodes so that the index buffers stay bounded; then one wave per node, every
+   sum a fixed 64-lane butterfly: the same bits from run to run.  h_counts (3 entries, or NULL): nodes that took the linear
+   fallback, the constant fallback, and nodes whose nearest other site is at r2 = 0 -- their weights are undefined, their
+   outputs NaN and the return is GSL_EDOM.  Synchronises.  GSL_EINVAL: dim not 2 or 3, nq < nc, nw < 1, max(nq, nw) + 2 > 64
+   or > n, xtda < dim -- checked first; then GSL_EFAULT: a NULL context or pointer.  Nothing touches the device before.
+   gsl_sinterp_hip_shepard_eval: d_s[m] (or NULL), the gradient (row k at d_g + k * gtda, or NULL) and d_leaf[m] (or NULL)
+   at the targets d_y (m x dim, pitch ytda).  d_leaf = the number of nodes with W_i > 0 (not bounded by 64).  SPECIAL TARGETS:
+   r2 = 0 to a node: the f of the smallest such row, that node's gradient c_lin / Rq, leaf 1; sum W not finite (within
+   ~1e-154 of a node): the same from the nearest node under the key (r2, row); no node with W > 0: NaN, NaN, -1; a NaN
+   coordinate: NaN, NaN, -1 and no error.  h_n_outside != NULL: the call synchronises, stores the number of uncovered targets
+   and returns GSL_EDOM when it is not 0 (every other target has been stored); NULL: asynchronous, no such status.
+   A target's result depends on (model, target) alone: the same bits from run to run, alone or in a batch of any size
+   (batches of 4096 and more run in cell order), with or without the gradient.  The nodes are packed once per model into
+   cell-ordered records kept in the context, keyed by model_id as in gsl_sinterp_hip_rbf_eval_model (0 = do not cache);
+   the _pack_count / _fit_count entries count the packs and fits of a context.  GSL_EINVAL: dim, xtda / ytda / gtda < dim;
+   then GSL_EFAULT: a NULL context or model pointer, d_y with m > 0. */
+int gsl_sinterp_hip_shepard_fit(gsl_sinterp_hip_ctx *ctx, const double *d_x, size_t n, int dim, size_t xtda, const double *d_f,
+                                size_t nq, size_t nw, double *d_rq, double *d_rw, double *d_coef /* n x nc */,
+                                size_t *h_counts /* linear fallbacks, constant fallbacks, coincident nodes; or NULL */);
+int gsl_sinterp_hip_shepard_eval(gsl_sinterp_hip_ctx *ctx, const double *d_x, size_t n, int dim, size_t xtda, const double *d_f,
+                                 const double *d_rq, const double *d_rw, const double *d_coef, const double *d_y, size_t m,
+                                 size_t ytda, double *d_s /* or NULL */, double *d_g /* or NULL */, size_t gtda, int *d_leaf /* or NULL */,
+                                 size_t *h_n_outside /* or NULL */, unsigned long long model_id);
+unsigned long long gsl_sinterp_hip_shepard_pack_count(const gsl_sinterp_hip_ctx *ctx);
+unsigned long long gsl_sinterp_hip_shepard_fit_count(const gsl_sinterp_hip_ctx *ctx);
+
 /* Leave-one-out from a Cholesky factor K = L L^T (lower triangle of d_llt, as cholesky_decomp1, factor_solve, rbf_solve
    route 1 and krige_solve route 7 leave it): d_g[i] = (K^-1)_ii = |row i of L^-T|^2, i < n, in N^3 / 3 + O(chunk N^2)
    flops (fp64 MFMA GEMM) -- the recursion of the variance entry started from the identity, with the rows taken `chunk`
