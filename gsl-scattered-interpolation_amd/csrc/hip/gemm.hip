@@ -559,6 +559,13 @@ gemm_minus_streamk_kernel(GemmArgs g, StreamK x, RiderArgs rd)
        Like every kernel here it relies on the caller having ordered the producer of C before the call on the
        context's stream; where in the launch C is read does not make an unordered writer safe. */
     constexpr bool CPRE = FM * FN <= 8;
+    /* Larger wave tiles (64 x 64: no spare registers for a prefetch), N.T operands: the owner's accumulators START as the
+       C tile and every K-step subtracts from it, as in gemm_minus_smallk_kernel; the epilogue is a plain store, no
+       load and no subtract, whose drain overlaps the next segment's set-up.  The arithmetic is
+       ((C - a1 b1) - a2 b2) ... - partials in ascending workgroup order, where it was C - (sum of all of them).
+       The [k][n] instantiations keep the read-modify-write epilogue and their bits (the LU pivot sequences). */
+    constexpr bool CACC = !CPRE && !BKN;
+    static_assert(!(CACC && RIDER), "the rider's hand-off stores come from the prefetched-C epilogue");
     double4_t cpre[CPRE ? FM : 1][CPRE ? FN : 1];
     auto load_cpre = [&]() {
       if constexpr (CPRE) {
@@ -618,10 +625,52 @@ gemm_minus_streamk_kernel(GemmArgs g, StreamK x, RiderArgs rd)
         }
       };
 
+      if constexpr (!CACC) {
 #pragma unroll
-      for (int i = 0; i < FM; i++)
+        for (int i = 0; i < FM; i++)
 #pragma unroll
-        for (int j = 0; j < FN; j++) acc[i][j] = (double4_t){0.0, 0.0, 0.0, 0.0};
+          for (int j = 0; j < FN; j++) acc[i][j] = (double4_t){0.0, 0.0, 0.0, 0.0};
+      } else if (s0 == 0) {
+        /* owner: the C tile goes straight into the accumulators, entries above the diagonal included (they feed only
+           entries that are never stored).  Issued before the ring's first DMA: older than every DMA group, so each
+           counted vmcnt wait of the K loop -- all of which leave only DMA groups outstanding -- covers these loads too,
+           and their latency shares the window in which the ring fills.  One lane pointer walks down the 16 row groups:
+           64 addresses up front do not fit beside the accumulators (the loop runs at 256 VGPRs) */
+        const __attribute__((address_space(1))) double *cl =
+            (const __attribute__((address_space(1))) double *)(g.C + (row0 + wr * WM + fq) * g.ldc + col0 + wc * WN + fr);
+#pragma unroll
+        for (int i = 0; i < FM; i++)
+#pragma unroll
+          for (int rg = 0; rg < 4; rg++) {
+#pragma unroll
+            for (int j = 0; j < FN; j++) acc[i][j][rg] = cl[j * 16];
+            cl += 4 * g.ldc;
+            asm volatile("" : "+v"(cl));
+          }
+      } else {
+        /* -0.0: negate_c() below turns it into the +0.0 these segments have always started from.  Made here, from a
+           laundered register: as a loop invariant it would be kept, and spilled, across the segments */
+        double z = 0.0;
+        asm volatile("" : "+v"(z));
+        z = -z;
+#pragma unroll
+        for (int i = 0; i < FM; i++)
+#pragma unroll
+          for (int j = 0; j < FN; j++) acc[i][j] = (double4_t){z, z, z, z};
+      }
+      /* -C in the owner's accumulators: the MFMAs add the products, the epilogue negates once more.  Negation is exact,
+         so this is ((C - a1 b1) - a2 b2) ... bit for bit.  Every segment negates, owner or not: one path, so the
+         compiler's wait for the loaded values stands exactly once, here, behind the ring's first DMAs and outside the
+         K loop.  (It is a vmcnt(0) -- the backend does not count across direct-to-LDS loads in flight -- so the owner
+         starts its K loop with all three groups landed instead of the first; they were issued back to back.) */
+      auto negate_c = [&]() {
+        if constexpr (CACC) {
+#pragma unroll
+          for (int i = 0; i < FM; i++)
+#pragma unroll
+            for (int j = 0; j < FN; j++) acc[i][j] = -acc[i][j];
+        }
+      };
 
       __syncthreads();                                   /* the ring is free: previous segment fully read */
       if constexpr (PIPE) {
@@ -656,6 +705,7 @@ gemm_minus_streamk_kernel(GemmArgs g, StreamK x, RiderArgs rd)
         issue(0, (size_t)s0 * GK);
         if (nst > 1) issue(1, (size_t)(s0 + 1) * GK);
         if (nst > 2) issue(2, (size_t)(s0 + 2) * GK);
+        negate_c();
         wait_keep(nst > 2 ? 2 : (int)nst - 1);
         __builtin_amdgcn_s_barrier();
         __builtin_amdgcn_sched_barrier(0);
@@ -704,6 +754,7 @@ gemm_minus_streamk_kernel(GemmArgs g, StreamK x, RiderArgs rd)
       } else {
       issue(0, (size_t)s0 * GK);
       if (s0 + 1 < s1) issue(1, (size_t)(s0 + 1) * GK);
+      negate_c();
       for (unsigned s = s0; s < s1; s++) {
         const unsigned rel = s - s0;
         /* group s has landed once at most the DMAs of group s+1 are still outstanding */
@@ -810,6 +861,7 @@ gemm_minus_streamk_kernel(GemmArgs g, StreamK x, RiderArgs rd)
               double *p = g.C + grow * g.ldc + gcol;
               double v;
               if constexpr (CPRE) v = cpre[i][j][rg] - acc[i][j][rg];
+              else if constexpr (CACC) v = -acc[i][j][rg];
               else v = *p - acc[i][j][rg];
               if (hand) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   /* write-through: read by the rider */
               else *p = v;
@@ -827,7 +879,7 @@ gemm_minus_streamk_kernel(GemmArgs g, StreamK x, RiderArgs rd)
         }
       }
 #ifdef SINTERP_DIAG_PROF
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      if constexpr (!CACC) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   /* CACC: the drain is stamped where the shipped kernel pays it, in the next prologue */
       GEMM_TS_MARK(3);
 #endif
     }

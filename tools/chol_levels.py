@@ -2,8 +2,9 @@
 the launches chol_panel (csrc/hip/chol.hip) issues, grouped by recursion level, with achieved TFLOP/s
 (algorithmic flops: lower part only on the square block).  Tells which levels of the recursion sit
 furthest below the MFMA roofline.   usage: python tools/chol_levels.py [N]"""
-import sys, collections
-sys.path.insert(0, '/root/repo'); sys.path.insert(0, '/root/repo/tests')
+import os, sys, collections
+_R = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, _R); sys.path.insert(0, os.path.join(_R, "tests"))
 import torch
 import __graft_entry__ as g
 pkg = g.load_package()

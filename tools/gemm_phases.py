@@ -7,6 +7,9 @@ usage: python tools/gemm_phases.py [variant ...]   (variant: rule, r4, or a GSL_
 import ctypes as C, os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SHAPES = [(8192, 128, 128), (16128, 256, 256), (8192, 512, 512), (8192, 1024, 1024), (12288, 2048, 2048)]
+# the seven launches of the 256x128 tile in the N = 16384 recursion (K = 8192, 4096, 2048; tools/chol_levels.py)
+SHAPES += [(8192, 8192, 8192), (12288, 4096, 4096), (4096, 4096, 4096),
+           (14336, 2048, 2048), (10240, 2048, 2048), (6144, 2048, 2048), (2048, 2048, 2048)]
 
 if len(sys.argv) > 1 and sys.argv[1] == "child":
     os.environ.setdefault("GSL_SINTERP_LIBRARY", os.path.join(ROOT, "gsl-scattered-interpolation_amd", "libgsl_sinterp_prof.so"))
