@@ -796,6 +796,35 @@ bary_eval_kernel(int n_nodes, const NodeRec *__restrict__ rec, const LeafRec *__
 static int lw_build(gsl_sinterp_hip_ctx *ctx, int n_nodes, const int *d_type, const int *d_pidx, const int *d_links, int n_points,
                     const double *d_points, const Geom &g, const NodeRec *d_records);
 
+#define LW_SLICES 8   /* most slices of 256 targets a workgroup of leafwalk_kernel takes */
+/* The GSL_SINTERP_* switches of the barycentric evaluation, read here and nowhere else.  `sort` and the
+   developer knobs below it are read at every call (tests flip NO_SORT inside one process); the rest once per process. */
+struct BarySwitches {
+  bool no_fast, no_affine, no_side, no_lw, no_jump;
+  bool sort;                          /* sinterp_sort_wanted(m) */
+  int per_cell, walk_wgs_per_cu, walk_batch;   /* developer; walk_wgs_per_cu 0: what the occupancy query says */
+  int lw_slices; double lw_f;         /* developer, once per process */
+};
+static BarySwitches bary_switches(size_t m)
+{
+  BarySwitches s;
+  s.no_fast = SINTERP_ENV_ONCE("GSL_SINTERP_NO_FASTDIV");
+  s.no_affine = SINTERP_ENV_ONCE("GSL_SINTERP_NO_AFFINE_WALK");
+  s.no_side = SINTERP_ENV_ONCE("GSL_SINTERP_NO_SIDE_STREAM");
+  s.no_lw = SINTERP_ENV_ONCE("GSL_SINTERP_NO_LEAFWALK");
+  s.no_jump = SINTERP_ENV_ONCE("GSL_SINTERP_NO_JUMP");
+  s.sort = sinterp_sort_wanted(m);
+  s.per_cell = sinterp_env_int("GSL_SINTERP_BARY_PER_CELL", 64);
+  s.walk_wgs_per_cu = sinterp_env_int("GSL_SINTERP_WALK_WGS_PER_CU", 0);
+  s.walk_batch = sinterp_env_int("GSL_SINTERP_WALK_BATCH", 0);
+  if (s.walk_batch <= 0) s.walk_batch = WALK_BATCH;
+  static const int lw_slices_env = sinterp_env_int("GSL_SINTERP_LW_SLICES", 0);   /* 1 .. 8 */
+  s.lw_slices = lw_slices_env >= 1 && lw_slices_env <= LW_SLICES ? lw_slices_env : 1;
+  static const double lw_f_env = sinterp_env_double("GSL_SINTERP_LW_F", 4.0);
+  s.lw_f = lw_f_env;
+  return s;
+}
+
 /* ------------------------------------------------------------------------ */
 extern "C" int gsl_sinterp_hip_tree_pack(gsl_sinterp_hip_ctx *ctx, int n_nodes, const int *d_type, const int *d_pidx,
                                          const int *d_links, int n_points, const double *d_points,
@@ -817,14 +846,13 @@ extern "C" int gsl_sinterp_hip_tree_pack(gsl_sinterp_hip_ctx *ctx, int n_nodes, 
      built once here; evaluations of these records on this context start their walks from it */
   /* certified leaf walk: seed grid + per-leaf line lists + margin constants (see "Certified leaf walk") */
   ctx->lw_rec = NULL;
-  const bool no_lw = SINTERP_ENV_ONCE("GSL_SINTERP_NO_LEAFWALK");
-  if (!no_lw && n_nodes >= 2048 && n_points >= 3 && d_points) {
+  const BarySwitches sw = bary_switches(0);
+  if (!sw.no_lw && n_nodes >= 2048 && n_points >= 3 && d_points) {
     int st = lw_build(ctx, n_nodes, d_type, d_pidx, d_links, n_points, d_points, g, (const NodeRec *)d_records);
     if (st) return st;
   }
   ctx->jump_rec = NULL;
-  const bool no_jump = SINTERP_ENV_ONCE("GSL_SINTERP_NO_JUMP");
-  if (!no_jump && n_nodes >= 2048 && n_points >= 3 && d_points) {
+  if (!sw.no_jump && n_nodes >= 2048 && n_points >= 3 && d_points) {
     int G = 32;
     /* cells per node: what stops the descent of a cell is a HISTORIC edge crossing it (flips leave them all over the final
        triangles), so the share of targets that start at their leaf grows with the resolution -- measured at C5 (450 k nodes,
@@ -1484,7 +1512,6 @@ __device__ __forceinline__ bool leafwalk_target(int n_nodes, const NodeRec *__re
    counter cost more than the walk itself (0.92 ms against 0.4 ms at C5).  slices = 1 by default: with 8 slices (one atomic
    per 2048 targets) the grid is only 2.4 rounds of resident workgroups and its tail costs more than the atomics save --
    C5 step 1.231 / 1.185 / 1.158 / 1.148 ms for 8 / 4 / 2 / 1 slices (GSL_SINTERP_LW_SLICES, developer). */
-#define LW_SLICES 8
 __global__ void __launch_bounds__(256)
 leafwalk_kernel(int n_nodes, const NodeRec *__restrict__ rec, const LeafRec *__restrict__ tab, const int *__restrict__ seed, LwGrid g,
                 const unsigned *__restrict__ off, const double *__restrict__ lines, double F, double c0c, double c1c,
@@ -1637,129 +1664,52 @@ static int lw_build(gsl_sinterp_hip_ctx *ctx, int n_nodes, const int *d_type, co
   return ST_SUCCESS;
 }
 
-/* One batch (or one chunk of a batch) on ctx->stream.  wrec != NULL: the certified walk with these records (built by
-   the caller), the walker lists / queue in the section `wslot` of the walk buffer; slot: section of the sort buffer
-   (-1: the whole buffer); m_cap: the largest chunk of the batch (sizes the sections); inner_side: the finish kernel
-   may run on the context's side stream (only when the caller does not use that stream for another chunk). */
-static int bary_eval_part(gsl_sinterp_hip_ctx *ctx, int n_nodes, const void *d_records, const void *d_leaftab, const double *h_scale,
-                          const double *d_targets, size_t m, size_t ttda, double *d_values, int *d_leaf, unsigned long long *d_count,
-                          const WalkRec *wrec, char *wsec, size_t m_cap, int slot, bool inner_side)
+/* Which locator runs in front of the exact kernel, and where the walks start.  The results do not depend on either.
+     LOC_LEAFWALK  batches in cell order on records this context packed: the certified leaf walk;
+     LOC_DAGWALK   large batches otherwise: per-batch affine walk records (a pass over the node records, ~n_nodes x 128
+                   bytes -- hence m >= n_nodes / 8) and the certified DAG walk;
+     LOC_EXACT     the exact kernel on every target.
+   What a locator cannot certify is queued for the exact kernel (31-bit positions: m < 2^31).
+     JUMP_PACKED   the table tree_pack built for these records on this context (its box also bins the sort);
+     JUMP_BATCH    records packed elsewhere (e.g. received by broadcast): a table over THIS batch's bounding box. */
+enum BaryLocator { LOC_EXACT, LOC_DAGWALK, LOC_LEAFWALK };
+enum BaryJump { JUMP_NONE, JUMP_PACKED, JUMP_BATCH };
+struct BaryRoute { BaryLocator loc; BaryJump jump; bool sort; int per_cell; };
+static BaryRoute bary_route(size_t m, int n_nodes, bool packed_here, bool lw_here, const BarySwitches &sw)
 {
-  const bool no_fast = SINTERP_ENV_ONCE("GSL_SINTERP_NO_FASTDIV");
-  const bool will_sort = m >= 4096 && !sinterp_env_flag("GSL_SINTERP_NO_SORT");
-  const bool use_walk = wrec != NULL;
-  ctx->lw_last = 0;
-  const unsigned n_slices = (unsigned)((m + WALK_SLICE - 1) / WALK_SLICE);
-  unsigned *todo_count = NULL;
-  int *todo = NULL;
-  WalkList wl;
-  memset(&wl, 0, sizeof wl);
-  if (use_walk) {
-    const size_t mp = ((m_cap + WALK_SLICE - 1) / WALK_SLICE) * WALK_SLICE;
-    auto up = [](size_t b) { return (b + 63) & ~(size_t)63; };
-    const size_t o_todo = 64, o_y = o_todo + up(m_cap * sizeof(int)), o_st = o_y + up(mp * sizeof(double2)),
-                 o_k = o_st + up(mp * sizeof(int4)), o_sc = o_k + up(mp * sizeof(int));
-    todo_count = (unsigned *)wsec;
-    todo = (int *)(wsec + o_todo);
-    wl.y = (double2 *)(wsec + o_y); wl.st = (int4 *)(wsec + o_st); wl.k = (int *)(wsec + o_k); wl.count = (unsigned *)(wsec + o_sc);
-    HIP_OK(ctx, hipMemsetAsync(todo_count, 0, 64, ctx->stream));
-  }
-  const bool no_jump = SINTERP_ENV_ONCE("GSL_SINTERP_NO_JUMP");
-  const bool have_table = !no_jump && ctx->jump_rec == d_records && ctx->jump_nodes == n_nodes && ctx->d_jumpt;
-  sinterp_sorted srt;
-  bool sorted = false;
-  if (will_sort) {
-    /* bin by the data's bounding box when tree_pack kept one for these records: saves the pass over the targets */
-    const int per_cell = sinterp_env_int("GSL_SINTERP_BARY_PER_CELL", 64);   /* developer */
-    int st = sinterp_sort_reorder(ctx, d_targets, m, ttda, 2, per_cell, &srt, m_cap, slot,
-                                  have_table ? (const unsigned long long *)ctx->d_jumpt : (const unsigned long long *)NULL);
-    if (st) return st;
-    sorted = true;
-  }
-  int *d_jump = NULL;
-  int G = 0;
-  const unsigned long long *d_jbox = NULL;
-  if (have_table) {
-    /* the table tree_pack built for these records on this context */
-    d_jump = (int *)((char *)ctx->d_jumpt + 64);
-    d_jbox = (const unsigned long long *)ctx->d_jumpt;
-    G = ctx->jump_G;
-  } else if (sorted && !no_jump && n_nodes >= 2048 && slot < 0) {
-    /* records packed elsewhere (e.g. received by broadcast): a table over THIS batch's bounding box */
-    /* grid fine enough that a cell is about the size of the final triangles (~n_nodes/9 points) */
-    G = 32;
-    while (G < 1024 && (double)(2 * G) * (2 * G) <= (double)n_nodes) G *= 2;
-    void *jb = NULL;
-    int st = sinterp_sortbuf2(ctx, (size_t)G * G * sizeof(int), &jb);
-    if (st) return st;
-    d_jump = (int *)jb;
-    hipLaunchKernelGGL(jump_build_kernel, dim3((unsigned)((G * G + 255) / 256)), dim3(256), 0, ctx->stream, n_nodes,
-                       (const NodeRec *)d_records, h_scale[0], h_scale[1], (const unsigned long long *)srt.box, G, d_jump, (const int *)NULL, 0);
-    d_jbox = srt.box;
-  }
-  size_t blocks = (m + 255) / 256;
-  if (blocks > 65536) blocks = 65536;
-  const double *yt = sorted ? (const double *)srt.ys : d_targets;
-  const size_t yl = sorted ? (size_t)2 : ttda;
-  const bool via_map = sorted && srt.two_level;            /* results go to srt.res1 through srt.inv, see store_result */
-  double *vt = sorted ? (via_map ? srt.res1 : srt.vs) : d_values;
-  int *lt = sorted ? (via_map ? (int *)srt.inv : (int *)NULL) : d_leaf;
-  const int packed = (sorted && d_leaf != NULL ? 1 : 0) | (via_map ? 2 : 0);   /* 1: {value, leaf} pairs */
-  const int *perm = NULL;
-  const unsigned *m_dev = NULL;
-  bool side = false;
-  if (use_walk) {
-    hipLaunchKernelGGL(bary_start_kernel, dim3(n_slices), dim3(WALK_SLICE), 0, ctx->stream, n_nodes, (const NodeRec *)d_records,
-                       (const WalkRec *)wrec, (const LeafRec *)d_leaftab, h_scale[0], h_scale[1], yt, m, yl, vt, lt,
-                       (const int *)d_jump, G, d_jbox, todo_count, todo, wl, packed);
-    /* persistent waves, as many as are resident at once, drawing slices of the walker list from a counter */
-    static int s_cus[64], s_per_cu[64];   /* per device, queried once */
-    const int dv = ctx->device >= 0 && ctx->device < 64 ? ctx->device : 0;
-    if (s_cus[dv] == 0) {
-      int c = 0, w = 0;                        /* w: resident workgroups per CU (the LDS images bound it) */
-      HIP_OK(ctx, hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, ctx->device));
-      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&w, bary_walk_kernel, 64, 0) != hipSuccess || w < 1) w = 16;
-      s_per_cu[dv] = w;
-      s_cus[dv] = c > 0 ? c : 256;
-    }
-    const int cus = s_cus[dv];
-    int per_cu = s_per_cu[dv];
-    int batch = WALK_BATCH;
-    if (sinterp_env_int("GSL_SINTERP_WALK_WGS_PER_CU", 0) > 0) per_cu = sinterp_env_int("GSL_SINTERP_WALK_WGS_PER_CU", 0);
-    if (sinterp_env_int("GSL_SINTERP_WALK_BATCH", 0) > 0) batch = sinterp_env_int("GSL_SINTERP_WALK_BATCH", 0);
-    size_t wblocks = (size_t)(cus > 0 ? cus : 256) * (size_t)per_cu;
-    if (wblocks > n_slices) wblocks = n_slices;
-    hipLaunchKernelGGL(bary_walk_kernel, dim3((unsigned)wblocks), dim3(64), 0, ctx->stream, (const WalkRec *)wrec, wl, n_slices,
-                       todo_count, todo, (unsigned long long *)(todo_count + 2), batch);
-    hipStream_t fs = ctx->stream;
-    side = inner_side && ctx->side_stream != NULL;
-    if (side) {                                  /* the finish kernel beside the exact kernel (disjoint targets) */
-      HIP_OK(ctx, hipEventRecord(ctx->side_ev[2], ctx->stream));
-      HIP_OK(ctx, hipStreamWaitEvent(ctx->side_stream, ctx->side_ev[2], 0));
-      fs = ctx->side_stream;
-    }
-    hipLaunchKernelGGL(bary_finish_kernel, dim3(n_slices), dim3(WALK_SLICE), 0, fs, (const NodeRec *)d_records,
-                       (const LeafRec *)d_leaftab, h_scale[0], h_scale[1], wl, vt, lt, packed);
-    if (side) HIP_OK(ctx, hipEventRecord(ctx->side_ev[3], ctx->side_stream));
-    perm = todo;
-    m_dev = todo_count;
-    if (blocks > 2048) blocks = 2048;          /* the queue is normally (almost) empty */
-  }
-  if (no_fast)
-    hipLaunchKernelGGL(bary_eval_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, n_nodes,
-                       (const NodeRec *)d_records, (const LeafRec *)d_leaftab, h_scale[0], h_scale[1], yt, m, yl, vt, lt, d_count,
-                       perm, (const int *)d_jump, G, d_jbox, m_dev, packed);
-  else
-    hipLaunchKernelGGL(bary_eval_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, n_nodes,
-                       (const NodeRec *)d_records, (const LeafRec *)d_leaftab, h_scale[0], h_scale[1], yt, m, yl, vt, lt, d_count,
-                       perm, (const int *)d_jump, G, d_jbox, m_dev, packed);
-  LAUNCH_CHECK(ctx);
-  if (side) HIP_OK(ctx, hipStreamWaitEvent(ctx->stream, ctx->side_ev[3], 0));   /* join the finish kernel */
-  if (sorted) {
-    int st = (packed & 1) ? sinterp_unsort_packed(ctx, &srt, m, d_values, d_leaf) : sinterp_unsort(ctx, &srt, m, d_values, d_leaf);
-    if (st) return st;
-  }
-  return ST_SUCCESS;
+  BaryRoute r;
+  r.sort = sw.sort;
+  const bool fast = !sw.no_fast && sw.sort && m < 0x7fffffffULL;
+  r.loc = fast && !sw.no_lw && lw_here ? LOC_LEAFWALK
+        : fast && !sw.no_affine && m >= (size_t)n_nodes / 8 ? LOC_DAGWALK : LOC_EXACT;
+  r.jump = sw.no_jump ? JUMP_NONE
+         : packed_here ? JUMP_PACKED
+         : r.loc != LOC_LEAFWALK && sw.sort && n_nodes >= 2048 ? JUMP_BATCH : JUMP_NONE;
+  r.per_cell = r.loc == LOC_LEAFWALK ? 64 : sw.per_cell;
+  return r;
+}
+
+/* ctx->d_walk for one batch (byte offsets, sections 64-byte aligned): [queue counter; the walk kernel's slice counter at
+   byte 8] [todo: m positions] and, for the DAG walk, [walker list: y | st | k | per-slice counts] [n_nodes walk records].
+   bytes = 0: the exact kernel alone needs none of it. */
+struct WalkLayout { size_t o_todo, o_y, o_st, o_k, o_cnt, o_rec, bytes; };
+static WalkLayout walk_layout(BaryLocator loc, size_t m, int n_nodes)
+{
+  WalkLayout L;
+  memset(&L, 0, sizeof L);
+  if (loc == LOC_EXACT) return L;
+  L.o_todo = 64;
+  L.bytes = L.o_todo + m * sizeof(int);
+  if (loc == LOC_LEAFWALK) return L;
+  auto up = [](size_t b) { return (b + 63) & ~(size_t)63; };
+  const size_t mp = ((m + WALK_SLICE - 1) / WALK_SLICE) * WALK_SLICE;
+  L.o_y = up(L.bytes);
+  L.o_st = L.o_y + up(mp * sizeof(double2));
+  L.o_k = L.o_st + up(mp * sizeof(int4));
+  L.o_cnt = L.o_k + up(mp * sizeof(int));
+  L.o_rec = L.o_cnt + up((mp / WALK_SLICE) * sizeof(unsigned));
+  L.bytes = L.o_rec + up((size_t)n_nodes * sizeof(WalkRec));
+  return L;
 }
 
 /* developer / test hook: how many targets of the LAST large batch on this context the fast locator (certified leaf walk, or the
@@ -1772,50 +1722,35 @@ extern "C" int gsl_sinterp_hip_bary_last_queue(gsl_sinterp_hip_ctx *ctx, unsigne
   if (h_leafwalk) *h_leafwalk = ctx->lw_last;
   if (!ctx->d_walk) return ST_SUCCESS;
   HIP_OK(ctx, hipStreamSynchronize(ctx->stream));
-  HIP_OK(ctx, hipMemcpy(h_queued, ctx->lw_rec ? ctx->d_walk : (void *)((char *)ctx->d_walk + 0), sizeof(unsigned), hipMemcpyDeviceToHost));
+  HIP_OK(ctx, hipMemcpy(h_queued, ctx->d_walk, sizeof(unsigned), hipMemcpyDeviceToHost));
   return ST_SUCCESS;
 }
 
-/* a batch of >= 4096 targets through the certified leaf walk (records packed by tree_pack on this context) */
-static int bary_eval_leafwalk(gsl_sinterp_hip_ctx *ctx, int n_nodes, const void *d_records, const void *d_leaftab, const double *h_scale,
-                              const double *d_targets, size_t m, size_t ttda, double *d_values, int *d_leaf, unsigned long long *d_count)
+/* the side stream of the DAG walk (created at first use; without one everything runs on the main stream) */
+static bool bary_side_stream(gsl_sinterp_hip_ctx *ctx)
 {
-  const bool no_jump = SINTERP_ENV_ONCE("GSL_SINTERP_NO_JUMP");
-  const bool have_table = !no_jump && ctx->jump_rec == d_records && ctx->jump_nodes == n_nodes && ctx->d_jumpt;
-  sinterp_sorted srt;
-  int st = sinterp_sort_reorder(ctx, d_targets, m, ttda, 2, 64, &srt, m, -1,
-                                have_table ? (const unsigned long long *)ctx->d_jumpt : (const unsigned long long *)NULL);
-  if (st) return st;
-  void *wb = NULL;
-  st = sinterp_walkbuf(ctx, 64 + m * sizeof(int), &wb);
-  if (st) return st;
-  unsigned *todo_count = (unsigned *)wb;
-  int *todo = (int *)((char *)wb + 64);
-  HIP_OK(ctx, hipMemsetAsync(todo_count, 0, 64, ctx->stream));
-  const bool via_map = srt.two_level;
-  double *vt = via_map ? srt.res1 : srt.vs;
-  int *lt = via_map ? (int *)srt.inv : (int *)NULL;
-  const int packed = (d_leaf != NULL ? 1 : 0) | (via_map ? 2 : 0);
-  static const int lw_slices_env = sinterp_env_int("GSL_SINTERP_LW_SLICES", 0);   /* developer: 1 .. 8 */
-  const int lw_slices = lw_slices_env >= 1 && lw_slices_env <= LW_SLICES ? lw_slices_env : 1;
-  static const double lwF = sinterp_env_double("GSL_SINTERP_LW_F", 4.0);   /* developer */
-  ctx->lw_last = 1;
-  LwGrid lg;
-  lg.lo0 = ctx->lw_lo[0]; lg.lo1 = ctx->lw_lo[1]; lg.w0 = ctx->lw_w[0]; lg.w1 = ctx->lw_w[1]; lg.G = ctx->lw_Gs;
-  const size_t cells = (size_t)ctx->lw_Gs * ctx->lw_Gs;
-  const int *seed = (const int *)((const char *)ctx->d_lw_a + 64);
-  const unsigned *off = (const unsigned *)(seed + 2 * cells);
-  hipLaunchKernelGGL(leafwalk_kernel, dim3((unsigned)((m + (size_t)lw_slices * 256 - 1) / ((size_t)lw_slices * 256))), dim3(256), 0, ctx->stream, n_nodes, (const NodeRec *)d_records,
-                     (const LeafRec *)d_leaftab, seed, lg, off, (const double *)ctx->d_lw_lines, lwF, ctx->lw_c[0],
-                     ctx->lw_c[1], h_scale[0], h_scale[1], (const double *)srt.ys, m, (size_t)2, vt, lt, todo_count, todo, packed, lw_slices);
-  /* what the margin test (or the walk) left: the reference's arithmetic at every step of the DAG */
-  const int *d_jump = have_table ? (const int *)((const char *)ctx->d_jumpt + 64) : (const int *)NULL;
-  hipLaunchKernelGGL(bary_eval_kernel<true>, dim3(2048), dim3(256), 0, ctx->stream, n_nodes, (const NodeRec *)d_records,
-                     (const LeafRec *)d_leaftab, h_scale[0], h_scale[1], (const double *)srt.ys, m, (size_t)2, vt, lt, d_count, (const int *)todo,
-                     d_jump, have_table ? ctx->jump_G : 0, have_table ? (const unsigned long long *)ctx->d_jumpt : (const unsigned long long *)NULL,
-                     (const unsigned *)todo_count, packed);
-  LAUNCH_CHECK(ctx);
-  return (packed & 1) ? sinterp_unsort_packed(ctx, &srt, m, d_values, d_leaf) : sinterp_unsort(ctx, &srt, m, d_values, d_leaf);
+  if (!ctx->side_stream) {
+    if (hipStreamCreateWithFlags(&ctx->side_stream, hipStreamNonBlocking) != hipSuccess) ctx->side_stream = NULL;
+    for (int i = 0; i < 4 && ctx->side_stream; i++)
+      if (hipEventCreateWithFlags(&ctx->side_ev[i], hipEventDisableTiming) != hipSuccess) { (void)hipStreamDestroy(ctx->side_stream); ctx->side_stream = NULL; }
+  }
+  return ctx->side_stream != NULL;
+}
+
+/* resident workgroups of bary_walk_kernel on the context's device (queried once per device) */
+static int bary_walk_resident(gsl_sinterp_hip_ctx *ctx, int wgs_per_cu, size_t *out)
+{
+  static int s_cus[64], s_per_cu[64];
+  const int dv = ctx->device >= 0 && ctx->device < 64 ? ctx->device : 0;
+  if (s_cus[dv] == 0) {
+    int c = 0, w = 0;                        /* w: resident workgroups per CU (the LDS images bound it) */
+    HIP_OK(ctx, hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, ctx->device));
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&w, bary_walk_kernel, 64, 0) != hipSuccess || w < 1) w = 16;
+    s_per_cu[dv] = w;
+    s_cus[dv] = c > 0 ? c : 256;
+  }
+  *out = (size_t)s_cus[dv] * (size_t)(wgs_per_cu > 0 ? wgs_per_cu : s_per_cu[dv]);
+  return ST_SUCCESS;
 }
 
 extern "C" int gsl_sinterp_hip_bary_eval(gsl_sinterp_hip_ctx *ctx, int n_nodes, const void *d_records,
@@ -1831,83 +1766,115 @@ extern "C" int gsl_sinterp_hip_bary_eval(gsl_sinterp_hip_ctx *ctx, int n_nodes, 
   if (m == 0) return ST_SUCCESS;
   unsigned long long *d_count = (unsigned long long *)ctx->d_scratch;
   HIP_OK(ctx, hipMemsetAsync(d_count, 0, sizeof(unsigned long long), ctx->stream));
-  /* m >= 4096: the targets are gathered into grid-cell order, swept contiguously, and the results
-     un-sorted afterwards (see sinterp_sort_reorder) */
-  const bool no_fast = SINTERP_ENV_ONCE("GSL_SINTERP_NO_FASTDIV");
-  const bool no_affine = SINTERP_ENV_ONCE("GSL_SINTERP_NO_AFFINE_WALK");
-  const bool no_side = SINTERP_ENV_ONCE("GSL_SINTERP_NO_SIDE_STREAM");
-  const bool will_sort = m >= 4096 && !sinterp_env_flag("GSL_SINTERP_NO_SORT");
-  /* batches in cell order on records this context packed: the certified leaf walk (round 4) */
-  const bool no_lw = SINTERP_ENV_ONCE("GSL_SINTERP_NO_LEAFWALK");
-  if (!no_lw && !no_fast && will_sort && m < 0x7fffffffULL && ctx->lw_rec == d_records && ctx->lw_nodes == n_nodes && ctx->d_lw_lines) {
-    int st = bary_eval_leafwalk(ctx, n_nodes, d_records, d_leaftab, h_scale, d_targets, m, ttda, d_values, d_leaf, d_count);
+  const BarySwitches sw = bary_switches(m);
+  const BaryRoute rt = bary_route(m, n_nodes, ctx->jump_rec == d_records && ctx->jump_nodes == n_nodes && ctx->d_jumpt,
+                                  ctx->lw_rec == d_records && ctx->lw_nodes == n_nodes && ctx->d_lw_lines, sw);
+  ctx->lw_last = rt.loc == LOC_LEAFWALK;
+  const NodeRec *rec = (const NodeRec *)d_records;
+  const LeafRec *tab = (const LeafRec *)d_leaftab;
+  const double s0 = h_scale[0], s1 = h_scale[1];
+  int st;
+
+  const WalkLayout L = walk_layout(rt.loc, m, n_nodes);
+  char *wb = NULL;
+  if (L.bytes) {
+    void *p = NULL;
+    st = sinterp_walkbuf(ctx, L.bytes, &p);
     if (st) return st;
-    if (h_n_outside) {
-      unsigned long long cnt = 0;
-      HIP_OK(ctx, hipStreamSynchronize(ctx->stream));
-      HIP_OK(ctx, hipMemcpy(&cnt, d_count, sizeof cnt, hipMemcpyDeviceToHost));
-      HIP_OK(ctx, hipStreamSynchronize(ctx->stream));
-      *h_n_outside = (long long)cnt;
-      if (cnt) return sinterp_fail(ctx, ST_EDOM, "bary_eval: target(s) outside the caging simplex", hipSuccess, __FILE__, __LINE__);
-    }
-    return ST_SUCCESS;
+    wb = (char *)p;
+    HIP_OK(ctx, hipMemsetAsync(wb, 0, 64, ctx->stream));
   }
-  /* Large batches: per-batch affine walk records (a pass over the node records: ~n_nodes x 128 bytes) and the
-     certified walk; what it could not certify is queued for the exact kernel.  The results do not depend on
-     which kernel walked a target. */
-  const bool use_walk = !no_fast && !no_affine && will_sort && m < 0x7fffffffULL && m >= (size_t)n_nodes / 8;
-  if (!no_side && use_walk && !ctx->side_stream) {
-    if (hipStreamCreateWithFlags(&ctx->side_stream, hipStreamNonBlocking) != hipSuccess) ctx->side_stream = NULL;
-    for (int i = 0; i < 4 && ctx->side_stream; i++)
-      if (hipEventCreateWithFlags(&ctx->side_ev[i], hipEventDisableTiming) != hipSuccess) { (void)hipStreamDestroy(ctx->side_stream); ctx->side_stream = NULL; }
-  }
-  const bool side = use_walk && !no_side && ctx->side_stream != NULL;
-  /* (cutting a large batch into chunks on two streams was measured slower in round 3 -- DESIGN.md 6 -- and removed) */
-  const int n_chunks = 1;
-  const size_t m_cap = m;
-  WalkRec *wrec = NULL;
-  char *wsec[2] = {NULL, NULL};
-  if (use_walk) {
-    const size_t mp = ((m_cap + WALK_SLICE - 1) / WALK_SLICE) * WALK_SLICE;
-    auto up = [](size_t b) { return (b + 63) & ~(size_t)63; };
-    const size_t o_rec = up((size_t)n_nodes * sizeof(WalkRec));
-    const size_t sec = 64 + up(m_cap * sizeof(int)) + up(mp * sizeof(double2)) + up(mp * sizeof(int4)) + up(mp * sizeof(int)) +
-                       up((mp / WALK_SLICE) * sizeof(unsigned));
-    void *wb = NULL;
-    int st = sinterp_walkbuf(ctx, o_rec + sec * (n_chunks > 1 ? 2 : 1), &wb);
-    if (st) return st;
-    wrec = (WalkRec *)wb;
-    wsec[0] = (char *)wb + o_rec;
-    wsec[1] = n_chunks > 1 ? wsec[0] + sec : wsec[0];
+  unsigned *todo_count = (unsigned *)wb;                  /* NULL: the exact kernel takes every target */
+  int *todo = wb ? (int *)(wb + L.o_todo) : NULL;
+  WalkRec *wrec = rt.loc == LOC_DAGWALK ? (WalkRec *)(wb + L.o_rec) : NULL;
+  const bool side = rt.loc == LOC_DAGWALK && !sw.no_side && bary_side_stream(ctx);
+  if (rt.loc == LOC_DAGWALK) {
+    /* the walk records are built beside the main stream, which waits for them before it goes on */
     hipStream_t ps = ctx->stream;
     if (side) {
       HIP_OK(ctx, hipEventRecord(ctx->side_ev[0], ctx->stream));          /* after whatever produced the records */
       HIP_OK(ctx, hipStreamWaitEvent(ctx->side_stream, ctx->side_ev[0], 0));
       ps = ctx->side_stream;
     }
-    hipLaunchKernelGGL(walk_pack_kernel, dim3((unsigned)((n_nodes + 255) / 256)), dim3(256), 0, ps, n_nodes,
-                       (const NodeRec *)d_records, h_scale[0], h_scale[1], wrec);
+    hipLaunchKernelGGL(walk_pack_kernel, dim3((unsigned)((n_nodes + 255) / 256)), dim3(256), 0, ps, n_nodes, rec, s0, s1, wrec);
     LAUNCH_CHECK(ctx);
-    if (side) HIP_OK(ctx, hipEventRecord(ctx->side_ev[1], ctx->side_stream));
+    if (side) {
+      HIP_OK(ctx, hipEventRecord(ctx->side_ev[1], ctx->side_stream));
+      HIP_OK(ctx, hipStreamWaitEvent(ctx->stream, ctx->side_ev[1], 0));
+    }
   }
-  int st = ST_SUCCESS;
-  {
-    /* the walk records are built on the side stream while the targets are sorted on the main one; the sort comes
-       first inside bary_eval_part, so the join is placed in front of it only when there is no side stream */
-    if (side) HIP_OK(ctx, hipStreamWaitEvent(ctx->stream, ctx->side_ev[1], 0));
-    st = bary_eval_part(ctx, n_nodes, d_records, d_leaftab, h_scale, d_targets, m, ttda, d_values, d_leaf, d_count, wrec, wsec[0], m_cap,
-                        -1, side);
-  }
+
+  /* m >= 4096: the targets are gathered into grid-cell order, swept contiguously, and the results un-sorted afterwards
+     (see sinterp_sort_reorder); binned by the data's bounding box when tree_pack kept one: saves the pass over the targets */
+  const unsigned long long *d_jbox = rt.jump == JUMP_PACKED ? (const unsigned long long *)ctx->d_jumpt : (const unsigned long long *)NULL;
+  sinterp_route r;
+  st = sinterp_route_begin(ctx, d_targets, m, ttda, 2, rt.per_cell, d_jbox, d_values, d_leaf, rt.sort, &r);
   if (st) return st;
-  if (h_n_outside) {
-    unsigned long long cnt = 0;
-    HIP_OK(ctx, hipStreamSynchronize(ctx->stream));
-    HIP_OK(ctx, hipMemcpy(&cnt, d_count, sizeof cnt, hipMemcpyDeviceToHost));
-    HIP_OK(ctx, hipStreamSynchronize(ctx->stream));
-    *h_n_outside = (long long)cnt;
-    if (cnt) return sinterp_fail(ctx, ST_EDOM, "bary_eval: target(s) outside the caging simplex", hipSuccess, __FILE__, __LINE__);
+  const int *d_jump = NULL;
+  int G = 0;
+  if (rt.jump == JUMP_PACKED) {
+    d_jump = (const int *)((const char *)ctx->d_jumpt + 64);
+    G = ctx->jump_G;
+  } else if (rt.jump == JUMP_BATCH) {
+    /* grid fine enough that a cell is about the size of the final triangles (~n_nodes/9 points) */
+    G = 32;
+    while (G < 1024 && (double)(2 * G) * (2 * G) <= (double)n_nodes) G *= 2;
+    void *jb = NULL;
+    st = sinterp_sortbuf2(ctx, (size_t)G * G * sizeof(int), &jb);
+    if (st) return st;
+    d_jbox = r.srt.box;
+    hipLaunchKernelGGL(jump_build_kernel, dim3((unsigned)((G * G + 255) / 256)), dim3(256), 0, ctx->stream, n_nodes, rec, s0, s1,
+                       d_jbox, G, (int *)jb, (const int *)NULL, 0);
+    d_jump = (const int *)jb;
   }
-  return ST_SUCCESS;
+
+  size_t blocks = (m + 255) / 256;                        /* of the exact kernel */
+  if (blocks > 65536) blocks = 65536;
+  if (rt.loc == LOC_LEAFWALK) {
+    LwGrid lg;
+    lg.lo0 = ctx->lw_lo[0]; lg.lo1 = ctx->lw_lo[1]; lg.w0 = ctx->lw_w[0]; lg.w1 = ctx->lw_w[1]; lg.G = ctx->lw_Gs;
+    const size_t cells = (size_t)ctx->lw_Gs * ctx->lw_Gs, per_wg = (size_t)sw.lw_slices * 256;
+    const int *seed = (const int *)((const char *)ctx->d_lw_a + 64);
+    const unsigned *off = (const unsigned *)(seed + 2 * cells);
+    hipLaunchKernelGGL(leafwalk_kernel, dim3((unsigned)((m + per_wg - 1) / per_wg)), dim3(256), 0, ctx->stream, n_nodes, rec, tab, seed, lg,
+                       off, (const double *)ctx->d_lw_lines, sw.lw_f, ctx->lw_c[0], ctx->lw_c[1], s0, s1, r.y, m, r.ytda, r.values,
+                       r.leaf, todo_count, todo, r.packed, sw.lw_slices);
+    blocks = 2048;                             /* what the margin test (or the walk) left: normally ~1 % */
+  } else if (rt.loc == LOC_DAGWALK) {
+    const unsigned n_slices = (unsigned)((m + WALK_SLICE - 1) / WALK_SLICE);
+    WalkList wl;
+    wl.y = (double2 *)(wb + L.o_y); wl.st = (int4 *)(wb + L.o_st); wl.k = (int *)(wb + L.o_k); wl.count = (unsigned *)(wb + L.o_cnt);
+    hipLaunchKernelGGL(bary_start_kernel, dim3(n_slices), dim3(WALK_SLICE), 0, ctx->stream, n_nodes, rec, (const WalkRec *)wrec, tab, s0, s1, r.y, m,
+                       r.ytda, r.values, r.leaf, d_jump, G, d_jbox, todo_count, todo, wl, r.packed);
+    /* persistent waves, as many as are resident at once, drawing slices of the walker list from a counter */
+    size_t wblocks = 0;
+    st = bary_walk_resident(ctx, sw.walk_wgs_per_cu, &wblocks);
+    if (st) return st;
+    if (wblocks > n_slices) wblocks = n_slices;
+    hipLaunchKernelGGL(bary_walk_kernel, dim3((unsigned)wblocks), dim3(64), 0, ctx->stream, (const WalkRec *)wrec, wl, n_slices, todo_count, todo,
+                       (unsigned long long *)(todo_count + 2), sw.walk_batch);
+    hipStream_t fs = ctx->stream;
+    if (side) {                                  /* the finish kernel beside the exact kernel (disjoint targets) */
+      HIP_OK(ctx, hipEventRecord(ctx->side_ev[2], ctx->stream));
+      HIP_OK(ctx, hipStreamWaitEvent(ctx->side_stream, ctx->side_ev[2], 0));
+      fs = ctx->side_stream;
+    }
+    hipLaunchKernelGGL(bary_finish_kernel, dim3(n_slices), dim3(WALK_SLICE), 0, fs, rec, tab, s0, s1, wl, r.values, r.leaf, r.packed);
+    if (side) HIP_OK(ctx, hipEventRecord(ctx->side_ev[3], ctx->side_stream));
+    if (blocks > 2048) blocks = 2048;          /* the queue is normally (almost) empty */
+  }
+  /* the reference's arithmetic at every step of the DAG: every target, or the locator's queue */
+  if (sw.no_fast)
+    hipLaunchKernelGGL(bary_eval_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, n_nodes, rec, tab, s0, s1, r.y, m,
+                       r.ytda, r.values, r.leaf, d_count, (const int *)todo, d_jump, G, d_jbox, (const unsigned *)todo_count, r.packed);
+  else
+    hipLaunchKernelGGL(bary_eval_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, n_nodes, rec, tab, s0, s1, r.y, m,
+                       r.ytda, r.values, r.leaf, d_count, (const int *)todo, d_jump, G, d_jbox, (const unsigned *)todo_count, r.packed);
+  LAUNCH_CHECK(ctx);
+  if (side) HIP_OK(ctx, hipStreamWaitEvent(ctx->stream, ctx->side_ev[3], 0));   /* join the finish kernel */
+  st = sinterp_route_end(ctx, &r, m, d_values, d_leaf);
+  if (st) return st;
+  return sinterp_outside_count(ctx, d_count, h_n_outside, "bary_eval: target(s) outside the caging simplex");
 }
 
 
@@ -2099,6 +2066,13 @@ mesh_scan_kernel(int n_tri, const NodeRec *__restrict__ rec, const LeafRec *__re
   }
 }
 
+static MeshGrid mesh_grid(const double *h_geom, int G)
+{
+  MeshGrid mg;
+  mg.lo0 = h_geom[4]; mg.lo1 = h_geom[5]; mg.w0 = (h_geom[6] - h_geom[4]) / G; mg.w1 = (h_geom[7] - h_geom[5]) / G; mg.G = G;
+  return mg;
+}
+
 /* h_geom[8] = shift(2), scale(2), bounding box of the points lo0, lo1, hi0, hi1; d_seed: 2 G^2 ints */
 extern "C" int gsl_sinterp_hip_mesh_pack(gsl_sinterp_hip_ctx *ctx, int n_tri, const int *d_tri, const int *d_nbr, int n_points,
                                          const double *d_points, const double *h_geom, int G, void *d_records, int *d_seed)
@@ -2114,8 +2088,7 @@ extern "C" int gsl_sinterp_hip_mesh_pack(gsl_sinterp_hip_ctx *ctx, int n_tri, co
   g.scale[0] = h_geom[2]; g.scale[1] = h_geom[3];
   hipLaunchKernelGGL(tree_pack_kernel, dim3((n_tri + 255) / 256), dim3(256), 0, ctx->stream, n_tri, (const int *)NULL, d_tri, d_nbr,
                      n_points, d_points, g, (NodeRec *)d_records);
-  MeshGrid mg;
-  mg.lo0 = h_geom[4]; mg.lo1 = h_geom[5]; mg.w0 = (h_geom[6] - h_geom[4]) / G; mg.w1 = (h_geom[7] - h_geom[5]) / G; mg.G = G;
+  const MeshGrid mg = mesh_grid(h_geom, G);
   const size_t cells = (size_t)G * G;
   hipLaunchKernelGGL(mesh_seed_init_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, ctx->stream, d_seed + cells, cells);
   hipLaunchKernelGGL(mesh_seed_kernel, dim3((n_tri + 255) / 256), dim3(256), 0, ctx->stream, n_tri, d_tri, n_points, d_points, mg,
@@ -2144,42 +2117,22 @@ extern "C" int gsl_sinterp_hip_mesh_eval(gsl_sinterp_hip_ctx *ctx, int n_tri, co
   if (st) return st;
   unsigned *todo = (unsigned *)buf;
   HIP_OK(ctx, hipMemsetAsync(todo, 0, sizeof(unsigned), ctx->stream));
-  MeshGrid mg;
-  mg.lo0 = h_geom[4]; mg.lo1 = h_geom[5]; mg.w0 = (h_geom[6] - h_geom[4]) / G; mg.w1 = (h_geom[7] - h_geom[5]) / G; mg.G = G;
   /* batches of >= 4096 targets: the DAG path's reorder (cell order, two-level from 2^18 targets), results through the
      order's map, un-sorted afterwards.  A result depends on (mesh, target) only: same bits either way. */
-  const bool will_sort = m >= 4096 && !sinterp_env_flag("GSL_SINTERP_NO_SORT");
-  sinterp_sorted srt;
-  if (will_sort) {
-    st = sinterp_sort_reorder(ctx, d_targets, m, ttda, 2, 64, &srt, m, -1, (const unsigned long long *)NULL);
-    if (st) return st;
-  }
-  const double *yt = will_sort ? (const double *)srt.ys : d_targets;
-  const size_t yl = will_sort ? (size_t)2 : ttda;
-  const bool via_map = will_sort && srt.two_level;
-  double *vt = will_sort ? (via_map ? srt.res1 : srt.vs) : d_values;
-  int *lt = will_sort ? (via_map ? (int *)srt.inv : (int *)NULL) : d_tri;
-  const int packed = (will_sort && d_tri != NULL ? 1 : 0) | (via_map ? 2 : 0);
+  sinterp_route r;
+  st = sinterp_route_begin(ctx, d_targets, m, ttda, 2, 64, (const unsigned long long *)NULL, d_values, d_tri, sinterp_sort_wanted(m), &r);
+  if (st) return st;
   /* a straight walk from a grid seed crosses a handful of triangles; the bound only guards against cycles (an imported
      non-Delaunay mesh can make the walk circle: such targets go to the exhaustive scan after 64 + 4 G steps at most) */
   const int max_steps = 64 + 4 * G;
   hipLaunchKernelGGL(mesh_walk_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, ctx->stream, n_tri, (const NodeRec *)d_records,
-                     (const LeafRec *)d_leaftab, d_seed, mg, h_geom[2], h_geom[3], convex, max_steps, yt, m, yl, vt,
-                     lt, d_count, todo, packed);
+                     (const LeafRec *)d_leaftab, d_seed, mesh_grid(h_geom, G), h_geom[2], h_geom[3], convex, max_steps, r.y, m, r.ytda,
+                     r.values, r.leaf, d_count, todo, r.packed);
   hipLaunchKernelGGL(mesh_scan_kernel, dim3(256), dim3(256), 0, ctx->stream, n_tri, (const NodeRec *)d_records,
-                     (const LeafRec *)d_leaftab, h_geom[2], h_geom[3], yt, yl, vt, lt, d_count,
-                     (const unsigned *)todo, packed);
+                     (const LeafRec *)d_leaftab, h_geom[2], h_geom[3], r.y, r.ytda, r.values, r.leaf, d_count,
+                     (const unsigned *)todo, r.packed);
   LAUNCH_CHECK(ctx);
-  if (will_sort) {
-    st = (packed & 1) ? sinterp_unsort_packed(ctx, &srt, m, d_values, d_tri) : sinterp_unsort(ctx, &srt, m, d_values, d_tri);
-    if (st) return st;
-  }
-  if (h_n_outside) {
-    unsigned long long c = 0;
-    HIP_OK(ctx, hipStreamSynchronize(ctx->stream));
-    HIP_OK(ctx, hipMemcpy(&c, d_count, sizeof c, hipMemcpyDeviceToHost));
-    *h_n_outside = (long long)c;
-    if (c) { snprintf(ctx->err, sizeof ctx->err, "mesh_eval: %llu target(s) outside the triangulation", c); return ST_EDOM; }
-  }
-  return ST_SUCCESS;
+  st = sinterp_route_end(ctx, &r, m, d_values, d_tri);
+  if (st) return st;
+  return sinterp_outside_count(ctx, d_count, h_n_outside, "mesh_eval: %llu target(s) outside the triangulation");
 }

@@ -27,7 +27,7 @@ struct gsl_sinterp_hip_ctx {
   size_t aux_bytes;
   void *d_inv;              /* inverted 64x64 diagonal blocks of the triangular sweeps */
   size_t inv_bytes;
-  void *d_sort;             /* target permutation + cell counters (sort.hip) */
+  void *d_sort;             /* target permutation / reordered targets + cell counters of ONE batch (sort.hip) */
   size_t sort_bytes;
   void *d_sort2;            /* the same for the centres of the Gaussian sweep */
   size_t sort2_bytes;
@@ -48,7 +48,8 @@ struct gsl_sinterp_hip_ctx {
   CentKey local_key;
   int local_g;
   unsigned long long local_packs;
-  void *d_walk;             /* affine walk records + queue of the barycentric walk (bary.hip), rebuilt per batch */
+  void *d_walk;             /* queue counter + queue of a located sweep, then the barycentric DAG walk's records and lists
+                               (bary.hip: WalkLayout), rebuilt per batch */
   size_t walk_bytes;
   hipStream_t side_stream;  /* bary.hip: independent kernels of one evaluation run beside the main stream */
   hipEvent_t side_ev[4];    /* fork / join events of the side stream (created with the stream) */
@@ -246,7 +247,9 @@ int sinterp_sort_targets(gsl_sinterp_hip_ctx *ctx, const double *d_y, size_t m, 
 /* The same sort, but the targets are physically gathered into cell order (dense [m][dim]) and the
    results come back through sinterp_unsort: the sweep kernels then read and write contiguously, the
    only scattered accesses are one 8*dim-byte write per target here and one 8(+4)-byte READ per target in
-   the un-sort (a permutation-indirect kernel pays a scattered read AND partial-sector scattered writes). */
+   the un-sort (a permutation-indirect kernel pays a scattered read AND partial-sector scattered writes).
+   The arrays live in the context's sort buffer, laid out for this batch alone: they are valid until the next sort on
+   the context. */
 struct sinterp_sorted {
   double *ys;                   /* [m][dim] targets in cell order */
   double *vs;                   /* [m] values in cell order (filled by the sweep); room for [m] {value, leaf} pairs */
@@ -260,7 +263,7 @@ struct sinterp_sorted {
   unsigned *tl_cnt; unsigned tl_nb, tl_nwg, tl_ch;   /* (internal: first coarse position of every (bin, workgroup) run, for the staged un-sort) */
 };
 int sinterp_sort_reorder(gsl_sinterp_hip_ctx *ctx, const double *d_y, size_t m, size_t ytda, int dim, int per_cell,
-                         sinterp_sorted *out, size_t m_cap, int slot, const unsigned long long *box_in);
+                         sinterp_sorted *out, const unsigned long long *box_in);
 /* whether a batch of m targets takes the two-level route (results through inv / res1) */
 bool sinterp_sort_reorder_is_two_level(size_t m);
 int sinterp_unsort(gsl_sinterp_hip_ctx *ctx, const sinterp_sorted *s, size_t m, double *d_values, int *d_leaf);
@@ -296,6 +299,23 @@ __device__ __forceinline__ void store_result(double *__restrict__ values, int *_
     if (leaf_out) leaf_out[k] = leaf;
   }
 }
+/* Host side of the same convention (sort.hip): what a located sweep reads and where it stores.  Unsorted: the caller's
+   arrays, packed = 0.  Sorted, one level: values = srt.vs, {value, leaf} pairs (bit 0) when a leaf output is wanted, no
+   leaf array.  Sorted, two levels: values = srt.res1, leaf = srt.inv reinterpreted (bit 1), pairs likewise. */
+struct sinterp_route {
+  const double *y; size_t ytda;   /* the targets as the kernels see them */
+  double *values; int *leaf;      /* store_result's arguments ... */
+  int packed;                     /* ... and its mode */
+  bool sorted; sinterp_sorted srt;
+};
+/* the batch size from which a located sweep reorders its targets, unless GSL_SINTERP_NO_SORT=1 (read per call) */
+bool sinterp_sort_wanted(size_t m);
+int sinterp_route_begin(gsl_sinterp_hip_ctx *ctx, const double *d_targets, size_t m, size_t ttda, int dim, int per_cell,
+                        const unsigned long long *box_in, double *d_values, int *d_leaf, bool sort, sinterp_route *r);
+/* the un-sort that matches r->packed into the caller's arrays, or nothing */
+int sinterp_route_end(gsl_sinterp_hip_ctx *ctx, const sinterp_route *r, size_t m, double *d_values, int *d_leaf);
+/* h_n_outside != NULL: waits for the stream, *h_n_outside = *d_count, and ST_EDOM with the message `what` when it is not 0 */
+int sinterp_outside_count(gsl_sinterp_hip_ctx *ctx, const unsigned long long *d_count, long long *h_n_outside, const char *what);
 /* sort.hip: bounding box of n points as order-preserving keys, box[2c] = min, box[2c+1] = max (device, 48 bytes) */
 int sinterp_bbox_keys(gsl_sinterp_hip_ctx *ctx, const double *d_p, size_t n, size_t tda, int dim, unsigned long long *d_box);
 int sinterp_centbuf(gsl_sinterp_hip_ctx *ctx, size_t bytes, void **out);

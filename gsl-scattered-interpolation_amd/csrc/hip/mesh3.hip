@@ -388,38 +388,20 @@ extern "C" int gsl_sinterp_hip_mesh3_eval(gsl_sinterp_hip_ctx *ctx, int n_tet, c
   HIP_OK(ctx, hipMemsetAsync(todo, 0, sizeof(unsigned), ctx->stream));
   /* batches of >= 4096 targets: the 2-D path's reorder (cell order, two-level from 2^18 targets), results through the
      order's map, un-sorted afterwards.  A result depends on (mesh, target) only: same bits either way. */
-  const bool will_sort = m >= 4096 && !sinterp_env_flag("GSL_SINTERP_NO_SORT");
-  sinterp_sorted srt;
-  if (will_sort) {
-    st = sinterp_sort_reorder(ctx, d_targets, m, ttda, 3, 64, &srt, m, -1, (const unsigned long long *)NULL);
-    if (st) return st;
-  }
-  const double *yt = will_sort ? (const double *)srt.ys : d_targets;
-  const size_t yl = will_sort ? (size_t)3 : ttda;
-  const bool via_map = will_sort && srt.two_level;
-  double *vt = will_sort ? (via_map ? srt.res1 : srt.vs) : d_values;
-  int *lt = will_sort ? (via_map ? (int *)srt.inv : (int *)NULL) : d_tet;
-  const int packed = (will_sort && d_tet != NULL ? 1 : 0) | (via_map ? 2 : 0);
+  sinterp_route r;
+  st = sinterp_route_begin(ctx, d_targets, m, ttda, 3, 64, (const unsigned long long *)NULL, d_values, d_tet, sinterp_sort_wanted(m), &r);
+  if (st) return st;
   /* a straight walk from a grid seed crosses a handful of tetrahedra; the bound only guards against cycles and long
      detours in badly shaped (non-Delaunay) input: whatever exceeds it without a best violation <= MESH_GAP is scanned */
   const int max_steps = 64 + 6 * G;
   const Mesh3Geom geo = mesh3_geom(h_geom);
   hipLaunchKernelGGL(mesh3_walk_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, ctx->stream, n_tet, (const TetRec *)d_records,
-                     (const TetTab *)d_table, d_seed, mesh3_grid(h_geom, G), geo, convex, max_steps, yt, m, yl, vt, lt, d_count, todo,
-                     packed);
+                     (const TetTab *)d_table, d_seed, mesh3_grid(h_geom, G), geo, convex, max_steps, r.y, m, r.ytda, r.values, r.leaf,
+                     d_count, todo, r.packed);
   hipLaunchKernelGGL(mesh3_scan_kernel, dim3(256), dim3(256), 0, ctx->stream, n_tet, (const TetRec *)d_records, (const TetTab *)d_table,
-                     geo, yt, yl, vt, lt, d_count, (const unsigned *)todo, packed);
+                     geo, r.y, r.ytda, r.values, r.leaf, d_count, (const unsigned *)todo, r.packed);
   LAUNCH_CHECK(ctx);
-  if (will_sort) {
-    st = (packed & 1) ? sinterp_unsort_packed(ctx, &srt, m, d_values, d_tet) : sinterp_unsort(ctx, &srt, m, d_values, d_tet);
-    if (st) return st;
-  }
-  if (h_n_outside) {
-    unsigned long long c = 0;
-    HIP_OK(ctx, hipStreamSynchronize(ctx->stream));
-    HIP_OK(ctx, hipMemcpy(&c, d_count, sizeof c, hipMemcpyDeviceToHost));
-    *h_n_outside = (long long)c;
-    if (c) { snprintf(ctx->err, sizeof ctx->err, "mesh3_eval: %llu target(s) outside the tetrahedral mesh", c); return ST_EDOM; }
-  }
-  return ST_SUCCESS;
+  st = sinterp_route_end(ctx, &r, m, d_values, d_tet);
+  if (st) return st;
+  return sinterp_outside_count(ctx, d_count, h_n_outside, "mesh3_eval: %llu target(s) outside the tetrahedral mesh");
 }

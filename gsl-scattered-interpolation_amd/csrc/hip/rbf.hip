@@ -27,8 +27,7 @@ template <class F> static auto with_dim_tile(int dim, int ct, F &&f)
   }
 }
 
-/* developer switches: "1" turns the target sort (read at every call) / the tile culling (read once per process) off */
-static bool no_sort() { return sinterp_env_flag("GSL_SINTERP_NO_SORT"); }
+/* developer switch: "1" turns the tile culling (read once per process) off */
 static bool no_cull() { return SINTERP_ENV_ONCE("GSL_SINTERP_NO_CULL"); }
 
 struct RbfTables {
@@ -921,7 +920,7 @@ static int rbf_sweep_dispatch(gsl_sinterp_hip_ctx *ctx, int kind, const sweep_jo
 
 /* Gaussian / Wendland: group the targets spatially so that whole waves skip negligible (Wendland: zero) terms
    together (the kinds that are not culled take every term: nothing to skip, no sort) */
-static bool wants_target_sort(int kind, size_t m) { return kind_is_culled(kind) && m >= 4096 && !no_sort(); }
+static bool wants_target_sort(int kind, size_t m) { return kind_is_culled(kind) && sinterp_sort_wanted(m); }
 
 extern "C" int gsl_sinterp_hip_rbf_eval(gsl_sinterp_hip_ctx *ctx, int kind, double eps, const double *d_x, size_t n,
                                         int dim, size_t xtda, const double *d_w, const double *d_y, size_t m,
@@ -949,7 +948,7 @@ extern "C" int gsl_sinterp_hip_rbf_eval_model(gsl_sinterp_hip_ctx *ctx, int kind
        the permutation route (histogram atomics, perm scatter, gather + scatter inside the sweep) */
     if (sinterp_sort_reorder_is_two_level(m)) {
       sinterp_sorted srt;
-      st = sinterp_sort_reorder(ctx, d_y, m, ytda, dim, 64, &srt, m, -1, (const unsigned long long *)NULL);
+      st = sinterp_sort_reorder(ctx, d_y, m, ytda, dim, 64, &srt, (const unsigned long long *)NULL);
       if (st) return st;
       if (srt.two_level) {
         j.y = (const double *)srt.ys; j.ytda = (size_t)dim; j.s = srt.res1; j.omap = (const unsigned *)srt.inv;

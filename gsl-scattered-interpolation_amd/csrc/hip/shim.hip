@@ -260,68 +260,7 @@ int sinterp_capture_end(gsl_sinterp_hip_ctx *ctx, hipStream_t saved, int which, 
   return ST_SUCCESS;
 }
 
-int sinterp_workspace(gsl_sinterp_hip_ctx *ctx, size_t bytes, void **out)
-{
-  if (bytes > ctx->work_bytes) {
-    if (ctx->d_work) {
-      HIP_OK(ctx, hipStreamSynchronize(ctx->stream));
-      HIP_OK(ctx, hipFree(ctx->d_work));
-      ctx->d_work = NULL; ctx->work_bytes = 0;
-    }
-    HIP_OK(ctx, hipMalloc(&ctx->d_work, bytes));
-    ctx->work_bytes = bytes;
-  }
-  *out = ctx->d_work;
-  return ST_SUCCESS;
-}
-
-int sinterp_aux(gsl_sinterp_hip_ctx *ctx, size_t bytes, void **out)
-{
-  if (bytes > ctx->aux_bytes) {
-    if (ctx->d_aux) {
-      HIP_OK(ctx, hipStreamSynchronize(ctx->stream));
-      HIP_OK(ctx, hipFree(ctx->d_aux));
-      ctx->d_aux = NULL; ctx->aux_bytes = 0;
-    }
-    HIP_OK(ctx, hipMalloc(&ctx->d_aux, bytes));
-    ctx->aux_bytes = bytes;
-  }
-  *out = ctx->d_aux;
-  return ST_SUCCESS;
-}
-
-int sinterp_invbuf(gsl_sinterp_hip_ctx *ctx, size_t bytes, void **out)
-{
-  if (bytes > ctx->inv_bytes) {
-    if (ctx->d_inv) {
-      HIP_OK(ctx, hipStreamSynchronize(ctx->stream));
-      HIP_OK(ctx, hipFree(ctx->d_inv));
-      ctx->d_inv = NULL; ctx->inv_bytes = 0;
-      for (int i = 2; i < 4; i++)                      /* cached sweep graphs bake this pointer */
-        if (ctx->graph[i].exec) { (void)hipGraphExecDestroy(ctx->graph[i].exec); ctx->graph[i].exec = NULL; }
-    }
-    HIP_OK(ctx, hipMalloc(&ctx->d_inv, bytes));
-    ctx->inv_bytes = bytes;
-  }
-  *out = ctx->d_inv;
-  return ST_SUCCESS;
-}
-
-int sinterp_sortbuf(gsl_sinterp_hip_ctx *ctx, size_t bytes, void **out)
-{
-  if (bytes > ctx->sort_bytes) {
-    if (ctx->d_sort) {
-      HIP_OK(ctx, hipStreamSynchronize(ctx->stream));
-      HIP_OK(ctx, hipFree(ctx->d_sort));
-      ctx->d_sort = NULL; ctx->sort_bytes = 0;
-    }
-    HIP_OK(ctx, hipMalloc(&ctx->d_sort, bytes));
-    ctx->sort_bytes = bytes;
-  }
-  *out = ctx->d_sort;
-  return ST_SUCCESS;
-}
-
+/* grow-only buffers owned by the context: a larger request replaces the buffer (after the stream has drained) */
 static int grow_buf(gsl_sinterp_hip_ctx *ctx, void **buf, size_t *have, size_t bytes, void **out)
 {
   if (bytes > *have) {
@@ -335,6 +274,18 @@ static int grow_buf(gsl_sinterp_hip_ctx *ctx, void **buf, size_t *have, size_t b
   }
   *out = *buf;
   return ST_SUCCESS;
+}
+int sinterp_workspace(gsl_sinterp_hip_ctx *ctx, size_t bytes, void **out) { return grow_buf(ctx, &ctx->d_work, &ctx->work_bytes, bytes, out); }
+int sinterp_aux(gsl_sinterp_hip_ctx *ctx, size_t bytes, void **out) { return grow_buf(ctx, &ctx->d_aux, &ctx->aux_bytes, bytes, out); }
+int sinterp_sortbuf(gsl_sinterp_hip_ctx *ctx, size_t bytes, void **out) { return grow_buf(ctx, &ctx->d_sort, &ctx->sort_bytes, bytes, out); }
+int sinterp_invbuf(gsl_sinterp_hip_ctx *ctx, size_t bytes, void **out)
+{
+  const bool replaced = bytes > ctx->inv_bytes && ctx->d_inv;
+  const int st = grow_buf(ctx, &ctx->d_inv, &ctx->inv_bytes, bytes, out);
+  if (replaced)                                          /* cached sweep graphs bake the old pointer */
+    for (int i = 2; i < 4; i++)
+      if (ctx->graph[i].exec) { (void)hipGraphExecDestroy(ctx->graph[i].exec); ctx->graph[i].exec = NULL; }
+  return st;
 }
 int sinterp_sortbuf2(gsl_sinterp_hip_ctx *ctx, size_t bytes, void **out) { return grow_buf(ctx, &ctx->d_sort2, &ctx->sort2_bytes, bytes, out); }
 int sinterp_walkbuf(gsl_sinterp_hip_ctx *ctx, size_t bytes, void **out) { return grow_buf(ctx, &ctx->d_walk, &ctx->walk_bytes, bytes, out); }

@@ -752,75 +752,52 @@ static int tl_unsort(gsl_sinterp_hip_ctx *ctx, const sinterp_sorted *s, size_t m
   return ST_SUCCESS;
 }
 
-/* m_cap >= m sizes the buffer section (two sections -- `slot` 0 / 1 -- so that two chunks of one batch can be in
-   flight on two streams); box_in != NULL: bounding-box keys to bin by (e.g. the data's box kept with the jump table)
-   instead of a pass over the targets -- points outside it land in the border cells, which only costs locality */
+/* The buffer (grow-only, the whole of ctx->d_sort) is sized for this batch.  box_in != NULL: bounding-box keys to bin by
+   (e.g. the data's box kept with the jump table) instead of a pass over the targets -- points outside it land in the
+   border cells, which only costs locality */
 int sinterp_sort_reorder(gsl_sinterp_hip_ctx *ctx, const double *d_y, size_t m, size_t ytda, int dim, int per_cell,
-                         sinterp_sorted *out, size_t m_cap, int slot, const unsigned long long *box_in)
+                         sinterp_sorted *out, const unsigned long long *box_in)
 {
   memset(out, 0, sizeof *out);
   if (m == 0) return ST_SUCCESS;
-  if (m_cap < m) m_cap = m;
-  if (m_cap > 0x7fffffffULL) return sinterp_fail(ctx, ST_EINVAL, "sort_reorder: more than 2^31 targets", hipSuccess, __FILE__, __LINE__);
+  if (m > 0x7fffffffULL) return sinterp_fail(ctx, ST_EINVAL, "sort_reorder: more than 2^31 targets", hipSuccess, __FILE__, __LINE__);
+  const bool lvl2 = sort_two_level(m), morton = lvl2 && dim >= 2, two = lvl2 && dim >= 1 && dim <= 3;
   const int gmax = dim == 1 ? (1 << 20) : (dim == 2 ? 1024 : 100);
-  /* cells per axis for a batch of mm targets.  The two-level route numbers its cells by Morton code: a power-of-two grid
-     makes the id space dense (runs of ids are compact blocks at every scale) -- C3 sweep 1.27 -> 1.14 ms, C4 1.19 -> 1.15,
-     C5 1.57 -> 1.55 against the same scheme on the 25^3 / 395^2 grids; the nearer power of two in ratio, so a cell holds
-     between per_cell / 2^(dim/2) and per_cell 2^(dim/2) targets.  Monotone in mm (the capacity below relies on it). */
-  auto grid_of = [&](size_t mm) {
-    const double cells = (double)mm / (double)(per_cell > 0 ? per_cell : 64);
-    int gg = (int)ceil(pow(cells < 1 ? 1.0 : cells, 1.0 / dim));
-    gg = gg < 1 ? 1 : (gg > gmax ? gmax : gg);
-    if (dim >= 2 && sort_two_level(mm)) {
-      int p2 = 1;
-      while (p2 * 2 <= gg) p2 *= 2;                    /* p2 <= gg < 2 p2 */
-      gg = ((double)gg / p2 > (double)(2 * p2) / gg) ? 2 * p2 : p2;
-      const int gcap = dim == 2 ? 1024 : 128;
-      if (gg > gcap) gg = gcap;
-    }
-    return gg;
-  };
-  const int g = grid_of(m), gc = grid_of(m_cap);
-  /* the two-level route's id space is (2^bits)^dim, 2^bits >= g (= g^dim for its power-of-two grids) */
-  auto id_space = [&](int gg, bool morton) {
-    int side = gg;
-    if (morton && dim >= 2) { side = 1; while (side < gg) side *= 2; }
-    size_t c = 1;
-    for (int q = 0; q < dim; q++) c *= (size_t)side;
-    return c;
-  };
-  const size_t ncell = id_space(g, sort_two_level(m));
-  size_t ncell_cap = id_space(gc, sort_two_level(m_cap));
-  {
-    /* a smaller batch in a section sized for m_cap may take the one-level route on a (non power-of-two) grid */
-    const double cc = (double)m_cap / (double)(per_cell > 0 ? per_cell : 64);
-    int gr = (int)ceil(pow(cc < 1 ? 1.0 : cc, 1.0 / dim));
-    gr = gr < 1 ? 1 : (gr > gmax ? gmax : gr);
-    const size_t raw = id_space(gr, false);
-    if (ncell_cap < raw) ncell_cap = raw;
-    if (ncell_cap < ncell) ncell_cap = ncell;
+  /* cells per axis.  The two-level route numbers its cells by Morton code: a power-of-two grid makes the id space dense
+     (runs of ids are compact blocks at every scale) -- C3 sweep 1.27 -> 1.14 ms, C4 1.19 -> 1.15, C5 1.57 -> 1.55 against
+     the same scheme on the 25^3 / 395^2 grids; the nearer power of two in ratio, so a cell holds between
+     per_cell / 2^(dim/2) and per_cell 2^(dim/2) targets. */
+  const double cells = (double)m / (double)(per_cell > 0 ? per_cell : 64);
+  int g = (int)ceil(pow(cells < 1 ? 1.0 : cells, 1.0 / dim));
+  g = g < 1 ? 1 : (g > gmax ? gmax : g);
+  if (morton) {
+    int p2 = 1;
+    while (p2 * 2 <= g) p2 *= 2;                       /* p2 <= g < 2 p2 */
+    g = ((double)g / p2 > (double)(2 * p2) / g) ? 2 * p2 : p2;
+    const int gcap = dim == 2 ? 1024 : 128;
+    if (g > gcap) g = gcap;
   }
-  /* layout: box | ys | vs | ls | cellid | slot | count(+1) [| t_y (later res1) | inv | fin | cnt | ubase | grid : two-level] ; every section
-     16-byte aligned */
+  size_t ncell = 1;                                    /* g^dim: the Morton id space of a power-of-two grid is exactly that */
+  for (int q = 0; q < dim; q++) ncell *= (size_t)g;
+  /* layout: box | ys | vs | ls | cellid | slot | count(+1 + run sums of the scan) [| t_y (later res1) | inv | fin | cnt | ubase | grid :
+     two-level] ; every section 16-byte aligned */
   auto up = [](size_t b) { return (b + 15) & ~(size_t)15; };
-  const bool two = sort_two_level(m_cap) && dim >= 1 && dim <= 3;
-  const size_t tl_ch = dim == 3 ? TlGeom<3>::CH : TlGeom<2>::CH, tl_p = TlGeom<2>::P;
-  const size_t nwg_cap = (m_cap + tl_ch - 1) / tl_ch, nu_cap = (m_cap + tl_p - 1) / tl_p;
-  const size_t cnt_n = (size_t)TL_NB * nwg_cap;
-  const size_t o_ys = 64, o_vs = o_ys + up(m_cap * dim * 8), o_ls = o_vs + up(m_cap * 16), o_cell = o_ls + up(m_cap * 4),
-               o_slot = o_cell + up(m_cap * 4), o_cnt = o_slot + up(m_cap * 4),
-               o_ty = o_cnt + up((ncell_cap + 1) * 4 + (ncell_cap / 1024 + 8) * 4),
-               o_inv = o_ty + (two ? up(m_cap * (dim * 8 > 16 ? dim * 8 : 16)) : 0), o_fin = o_inv + (two ? up(m_cap * 4) : 0),
-               o_ca = o_fin + (two ? up(m_cap * 4) : 0), o_ub = o_ca + (two ? up((cnt_n + 1) * 4 + (cnt_n / 1024 + 8) * 4) : 0),
-               o_grid = o_ub + (two ? up(nu_cap * TL_W * 4) : 0), bytes = (o_grid + (two ? 64 : 0) + 255) & ~(size_t)255;
+  const size_t tl_ch = dim == 3 ? TlGeom<3>::CH : TlGeom<2>::CH;
+  const size_t nwg = (m + tl_ch - 1) / tl_ch, nu = (m + TL_PU - 1) / TL_PU, cnt_n = (size_t)TL_NB * nwg;
+  const size_t o_ys = 64, o_vs = o_ys + up(m * dim * 8), o_ls = o_vs + up(m * 16), o_cell = o_ls + up(m * 4),
+               o_slot = o_cell + up(m * 4), o_cnt = o_slot + up(m * 4),
+               o_ty = o_cnt + up((ncell + 1) * 4 + (ncell / 1024 + 8) * 4),
+               o_inv = o_ty + (two ? up(m * (dim * 8 > 16 ? dim * 8 : 16)) : 0), o_fin = o_inv + (two ? up(m * 4) : 0),
+               o_ca = o_fin + (two ? up(m * 4) : 0), o_ub = o_ca + (two ? up((cnt_n + 1) * 4 + (cnt_n / 1024 + 8) * 4) : 0),
+               o_grid = o_ub + (two ? up(nu * TL_W * 4) : 0), bytes = (o_grid + (two ? 64 : 0) + 255) & ~(size_t)255;
   void *buf = NULL;
-  int st = sinterp_sortbuf(ctx, bytes * (slot >= 0 ? 2 : 1), &buf);
+  int st = sinterp_sortbuf(ctx, bytes, &buf);
   if (st) return st;
-  char *b = (char *)buf + (slot > 0 ? bytes : 0);
+  char *b = (char *)buf;
   out->box = (unsigned long long *)b;
   out->ys = (double *)(b + o_ys); out->vs = (double *)(b + o_vs); out->ls = (int *)(b + o_ls);
   out->cellid = (unsigned *)(b + o_cell); out->slot = (unsigned *)(b + o_slot); out->offset = (unsigned *)(b + o_cnt);
-  out->two_level = two && m >= TL_MIN_M;
+  out->two_level = two;
   out->fin = (unsigned *)(b + o_fin); out->res1 = (double *)(b + o_ty); out->inv = (unsigned *)(b + o_inv);
   HIP_OK(ctx, hipMemsetAsync(out->offset, 0, ncell * 4, ctx->stream));
   size_t blocks = (m + 255) / 256;
@@ -888,6 +865,46 @@ int sinterp_unsort(gsl_sinterp_hip_ctx *ctx, const sinterp_sorted *s, size_t m, 
                      (const int *)s->ls, d_leaf);
   LAUNCH_CHECK(ctx);
   return ST_SUCCESS;
+}
+
+bool sinterp_sort_wanted(size_t m) { return m >= 4096 && !sinterp_env_flag("GSL_SINTERP_NO_SORT"); }
+
+/* The sorted-target protocol of the located sweeps, once: what the kernels read and store_result's three arguments
+   (common.h) for a batch that is swept in place (sort = false) or in cell order. */
+int sinterp_route_begin(gsl_sinterp_hip_ctx *ctx, const double *d_targets, size_t m, size_t ttda, int dim, int per_cell,
+                        const unsigned long long *box_in, double *d_values, int *d_leaf, bool sort, sinterp_route *r)
+{
+  r->y = d_targets; r->ytda = ttda; r->values = d_values; r->leaf = d_leaf; r->packed = 0; r->sorted = sort;
+  if (!sort) return ST_SUCCESS;
+  int st = sinterp_sort_reorder(ctx, d_targets, m, ttda, dim, per_cell, &r->srt, box_in);
+  if (st) return st;
+  const bool via_map = r->srt.two_level;                 /* results go to res1 through inv */
+  r->y = r->srt.ys; r->ytda = (size_t)dim;
+  r->values = via_map ? r->srt.res1 : r->srt.vs;
+  r->leaf = via_map ? (int *)r->srt.inv : (int *)NULL;   /* one level with a leaf output: pairs, no leaf array */
+  r->packed = (d_leaf != NULL ? 1 : 0) | (via_map ? 2 : 0);
+  return ST_SUCCESS;
+}
+
+int sinterp_route_end(gsl_sinterp_hip_ctx *ctx, const sinterp_route *r, size_t m, double *d_values, int *d_leaf)
+{
+  if (!r->sorted) return ST_SUCCESS;
+  return (r->packed & 1) ? sinterp_unsort_packed(ctx, &r->srt, m, d_values, d_leaf) : sinterp_unsort(ctx, &r->srt, m, d_values, d_leaf);
+}
+
+/* A synchronous copy into pageable memory behind one synchronise (no asynchronous D2H there).  `what` with a
+   conversion receives the count; without one it is reported in sinterp_fail's form. */
+int sinterp_outside_count(gsl_sinterp_hip_ctx *ctx, const unsigned long long *d_count, long long *h_n_outside, const char *what)
+{
+  if (!h_n_outside) return ST_SUCCESS;
+  unsigned long long c = 0;
+  HIP_OK(ctx, hipStreamSynchronize(ctx->stream));
+  HIP_OK(ctx, hipMemcpy(&c, d_count, sizeof c, hipMemcpyDeviceToHost));
+  *h_n_outside = (long long)c;
+  if (!c) return ST_SUCCESS;
+  if (!strchr(what, '%')) return sinterp_fail(ctx, ST_EDOM, what, hipSuccess, __FILE__, __LINE__);
+  snprintf(ctx->err, sizeof ctx->err, what, c);
+  return ST_EDOM;
 }
 
 int sinterp_bbox_keys(gsl_sinterp_hip_ctx *ctx, const double *d_p, size_t n, size_t tda, int dim, unsigned long long *d_box)
