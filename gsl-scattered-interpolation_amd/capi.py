@@ -194,6 +194,10 @@ SIGNATURES = {
     "simplex_tree_device_eval_many": (_i, [_vp, _pm, _pv, _pi]),
     "simplex_tree_device_eval_resident": (_i, [_vp, _vp, _sz, _sz, _vp, _vp]),
     "simplex_tree_device_ctx": (_vp, [_vp]),
+    "simplex_tree_device_set_responses": (_i, [_vp, _pm]),
+    "simplex_tree_device_n_responses": (_sz, [_vp]),
+    "simplex_tree_device_eval_fields_many": (_i, [_vp, _pm, _pm, _pm, _pi]),
+    "simplex_tree_device_eval_fields_resident": (_i, [_vp, _vp, _sz, _sz, _vp, _sz, _vp, _sz, _vp]),
     "check_leaf_nodes": (None, [_pt, _vp]),
     "check_delaunay": (_i, [_pt, _pm]),
     "output_triangulation": (None, [_pt, _pm, _pv, _i, C.c_char_p, C.c_char_p, C.c_char_p]),
@@ -232,6 +236,13 @@ SIGNATURES = {
     "simplex_mesh_device_eval_many": (_i, [_vp, _pm, _pv, _pi]),
     "simplex_mesh_device_eval_resident": (_i, [_vp, _vp, _sz, _sz, _vp, _vp]),
     "simplex_mesh_device_ctx": (_vp, [_vp]),
+    "simplex_mesh_device_set_responses": (_i, [_vp, _pm]),
+    "simplex_mesh_device_n_responses": (_sz, [_vp]),
+    "simplex_mesh_device_eval_fields_many": (_i, [_vp, _pm, _pm, _pm, _pi]),
+    "simplex_mesh_device_eval_fields_resident": (_i, [_vp, _vp, _sz, _sz, _vp, _sz, _vp, _sz, _vp]),
+    "gsl_sinterp_hip_bary_fields_eval": (_i, [_vp, _i, _vp, _vp, _i, _vp, _i, _sz, _pd, _vp, _vp, _sz, _sz, _vp, _sz, _vp, _sz]),
+    "gsl_sinterp_hip_mesh3_fields_eval": (_i, [_vp, _i, _vp, _vp, _i, _vp, _i, _sz, _pd, _vp, _vp, _sz, _sz, _vp, _sz, _vp, _sz]),
+    "gsl_sinterp_hip_sort_wanted": (_i, [_sz]),
     "simplex_mesh_device_eval_natural_many": (_i, [_vp, _pm, _pv, _pi]),
     "simplex_mesh_device_eval_natural_resident": (_i, [_vp, _vp, _sz, _sz, _vp, _vp]),
     "simplex_mesh_device_bind_gradients": (_i, [_vp, _pm]),
@@ -317,6 +328,10 @@ SIGNATURES = {
     "gsl_sinterp_eval_fields_e": (_i, [C.POINTER(gsl_sinterp), _pv, _pv]),
     "gsl_sinterp_eval_fields_many": (_i, [C.POINTER(gsl_sinterp), _pm, _pm]),
     "gsl_sinterp_eval_fields_resident": (_i, [C.POINTER(gsl_sinterp), _vp, _sz, _sz, _vp, _sz]),
+    "gsl_sinterp_linear_init_fields": (_i, [C.POINTER(gsl_sinterp), _pm, _pm]),
+    "gsl_sinterp_linear_eval_fields_e": (_i, [C.POINTER(gsl_sinterp), _pv, _pv, _pm]),
+    "gsl_sinterp_linear_eval_fields_many": (_i, [C.POINTER(gsl_sinterp), _pm, _pm, _pm, _pi]),
+    "gsl_sinterp_linear_eval_fields_resident": (_i, [C.POINTER(gsl_sinterp), _vp, _sz, _sz, _vp, _sz, _vp, _sz, _vp]),
     "gsl_sinterp_get_field_weights": (_i, [C.POINTER(gsl_sinterp), _sz, _pv]),
     "gsl_sinterp_field_mean": (_i, [C.POINTER(gsl_sinterp), _sz, _pd]),
     "gsl_sinterp_field_poly": (_i, [C.POINTER(gsl_sinterp), _sz, _pv]),
@@ -941,6 +956,26 @@ class DeviceTree:
     def eval_resident(self, d_targets, m, ttda, d_values, d_leaf):
         return lib().simplex_tree_device_eval_resident(self._h, d_targets, m, ttda, d_values, d_leaf)
 
+    def set_responses(self, F):
+        """F: n_points x K responses (row stride honoured), independent of set_response"""
+        return lib().simplex_tree_device_set_responses(self._h, C.byref(as_matrix(F)))
+
+    def n_responses(self):
+        return int(lib().simplex_tree_device_n_responses(self._h))
+
+    def eval_fields_many(self, targets, want_grad=False, want_leaf=True, out=None):
+        """(status, S [m x K], G [m x K dim] or None, leaf or None) from one locate; out = (S, G or None) preallocated"""
+        m, dim, k = targets.shape[0], targets.shape[1], max(self.n_responses(), 1)
+        S = np.empty((m, k), dtype=np.float64) if out is None else out[0]
+        G = (np.empty((m, k * dim), dtype=np.float64) if out is None else out[1]) if want_grad else None
+        leaf = np.empty(m, dtype=np.int32) if want_leaf else None
+        st = lib().simplex_tree_device_eval_fields_many(self._h, C.byref(as_matrix(targets)), C.byref(as_matrix(S)),
+                                            C.byref(as_matrix(G)) if want_grad else None, leaf.ctypes.data_as(_pi) if want_leaf else None)
+        return st, S, G, leaf
+
+    def eval_fields_resident(self, d_targets, m, ttda, d_S, stda, d_G=None, gtda=0, d_leaf=None):
+        return lib().simplex_tree_device_eval_fields_resident(self._h, d_targets, m, ttda, d_S, stda, d_G, gtda, d_leaf)
+
     def n_devices(self):
         return lib().simplex_tree_device_n_devices(self._h)
 
@@ -1134,6 +1169,26 @@ class DeviceMesh:
     def eval_cubic_resident(self, d_targets, m, ttda, d_values, d_grad=None, gtda=2, d_tri=None):
         return lib().simplex_mesh_device_eval_cubic_resident(self._h, d_targets, m, ttda, d_values, d_grad, gtda, d_tri)
 
+    def set_responses(self, F):
+        """F: n_points x K responses (row stride honoured), independent of set_response"""
+        return lib().simplex_mesh_device_set_responses(self._h, C.byref(as_matrix(F)))
+
+    def n_responses(self):
+        return int(lib().simplex_mesh_device_n_responses(self._h))
+
+    def eval_fields_many(self, targets, want_grad=False, want_leaf=True, out=None):
+        """(status, S [m x K], G [m x K dim] or None, leaf or None) from one locate; out = (S, G or None) preallocated"""
+        m, dim, k = targets.shape[0], targets.shape[1], max(self.n_responses(), 1)
+        S = np.empty((m, k), dtype=np.float64) if out is None else out[0]
+        G = (np.empty((m, k * dim), dtype=np.float64) if out is None else out[1]) if want_grad else None
+        leaf = np.empty(m, dtype=np.int32) if want_leaf else None
+        st = lib().simplex_mesh_device_eval_fields_many(self._h, C.byref(as_matrix(targets)), C.byref(as_matrix(S)),
+                                            C.byref(as_matrix(G)) if want_grad else None, leaf.ctypes.data_as(_pi) if want_leaf else None)
+        return st, S, G, leaf
+
+    def eval_fields_resident(self, d_targets, m, ttda, d_S, stda, d_G=None, gtda=0, d_leaf=None):
+        return lib().simplex_mesh_device_eval_fields_resident(self._h, d_targets, m, ttda, d_S, stda, d_G, gtda, d_leaf)
+
     def n_devices(self):
         return lib().simplex_mesh_device_n_devices(self._h)
 
@@ -1294,6 +1349,34 @@ class Sinterp:
 
     def eval_fields_resident(self, d_y, m, ytda, d_s, stda):
         return lib().gsl_sinterp_eval_fields_resident(self._p, d_y, m, ytda, d_s, stda)
+
+    def linear_init_fields(self, x, F):
+        """the linear types: F is size x K (row stride honoured); field 0 is the interpolant of every other entry"""
+        return lib().gsl_sinterp_linear_init_fields(self._p, C.byref(as_matrix(x)), C.byref(as_matrix(F)))
+
+    def linear_eval_fields_e(self, y, want_grad=False):
+        """(status, s [K], g [K x dim] or None) at one target; NaN on failure"""
+        k = max(self.n_fields(), 1)
+        s = np.full(k, np.nan)
+        g = np.full((k, self._p.contents.dim), np.nan) if want_grad else None
+        st = lib().gsl_sinterp_linear_eval_fields_e(self._p, C.byref(as_vector(np.ascontiguousarray(y, dtype=np.float64))), C.byref(as_vector(s)),
+                                                    C.byref(as_matrix(g)) if want_grad else None)
+        return st, s, g
+
+    def linear_eval_fields_many(self, y, want_grad=False, want_leaf=False, out=None):
+        """(status, S [m x K], G [m x K dim] or None, leaf or None) from one locate; out = (S, G or None) preallocated
+        (row strides honoured)"""
+        m, k = y.shape[0], max(self.n_fields(), 1)
+        S = np.empty((m, k), dtype=np.float64) if out is None else out[0]
+        G = (np.empty((m, k * self._p.contents.dim), dtype=np.float64) if out is None else out[1]) if want_grad else None
+        leaf = np.empty(m, dtype=np.int32) if want_leaf else None
+        st = lib().gsl_sinterp_linear_eval_fields_many(self._p, C.byref(as_matrix(y)), C.byref(as_matrix(S)),
+                                                       C.byref(as_matrix(G)) if want_grad else None,
+                                                       leaf.ctypes.data_as(_pi) if want_leaf else None)
+        return st, S, G, leaf
+
+    def linear_eval_fields_resident(self, d_y, m, ytda, d_S, stda, d_G=None, gtda=0, d_leaf=None):
+        return lib().gsl_sinterp_linear_eval_fields_resident(self._p, d_y, m, ytda, d_S, stda, d_G, gtda, d_leaf)
 
     def field_weights(self, q):
         w = np.empty(self._p.contents.size, dtype=np.float64)

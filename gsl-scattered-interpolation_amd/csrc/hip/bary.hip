@@ -24,18 +24,11 @@
  * response column.
  */
 #include "common.h"
+#include "linear_finish.h"   /* NodeRec, META_*, solve_node, load_rec, BARY_INTERP: shared with linear_fields.hip */
 #include <math.h>
 #include <stdlib.h>
 #include <algorithm>
 #include <vector>
-
-struct __attribute__((aligned(64))) NodeRec {
-  double x0, x1;
-  double u00, u01, l10, u11;
-  int child[3];
-  int meta;
-};
-static_assert(sizeof(NodeRec) == GSL_SINTERP_TREE_RECORD_BYTES, "record size");
 
 struct __attribute__((aligned(32))) LeafRec {
   double f[3];
@@ -43,11 +36,6 @@ struct __attribute__((aligned(32))) LeafRec {
   int pad;
 };
 static_assert(sizeof(LeafRec) == GSL_SINTERP_TREE_LEAFTAB_BYTES, "leaf table size");
-
-#define META_TYPE(m) ((m) & 3)
-#define META_SWAPPED(m) (((m) >> 2) & 1)
-#define META_SINGULAR(m) (((m) >> 3) & 1)
-#define META_NCHILD(m) (((m) >> 4) & 3)
 
 struct Geom { double seed[6]; double shift[2]; double scale[2]; };
 
@@ -106,22 +94,6 @@ __global__ void tree_bind_kernel(int n_nodes, const int *__restrict__ pidx, int 
 }
 
 /* ------------------------------------------------------------------------ */
-/* coords <- U^-1 L^-1 P ((y - x0) * scale)   (linear_simplex.c:644-649)      */
-__device__ __forceinline__ void solve_node(const NodeRec &r, double y0, double y1, double s0, double s1,
-                                           double &c0, double &c1)
-{
-  double b0 = (y0 - r.x0) * s0;
-  double b1 = (y1 - r.x1) * s1;
-  const bool sw = META_SWAPPED(r.meta);
-  double t0 = sw ? b1 : b0;
-  double t1 = sw ? b0 : b1;
-  t1 -= r.l10 * t0;
-  t1 = t1 / r.u11;
-  t0 -= r.u01 * t1;
-  t0 = t0 / r.u00;
-  c0 = t0; c1 = t1;
-}
-
 __device__ __forceinline__ bool inside_unit(double c0, double c1)
 {
   double tot = 0;
@@ -196,18 +168,6 @@ __device__ __forceinline__ int classify_fast(const NodeRec &r, double y0, double
   if (lo >= B && hi <= 1.0 - B) return 1;
   if (lo <= -B || hi >= 1.0 + B) return -1;
   return 0;
-}
-
-__device__ __forceinline__ NodeRec load_rec(const NodeRec *__restrict__ rec, int k)
-{
-  /* four 16-byte loads of one aligned 64-byte line */
-  const double2 *p = reinterpret_cast<const double2 *>(rec + k);
-  double2 a = p[0], b = p[1], c = p[2];
-  int4 d = *reinterpret_cast<const int4 *>(p + 3);
-  NodeRec r;
-  r.x0 = a.x; r.x1 = a.y; r.u00 = b.x; r.u01 = b.y; r.l10 = c.x; r.u11 = c.y;
-  r.child[0] = d.x; r.child[1] = d.y; r.child[2] = d.z; r.meta = d.w;
-  return r;
 }
 
 /* ------------------------------------------------------------------------ */
@@ -481,12 +441,7 @@ __device__ __forceinline__ void finish_target(const NodeRec *__restrict__ rec, c
   double c0, c1;
   solve_node(cur, y0, y1, s0, s1, c0, c1);
   const LeafRec lr = tab[node];
-  double tot = 0, interp = 0;
-  tot += c0;
-  if (lr.mask & 1) interp += c0 * lr.f[0];
-  tot += c1;
-  if (lr.mask & 2) interp += c1 * lr.f[1];
-  if (lr.mask & 4) interp += (1 - tot) * lr.f[2];
+  BARY_INTERP(interp, c0, c1, lr.mask, lr.f[0], lr.f[1], lr.f[2]);
   store_result(values, leaf_out, k, interp, node, packed);
 }
 
@@ -781,12 +736,7 @@ bary_eval_kernel(int n_nodes, const NodeRec *__restrict__ rec, const LeafRec *__
     /* interp_point recomputes the coordinates in the final leaf */
     if (!META_SINGULAR(cur.meta)) solve_node(cur, y0, y1, s0, s1, c0, c1);
     const LeafRec lr = tab[node];
-    double tot = 0, interp = 0;
-    tot += c0;
-    if (lr.mask & 1) interp += c0 * lr.f[0];
-    tot += c1;
-    if (lr.mask & 2) interp += c1 * lr.f[1];
-    if (lr.mask & 4) interp += (1 - tot) * lr.f[2];
+    BARY_INTERP(interp, c0, c1, lr.mask, lr.f[0], lr.f[1], lr.f[2]);
     store_result(values, leaf_out, k, interp, node, packed);
   }
 }
@@ -1432,12 +1382,7 @@ __device__ __forceinline__ void leaf_finish(const NodeRec &cur, const LeafRec *_
                                             double *__restrict__ values, int *__restrict__ leaf_out, int packed)
 {
   const LeafRec lr = tab[t];
-  double tot = 0, interp = 0;                                  /* linear_simplex.c:678-711 */
-  tot += c0;
-  if (lr.mask & 1) interp += c0 * lr.f[0];
-  tot += c1;
-  if (lr.mask & 2) interp += c1 * lr.f[1];
-  if (lr.mask & 4) interp += (1 - tot) * lr.f[2];
+  BARY_INTERP(interp, c0, c1, lr.mask, lr.f[0], lr.f[1], lr.f[2]);
   store_result(values, leaf_out, k, interp, t, packed);
 }
 
@@ -1952,12 +1897,7 @@ __device__ __forceinline__ void mesh_finish(const NodeRec &cur, const LeafRec *_
   double c0, c1;
   solve_node(cur, y0, y1, s0, s1, c0, c1);
   const LeafRec lr = tab[t];
-  double tot = 0, interp = 0;                                  /* linear_simplex.c:678-711 */
-  tot += c0;
-  if (lr.mask & 1) interp += c0 * lr.f[0];
-  tot += c1;
-  if (lr.mask & 2) interp += c1 * lr.f[1];
-  if (lr.mask & 4) interp += (1 - tot) * lr.f[2];
+  BARY_INTERP(interp, c0, c1, lr.mask, lr.f[0], lr.f[1], lr.f[2]);
   store_result(values, tri_out, k, interp, t, packed);
 }
 

@@ -18,22 +18,13 @@
  * on the walk.  A separate 32-byte table {f(v0) .. f(v3)} is bound to one response column and read once per target.
  */
 #include "common.h"
+#include "linear_finish.h"   /* TetRec, load_tet, tet_coords, TET_INTERP: shared with linear_fields.hip */
 #include <math.h>
 #include <stdlib.h>
-
-struct __attribute__((aligned(128))) TetRec {
-  double x[3];
-  double inv[9];
-  int nbr[4];
-  int meta;
-  int pad[3];
-};
-static_assert(sizeof(TetRec) == GSL_SINTERP_MESH3_RECORD_BYTES, "record size");
 
 struct __attribute__((aligned(32))) TetTab { double f[4]; };
 static_assert(sizeof(TetTab) == GSL_SINTERP_MESH3_TABLE_BYTES, "response table size");
 
-#define TET_SINGULAR(m) ((m) & 1)
 #define MESH3_SINGULAR_REL 1e-12   /* |det| <= this x the product of the three edge lengths: flat */
 #define MESH3_SEED_RINGS 4         /* empty seed cells look this many shells of cells around themselves */
 #define MESH3_EXTRA_STEPS 8        /* steps the walk still takes after it has seen a violation <= MESH_GAP */
@@ -96,31 +87,6 @@ __global__ void mesh3_bind_kernel(int n_tet, const int *__restrict__ tet, int n_
   tab[t] = r;
 }
 
-/* eight 16-byte loads of one aligned 128-byte line */
-__device__ __forceinline__ TetRec load_tet(const TetRec *__restrict__ rec, int t)
-{
-  const double2 *p = reinterpret_cast<const double2 *>(rec + t);
-  const double2 a = p[0], b = p[1], c = p[2], d = p[3], e = p[4], f = p[5];
-  const int4 n = *reinterpret_cast<const int4 *>(p + 6), m = *reinterpret_cast<const int4 *>(p + 7);
-  TetRec r;
-  r.x[0] = a.x; r.x[1] = a.y; r.x[2] = b.x;
-  r.inv[0] = b.y; r.inv[1] = c.x; r.inv[2] = c.y; r.inv[3] = d.x; r.inv[4] = d.y; r.inv[5] = e.x;
-  r.inv[6] = e.y; r.inv[7] = f.x; r.inv[8] = f.y;
-  r.nbr[0] = n.x; r.nbr[1] = n.y; r.nbr[2] = n.z; r.nbr[3] = n.w;
-  r.meta = m.x; r.pad[0] = r.pad[1] = r.pad[2] = 0;
-  return r;
-}
-
-/* barycentric coordinates of the standardised target z in the record's tetrahedron */
-__device__ __forceinline__ void tet_coords(const TetRec &r, const double z[3], double c[4])
-{
-  const double b0 = z[0] - r.x[0], b1 = z[1] - r.x[1], b2 = z[2] - r.x[2];
-  c[0] = r.inv[0] * b0 + r.inv[1] * b1 + r.inv[2] * b2;
-  c[1] = r.inv[3] * b0 + r.inv[4] * b1 + r.inv[5] * b2;
-  c[2] = r.inv[6] * b0 + r.inv[7] * b1 + r.inv[8] * b2;
-  c[3] = 1.0 - (c[0] + c[1] + c[2]);
-}
-
 /* the closed rule: all four coordinates in [0, 1] (false on NaN) */
 __device__ __forceinline__ bool tet_inside(const double c[4])
 {
@@ -144,7 +110,7 @@ __device__ __forceinline__ void tet_finish(const TetRec &r, const TetTab *__rest
   double c[4];
   tet_coords(r, z, c);
   const double4 f = *reinterpret_cast<const double4 *>(tab + t);
-  const double v = ((c[0] * f.x + c[1] * f.y) + c[2] * f.z) + c[3] * f.w;
+  const double v = TET_INTERP(c, f.x, f.y, f.z, f.w);
   store_result(values, tet_out, k, v, t, packed);
 }
 

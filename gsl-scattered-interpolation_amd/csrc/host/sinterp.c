@@ -328,6 +328,89 @@ static int host_stage_end(host_stage *hs, int st, int download)
 }
 
 /* ======================================================================== */
+/* several responses on a mirror (csrc/hip/linear_fields.hip): what the tree  */
+/* and the mesh mirror share                                                  */
+/* ======================================================================== */
+/* the binding of set_responses on member 0 and the scratch of a fields batch: the values the locate writes (dropped) and,
+   for a caller that keeps none, its simplex indices; grow-only */
+typedef struct {
+  double *d_F;                          /* n_points x nf, dense, in the vertex order of the mirror's ids */
+  size_t nf, f_doubles;
+  double *d_val;
+  int *d_leaf;
+  size_t cap;
+  int tab_defined;                      /* the response table the locate reads holds defined bytes (zeros, or a response) */
+} fields_set;
+
+static void fields_set_release(fields_set *fs, gsl_sinterp_hip_ctx *c)
+{
+  if (c) { gsl_sinterp_hip_free(c, fs->d_F); gsl_sinterp_hip_free(c, fs->d_val); gsl_sinterp_hip_free(c, fs->d_leaf); }
+  memset(fs, 0, sizeof *fs);
+}
+
+/* h: np x K dense, already in the mirror's vertex order.  The locate reads the scalar binding's response table whatever
+   it holds (its values are dropped); a mirror that never had set_response gets a table of zeros once, so that no
+   evaluation reads bytes nobody wrote.  response_bound is not touched: the scalar entries still ask for set_response. */
+static int fields_bind(fields_set *fs, gsl_sinterp_hip_ctx *c, const double *h, size_t np, size_t K, int response_bound, void *d_tab,
+                       size_t tab_bytes)
+{
+  int st = GSL_SUCCESS;
+  const size_t cnt = (np > 0 ? np : 1) * K;
+  if (cnt != fs->f_doubles) {
+    gsl_sinterp_hip_free(c, fs->d_F); fs->d_F = NULL; fs->f_doubles = 0; fs->nf = 0;
+    st = gsl_sinterp_hip_malloc(c, (void **)&fs->d_F, cnt * sizeof(double));
+    if (!st) fs->f_doubles = cnt;
+  }
+  if (!st && np > 0) st = gsl_sinterp_hip_h2d(c, fs->d_F, h, np * K * sizeof(double));
+  if (!st && !response_bound && !fs->tab_defined) {
+    void *z = calloc(1, tab_bytes);
+    if (!z) return GSL_ENOMEM;
+    st = gsl_sinterp_hip_h2d(c, d_tab, z, tab_bytes);
+    free(z);
+  }
+  if (!st) st = gsl_sinterp_hip_sync(c);
+  if (!st) { fs->nf = K; fs->tab_defined = 1; } else fs->nf = 0;
+  return st;
+}
+
+static int fields_scratch(fields_set *fs, gsl_sinterp_hip_ctx *c, size_t m)
+{
+  if (m <= fs->cap) return GSL_SUCCESS;
+  gsl_sinterp_hip_free(c, fs->d_val); gsl_sinterp_hip_free(c, fs->d_leaf);
+  fs->d_val = NULL; fs->d_leaf = NULL; fs->cap = 0;
+  int st = gsl_sinterp_hip_malloc(c, (void **)&fs->d_val, m * sizeof(double));
+  if (!st) st = gsl_sinterp_hip_malloc(c, (void **)&fs->d_leaf, m * sizeof(int));
+  if (!st) fs->cap = m;
+  return st;
+}
+
+/* the host batch of both mirrors: shapes, one-shot staging, the resident entry `fn`, the outside count.  A batch with a
+   target outside is downloaded whole (NaN rows, index -1) before GSL_EDOM is raised. */
+typedef int (*fields_resident_fn)(void *dev, const double *d_y, size_t m, size_t ytda, double *d_S, size_t stda, double *d_G, size_t gtda,
+                                  int *d_leaf);
+static int fields_eval_host(gsl_sinterp_hip_ctx *c, size_t dim, size_t K, const gsl_matrix *targets, gsl_matrix *S, gsl_matrix *G, int *leaf,
+                            fields_resident_fn fn, void *dev)
+{
+  if (targets->size2 != dim) GSL_ERROR("eval_fields_many: targets must be M x dim of the mirror", GSL_EBADLEN);
+  const size_t m = targets->size1;
+  if (S->size1 != m || S->size2 != K) GSL_ERROR("eval_fields_many: S must be M x K", GSL_EBADLEN);
+  if (G && (G->size1 != m || G->size2 != K * dim)) GSL_ERROR("eval_fields_many: G must be M x (K dim)", GSL_EBADLEN);
+  if (m == 0) return GSL_SUCCESS;
+  stage_out out[3] = {STAGE_MATRIX(S), {G ? K * dim : 0, 0, G ? G->data : NULL, G ? G->tda : 0, NULL, NULL}, STAGE_INTS(leaf, 1)};
+  host_stage hs;
+  int st = host_stage_begin(&hs, c, targets, dim, out, 3), es = GSL_SUCCESS;
+  if (!hs.h) GSL_ERROR("eval_fields_many: out of memory", GSL_ENOMEM);
+  long long outside_n = 0;
+  if (!st) es = fn(dev, hs.d_y, m, dim, (double *)out[0].d, K, (double *)out[1].d, K * dim, (int *)out[2].d);
+  if (!st && !es) st = gsl_sinterp_hip_count_negative(c, (const int *)out[2].d, m, &outside_n);
+  st = host_stage_end(&hs, st, !es);
+  if (st) GSL_ERROR(gsl_sinterp_hip_last_error(c), st);
+  if (es) return es;
+  if (outside_n) GSL_ERROR("eval_fields_many: target(s) outside the triangulation (NaN rows, index -1)", GSL_EDOM);
+  return GSL_SUCCESS;
+}
+
+/* ======================================================================== */
 /* simplex_tree_device                                                       */
 /* ======================================================================== */
 struct simplex_tree_device {
@@ -344,6 +427,7 @@ struct simplex_tree_device {
   void *m_records[SINTERP_MAX_DEVICES], *m_leaftab[SINTERP_MAX_DEVICES];
   int *m_pidx[SINTERP_MAX_DEVICES];
   chunk_set cs;                    /* single-device mirror: pipelined host batches */
+  fields_set fs;                   /* simplex_tree_device_set_responses (member 0) */
 };
 
 gsl_sinterp_hip_ctx *simplex_tree_device_ctx(simplex_tree_device *dev) { return dev ? dev->ctx : NULL; }
@@ -351,6 +435,7 @@ gsl_sinterp_hip_ctx *simplex_tree_device_ctx(simplex_tree_device *dev) { return 
 void simplex_tree_device_free(simplex_tree_device *dev)
 {
   if (!dev) return;
+  if (dev->ctx) fields_set_release(&dev->fs, dev->ctx);
   if (dev->ss.grp) {
     for (int i = 0; i < dev->ss.n; i++) {
       gsl_sinterp_hip_ctx *c = gsl_sinterp_hip_group_ctx(dev->ss.grp, i);
@@ -621,6 +706,59 @@ int simplex_tree_device_eval_many(simplex_tree_device *dev, const gsl_matrix *ta
   return GSL_SUCCESS;
 }
 
+/* ---- several responses on the same tree (csrc/hip/linear_fields.hip) ---- */
+size_t simplex_tree_device_n_responses(const simplex_tree_device *dev) { return dev ? dev->fs.nf : 0; }
+
+int simplex_tree_device_set_responses(simplex_tree_device *dev, const gsl_matrix *F)
+{
+  if (!dev || !F) GSL_ERROR("simplex_tree_device_set_responses: null argument", GSL_EFAULT);
+  const size_t np = (size_t)dev->n_points, K = F->size2;
+  if (K < 1 || K > GSL_SINTERP_MAX_FIELDS) GSL_ERROR("simplex_tree_device_set_responses: 1 .. GSL_SINTERP_MAX_FIELDS responses", GSL_EINVAL);
+  if (F->size1 < np) GSL_ERROR("simplex_tree_device_set_responses: fewer rows than the point set", GSL_EBADLEN);
+  double *h = (double *)malloc((np > 0 ? np : 1) * K * sizeof(double));
+  if (!h) GSL_ERROR("simplex_tree_device_set_responses: out of memory", GSL_ENOMEM);
+  for (size_t i = 0; i < np; i++)                      /* insertion order, as set_response */
+    memcpy(h + i * K, F->data + dev->tree->shuffle->data[i] * F->tda, K * sizeof(double));
+  int st = fields_bind(&dev->fs, dev->ctx, h, np, K, dev->response_bound, dev->d_leaftab, (size_t)dev->n_nodes * GSL_SINTERP_TREE_LEAFTAB_BYTES);
+  free(h);
+  if (st == GSL_ENOMEM) GSL_ERROR("simplex_tree_device_set_responses: out of memory", GSL_ENOMEM);
+  HIP_TRY(st, dev->ctx);
+  return GSL_SUCCESS;
+}
+
+int simplex_tree_device_eval_fields_resident(simplex_tree_device *dev, const double *d_targets, size_t m, size_t ttda, double *d_S,
+                                             size_t stda, double *d_G, size_t gtda, simplex_index *d_leaf)
+{
+  if (!dev) GSL_ERROR("simplex_tree_device_eval_fields_resident: null device tree", GSL_EFAULT);
+  const size_t K = dev->fs.nf;
+  if (K == 0) GSL_ERROR("simplex_tree_device_eval_fields_resident: no responses bound", GSL_EINVAL);
+  if (m > 0 && (!d_targets || !d_S)) GSL_ERROR("simplex_tree_device_eval_fields_resident: null argument", GSL_EFAULT);
+  if (ttda < 2) GSL_ERROR("simplex_tree_device_eval_fields_resident: target rows shorter than 2", GSL_EBADLEN);
+  if (stda < K || (d_G && gtda < 2 * K)) GSL_ERROR("simplex_tree_device_eval_fields_resident: row pitch below K (values) or 2 K (gradients)", GSL_EINVAL);
+  if (m == 0) return GSL_SUCCESS;
+  gsl_sinterp_hip_ctx *c = dev->ctx;                    /* a multi-device mirror: member 0 evaluates every target */
+  HIP_TRY(fields_scratch(&dev->fs, c, m), c);
+  int *loc = d_leaf ? d_leaf : dev->fs.d_leaf;
+  HIP_TRY(gsl_sinterp_hip_bary_eval(c, dev->n_nodes, dev->d_records, dev->d_leaftab, dev->scale, d_targets, m, ttda, dev->fs.d_val, loc,
+                                    (long long *)NULL), c);
+  HIP_TRY(gsl_sinterp_hip_bary_fields_eval(c, dev->n_nodes, dev->d_records, dev->d_pidx, dev->n_points, dev->fs.d_F, (int)K, K, dev->scale,
+                                           loc, d_targets, m, ttda, d_S, stda, d_G, gtda), c);
+  return GSL_SUCCESS;
+}
+
+static int tree_fields_fn(void *dev, const double *d_y, size_t m, size_t ytda, double *d_S, size_t stda, double *d_G, size_t gtda, int *d_leaf)
+{
+  return simplex_tree_device_eval_fields_resident((simplex_tree_device *)dev, d_y, m, ytda, d_S, stda, d_G, gtda, d_leaf);
+}
+
+int simplex_tree_device_eval_fields_many(simplex_tree_device *dev, const gsl_matrix *targets, gsl_matrix *S, gsl_matrix *G,
+                                         simplex_index *leaf)
+{
+  if (!dev || !targets || !S) GSL_ERROR("simplex_tree_device_eval_fields_many: null argument", GSL_EFAULT);
+  if (dev->fs.nf == 0) GSL_ERROR("simplex_tree_device_eval_fields_many: no responses bound", GSL_EINVAL);
+  return fields_eval_host(dev->ctx, 2, dev->fs.nf, targets, S, G, leaf, &tree_fields_fn, dev);
+}
+
 /* reference: check_leaf_nodes / check_delaunay (linear_simplex_integrity_check.c:121-168) */
 int simplex_tree_check_device(simplex_tree *tree, gsl_matrix *data, int device, long long *leaf_violations,
                               long long *delaunay_violations)
@@ -701,6 +839,7 @@ struct simplex_mesh_device {
   /* grow-only: the triangle indices of a resident natural / cubic batch whose caller did not ask for them */
   int *sw_leaf;
   size_t sw_leaf_cap;
+  fields_set fs;                   /* simplex_mesh_device_set_responses (member 0) */
 };
 
 gsl_sinterp_hip_ctx *simplex_mesh_device_ctx(simplex_mesh_device *dev) { return dev ? dev->ctx : NULL; }
@@ -721,6 +860,7 @@ void simplex_mesh_device_free(simplex_mesh_device *dev)
     gsl_sinterp_hip_free(c, dev->m_tri[r]); gsl_sinterp_hip_free(c, dev->m_seed[r]);
   }
   if (dev->ctx) {
+    fields_set_release(&dev->fs, dev->ctx);
     gsl_sinterp_hip_free(dev->ctx, dev->nn_rec); gsl_sinterp_hip_free(dev->ctx, dev->sw_leaf);
     gsl_sinterp_hip_free(dev->ctx, dev->ct_g); gsl_sinterp_hip_free(dev->ctx, dev->ct_rec);
   }
@@ -888,6 +1028,63 @@ int simplex_mesh_device_eval_many(simplex_mesh_device *dev, const gsl_matrix *ta
   if (st != GSL_SUCCESS) GSL_ERROR("simplex_mesh_device_eval_many: evaluation failed", st);
   if (outside_n) GSL_ERROR("simplex_mesh_device_eval_many: target(s) outside the triangulation", GSL_EDOM);
   return GSL_SUCCESS;
+}
+
+/* ---- several responses on the same mirror (csrc/hip/linear_fields.hip) ---- */
+size_t simplex_mesh_device_n_responses(const simplex_mesh_device *dev) { return dev ? dev->fs.nf : 0; }
+
+int simplex_mesh_device_set_responses(simplex_mesh_device *dev, const gsl_matrix *F)
+{
+  if (!dev || !F) GSL_ERROR("simplex_mesh_device_set_responses: null argument", GSL_EFAULT);
+  const size_t np = (size_t)dev->n_points, K = F->size2;
+  if (K < 1 || K > GSL_SINTERP_MAX_FIELDS) GSL_ERROR("simplex_mesh_device_set_responses: 1 .. GSL_SINTERP_MAX_FIELDS responses", GSL_EINVAL);
+  if (F->size1 < np) GSL_ERROR("simplex_mesh_device_set_responses: fewer rows than the point set", GSL_EBADLEN);
+  double *h = (double *)malloc(np * K * sizeof(double));
+  if (!h) GSL_ERROR("simplex_mesh_device_set_responses: out of memory", GSL_ENOMEM);
+  for (size_t i = 0; i < np; i++) memcpy(h + i * K, F->data + i * F->tda, K * sizeof(double));
+  const size_t tab_bytes = (size_t)dev->n_tri * (dev->dim == 2 ? GSL_SINTERP_TREE_LEAFTAB_BYTES : GSL_SINTERP_MESH3_TABLE_BYTES);
+  int st = fields_bind(&dev->fs, dev->ctx, h, np, K, dev->response_bound, dev->m_leaftab[0], tab_bytes);
+  free(h);
+  if (st == GSL_ENOMEM) GSL_ERROR("simplex_mesh_device_set_responses: out of memory", GSL_ENOMEM);
+  if (st) GSL_ERROR(gsl_sinterp_hip_last_error(dev->ctx), st);
+  return GSL_SUCCESS;
+}
+
+int simplex_mesh_device_eval_fields_resident(simplex_mesh_device *dev, const double *d_targets, size_t m, size_t ttda, double *d_S,
+                                             size_t stda, double *d_G, size_t gtda, int *d_triangle)
+{
+  if (!dev) GSL_ERROR("simplex_mesh_device_eval_fields_resident: null device mirror", GSL_EFAULT);
+  const size_t K = dev->fs.nf, d = (size_t)dev->dim;
+  if (K == 0) GSL_ERROR("simplex_mesh_device_eval_fields_resident: no responses bound", GSL_EINVAL);
+  if (m > 0 && (!d_targets || !d_S)) GSL_ERROR("simplex_mesh_device_eval_fields_resident: null argument", GSL_EFAULT);
+  if (ttda < d) GSL_ERROR("simplex_mesh_device_eval_fields_resident: target rows shorter than the mesh's dimension", GSL_EBADLEN);
+  if (stda < K || (d_G && gtda < d * K))
+    GSL_ERROR("simplex_mesh_device_eval_fields_resident: row pitch below K (values) or K dim (gradients)", GSL_EINVAL);
+  if (m == 0) return GSL_SUCCESS;
+  gsl_sinterp_hip_ctx *c = dev->ctx;                    /* resident buffers live on ONE device: member 0 evaluates them */
+  int st = fields_scratch(&dev->fs, c, m);
+  int *loc = d_triangle ? d_triangle : dev->fs.d_leaf;
+  if (!st) st = (d == 2 ? gsl_sinterp_hip_mesh_eval : gsl_sinterp_hip_mesh3_eval)(c, dev->n_tri, dev->m_records[0], dev->m_leaftab[0], dev->m_seed[0],
+                                                                                 dev->G, dev->geom, dev->convex, d_targets, m, ttda,
+                                                                                 dev->fs.d_val, loc, (long long *)NULL);
+  if (!st && d == 2) st = gsl_sinterp_hip_bary_fields_eval(c, dev->n_tri, dev->m_records[0], dev->m_tri[0], dev->n_points, dev->fs.d_F, (int)K, K,
+                                                           dev->geom + 2, loc, d_targets, m, ttda, d_S, stda, d_G, gtda);
+  if (!st && d == 3) st = gsl_sinterp_hip_mesh3_fields_eval(c, dev->n_tri, dev->m_records[0], dev->m_tri[0], dev->n_points, dev->fs.d_F, (int)K, K,
+                                                            dev->geom, loc, d_targets, m, ttda, d_S, stda, d_G, gtda);
+  if (st) GSL_ERROR(gsl_sinterp_hip_last_error(c), st);
+  return GSL_SUCCESS;
+}
+
+static int mesh_fields_fn(void *dev, const double *d_y, size_t m, size_t ytda, double *d_S, size_t stda, double *d_G, size_t gtda, int *d_leaf)
+{
+  return simplex_mesh_device_eval_fields_resident((simplex_mesh_device *)dev, d_y, m, ytda, d_S, stda, d_G, gtda, d_leaf);
+}
+
+int simplex_mesh_device_eval_fields_many(simplex_mesh_device *dev, const gsl_matrix *targets, gsl_matrix *S, gsl_matrix *G, int *triangle)
+{
+  if (!dev || !targets || !S) GSL_ERROR("simplex_mesh_device_eval_fields_many: null argument", GSL_EFAULT);
+  if (dev->fs.nf == 0) GSL_ERROR("simplex_mesh_device_eval_fields_many: no responses bound", GSL_EINVAL);
+  return fields_eval_host(dev->ctx, (size_t)dev->dim, dev->fs.nf, targets, S, G, triangle, &mesh_fields_fn, dev);
 }
 
 /* ---- natural neighbours on the same mirror (csrc/hip/natural.hip) ---- */
@@ -1663,7 +1860,8 @@ typedef struct {
   simplex_tree *tree;
   simplex_tree_device *dev;
   gsl_matrix *x; /* private copy of the centres: the tree keeps pointers into it */
-  gsl_vector *f; /* private copy of the response (checkpoints) */
+  gsl_vector *f; /* private copy of the response (checkpoints); field 0 after gsl_sinterp_linear_init_fields */
+  size_t nf;     /* fields held: 0 before the first init, 1 after init / fread, K after gsl_sinterp_linear_init_fields */
 } simplex_state;
 static simplex_state *tree_of(const gsl_sinterp *interp);
 
@@ -1692,8 +1890,11 @@ static int simplex_mirror(gsl_sinterp *interp, simplex_state *st)
   simplex_tree_device_free(st->dev);
   st->dev = interp->n_devices > 1 ? simplex_tree_device_alloc_multi(st->tree, st->x, interp->devices, interp->n_devices)
                                   : simplex_tree_device_alloc(st->tree, st->x, interp->device);
+  st->nf = 0;
   if (!st->dev) return GSL_EFAILED;
-  return simplex_tree_device_set_response(st->dev, st->f);
+  int s = simplex_tree_device_set_response(st->dev, st->f);
+  if (!s) st->nf = 1;
+  return s;
 }
 
 static int simplex_init(gsl_sinterp *interp, const gsl_matrix *x, const gsl_vector *f)
@@ -1747,6 +1948,8 @@ typedef struct {
   simplex_mesh_device *dev;
   gsl_matrix *x;             /* private copies (checkpoints) */
   gsl_vector *f;
+  size_t nf;                 /* the linear types: fields held (0 before the first init, 1 after init / fread, K after
+                                gsl_sinterp_linear_init_fields) */
   /* the Clough-Tocher types only: g_set = the caller's gradients (gsl_sinterp_set_gradients; NULL = estimate), g = the
      gradients in use after init / fread, the stopping rule of the estimate (0 = the mirror's defaults) and what it took */
   gsl_matrix *g_set, *g;
@@ -1792,10 +1995,12 @@ static int mesh_type_mirror(gsl_sinterp *interp, mesh_state *st, const gsl_matri
       GSL_ERROR("gsl_sinterp_init: natural neighbours need a Delaunay triangulation (simplex_mesh_delaunay_metric is 0)", GSL_EINVAL);
   }
   simplex_mesh_device_free(st->dev);
+  st->nf = 0;
   st->dev = interp->n_devices > 1 ? simplex_mesh_device_alloc_multi(st->mesh, interp->devices, interp->n_devices)
                                   : simplex_mesh_device_alloc(st->mesh, interp->device);
   if (!st->dev) return GSL_EFAILED;
   int s = simplex_mesh_device_set_response(st->dev, st->f);
+  if (!s) st->nf = 1;
   if (s || d->method != MESH_CUBIC) return s;
   if (st->g_rtol > 0.0) s = simplex_mesh_device_set_gradient_options(st->dev, st->g_rtol, st->g_maxiter);
   if (!s) s = simplex_mesh_device_bind_gradients(st->dev, known);
@@ -2689,9 +2894,14 @@ int gsl_sinterp_init_fields(gsl_sinterp *interp, const gsl_matrix *x, const gsl_
   return rbf_init_fields(interp, x, F->data, F->tda, 1, F->size2);
 }
 
+static int linear_fields_status(const gsl_sinterp *interp);
+
 size_t gsl_sinterp_n_fields(const gsl_sinterp *interp)
 {
-  const rbf_state *st = interp ? rbf_of(interp) : NULL;
+  if (!interp) return 0;
+  if (tree_of(interp)) return tree_of(interp)->dev ? tree_of(interp)->nf : 0;
+  if (mesh_method(interp, MESH_LINEAR)) return mesh_of(interp)->dev ? mesh_of(interp)->nf : 0;
+  const rbf_state *st = rbf_of(interp);
   return st && st->d_w ? st->nf : 0;
 }
 
@@ -2755,6 +2965,119 @@ int gsl_sinterp_eval_fields_e(const gsl_sinterp *interp, const gsl_vector *y, gs
   int st = gsl_sinterp_eval_fields_many(interp, &Y.matrix, &S.matrix);
   if (st != GSL_SUCCESS) return st;
   for (size_t q = 0; q < K; q++) gsl_vector_set(s, q, out[q]);
+  return GSL_SUCCESS;
+}
+
+/* ---- several responses and their gradients on the linear types: the separate entries (csrc/hip/linear_fields.hip) ---- */
+static int linear_fields_status(const gsl_sinterp *interp)
+{
+  if (!tree_of(interp) && !mesh_method(interp, MESH_LINEAR))
+    GSL_ERROR("gsl_sinterp_linear fields: gsl_sinterp_linear_simplex and gsl_sinterp_linear_mesh only", GSL_EUNSUP);
+  return GSL_SUCCESS;
+}
+
+int gsl_sinterp_linear_init_fields(gsl_sinterp *interp, const gsl_matrix *x, const gsl_matrix *F)
+{
+  if (!interp || !x || !F) GSL_ERROR("gsl_sinterp_linear_init_fields: null argument", GSL_EFAULT);
+  int fs = linear_fields_status(interp);
+  if (fs) return fs;
+  if (F->size1 != interp->size) GSL_ERROR("gsl_sinterp_linear_init_fields: the response matrix must have size rows", GSL_EBADLEN);
+  if (x->size1 != interp->size || x->size2 != interp->dim) GSL_ERROR("gsl_sinterp_linear_init_fields: the centre matrix must be size x dim", GSL_EBADLEN);
+  if (F->size2 < 1 || F->size2 > GSL_SINTERP_MAX_FIELDS) GSL_ERROR("gsl_sinterp_linear_init_fields: 1 .. GSL_SINTERP_MAX_FIELDS fields", GSL_EINVAL);
+  /* gsl_sinterp_init with column 0 as the response: tree or imported triangulation, mirror, scalar binding */
+  gsl_vector f0 = {F->size1, F->tda, F->data, NULL, 0};
+  int s = interp->type->init(interp, x, &f0);
+  if (s) return s;
+  if (tree_of(interp)) {
+    simplex_state *st = tree_of(interp);
+    s = simplex_tree_device_set_responses(st->dev, F);
+    st->nf = s ? 0 : F->size2;
+  } else {
+    mesh_state *st = mesh_of(interp);
+    s = simplex_mesh_device_set_responses(st->dev, F);
+    st->nf = s ? 0 : F->size2;
+  }
+  return s;
+}
+
+/* K of an initialised linear interpolant, 0 = not initialised.  An interpolant that came from gsl_sinterp_init or
+   gsl_sinterp_fread holds one field whose matrix binding is made here, at the first use, from the private response copy */
+static size_t linear_fields_ready(const gsl_sinterp *interp, int *status)
+{
+  *status = GSL_SUCCESS;
+  if (tree_of(interp)) {
+    const simplex_state *st = tree_of(interp);
+    if (!st->dev || st->nf == 0) return 0;
+    if (simplex_tree_device_n_responses(st->dev) == 0) {
+      gsl_matrix_view F = gsl_matrix_view_array_with_tda(st->f->data, st->n, 1, st->f->stride);
+      *status = simplex_tree_device_set_responses(st->dev, &F.matrix);
+    }
+    return *status ? 0 : st->nf;
+  }
+  const mesh_state *st = mesh_of(interp);
+  if (!st->dev || st->nf == 0) return 0;
+  if (simplex_mesh_device_n_responses(st->dev) == 0) {
+    gsl_matrix_view F = gsl_matrix_view_array_with_tda(st->f->data, st->n, 1, st->f->stride);
+    *status = simplex_mesh_device_set_responses(st->dev, &F.matrix);
+  }
+  return *status ? 0 : st->nf;
+}
+
+int gsl_sinterp_linear_eval_fields_resident(const gsl_sinterp *interp, const double *d_y, size_t m, size_t ytda, double *d_S, size_t stda,
+                                            double *d_G, size_t gtda, int *d_leaf)
+{
+  if (!interp) GSL_ERROR("gsl_sinterp_linear_eval_fields_resident: null interpolant", GSL_EFAULT);
+  if (m > 0 && (!d_y || !d_S)) GSL_ERROR("gsl_sinterp_linear_eval_fields_resident: null argument", GSL_EFAULT);
+  int fs = linear_fields_status(interp);
+  if (fs) return fs;
+  const size_t K = linear_fields_ready(interp, &fs);
+  if (fs) return fs;
+  if (K == 0) GSL_ERROR("gsl_sinterp_linear_eval_fields: interpolant not initialised", GSL_EINVAL);
+  if (stda < K || (d_G && gtda < K * interp->dim))
+    GSL_ERROR("gsl_sinterp_linear_eval_fields_resident: row pitch below K (values) or K dim (gradients)", GSL_EINVAL);
+  if (tree_of(interp)) return simplex_tree_device_eval_fields_resident(tree_of(interp)->dev, d_y, m, ytda, d_S, stda, d_G, gtda, d_leaf);
+  return simplex_mesh_device_eval_fields_resident(mesh_of(interp)->dev, d_y, m, ytda, d_S, stda, d_G, gtda, d_leaf);
+}
+
+int gsl_sinterp_linear_eval_fields_many(const gsl_sinterp *interp, const gsl_matrix *y, gsl_matrix *S, gsl_matrix *G, int *leaf)
+{
+  if (!interp || !y || !S) GSL_ERROR("gsl_sinterp_linear_eval_fields_many: null argument", GSL_EFAULT);
+  int fs = linear_fields_status(interp);
+  if (fs) return fs;
+  const size_t m = y->size1, dim = interp->dim;
+  if (y->size2 != dim) GSL_ERROR("target matrix must have dim columns", GSL_EBADLEN);
+  if (S->size1 != m) GSL_ERROR("output matrix must have one row per target", GSL_EBADLEN);
+  const size_t K = linear_fields_ready(interp, &fs);
+  if (fs) return fs;
+  if (K == 0) GSL_ERROR("gsl_sinterp_linear_eval_fields: interpolant not initialised", GSL_EINVAL);
+  if (S->size2 != K) GSL_ERROR("output matrix must have one column per field", GSL_EBADLEN);
+  if (G && (G->size1 != m || G->size2 != K * dim)) GSL_ERROR("gradient matrix must be (number of targets) x (K dim)", GSL_EBADLEN);
+  if (tree_of(interp)) return simplex_tree_device_eval_fields_many(tree_of(interp)->dev, y, S, G, leaf);
+  return simplex_mesh_device_eval_fields_many(mesh_of(interp)->dev, y, S, G, leaf);
+}
+
+int gsl_sinterp_linear_eval_fields_e(const gsl_sinterp *interp, const gsl_vector *y, gsl_vector *s, gsl_matrix *g)
+{
+  if (s) for (size_t q = 0; q < s->size; q++) gsl_vector_set(s, q, GSL_NAN);
+  if (g) for (size_t q = 0; q < g->size1; q++) for (size_t a = 0; a < g->size2; a++) gsl_matrix_set(g, q, a, GSL_NAN);
+  if (!interp || !y || !s) GSL_ERROR("gsl_sinterp_linear_eval_fields_e: null argument", GSL_EFAULT);
+  int fs = linear_fields_status(interp);
+  if (fs) return fs;
+  const size_t dim = interp->dim;
+  if (y->size != dim) GSL_ERROR("target must have dim components", GSL_EBADLEN);
+  const size_t K = gsl_sinterp_n_fields(interp);
+  if (K == 0) GSL_ERROR("gsl_sinterp_linear_eval_fields: interpolant not initialised", GSL_EINVAL);
+  if (s->size != K) GSL_ERROR("output must have one entry per field", GSL_EBADLEN);
+  if (g && (g->size1 != K || g->size2 != dim)) GSL_ERROR("gradient must be K x dim", GSL_EBADLEN);
+  double yy[3], out[GSL_SINTERP_MAX_FIELDS], gg[GSL_SINTERP_MAX_FIELDS * 3];
+  for (size_t c = 0; c < dim; c++) yy[c] = gsl_vector_get(y, c);
+  gsl_matrix_view Y = gsl_matrix_view_array(yy, 1, dim), S = gsl_matrix_view_array(out, 1, K), G = gsl_matrix_view_array(gg, 1, K * dim);
+  int st = gsl_sinterp_linear_eval_fields_many(interp, &Y.matrix, &S.matrix, g ? &G.matrix : NULL, NULL);
+  if (st != GSL_SUCCESS) return st;
+  for (size_t q = 0; q < K; q++) {
+    gsl_vector_set(s, q, out[q]);
+    if (g) for (size_t a = 0; a < dim; a++) gsl_matrix_set(g, q, a, gg[q * dim + a]);
+  }
   return GSL_SUCCESS;
 }
 
@@ -3158,6 +3481,7 @@ int gsl_sinterp_fwrite(FILE *stream, const gsl_sinterp *interp)
   if (tree_of(interp)) {
     const simplex_state *st = tree_of(interp);
     if (!st->dev || !st->tree || !st->x || !st->f) GSL_ERROR("gsl_sinterp_fwrite: interpolant not initialised", GSL_EINVAL);
+    if (st->nf > 1) GSL_ERROR("gsl_sinterp_fwrite: the GSLSINT1 format holds one response (interpolant with several fields)", GSL_EUNSUP);
     if (!header_fwrite(stream, interp, 0.0, interp->init_flags)) GSL_ERROR("fwrite failed", GSL_EFAILED);
     int s = simplex_tree_fwrite(stream, st->tree);
     if (s) return s;
@@ -3170,6 +3494,7 @@ int gsl_sinterp_fwrite(FILE *stream, const gsl_sinterp *interp)
   if (mesh_of(interp)) {
     const mesh_state *st = mesh_of(interp);
     if (!st->dev || !st->mesh || !st->x || !st->f) GSL_ERROR("gsl_sinterp_fwrite: interpolant not initialised", GSL_EINVAL);
+    if (st->nf > 1) GSL_ERROR("gsl_sinterp_fwrite: the GSLSINT1 format holds one response (interpolant with several fields)", GSL_EUNSUP);
     if (!header_fwrite(stream, interp, 0.0, 0)) GSL_ERROR("fwrite failed", GSL_EFAILED);
     int s = simplex_mesh_fwrite(stream, st->mesh);
     if (s) return s;

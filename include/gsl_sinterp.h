@@ -163,6 +163,24 @@ int simplex_tree_device_eval_many(simplex_tree_device *dev, const gsl_matrix *ta
 int simplex_tree_device_eval_resident(simplex_tree_device *dev, const double *d_targets, size_t m,
                                       size_t ttda, double *d_values, simplex_index *d_leaf);
 gsl_sinterp_hip_ctx *simplex_tree_device_ctx(simplex_tree_device *dev);
+/* Several responses on the same tree, with per-leaf gradients, from ONE locate ("Several responses on a
+   mesh"; csrc/hip/linear_fields.hip).  set_responses binds F, n_points x K (1 <= K <= 64, F->tda honoured, rows = rows of
+   the data matrix); it and set_response are independent bindings, neither disturbs the other.  eval_fields_many:
+   targets M x 2, S M x K, G (or NULL) M x 2 K with entry (k, 2 q + a) = d(field q)/dy_a, leaf (or NULL); tda of every
+   matrix honoured.  Column q of S holds the bits eval_many returns with column q of F bound; the gradient is that of the
+   affine function of the located leaf (cage vertices carry 0, as in the value), equal bits for every target of a leaf,
+   and the value bits do not depend on G.  A row outside the cage gives NaN in S and G, leaf -1 and GSL_EDOM after every
+   other row has been stored.  eval_fields_resident: row k of d_S at d_S + k * stda (stda >= K), of d_G at d_G + k * gtda
+   (gtda >= 2 K), padding untouched; asynchronous, nothing is read back (no GSL_EDOM: the NaN rows and d_leaf tell).
+   The unchanged locate of eval_many runs once, then the fields sweep.  On a multi-device mirror the first device
+   evaluates every target (no sharding of field batches).  GSL_EINVAL: K = 0, K > 64, no responses bound, stda or gtda
+   too small; GSL_EBADLEN: shapes; GSL_EFAULT: NULL. */
+int simplex_tree_device_set_responses(simplex_tree_device *dev, const gsl_matrix *F);
+size_t simplex_tree_device_n_responses(const simplex_tree_device *dev);     /* K of the last set_responses, 0 = none */
+int simplex_tree_device_eval_fields_many(simplex_tree_device *dev, const gsl_matrix *targets, gsl_matrix *S, gsl_matrix *G,
+                                         simplex_index *leaf);
+int simplex_tree_device_eval_fields_resident(simplex_tree_device *dev, const double *d_targets, size_t m, size_t ttda, double *d_S,
+                                             size_t stda, double *d_G, size_t gtda, simplex_index *d_leaf);
 /* Mirror on several GPUs: the raw DAG arrays are replicated with one broadcast per array, every member
    packs its own records; eval_many shards the targets (eval_resident uses the first device). */
 simplex_tree_device *simplex_tree_device_alloc_multi(simplex_tree *tree, gsl_matrix *data, const int *devices,
@@ -260,6 +278,15 @@ int simplex_mesh_device_set_response(simplex_mesh_device *dev, const gsl_vector 
 int simplex_mesh_device_eval_many(simplex_mesh_device *dev, const gsl_matrix *targets, gsl_vector *values, int *triangle);
 int simplex_mesh_device_eval_resident(simplex_mesh_device *dev, const double *d_targets, size_t m, size_t ttda,
                                       double *d_values, int *d_triangle);
+/* Several responses on the same mirror, with per-simplex gradients, from ONE locate: simplex_tree_device_set_responses /
+   _eval_fields_many / _eval_fields_resident above, for a mesh of dim 2 or 3 (rows of F = rows of the points; targets
+   M x dim; G M x (K dim), entry (k, q dim + a); gtda >= K dim).  Independent of set_response; the first device of a
+   group evaluates every target. */
+int simplex_mesh_device_set_responses(simplex_mesh_device *dev, const gsl_matrix *F);
+size_t simplex_mesh_device_n_responses(const simplex_mesh_device *dev);
+int simplex_mesh_device_eval_fields_many(simplex_mesh_device *dev, const gsl_matrix *targets, gsl_matrix *S, gsl_matrix *G, int *triangle);
+int simplex_mesh_device_eval_fields_resident(simplex_mesh_device *dev, const double *d_targets, size_t m, size_t ttda, double *d_S,
+                                             size_t stda, double *d_G, size_t gtda, int *d_triangle);
 /* Natural-neighbour (Sibson) interpolation on the same mirror: C1 away from the sites, exact at them, reproduces linear
    functions, local, no shape parameter and no solve ("Natural neighbours").  Same shapes and status
    conventions as the two entries above; `triangle` receives the triangle that contains the target.  A target within
@@ -576,7 +603,7 @@ int gsl_sinterp_eval_resident(const gsl_sinterp *interp, const double *d_y, size
    s(y) and ds/dy_a, a < dim, from one fused sweep (gsl_sinterp_hip_rbf_eval_grad) -- the analytic gradient of the radial
    sum plus the affine tail (gsl_sinterp_rbf_tps_affine) or nothing (kriging's mean is constant).  Every RBF-family
    type (kriging included) is supported; gsl_sinterp_linear_simplex and gsl_sinterp_linear_mesh give GSL_EUNSUP (their gradient is constant
-   per leaf: a separate entry).  The value is bit-identical to gsl_sinterp_eval_many's for the same target; a target with a
+   per leaf: gsl_sinterp_linear_eval_fields_* below, K = 1 after a plain init).  The value is bit-identical to gsl_sinterp_eval_many's for the same target; a target with a
    NaN coordinate gets NaN in the value and in every gradient component.
    eval_grad_many: y is m x dim, g is m x dim (g->tda honoured, padding untouched), s has m entries (s->stride honoured)
    or is NULL for a gradient-only call.  eval_grad_e: one target, g has dim entries; *s and g are NaN on failure.
@@ -611,13 +638,14 @@ int gsl_sinterp_eval_grad_resident(const gsl_sinterp *interp, const double *d_y,
    kriging variance does not depend on the responses: gsl_sinterp_set_variance is honoured by init_fields (shared route)
    and the variance entries work unchanged.  gsl_sinterp_init after init_fields returns the interpolant to one field, a
    second init_fields may change K; the eval_fields entries work on a one-field interpolant with K = 1.
-   gsl_sinterp_n_fields: 0 before the first init (and for the linear types), 1 after gsl_sinterp_init / gsl_sinterp_fread.
+   gsl_sinterp_n_fields: 0 before the first init, 1 after gsl_sinterp_init / gsl_sinterp_fread (the natural-neighbour,
+   Clough-Tocher and Shepard types: always 0; the linear types: K after gsl_sinterp_linear_init_fields).
    eval_fields_many: y is m x dim, S is m x K (S->tda honoured, padding untouched).  eval_fields_e: s has K entries, NaN
    on failure.  eval_fields_resident: everything in HBM, target k's field q at d_s[k * stda + q] (stda >= K).
    get_field_weights / field_mean (kriging) / field_poly (affine thin-plate spline) read field q back.
    GSL_EFAULT: a NULL argument; GSL_EUNSUP: gsl_sinterp_linear_simplex / gsl_sinterp_linear_mesh (several responses per
-   leaf are a separate piece of work); GSL_EBADLEN: F->size1 != size, x not size x dim, y->size2 != dim, S not m x K, a
-   vector whose length is not K / size / dim + 1, q >= K; GSL_EINVAL: not initialised, K = 0 or K > 64, stda < K, mean /
+   leaf are the separate entries gsl_sinterp_linear_init_fields / _eval_fields_* below); GSL_EBADLEN: F->size1 != size,
+   x not size x dim, y->size2 != dim, S not m x K, a vector whose length is not K / size / dim + 1, q >= K; GSL_EINVAL: not initialised, K = 0 or K > 64, stda < K, mean /
    poly asked of another type.  With a device list the model is broadcast whole and the first device evaluates every
    fields batch through plain staging (not sharded, not pipelined).  gsl_sinterp_fwrite of an interpolant with more than
    one field returns GSL_EUNSUP and writes nothing: the GSLSINT1 format holds one weight vector. */
@@ -629,6 +657,36 @@ int gsl_sinterp_eval_fields_resident(const gsl_sinterp *interp, const double *d_
 int gsl_sinterp_get_field_weights(const gsl_sinterp *interp, size_t q, gsl_vector *w);
 int gsl_sinterp_field_mean(const gsl_sinterp *interp, size_t q, double *mean);
 int gsl_sinterp_field_poly(const gsl_sinterp *interp, size_t q, gsl_vector *c);
+/* Several responses on the piecewise-linear types, and their gradients ("Several responses on a mesh"): the
+   separate entries the refusals of gsl_sinterp_init_fields and gsl_sinterp_eval_grad_* name.  They serve
+   gsl_sinterp_linear_simplex and gsl_sinterp_linear_mesh (dim 2 and 3); every other type answers GSL_EUNSUP before
+   anything touches the device.  SciPy's LinearNDInterpolator takes values of shape (N, K) the same way.
+   linear_init_fields(x, F): F is size x K (F->tda honoured, 1 <= K <= GSL_SINTERP_MAX_FIELDS).  Builds the tree or
+   validates the imported triangulation exactly as gsl_sinterp_init(x, column 0 of F) does -- set_tree_options,
+   set_triangulation and the device(s) honoured -- then binds all K columns.  To every other entry the result IS field
+   0's interpolant: eval_e / _many / _resident / _grid return the bits they return after gsl_sinterp_init(x, F[:, 0]);
+   gsl_sinterp_n_fields is K.  gsl_sinterp_init afterwards returns the interpolant to one field; a second
+   linear_init_fields may change K.  An interpolant initialised by gsl_sinterp_init or restored by gsl_sinterp_fread
+   answers the eval entries with K = 1: the linear gradient entry.  gsl_sinterp_fwrite with K > 1 is GSL_EUNSUP and
+   writes nothing.
+   The eval entries locate every target ONCE (the unchanged locate of gsl_sinterp_eval_many) and take the K values and,
+   when asked, the K gradients from the simplex found: column q of S holds the bits gsl_sinterp_eval_many returns
+   after gsl_sinterp_init(x, F[:, q]); the gradient of field q is that of the affine function of the located simplex
+   (on a leaf that touches the cage of gsl_sinterp_linear_simplex the cage vertices carry 0, as in the value), in raw
+   coordinates, the same bits for every target of a simplex; the value bits do not depend on whether gradients are asked.
+   eval_fields_e: s has K entries, g is K x dim or NULL; NaN on failure.  eval_fields_many: y m x dim, S m x K, G (or
+   NULL) m x (K dim) with entry (k, q dim + a) = d(field q)/dy_a, leaf (or NULL) m ints; every tda honoured, padding
+   untouched.  A target outside gives a NaN row, leaf -1 and GSL_EDOM after every other row has been stored.
+   eval_fields_resident: everything in HBM, rows at d_S + k * stda and d_G + k * gtda; nothing is read back.
+   GSL_EFAULT: NULL; GSL_EUNSUP: another type; GSL_EBADLEN: shapes; GSL_EINVAL: not initialised, K = 0 or K > 64, stda <
+   K or gtda < K dim.  With a device list the first device evaluates every target of these entries (field batches are
+   not sharded), and the _many entry copies through plain staging. */
+int gsl_sinterp_linear_init_fields(gsl_sinterp *interp, const gsl_matrix *x, const gsl_matrix *F);
+int gsl_sinterp_linear_eval_fields_e(const gsl_sinterp *interp, const gsl_vector *y, gsl_vector *s, gsl_matrix *g /* K x dim or NULL */);
+int gsl_sinterp_linear_eval_fields_many(const gsl_sinterp *interp, const gsl_matrix *y, gsl_matrix *S, gsl_matrix *G /* or NULL */,
+                                        int *leaf /* or NULL */);
+int gsl_sinterp_linear_eval_fields_resident(const gsl_sinterp *interp, const double *d_y, size_t m, size_t ytda, double *d_S, size_t stda,
+                                            double *d_G /* or NULL */, size_t gtda, int *d_leaf /* or NULL */);
 /* Gridded front-end (interpolation/scattered_interp_example.c:175-217): evaluate on the regular grid
    x_i = min[0] + i (max[0]-min[0])/n0, y_j = min[1] + j (max[1]-min[1])/n1 (the reference's steps: range / n_grid,
    the upper bounds excluded) with n0 = grid->size1, n1 = grid->size2; grid(i, j) receives the value.  The

@@ -168,6 +168,39 @@ int gsl_sinterp_hip_mesh3_eval(gsl_sinterp_hip_ctx *ctx, int n_tet, const void *
                                const int *d_seed, int G, const double *h_geom, int convex, const double *d_targets,
                                size_t m, size_t ttda, double *d_values, int *d_tet, long long *h_n_outside);
 
+/* Several responses on the piecewise-linear types, with per-simplex gradients (csrc/hip/linear_fields.hip; DESIGN.md 4,
+   "Several responses on a mesh").  A located sweep: d_located [m] = the simplex of every target as
+   gsl_sinterp_hip_bary_eval, gsl_sinterp_hip_mesh_eval (bary_fields_eval) or gsl_sinterp_hip_mesh3_eval
+   (mesh3_fields_eval) stored it for the same targets (run it first).  d_records: the records of tree_pack / mesh_pack /
+   mesh3_pack, unchanged.  d_vertices [3 n_simplices] (d_tet [4 n_tet]): the vertex ids the matching *_bind call takes
+   (the DAG's d_pidx, insertion order, < 0 = cage; or the triangles / tetrahedra of an imported mesh, row order).
+   d_F: n_points x nf, row v at d_F + v * ftda, in that vertex order; no per-simplex table is built, the rows are
+   gathered.  h_scale [2]: the scale tree_pack / mesh_pack were given; h_geom [12]: as for mesh3_pack (shift and scale
+   are read).  1 <= nf <= GSL_SINTERP_MAX_FIELDS.
+   d_S[k * stda + q] = field q at target k: the bits the scalar kernel stores in d_values[k] when its table is bound to
+   column q (same coordinates, same order of operations, cage vertices masked).  One exception: a target the exact DAG
+   walk left in a leaf whose record is flagged singular gets that record's own (non-finite) coordinates here, where
+   the walk kept those of the last regular node it passed.
+   d_G (may be NULL; the value bits do not depend on it): d_G[k * gtda + q * dim + a] = d/dy_a, in raw coordinates, of
+   the affine function field q's value is taken from in the located simplex, formed from the record (2-D: two
+   triangular solves with its LU; 3-D: its inverse) and the dim response differences, a cage vertex carrying 0 as in
+   the value: constant per simplex, equal bits for every target in it.
+   d_located[k] < 0 (or not below n_simplices): NaN in the nf values and the nf dim gradient components of row k.
+   Padding between nf and stda, and between nf dim and gtda, is not written.  GSL_EINVAL (nf < 1, nf > 64, ftda or
+   stda < nf, gtda < nf dim with d_G given, ttda < dim) and GSL_EFAULT (NULL) are decided before anything touches the
+   device; m = 0 is success; asynchronous on the context's stream. */
+int gsl_sinterp_hip_bary_fields_eval(gsl_sinterp_hip_ctx *ctx, int n_simplices, const void *d_records, const int *d_vertices,
+                                     int n_points, const double *d_F, int nf, size_t ftda, const double *h_scale,
+                                     const int *d_located, const double *d_targets, size_t m, size_t ttda, double *d_S,
+                                     size_t stda, double *d_G, size_t gtda);
+int gsl_sinterp_hip_mesh3_fields_eval(gsl_sinterp_hip_ctx *ctx, int n_tet, const void *d_records, const int *d_tet, int n_points,
+                                      const double *d_F, int nf, size_t ftda, const double *h_geom, const int *d_located,
+                                      const double *d_targets, size_t m, size_t ttda, double *d_S, size_t stda, double *d_G,
+                                      size_t gtda);
+/* 1 when a located sweep (bary_eval, mesh_eval, mesh3_eval) reorders a batch of m targets into cell order before it
+   walks (the sorted-target route), 0 when it walks them as given: the route helper itself, GSL_SINTERP_NO_SORT included */
+int gsl_sinterp_hip_sort_wanted(size_t m);
+
 /* Natural-neighbour (Sibson) interpolation on a 2-D Delaunay mesh (csrc/hip/natural.hip; DESIGN.md 4, "Natural
    neighbours").  natural_pack: one 80-byte, 16-byte-aligned record per triangle in METRIC coordinates (raw coordinate
    times h_metric[axis]: {1, 1} for a mesh that is Delaunay as given, the mesh's per-axis scale for one that is Delaunay
