@@ -99,6 +99,8 @@ class gsl_sinterp(C.Structure):
                 ("n_devices", C.c_int), ("devices", C.c_int * 64), ("solver", C.c_int), ("want_rcond", C.c_int),
                 ("rcond", C.c_double), ("route", C.c_int), ("nugget", C.c_double), ("want_variance", C.c_int),
                 ("want_loo", C.c_int), ("neighbours", C.c_size_t)]
+    # the C struct ends with `int drift` behind these: the library allocates every gsl_sinterp, the bindings read the order
+    # through gsl_sinterp_drift
 
 
 _vp, _i, _sz, _d = C.c_void_p, C.c_int, C.c_size_t, C.c_double
@@ -291,6 +293,20 @@ SIGNATURES = {
     "gsl_sinterp_hip_chol_inv_diag_work": (_sz, [_sz, _sz]),
     "gsl_sinterp_hip_chol_inv_diag": (_i, [_vp, _sz, _vp, _sz, _vp, _vp, _sz]),
     "gsl_sinterp_hip_loo_combine": (_i, [_vp, _sz, _sz, _vp, _vp, _d, _vp, _sz, _vp, _sz, _vp]),
+    "gsl_sinterp_hip_drift_terms": (_sz, [_i, _i]),
+    "gsl_sinterp_hip_drift_factor": (_i, [_sz, _pd, _pd]),
+    "gsl_sinterp_hip_drift_basis": (_i, [_vp, _i, _pd, _pd, _vp, _sz, _i, _sz, _vp, _sz]),
+    "gsl_sinterp_hip_ukrige_solve": (_i, [_vp, _i, _d, _d, _i, _pd, _pd, _vp, _sz, _i, _sz, _vp, _sz, _vp, _sz, _sz, _pd, _vp, _sz, _pd, _pd, _vp,
+                                          _pi]),
+    "gsl_sinterp_hip_drift_add": (_i, [_vp, _i, _pd, _pd, _pd, _sz, _vp, _sz, _i, _sz, _vp, _sz, _vp, _sz]),
+    "gsl_sinterp_hip_ukrige_variance_work": (_sz, [_sz, _sz, _sz]),
+    "gsl_sinterp_hip_ukrige_variance": (_i, [_vp, _i, _d, _i, _pd, _pd, _vp, _sz, _i, _sz, _vp, _sz, _vp, _sz, _vp, _pd, _vp, _sz, _sz, _vp,
+                                             _vp, _sz]),
+    "gsl_sinterp_hip_loo_combine_drift": (_i, [_vp, _sz, _sz, _vp, _vp, _sz, _sz, _pd, _vp, _sz, _vp, _sz, _vp]),
+    "gsl_sinterp_set_drift": (_i, [C.POINTER(gsl_sinterp), _i]),
+    "gsl_sinterp_drift": (_i, [C.POINTER(gsl_sinterp)]),
+    "gsl_sinterp_drift_terms": (_sz, [_sz, _i]),
+    "gsl_sinterp_drift_coefficients": (_i, [C.POINTER(gsl_sinterp), _sz, _pv, _pv, _pv]),
     "gsl_sinterp_set_loo": (_i, [C.POINTER(gsl_sinterp), _i]),
     "gsl_sinterp_loo_residuals": (_i, [C.POINTER(gsl_sinterp), _pm]),
     "gsl_sinterp_loo_variance": (_i, [C.POINTER(gsl_sinterp), _pv]),
@@ -298,6 +314,8 @@ SIGNATURES = {
     "gsl_sinterp_hip_knn": (_i, [_vp, _vp, _sz, _i, _sz, _vp, _sz, _sz, _sz, _vp, _vp, C.c_uint64]),
     "gsl_sinterp_hip_local_krige": (_i, [_vp, _i, _d, _d, _vp, _sz, _i, _sz, _vp, _vp, _sz, _sz, _sz, _vp, _vp, _vp,
                                          C.POINTER(C.c_size_t), C.c_uint64]),
+    "gsl_sinterp_hip_local_ukrige": (_i, [_vp, _i, _d, _d, _vp, _sz, _i, _sz, _vp, _vp, _sz, _sz, _sz, _vp, _vp, _vp,
+                                          C.POINTER(C.c_size_t), C.c_uint64]),
     "gsl_sinterp_hip_local_pack": (_i, [_vp, _vp, _sz, _i, _sz, _vp, C.c_uint64]),
     "gsl_sinterp_hip_local_pack_count": (C.c_uint64, [_vp]),
     "gsl_sinterp_set_neighbours": (_i, [C.POINTER(gsl_sinterp), _sz]),
@@ -615,6 +633,57 @@ class HipContext:
                                                       mean.ctypes.data_as(_pd), C.byref(route))
         return st, route.value, mean
 
+    # --- universal kriging (csrc/hip/drift.hip): order 1 or 2, h_shift / h_scale = dim doubles each
+    @staticmethod
+    def drift_terms(dim, order):
+        return lib().gsl_sinterp_hip_drift_terms(dim, order)
+
+    @staticmethod
+    def drift_factor(S):
+        """(status, Ls): the host Cholesky factor of the q x q S, lower triangle, row-major"""
+        S = np.ascontiguousarray(S, dtype=np.float64)
+        L = np.zeros_like(S)
+        st = lib().gsl_sinterp_hip_drift_factor(S.shape[0], S.ctypes.data_as(_pd), L.ctypes.data_as(_pd))
+        return st, L
+
+    def drift_basis(self, order, shift, scale, d_x, n, dim, xtda, d_P, ldp):
+        shift, scale = np.ascontiguousarray(shift, dtype=np.float64), np.ascontiguousarray(scale, dtype=np.float64)
+        return lib().gsl_sinterp_hip_drift_basis(self._h, order, shift.ctypes.data_as(_pd), scale.ctypes.data_as(_pd), d_x, n, dim, xtda,
+                                                 d_P, ldp)
+
+    def ukrige_solve(self, kind, eps, nugget, order, shift, scale, d_x, n, dim, xtda, d_phi, lda, d_w, ldw, nf, d_B=None, ldb=0, d_dinv=None):
+        """universal kriging of nf fields on one factor; returns (status, route, coef[nf, q], S[q, q], Ls[q, q])"""
+        shift, scale = np.ascontiguousarray(shift, dtype=np.float64), np.ascontiguousarray(scale, dtype=np.float64)
+        q = max(int(self.drift_terms(dim, order)), 1)
+        route, coef, S, Ls = C.c_int(0), np.zeros((max(nf, 1), q)), np.zeros((q, q)), np.zeros((q, q))
+        st = lib().gsl_sinterp_hip_ukrige_solve(self._h, kind, eps, nugget, order, shift.ctypes.data_as(_pd), scale.ctypes.data_as(_pd), d_x,
+                                                n, dim, xtda, d_phi, lda, d_w, ldw, nf, coef.ctypes.data_as(_pd), d_B, ldb,
+                                                S.ctypes.data_as(_pd), Ls.ctypes.data_as(_pd), d_dinv, C.byref(route))
+        return st, route.value, coef, S, Ls
+
+    def drift_add(self, order, shift, scale, coef, nf, d_y, m, dim, ytda, d_s, stda, d_g=None, gtda=0):
+        """d_s[k stda + f] += p(u(y_k))^T c_f, d_g likewise with the gradient; coef: nf x q"""
+        shift, scale = np.ascontiguousarray(shift, dtype=np.float64), np.ascontiguousarray(scale, dtype=np.float64)
+        coef = np.ascontiguousarray(coef, dtype=np.float64)
+        return lib().gsl_sinterp_hip_drift_add(self._h, order, shift.ctypes.data_as(_pd), scale.ctypes.data_as(_pd), coef.ctypes.data_as(_pd),
+                                               nf, d_y, m, dim, ytda, d_s, stda, d_g, gtda)
+
+    @staticmethod
+    def ukrige_variance_work(n, chunk, q):
+        return lib().gsl_sinterp_hip_ukrige_variance_work(n, chunk, q)
+
+    def ukrige_variance(self, kind, eps, order, shift, scale, d_x, n, dim, xtda, d_llt, lda, d_B, ldb, d_dinv, L, d_y, m, ytda, d_var,
+                        d_work, chunk):
+        shift, scale = np.ascontiguousarray(shift, dtype=np.float64), np.ascontiguousarray(scale, dtype=np.float64)
+        L = np.ascontiguousarray(L, dtype=np.float64)
+        return lib().gsl_sinterp_hip_ukrige_variance(self._h, kind, eps, order, shift.ctypes.data_as(_pd), scale.ctypes.data_as(_pd), d_x, n,
+                                                     dim, xtda, d_llt, lda, d_B, ldb, d_dinv, L.ctypes.data_as(_pd), d_y, m, ytda, d_var,
+                                                     d_work, chunk)
+
+    def loo_combine_drift(self, n, nf, d_g, d_B, ldb, q, L, d_w, ldw, d_e, lde, d_v):
+        L = np.ascontiguousarray(L, dtype=np.float64)
+        return lib().gsl_sinterp_hip_loo_combine_drift(self._h, n, nf, d_g, d_B, ldb, q, L.ctypes.data_as(_pd), d_w, ldw, d_e, lde, d_v)
+
     def device(self):
         return lib().gsl_sinterp_hip_ctx_device(self._h)
 
@@ -713,6 +782,13 @@ class HipContext:
         failed = C.c_size_t(0)
         st = lib().gsl_sinterp_hip_local_krige(self._h, kind, eps, nugget, d_x, n, dim, xtda, d_f, d_y, m, ytda, k, d_s, d_var, d_idx,
                                                C.byref(failed), model_id)
+        return st, failed.value
+
+    def local_ukrige(self, kind, eps, nugget, d_x, n, dim, xtda, d_f, d_y, m, ytda, k, d_s=None, d_var=None, d_idx=None, model_id=0):
+        """local_krige with a linear drift (k >= dim + 2); returns (status, failed)"""
+        failed = C.c_size_t(0)
+        st = lib().gsl_sinterp_hip_local_ukrige(self._h, kind, eps, nugget, d_x, n, dim, xtda, d_f, d_y, m, ytda, k, d_s, d_var, d_idx,
+                                                C.byref(failed), model_id)
         return st, failed.value
 
     def local_pack(self, d_x, n, dim, xtda, d_f=None, model_id=0):
@@ -1242,6 +1318,25 @@ class Sinterp:
         v = C.c_double(0)
         st = lib().gsl_sinterp_mean(self._p, C.byref(v))
         return st, v.value
+
+    def set_drift(self, order):
+        """kriging, before init: 0 = ordinary kriging, 1 / 2 = universal kriging with a linear / quadratic drift"""
+        return lib().gsl_sinterp_set_drift(self._p, int(order))
+
+    def drift(self):
+        return lib().gsl_sinterp_drift(self._p)
+
+    @staticmethod
+    def drift_terms(dim, order):
+        return lib().gsl_sinterp_drift_terms(dim, order)
+
+    def drift_coefficients(self, field=0):
+        """(status, c[q], shift[dim], scale[dim]) of an interpolant initialised with a drift"""
+        dim = self._p.contents.dim
+        q = max(int(self.drift_terms(dim, self.drift())), 1)
+        c, shift, scale = np.full(q, np.nan), np.full(dim, np.nan), np.full(dim, np.nan)
+        st = lib().gsl_sinterp_drift_coefficients(self._p, field, C.byref(as_vector(c)), C.byref(as_vector(shift)), C.byref(as_vector(scale)))
+        return st, c, shift, scale
 
     def set_variance(self, want=True):
         """kriging: the next init keeps the Cholesky factor (N^2 doubles on the device) for eval_variance_*"""

@@ -237,6 +237,16 @@ int sinterp_kv_update(const KvPass &p, size_t c0, size_t cw, size_t k0, size_t k
 int sinterp_kv_diag(const KvPass &p, size_t j0);
 /* inverse of every 32 x 32 diagonal block of L -> d_dinv[ceil(n / 32) * 1024] (krige_inv32_kernel) */
 int sinterp_krige_inv32(gsl_sinterp_hip_ctx *ctx, size_t n, const double *d_llt, size_t lda, double *d_dinv);
+/* drift.hip: the launchers behind the universal-kriging entries of solve.hip and krige_var.hip (order 1 or 2, arguments
+   checked by the callers).  basis: column t of P at d_P + t * ldp.  gram: d_G[a * ncols + b] = sum_i P_a[i] Y_b[i], a < q,
+   b < ncols, fixed summation order.  var_combine: d_var[k] = (1 - d_q[k]) + |Ls^-1 (p(u(y_k)) - d_bk[k * q ..])|^2, h_L = the
+   q x q row-major factor of gsl_sinterp_hip_drift_factor. */
+int sinterp_drift_basis(gsl_sinterp_hip_ctx *ctx, int order, const double *h_shift, const double *h_scale, const double *d_x, size_t n,
+                        int dim, size_t xtda, double *d_P, size_t ldp);
+int sinterp_drift_gram(gsl_sinterp_hip_ctx *ctx, const double *d_P, size_t ldp, const double *d_Y, size_t ldy, size_t n, int q, int ncols,
+                       double *d_G);
+int sinterp_drift_var_combine(gsl_sinterp_hip_ctx *ctx, int order, const double *h_shift, const double *h_scale, const double *h_L, int dim,
+                              const double *d_y, size_t rows, size_t ytda, const double *d_bk, const double *d_q, double *d_var);
 /* second grow-only buffer for vectors that must outlive factorisation workspaces */
 int sinterp_aux(gsl_sinterp_hip_ctx *ctx, size_t bytes, void **out);
 int sinterp_invbuf(gsl_sinterp_hip_ctx *ctx, size_t bytes, void **out);

@@ -319,6 +319,62 @@ extern "C" int gsl_sinterp_hip_krige_variance(gsl_sinterp_hip_ctx *ctx, int kind
   return ST_SUCCESS;
 }
 
+/* ------------------------------------------------------------------------ */
+/* The variance of universal kriging (drift.hip):
+       sigma^2(y) = 1 - |L^-1 k|^2 + r^T S^-1 r,     r = p(u(y)) - B^T k(y),     B = K^-1 P,  S = P^T B = Ls Ls^T.
+   |L^-1 k|^2 is the recursion above, untouched; B^T k comes per pass from the fields sweep with the q columns of B as
+   weights, into a rows x q scratch behind q; drift_var_combine_kernel takes the place of krige_combine_kernel. */
+extern "C" size_t gsl_sinterp_hip_ukrige_variance_work(size_t n, size_t chunk, size_t q)
+{
+  return gsl_sinterp_hip_krige_variance_work(n, chunk) + round_up(chunk ? chunk : 1, KV_RP) * q;
+}
+
+extern "C" int gsl_sinterp_hip_ukrige_variance(gsl_sinterp_hip_ctx *ctx, int kind, double eps, int order, const double *h_shift,
+                                               const double *h_scale, const double *d_x, size_t n, int dim, size_t xtda,
+                                               const double *d_llt, size_t lda, const double *d_B, size_t ldb, const double *d_dinv,
+                                               const double *h_L, const double *d_y, size_t m, size_t ytda, double *d_var,
+                                               double *d_work, size_t chunk)
+{
+  REQUIRE(ctx, ctx != NULL, ST_EFAULT);
+  HIP_OK(ctx, hipSetDevice(ctx->device));
+  EXCLUSIVE_SECTION(ctx);                          /* the stream-K updates spin on sibling workgroups */
+  REQUIRE(ctx, dim >= 1 && dim <= 3 && xtda >= (size_t)dim && ytda >= (size_t)dim && lda >= n && ldb >= n && chunk >= 1, ST_EINVAL);
+  REQUIRE(ctx, kind_is_pd(kind) && (order == 1 || order == 2), ST_EINVAL);
+  REQUIRE(ctx, h_shift && h_scale && h_L, ST_EFAULT);
+  REQUIRE(ctx, (m == 0 || n == 0) || (d_x && d_llt && d_B && d_dinv && d_y && d_var && d_work), ST_EFAULT);
+  if (m == 0 || n == 0) return ST_SUCCESS;
+  if (chunk > ((size_t)1 << 19)) chunk = (size_t)1 << 19;      /* rows / 16 is a grid dimension */
+  const size_t q = gsl_sinterp_hip_drift_terms(dim, order);
+  int st = sinterp_streamk_prepare(ctx);
+  if (st) return st;
+  const double *tbl = NULL;
+  st = sinterp_rbf_exp2_table(ctx, &tbl);
+  if (st) return st;
+  const double coef = kernel_coef(kind, eps);
+  KvPass p;
+  p.ctx = ctx; p.ldw = round_up(n, PB); p.L = d_llt; p.lda = lda; p.n = n; p.dinv = d_dinv;
+  p.Z = (double *)(((uintptr_t)d_work + 15) & ~(uintptr_t)15);
+  const size_t chunk_pad = round_up(chunk, KV_RP);
+  p.q = p.Z + chunk_pad * p.ldw;
+  double *bk = p.q + chunk_pad;                    /* rows x q: B^T k(y) of the pass */
+  for (size_t k0 = 0; k0 < m; k0 += chunk) {
+    const size_t rows = m - k0 < chunk ? m - k0 : chunk;
+    p.rows_pad = round_up(rows, KV_RP);
+    st = gsl_sinterp_hip_rbf_eval_fields(ctx, kind, eps, NULL, d_x, n, dim, xtda, d_B, ldb, q, d_y + k0 * ytda, rows, ytda, bk, q, 0);
+    if (st) return st;
+    with_kind(kind, [&](auto K) {
+      if constexpr (kind_is_pd(decltype(K)::value))          /* kind_is_pd(kind) was required above */
+        launch_cross_fill<decltype(K)::value>(ctx, coef, tbl, d_x, n, dim, xtda, d_y + k0 * ytda, rows, ytda, p.Z, p.ldw, p.rows_pad, p.q);
+    });
+    LAUNCH_CHECK(ctx);
+    st = kv_solve(p, PB);                          /* the default panel; GSL_SINTERP_KRIGE_PANEL is krige_variance's developer switch */
+    if (st) return st;
+    st = sinterp_drift_var_combine(ctx, order, h_shift, h_scale, h_L, dim, d_y + k0 * ytda, rows, ytda, bk, p.q, d_var + k0);
+    if (st) return st;
+  }
+  return ST_SUCCESS;
+}
+
 extern "C" int gsl_sinterp_hip_krige_variance_clamp(gsl_sinterp_hip_ctx *ctx, double *d_v, size_t m)
 {
   REQUIRE(ctx, ctx != NULL, ST_EFAULT);

@@ -343,6 +343,172 @@ local_krige_kernel(double coef, double nugget, const double *__restrict__ tbl, c
   }
 }
 
+/* Local UNIVERSAL kriging with a linear drift ("Universal kriging"): local_krige_kernel's search, fill and
+   in-register factorisation, with the DIM coordinate columns riding as further right-hand sides.  Local basis
+   u = (x_i - y) / h, h = the distance of the k-th (farthest) neighbour: at the target p = e_0, and the columns of
+   P_S = [1 | u] are of order one whatever the units of the coordinates.  With V = L^-1 P_S, g = L^-1 f_S, u = L^-1 k_S:
+       S = V^T V (lk_sum reductions, the same on every lane), a scalar Cholesky S = Ls Ls^T on every lane,
+       c = S^-1 V^T g,   s = c_0 + u^T (g - V c),   sigma^2 = phi(0) - u^T u + r^T S^-1 r,   r = e_0 - V^T u.
+   Failed (NaN in value and variance, counted): a K_S pivot as in local_krige_kernel; an S pivot not above 64 u times that
+   diagonal entry of S before elimination, or not finite (a collinear / coplanar neighbourhood); h = 0. */
+template <int KIND, int DIM, int KMAX>
+__global__ void __launch_bounds__(64)
+local_ukrige_kernel(double coef, double nugget, const double *__restrict__ tbl, const LkGrid *__restrict__ grid, int g,
+                    const unsigned *__restrict__ off, const double *__restrict__ rec, const double *__restrict__ yv, size_t ytda,
+                    const int *__restrict__ perm, int k, double *__restrict__ sout, double *__restrict__ vout, int *__restrict__ idx,
+                    unsigned *__restrict__ n_failed)
+{
+  constexpr int Q = DIM + 1;
+  __shared__ double s_t0[kind_uses_exp2(KIND) ? TBL_N : 1];
+  __shared__ double s_r2[128];
+  __shared__ int s_id[128];
+  __shared__ unsigned s_pos[128];
+  __shared__ double s_x[DIM][64];
+  const int lane = threadIdx.x;
+  if (kind_uses_exp2(KIND)) {
+#pragma unroll
+    for (int q = 0; q < TBL_N / 64; q++) s_t0[lane + 64 * q] = tbl[lane + 64 * q];
+  }
+  const size_t t = perm ? (size_t)perm[blockIdx.x] : (size_t)blockIdx.x;
+  double y[DIM];
+  bool isnan_y = false;
+#pragma unroll
+  for (int c = 0; c < DIM; c++) { y[c] = yv[t * ytda + c]; isnan_y |= y[c] != y[c]; }
+  if (isnan_y) {                                   /* no neighbours; not a failed pivot */
+    if (idx && lane < k) idx[t * (size_t)k + lane] = -1;
+    if (lane == 0) { if (sout) sout[t] = NAN; if (vout) vout[t] = NAN; }
+    return;
+  }
+  const LkGrid G = *grid;
+  LkList L;
+  L.s_r2 = s_r2; L.s_id = s_id; L.s_pos = s_pos;
+  lk_search<DIM>(L, y, G, g, off, rec, k, lane);   /* its first barrier also covers the table */
+  const bool real = lane < k && L.bid != LK_NONE;
+  if (idx && lane < k) idx[t * (size_t)k + lane] = real ? L.bid : -1;
+  if (!sout && !vout) return;
+  bool bad = __any(lane < k && !real);             /* fewer than k centres with a finite distance */
+
+  /* ---- fill (as local_krige_kernel) */
+  double xi[DIM], fi = 0.0;
+#pragma unroll
+  for (int c = 0; c < DIM; c++) xi[c] = 0.0;
+  if (real) {
+    const double *r = rec + (size_t)L.bpos * (DIM + 2);
+#pragma unroll
+    for (int c = 0; c < DIM; c++) xi[c] = r[c];
+    fi = r[DIM];
+  }
+#pragma unroll
+  for (int c = 0; c < DIM; c++) s_x[c][lane] = xi[c];
+  __syncthreads();
+  const double phi0 = phi_r2<KIND, 1>(0.0, coef, s_t0, s_t0);
+  const double diag = phi0 + nugget;
+  double a[KMAX];
+#pragma unroll
+  for (int j = 0; j < KMAX; j++) {
+    double r2 = 0.0;
+#pragma unroll
+    for (int c = 0; c < DIM; c++) { const double d = xi[c] - s_x[c][j]; r2 = fma(d, d, r2); }
+    const double v = phi_r2<KIND, 1>(r2, coef, s_t0, s_t0);
+    a[j] = (real && j < k) ? (j == lane ? diag : v) : (j == lane ? 1.0 : 0.0);
+    asm volatile("" : "+v"(a[j]) : : "memory");    /* one entry at a time, as in local_krige_kernel */
+  }
+  double bu = real ? phi_r2<KIND, 1>(L.br2, coef, s_t0, s_t0) : 0.0;      /* k_S */
+  double bv = real ? 1.0 : 0.0;                                           /* 1: the constant term of the drift */
+  double bg = real ? fi : 0.0;                                            /* f_S */
+  /* the neighbours arrive nearest first: lane k - 1 holds the farthest.  h = 0 (k coincident sites at the target) fails */
+  const double h = sqrt(lane_bcast(L.br2, k - 1));
+  bad |= !(h > 0.0) || !(h < INFINITY);
+  const double hinv = 1.0 / h;
+  double bp[DIM];                                                         /* the coordinate columns, u = (x_i - y) / h */
+#pragma unroll
+  for (int c = 0; c < DIM; c++) bp[c] = real ? (xi[c] - y[c]) * hinv : 0.0;
+
+  /* ---- factorisation and the 3 + DIM forward substitutions */
+  const double dmin = diag * (64.0 * DBL_EPSILON);
+#pragma unroll
+  for (int J = 0; J < KMAX; J++) {
+    double v = a[J];
+#pragma unroll
+    for (int kk = 0; kk < J; kk++) v = fma(-a[kk], lane_bcast(a[kk], J), v);
+    const double d = lane_bcast(v, J);
+    bad |= !(d > dmin) || !(d < INFINITY);
+    const double rinv = 1.0 / sqrt(d);
+    const double l = lane >= J ? v * rinv : 0.0;
+    a[J] = l;
+    const double uJ = lane_bcast(bu, J) * rinv, vJ = lane_bcast(bv, J) * rinv, gJ = lane_bcast(bg, J) * rinv;
+    bu = lane == J ? uJ : fma(-l, uJ, bu);
+    bv = lane == J ? vJ : fma(-l, vJ, bv);
+    bg = lane == J ? gJ : fma(-l, gJ, bg);
+#pragma unroll
+    for (int c = 0; c < DIM; c++) {
+      const double pJ = lane_bcast(bp[c], J) * rinv;
+      bp[c] = lane == J ? pJ : fma(-l, pJ, bp[c]);
+    }
+  }
+
+  /* ---- combine: V = [bv | bp], every sum in lk_sum's fixed order, everything below the same on every lane */
+  double V[Q];
+  V[0] = bv;
+#pragma unroll
+  for (int c = 0; c < DIM; c++) V[1 + c] = bp[c];
+  double S[Q][Q], Vg[Q], r[Q];
+#pragma unroll
+  for (int p = 0; p < Q; p++) {
+#pragma unroll
+    for (int q = 0; q <= p; q++) S[p][q] = lk_sum(V[p] * V[q]);
+    Vg[p] = lk_sum(V[p] * bg);
+    r[p] = (p == 0 ? 1.0 : 0.0) - lk_sum(V[p] * bu);
+  }
+  const double uu = lk_sum(bu * bu);
+  /* S = Ls Ls^T in place (lower triangle) */
+#pragma unroll
+  for (int j = 0; j < Q; j++) {
+    const double s0 = S[j][j];
+    double d = s0;
+#pragma unroll
+    for (int q = 0; q < j; q++) d = fma(-S[j][q], S[j][q], d);
+    bad |= !(d > 64.0 * DBL_EPSILON * s0) || !(d < INFINITY);
+    const double lj = sqrt(d);
+    S[j][j] = lj;
+#pragma unroll
+    for (int p = j + 1; p < Q; p++) {
+      double v = S[p][j];
+#pragma unroll
+      for (int q = 0; q < j; q++) v = fma(-S[p][q], S[j][q], v);
+      S[p][j] = v / lj;
+    }
+  }
+  /* c = S^-1 V^T g (two triangular solves); |Ls^-1 r|^2 */
+  double c[Q], rr = 0.0;
+#pragma unroll
+  for (int p = 0; p < Q; p++) {
+    double v = Vg[p], w = r[p];
+#pragma unroll
+    for (int q = 0; q < p; q++) { v = fma(-S[p][q], c[q], v); w = fma(-S[p][q], r[q], w); }
+    c[p] = v / S[p][p];
+    r[p] = w / S[p][p];
+    rr = fma(r[p], r[p], rr);
+  }
+#pragma unroll
+  for (int p = Q - 1; p >= 0; p--) {
+    double v = c[p];
+#pragma unroll
+    for (int q = p + 1; q < Q; q++) v = fma(-S[q][p], c[q], v);
+    c[p] = v / S[p][p];
+  }
+  double res = bg;                                  /* this lane's entry of g - V c */
+#pragma unroll
+  for (int p = 0; p < Q; p++) res = fma(-c[p], V[p], res);
+  double s = c[0] + lk_sum(bu * res), var = (phi0 - uu) + rr;
+  if (bad) { s = NAN; var = NAN; }
+  if (lane == 0) {
+    if (sout) sout[t] = s;
+    if (vout) vout[t] = var;
+    if (bad) atomicAdd(n_failed, 1u);
+  }
+}
+
 /* ------------------------------------------------------------------------ */
 struct lk_model {
   const LkGrid *grid;
@@ -428,6 +594,22 @@ static void launch_local_krige(gsl_sinterp_hip_ctx *ctx, double coef, double nug
                        ytda, perm, k, d_s, d_var, d_idx, lm.n_failed);
 }
 
+template <int KIND, int DIM>
+static void launch_local_ukrige(gsl_sinterp_hip_ctx *ctx, double coef, double nugget, const double *tbl, const lk_model &lm, const double *d_y,
+                                size_t m, size_t ytda, const int *perm, int k, double *d_s, double *d_var, int *d_idx)
+{
+  const dim3 grid((unsigned)m), block(64);
+  if (k <= 16)
+    hipLaunchKernelGGL((local_ukrige_kernel<KIND, DIM, 16>), grid, block, 0, ctx->stream, coef, nugget, tbl, lm.grid, lm.g, lm.off, lm.rec, d_y,
+                       ytda, perm, k, d_s, d_var, d_idx, lm.n_failed);
+  else if (k <= 32)
+    hipLaunchKernelGGL((local_ukrige_kernel<KIND, DIM, 32>), grid, block, 0, ctx->stream, coef, nugget, tbl, lm.grid, lm.g, lm.off, lm.rec, d_y,
+                       ytda, perm, k, d_s, d_var, d_idx, lm.n_failed);
+  else
+    hipLaunchKernelGGL((local_ukrige_kernel<KIND, DIM, 64>), grid, block, 0, ctx->stream, coef, nugget, tbl, lm.grid, lm.g, lm.off, lm.rec, d_y,
+                       ytda, perm, k, d_s, d_var, d_idx, lm.n_failed);
+}
+
 extern "C" int gsl_sinterp_hip_local_pack(gsl_sinterp_hip_ctx *ctx, const double *d_x, size_t n, int dim, size_t xtda, const double *d_f,
                                           unsigned long long model_id)
 {
@@ -497,6 +679,46 @@ extern "C" int gsl_sinterp_hip_local_krige(gsl_sinterp_hip_ctx *ctx, int kind, d
   if (h_n_failed) *h_n_failed = failed;
   if (failed)
     return sinterp_fail(ctx, ST_EDOM, "local_krige: a neighbourhood's covariance matrix is not positive definite (value and variance NaN there)",
+                        hipSuccess, __FILE__, __LINE__);
+  return ST_SUCCESS;
+}
+
+/* the same entry with a linear drift (local_ukrige_kernel): k >= dim + 2 neighbours */
+extern "C" int gsl_sinterp_hip_local_ukrige(gsl_sinterp_hip_ctx *ctx, int kind, double eps, double nugget, const double *d_x, size_t n, int dim,
+                                            size_t xtda, const double *d_f, const double *d_y, size_t m, size_t ytda, size_t k, double *d_s,
+                                            double *d_var, int *d_idx, size_t *h_n_failed, unsigned long long model_id)
+{
+  if (h_n_failed) *h_n_failed = 0;
+  REQUIRE(ctx, dim >= 1 && dim <= 3 && k >= (size_t)dim + 2 && k <= 64 && k <= n, ST_EINVAL);
+  REQUIRE(ctx, kind_is_pd(kind) && nugget >= 0.0 && nugget < INFINITY && eps > 0.0 && eps < INFINITY, ST_EINVAL);
+  REQUIRE(ctx, xtda >= (size_t)dim && ytda >= (size_t)dim && n <= 0x7fffffffULL && m <= 0x7fffffffULL, ST_EINVAL);
+  REQUIRE(ctx, ctx != NULL && d_x != NULL && d_f != NULL && (m == 0 || d_y != NULL), ST_EFAULT);
+  if (m == 0 || (!d_s && !d_var && !d_idx)) return ST_SUCCESS;
+  HIP_OK(ctx, hipSetDevice(ctx->device));
+  lk_model lm;
+  int st = local_pack(ctx, d_x, n, dim, xtda, d_f, model_id, &lm);
+  if (st) return st;
+  const double *tbl = NULL;
+  st = sinterp_rbf_exp2_table(ctx, &tbl);
+  if (st) return st;
+  int *perm = NULL;
+  st = local_target_order(ctx, d_y, m, ytda, dim, &perm);
+  if (st) return st;
+  HIP_OK(ctx, hipMemsetAsync(lm.n_failed, 0, sizeof(unsigned), ctx->stream));
+  const double coef = kernel_coef(kind, eps);
+  with_kind(kind, [&](auto K) {
+    if constexpr (kind_is_pd(decltype(K)::value))            /* kind_is_pd(kind) was required above */
+      with_dim(dim, [&](auto D) {
+        launch_local_ukrige<decltype(K)::value, decltype(D)::value>(ctx, coef, nugget, tbl, lm, d_y, m, ytda, perm, (int)k, d_s, d_var, d_idx);
+      });
+  });
+  LAUNCH_CHECK(ctx);
+  unsigned failed = 0;
+  HIP_OK(ctx, hipMemcpyAsync(&failed, lm.n_failed, sizeof failed, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_OK(ctx, hipStreamSynchronize(ctx->stream));
+  if (h_n_failed) *h_n_failed = failed;
+  if (failed)
+    return sinterp_fail(ctx, ST_EDOM, "local_ukrige: a neighbourhood's covariance matrix is not positive definite, or its sites do not determine a linear drift (value and variance NaN there)",
                         hipSuccess, __FILE__, __LINE__);
   return ST_SUCCESS;
 }

@@ -657,3 +657,109 @@ extern "C" int gsl_sinterp_hip_krige_solve_fields(gsl_sinterp_hip_ctx *ctx, int 
   if (h_route) *h_route = 7;
   return ST_SUCCESS;
 }
+
+
+/* ------------------------------------------------------------------------ */
+/* Universal kriging (route 12): a polynomial drift of order 1 or 2 in standardised coordinates (drift.hip),
+       [K P; P^T 0] [w; c] = [f; 0],  K = Phi + nugget I,      s(y) = p(u(y))^T c + sum_j w_j phi(|y - x_j|).
+   ONE fill and ONE factorisation carry the nf + q right-hand sides [F | P]: A = K^-1 F, B = K^-1 P; S = P^T B and T = P^T A
+   come from fixed-order reductions, the q x q system S c = T is solved on the host by Cholesky, w = A - B c.  There is no
+   pivoted fall-back: a K that is not positive definite is GSL_EDOM, and so is an S that is not (the drift functions are
+   linearly dependent on the sites). */
+__global__ void __launch_bounds__(256)
+ukrige_rhs_kernel(const double *__restrict__ f, size_t ldw, int nf, size_t n, double *__restrict__ Y)
+{
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  for (int q = 0; q < nf; q++) Y[(size_t)q * n + i] = f[(size_t)q * ldw + i];
+}
+
+/* w_f = A_f - sum_t c[f][t] B_t with A_f = Y column f, B_t = Y column nf + t, the terms in order */
+__global__ void __launch_bounds__(256)
+ukrige_combine_kernel(const double *__restrict__ Y, size_t n, int nf, int q, const double *__restrict__ coef, double *__restrict__ w,
+                      size_t ldw)
+{
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  for (int f = 0; f < nf; f++) {
+    double v = Y[(size_t)f * n + i];
+    for (int t = 0; t < q; t++) v = fma(-coef[f * q + t], Y[(size_t)(nf + t) * n + i], v);
+    w[(size_t)f * ldw + i] = v;
+  }
+}
+
+extern "C" int gsl_sinterp_hip_ukrige_solve(gsl_sinterp_hip_ctx *ctx, int kind, double eps, double nugget, int order,
+                                            const double *h_shift, const double *h_scale, const double *d_x, size_t n, int dim,
+                                            size_t xtda, double *d_phi, size_t lda, double *d_w, size_t ldw, size_t nf,
+                                            double *h_coef, double *d_B, size_t ldb, double *h_S, double *h_L, double *d_dinv,
+                                            int *h_route)
+{
+  REQUIRE(ctx, ctx != NULL, ST_EFAULT);
+  HIP_OK(ctx, hipSetDevice(ctx->device));
+  EXCLUSIVE_SECTION(ctx);
+  int st = fields_solve_args(ctx, kind, d_x, n, dim, xtda, d_phi, lda, d_w, ldw, nf);
+  if (st) return st;
+  REQUIRE(ctx, nugget >= 0.0 && (order == 1 || order == 2) && (!d_B || ldb >= n), ST_EINVAL);
+  REQUIRE(ctx, h_coef != NULL && h_shift != NULL && h_scale != NULL, ST_EFAULT);
+  const int q = (int)gsl_sinterp_hip_drift_terms(dim, order), nr = (int)nf + q;
+  if (h_route) *h_route = 0;
+  for (size_t e = 0; e < nf * (size_t)q; e++) h_coef[e] = 0.0;
+  if (n == 0) return ST_SUCCESS;
+  REQUIRE(ctx, n >= (size_t)q, ST_EINVAL);                /* fewer sites than drift functions: S cannot have full rank */
+  void *aux = NULL;
+  const size_t small = (size_t)q * nr + nf * (size_t)q + 16;
+  st = sinterp_aux(ctx, ((size_t)(nr + q) * n + small) * sizeof(double), &aux);
+  if (st) return st;
+  double *Y = (double *)aux, *Pk = Y + (size_t)nr * n, *G = Pk + (size_t)q * n, *d_coef = G + (size_t)q * nr;
+  const unsigned nb = (unsigned)((n + 255) / 256);
+  st = gsl_sinterp_hip_rbf_fill(ctx, kind, eps, d_x, n, dim, xtda, d_phi, lda);          /* both triangles, as krige_solve_fields */
+  if (st) return st;
+  if (nugget != 0.0) hipLaunchKernelGGL(diag_add_kernel, dim3(nb), dim3(256), 0, ctx->stream, d_phi, lda, n, nugget);
+  hipLaunchKernelGGL(ukrige_rhs_kernel, dim3(nb), dim3(256), 0, ctx->stream, (const double *)d_w, ldw, (int)nf, n, Y);
+  LAUNCH_CHECK(ctx);
+  st = sinterp_drift_basis(ctx, order, h_shift, h_scale, d_x, n, dim, xtda, Y + nf * n, n);
+  if (!st) st = sinterp_drift_basis(ctx, order, h_shift, h_scale, d_x, n, dim, xtda, Pk, n);
+  if (st) return st;
+  int info = 0;
+  st = sinterp_cholesky_factor_solve_many_sym(ctx, n, d_phi, lda, &info, Y, n, nr);
+  if (st) return st;                              /* GSL_EDOM: K is not positive definite */
+  st = sinterp_drift_gram(ctx, Pk, n, Y, n, n, q, nr, G);                                /* G = P^T [A | B] = [T | S] */
+  if (st) return st;
+  double hG[GSL_SINTERP_DRIFT_MAX_TERMS * (GSL_SINTERP_MAX_FIELDS + GSL_SINTERP_DRIFT_MAX_TERMS)];
+  double S[GSL_SINTERP_DRIFT_MAX_TERMS * GSL_SINTERP_DRIFT_MAX_TERMS], L[GSL_SINTERP_DRIFT_MAX_TERMS * GSL_SINTERP_DRIFT_MAX_TERMS];
+  HIP_OK(ctx, hipStreamSynchronize(ctx->stream));
+  HIP_OK(ctx, hipMemcpy(hG, G, sizeof(double) * (size_t)q * nr, hipMemcpyDeviceToHost));
+  for (int a = 0; a < q; a++)
+    for (int b = 0; b < q; b++) S[a * q + b] = hG[a * nr + (int)nf + b];
+  if (h_S) memcpy(h_S, S, sizeof(double) * (size_t)q * q);
+  if (gsl_sinterp_hip_drift_factor((size_t)q, S, L) != ST_SUCCESS)
+    return sinterp_fail(ctx, ST_EDOM, "ukrige_solve: P^T K^-1 P is not positive definite (the drift functions are linearly dependent on the sites)",
+                        hipSuccess, __FILE__, __LINE__);
+  if (h_L) memcpy(h_L, L, sizeof(double) * (size_t)q * q);
+  if (d_dinv) {                                   /* what ukrige_variance needs of the factor besides B and Ls */
+    st = sinterp_krige_inv32(ctx, n, d_phi, lda, d_dinv);
+    if (st) return st;
+  }
+  for (size_t f = 0; f < nf; f++) {               /* c_f = S^-1 T_f through the factor: two triangular solves */
+    double *c = h_coef + f * q;
+    for (int i = 0; i < q; i++) {
+      double v = hG[i * nr + (int)f];
+      for (int j = 0; j < i; j++) v -= L[i * q + j] * c[j];
+      c[i] = v / L[i * q + i];
+    }
+    for (int i = q - 1; i >= 0; i--) {
+      double v = c[i];
+      for (int j = i + 1; j < q; j++) v -= L[j * q + i] * c[j];
+      c[i] = v / L[i * q + i];
+    }
+  }
+  HIP_OK(ctx, hipMemcpyAsync(d_coef, h_coef, sizeof(double) * nf * q, hipMemcpyHostToDevice, ctx->stream));
+  hipLaunchKernelGGL(ukrige_combine_kernel, dim3(nb), dim3(256), 0, ctx->stream, (const double *)Y, n, (int)nf, q, (const double *)d_coef, d_w,
+                     ldw);
+  LAUNCH_CHECK(ctx);
+  if (d_B) HIP_OK(ctx, hipMemcpy2DAsync(d_B, ldb * sizeof(double), Y + nf * n, n * sizeof(double), n * sizeof(double), (size_t)q,
+                                        hipMemcpyDeviceToDevice, ctx->stream));
+  HIP_OK(ctx, hipStreamSynchronize(ctx->stream));                                        /* h_coef is the caller's buffer */
+  if (h_route) *h_route = 12;
+  return ST_SUCCESS;
+}

@@ -1449,6 +1449,15 @@ typedef struct {
      model.  d_w then holds the RESPONSES: nothing is solved at init, every target solves its own small system */
   size_t local_k;
   double local_nugget;
+  /* universal kriging (gsl_sinterp_set_drift, route 12): the order of the last init / fread (0 = ordinary kriging), the
+     number of drift functions, the standardisation of their coordinates, the coefficients of every field, and -- kept with
+     the factor for the variance -- B = K^-1 P on member 0 and the host Cholesky factor of S = P^T B */
+  int drift, local_drift;     /* local_drift: the local route (local_k > 0) runs with a linear drift */
+  size_t drift_q;
+  double drift_shift[3], drift_scale[3];
+  double f_coef[GSL_SINTERP_MAX_FIELDS][GSL_SINTERP_DRIFT_MAX_TERMS];
+  double *d_B;
+  double drift_L[GSL_SINTERP_DRIFT_MAX_TERMS * GSL_SINTERP_DRIFT_MAX_TERMS];
 } rbf_state;
 
 /* rows of the work matrix per pass of gsl_sinterp_hip_chol_inv_diag ("Leave-one-out") */
@@ -1485,8 +1494,9 @@ static void rbf_release_variance(rbf_state *st)
   if (st->ctx) {
     gsl_sinterp_hip_free(st->ctx, st->d_llt); gsl_sinterp_hip_free(st->ctx, st->d_b);
     gsl_sinterp_hip_free(st->ctx, st->d_dinv); gsl_sinterp_hip_free(st->ctx, st->d_vwork);
+    gsl_sinterp_hip_free(st->ctx, st->d_B);
   }
-  st->d_llt = st->d_b = st->d_dinv = st->d_vwork = NULL;
+  st->d_llt = st->d_b = st->d_dinv = st->d_vwork = st->d_B = NULL;
   st->llt_lda = st->vwork_doubles = 0; st->denom = 0.0; st->var_state = 0;
 }
 
@@ -1500,7 +1510,7 @@ static void rbf_release_loo(rbf_state *st)
    diagonal of the inverse, the combine, and the copy to the host arrays of the state.  Kriging takes b = K^-1 1 and
    1^T b from the kept variance data when there is one, from temporaries otherwise.  Everything allocated here is freed
    again: the factor is not kept for this. */
-static int rbf_compute_loo(rbf_state *st, const double *d_llt, size_t lda, size_t nf)
+static int rbf_compute_loo(rbf_state *st, const double *d_llt, size_t lda, size_t nf, const double *d_B)
 {
   gsl_sinterp_hip_ctx *c = st->ctx;
   const size_t n = st->n;
@@ -1512,7 +1522,7 @@ static int rbf_compute_loo(rbf_state *st, const double *d_llt, size_t lda, size_
   st->loo_e = (double *)malloc(n * nf * sizeof(double));
   st->loo_v = (double *)malloc(n * sizeof(double));
   int s = st->loo_e && st->loo_v ? GSL_SUCCESS : GSL_ENOMEM;
-  if (!s && st->krige) {
+  if (!s && st->krige && !st->drift) {
     if (st->var_state == 1) {
       d_b = st->d_b; denom = st->denom;
     } else {
@@ -1525,7 +1535,9 @@ static int rbf_compute_loo(rbf_state *st, const double *d_llt, size_t lda, size_
   if (!s) s = gsl_sinterp_hip_malloc(c, (void **)&d_out, n * (nf + 2) * sizeof(double));
   if (!s) s = gsl_sinterp_hip_malloc(c, (void **)&d_work, gsl_sinterp_hip_chol_inv_diag_work(n, chunk) * sizeof(double));
   if (!s) s = gsl_sinterp_hip_chol_inv_diag(c, n, d_llt, lda, d_out, d_work, chunk);
-  if (!s) s = gsl_sinterp_hip_loo_combine(c, n, nf, d_out, d_b, denom, st->d_w, n, d_out + 2 * n, n, d_out + n);
+  /* with a drift: Dubrule's rule takes B = K^-1 P and the factor of S = P^T B in place of b and 1^T b */
+  if (!s) s = st->drift ? gsl_sinterp_hip_loo_combine_drift(c, n, nf, d_out, d_B, n, st->drift_q, st->drift_L, st->d_w, n, d_out + 2 * n, n, d_out + n)
+                        : gsl_sinterp_hip_loo_combine(c, n, nf, d_out, d_b, denom, st->d_w, n, d_out + 2 * n, n, d_out + n);
   if (!s) s = gsl_sinterp_hip_d2h(c, st->loo_v, d_out + n, n * sizeof(double));
   if (!s) s = gsl_sinterp_hip_d2h(c, st->loo_e, d_out + 2 * n, n * nf * sizeof(double));
   if (s) (void)gsl_sinterp_hip_sync(c);                  /* nothing queued may still use the buffers freed below */
@@ -1577,12 +1589,28 @@ static int rbf_solve_column(gsl_sinterp *interp, rbf_state *st, double *d_phi, s
   return gsl_sinterp_hip_rbf_solve_ex(c, st->kind, st->eps, st->d_x, n, (int)dim, dim, d_phi, lda, d_w, interp->solver, rcond, route);
 }
 
+/* the standardisation of the drift's coordinates: shift = the centre of the sites' bounding box, scale = 1 / half-extent
+   per axis (1 for a zero extent); x packed n x dim */
+static void rbf_drift_geometry(const double *x, size_t n, size_t dim, double *shift, double *scale)
+{
+  for (size_t a = 0; a < dim; a++) {
+    double lo = x[a], hi = x[a];
+    for (size_t i = 1; i < n; i++) { const double v = x[i * dim + a]; if (v < lo) lo = v; if (v > hi) hi = v; }
+    const double half = 0.5 * (hi - lo);
+    shift[a] = lo + half;
+    scale[a] = half > 0.0 ? 1.0 / half : 1.0;
+  }
+  for (size_t a = dim; a < 3; a++) { shift[a] = 0.0; scale[a] = 1.0; }
+}
+
 /* f(i, q) = fdata[i * frow + q * fcol], nf fields: gsl_sinterp_init (nf = 1) and gsl_sinterp_init_fields */
 static int rbf_init_fields(gsl_sinterp *interp, const gsl_matrix *x, const double *fdata, size_t frow, size_t fcol, size_t nf)
 {
   rbf_state *st = rbf_of(interp);
   const size_t n = st->n, dim = st->dim;
   const int nd = interp->n_devices > 1 ? interp->n_devices : 1;
+  if (st->krige && interp->drift > 0 && n < gsl_sinterp_drift_terms(dim, interp->drift))
+    GSL_ERROR("gsl_sinterp_init: universal kriging needs at least as many sites as drift functions", GSL_EINVAL);
   rbf_release_variance(st);                             /* the factor of the previous model, if one was kept */
   rbf_release_loo(st);                                  /* ... and its leave-one-out data */
   int s = rbf_prepare_devices(interp, st, nf);
@@ -1592,6 +1620,7 @@ static int rbf_init_fields(gsl_sinterp *interp, const gsl_matrix *x, const doubl
   st->model_id = next_model_id();                       /* the buffers are about to change */
   st->eps = interp->shape > 0 ? interp->shape : rbf_default_eps(st->kind, n, dim);
   st->local_k = 0;
+  st->drift = 0; st->drift_q = 0;
 
   double *h_x = (double *)malloc(n * dim * sizeof(double));
   double *h_f = (double *)malloc(n * nf * sizeof(double));
@@ -1617,7 +1646,28 @@ static int rbf_init_fields(gsl_sinterp *interp, const gsl_matrix *x, const doubl
      types (their shifted-SPD / Woodbury solve is per field), an explicit solver, set_rcond, kriging on a semi-definite
      matrix (GSL_EDOM from the shared route) -- solves field by field, refilling d_phi each time: nf factorisations. */
   int shared = nf > 1 && st->kind != GSL_SINTERP_RBF_TPS && interp->solver == GSL_SINTERP_SOLVER_DEFAULT && !interp->want_rcond;
-  if (!s && shared) {
+  /* universal kriging (route 12): the drift functions ride the one factorisation with the fields; no per-field route and
+     no pivoted fall-back.  B is wanted by the variance (kept) and by leave-one-out (freed with the init) */
+  const int drift = st->krige ? interp->drift : 0;
+  double *d_B = NULL;
+  if (!s && drift) {
+    const size_t q = gsl_sinterp_drift_terms(dim, drift);
+    rbf_drift_geometry(h_x, n, dim, st->drift_shift, st->drift_scale);
+    if (interp->want_variance || interp->want_loo) s = gsl_sinterp_hip_malloc(c, (void **)&d_B, n * q * sizeof(double));
+    if (!s && interp->want_variance) s = gsl_sinterp_hip_malloc(c, (void **)&st->d_dinv, ((n + 31) / 32) * 1024 * sizeof(double));
+    double *coef = (double *)malloc(nf * q * sizeof(double));            /* field k's q coefficients at coef + k * q */
+    if (!s && !coef) s = GSL_ENOMEM;
+    if (!s) s = gsl_sinterp_hip_ukrige_solve(c, st->kind, st->eps, interp->nugget, drift, st->drift_shift, st->drift_scale, st->d_x, n, (int)dim,
+                                             dim, d_phi, lda, st->d_w, n, nf, coef, d_B, n, NULL, st->drift_L, st->d_dinv, &route);
+    if (!s) {
+      memset(st->f_coef, 0, sizeof st->f_coef);
+      for (size_t k = 0; k < nf; k++) memcpy(st->f_coef[k], coef + k * q, q * sizeof(double));
+      st->drift = drift; st->drift_q = q;
+    }
+    free(coef);
+    shared = 1;
+  }
+  if (!s && shared && !drift) {
     if (st->krige) {
       s = gsl_sinterp_hip_krige_solve_fields(c, st->kind, st->eps, interp->nugget, st->d_x, n, (int)dim, dim, d_phi, lda, st->d_w, n, nf,
                                              st->f_mean, &route);
@@ -1638,7 +1688,9 @@ static int rbf_init_fields(gsl_sinterp *interp, const gsl_matrix *x, const doubl
   /* kriging variance asked for: route 7 left L in the lower triangle of d_phi -- keep it (N^2 doubles, member 0 only)
      with b = K^-1 1, the inverted diagonal blocks and 1^T b; route 8 has no Cholesky factor to keep */
   if (!s && st->krige && interp->want_variance) {
-    if (route == 7) {
+    if (route == 12) {                                  /* B, Ls and the inverted diagonal blocks came with the solve */
+      st->d_llt = d_phi; st->llt_lda = lda; st->var_state = 1; d_phi = NULL; st->d_B = d_B;
+    } else if (route == 7) {
       s = gsl_sinterp_hip_malloc(c, (void **)&st->d_b, n * sizeof(double));
       if (!s) s = gsl_sinterp_hip_malloc(c, (void **)&st->d_dinv, ((n + 31) / 32) * 1024 * sizeof(double));
       if (!s) s = gsl_sinterp_hip_krige_variance_prepare(c, n, d_phi, lda, st->d_b, st->d_dinv, &st->denom);
@@ -1650,7 +1702,7 @@ static int rbf_init_fields(gsl_sinterp *interp, const gsl_matrix *x, const doubl
   /* leave-one-out asked for: routes 1 and 7 left L in the lower triangle of d_phi (with set_rcond too: the original
      stays ABOVE the diagonal), still alive here or just handed to the variance; every other route has no factor */
   if (!s && interp->want_loo) {
-    if (route == 1 || route == 7) s = rbf_compute_loo(st, st->d_llt ? st->d_llt : d_phi, lda, nf);
+    if (route == 1 || route == 7 || route == 12) s = rbf_compute_loo(st, st->d_llt ? st->d_llt : d_phi, lda, nf, d_B);
     else st->loo_state = 2;
   }
   /* replicate the solved model: ONE broadcast of the weight vector (+ centres) */
@@ -1659,8 +1711,15 @@ static int rbf_init_fields(gsl_sinterp *interp, const gsl_matrix *x, const doubl
   if (st->ss.grp)
     for (int r = 1; r < nd; r++) { int s2 = gsl_sinterp_hip_sync(gsl_sinterp_hip_group_ctx(st->ss.grp, r)); if (!s) s = s2; }
   gsl_sinterp_hip_free(c, d_phi);
+  if (d_B != st->d_B) gsl_sinterp_hip_free(c, d_B);     /* not handed to the variance */
   free(h_x); free(h_f);
   if (s) { rbf_release_variance(st); rbf_release_loo(st); }
+  if (s == GSL_EDOM && drift) {
+    /* d_w holds neither the responses nor weights now: nothing may evaluate it */
+    rbf_release_devices(st);
+    GSL_ERROR("gsl_sinterp_init: universal kriging: the covariance matrix is not positive definite, or the drift functions are linearly dependent on the sites",
+              GSL_EDOM);
+  }
   if (s == GSL_EDOM) GSL_ERROR("gsl_sinterp_init: kernel matrix is not positive definite", GSL_EDOM);
   HIP_TRY(s, c);
   st->nf = nf;
@@ -1729,6 +1788,11 @@ static int local_eval_many(const gsl_sinterp *interp, const gsl_matrix *y, gsl_v
 static int rbf_sweep(const rbf_state *st, gsl_sinterp_hip_ctx *c, const double *d_x, const double *d_w, const double *d_y, size_t m,
                      size_t ytda, double *d_s)
 {
+  if (st->drift) {                                      /* the unchanged plain sweep, then p(u)^T c; the coefficients go by value */
+    int s = gsl_sinterp_hip_rbf_eval_model(c, st->kind, st->eps, d_x, st->n, (int)st->dim, st->dim, d_w, d_y, m, ytda, d_s, st->model_id);
+    if (!s) s = gsl_sinterp_hip_drift_add(c, st->drift, st->drift_shift, st->drift_scale, st->f_coef[0], 1, d_y, m, (int)st->dim, ytda, d_s, 1, NULL, 0);
+    return s;
+  }
   if (st->krige)
     return gsl_sinterp_hip_krige_eval(c, st->kind, st->eps, st->mean, d_x, st->n, (int)st->dim, st->dim, d_w, d_y, m, ytda, d_s, st->model_id);
   if (st->affine)
@@ -1792,11 +1856,15 @@ static int local_init(gsl_sinterp *interp, const gsl_matrix *x, const gsl_vector
 {
   rbf_state *st = rbf_of(interp);
   const size_t n = st->n, dim = st->dim;
+  if (interp->drift > 1)
+    GSL_ERROR("gsl_sinterp_init: the local route (gsl_sinterp_set_neighbours) takes a linear drift only", GSL_EUNSUP);
+  if (interp->drift == 1 && interp->neighbours < dim + 2)
+    GSL_ERROR("gsl_sinterp_init: local kriging with a linear drift needs at least dim + 2 neighbours", GSL_EINVAL);
   rbf_release_variance(st);
   rbf_release_loo(st);
   int s = rbf_prepare_devices(interp, st, 1);
   if (s) return s;
-  st->nf = 0; st->local_k = 0;
+  st->nf = 0; st->local_k = 0; st->drift = 0; st->drift_q = 0; st->local_drift = 0;
   gsl_sinterp_hip_ctx *c = st->ctx;
   st->model_id = next_model_id();
   st->eps = interp->shape > 0 ? interp->shape : rbf_default_eps(st->kind, n, dim);
@@ -1814,7 +1882,7 @@ static int local_init(gsl_sinterp *interp, const gsl_matrix *x, const gsl_vector
   memset(st->f_mean, 0, sizeof st->f_mean); memset(st->f_poly, 0, sizeof st->f_poly);
   st->mean = GSL_NAN;                                   /* every neighbourhood estimates its own */
   interp->rcond = GSL_NAN; interp->route = 11;
-  st->local_k = interp->neighbours; st->local_nugget = interp->nugget;
+  st->local_k = interp->neighbours; st->local_nugget = interp->nugget; st->local_drift = interp->drift;
   st->nf = 1;
   return GSL_SUCCESS;
 }
@@ -1825,12 +1893,15 @@ static int local_eval_resident(const gsl_sinterp *interp, const double *d_y, siz
   const rbf_state *st = rbf_of(interp);
   if (m == 0) return GSL_SUCCESS;
   if (!d_y) GSL_ERROR("gsl_sinterp_eval: null argument", GSL_EFAULT);
-  int s = gsl_sinterp_hip_local_krige(st->ctx, st->kind, st->eps, st->local_nugget, st->d_x, st->n, (int)st->dim, st->dim, st->d_w, d_y, m, ytda,
-                                      st->local_k, d_s, d_var, d_idx, NULL, st->model_id);
+  int s = (st->local_drift ? gsl_sinterp_hip_local_ukrige : gsl_sinterp_hip_local_krige)(st->ctx, st->kind, st->eps, st->local_nugget, st->d_x, st->n,
+                                                                                          (int)st->dim, st->dim, st->d_w, d_y, m, ytda, st->local_k,
+                                                                                          d_s, d_var, d_idx, NULL, st->model_id);
   if ((s == GSL_SUCCESS || s == GSL_EDOM) && d_var)     /* rounding residue where sigma^2 = 0; NaN stays NaN */
     HIP_TRY(gsl_sinterp_hip_krige_variance_clamp(st->ctx, d_var, m), st->ctx);
   if (s == GSL_EDOM)
-    GSL_ERROR("gsl_sinterp_eval: local kriging: the covariance matrix of a neighbourhood is not positive definite (NaN at those targets)", GSL_EDOM);
+    GSL_ERROR(st->local_drift ? "gsl_sinterp_eval: local kriging: a neighbourhood's covariance matrix is not positive definite, or its sites do not determine the drift (NaN at those targets)"
+                              : "gsl_sinterp_eval: local kriging: the covariance matrix of a neighbourhood is not positive definite (NaN at those targets)",
+              GSL_EDOM);
   HIP_TRY(s, st->ctx);
   return GSL_SUCCESS;
 }
@@ -2368,6 +2439,41 @@ int gsl_sinterp_set_nugget(gsl_sinterp *interp, double nugget)
   return GSL_SUCCESS;
 }
 
+int gsl_sinterp_set_drift(gsl_sinterp *interp, int order)
+{
+  if (!interp) GSL_ERROR("gsl_sinterp_set_drift: null interpolant", GSL_EFAULT);
+  if (!desc_of(interp->type)->krige) GSL_ERROR("gsl_sinterp_set_drift: kriging interpolants only", GSL_EINVAL);
+  if (order < 0 || order > 2) GSL_ERROR("gsl_sinterp_set_drift: the order must be 0 (ordinary kriging), 1 or 2", GSL_EINVAL);
+  interp->drift = order;
+  return GSL_SUCCESS;
+}
+
+int gsl_sinterp_drift(const gsl_sinterp *interp) { return interp ? interp->drift : 0; }
+
+size_t gsl_sinterp_drift_terms(size_t dim, int order)
+{
+  return dim > 3 ? 0 : gsl_sinterp_hip_drift_terms((int)dim, order);     /* the one definition, next to the term order (drift.hip) */
+}
+
+int gsl_sinterp_drift_coefficients(const gsl_sinterp *interp, size_t field, gsl_vector *c, gsl_vector *shift, gsl_vector *scale)
+{
+  if (!interp || !c) GSL_ERROR("gsl_sinterp_drift_coefficients: null argument", GSL_EFAULT);
+  if (!desc_of(interp->type)->krige) GSL_ERROR("gsl_sinterp_drift_coefficients: kriging interpolants only", GSL_EINVAL);
+  if (is_local(interp)) GSL_ERROR("gsl_sinterp_drift_coefficients: not with gsl_sinterp_set_neighbours", GSL_EUNSUP);
+  const rbf_state *st = rbf_of(interp);
+  if (!st->d_w || st->nf == 0) GSL_ERROR("gsl_sinterp_drift_coefficients: interpolant not initialised", GSL_EINVAL);
+  if (!st->drift) GSL_ERROR("gsl_sinterp_drift_coefficients: initialised without a drift (gsl_sinterp_mean answers)", GSL_EINVAL);
+  if (field >= st->nf) GSL_ERROR("gsl_sinterp_drift_coefficients: no such field", GSL_EINVAL);
+  if (c->size != st->drift_q || (shift && shift->size != st->dim) || (scale && scale->size != st->dim))
+    GSL_ERROR("gsl_sinterp_drift_coefficients: c needs gsl_sinterp_drift_terms entries, shift and scale dim", GSL_EBADLEN);
+  for (size_t t = 0; t < st->drift_q; t++) gsl_vector_set(c, t, st->f_coef[field][t]);
+  for (size_t a = 0; a < st->dim; a++) {
+    if (shift) gsl_vector_set(shift, a, st->drift_shift[a]);
+    if (scale) gsl_vector_set(scale, a, st->drift_scale[a]);
+  }
+  return GSL_SUCCESS;
+}
+
 int gsl_sinterp_set_variance(gsl_sinterp *interp, int want)
 {
   if (!interp) GSL_ERROR("gsl_sinterp_set_variance: null interpolant", GSL_EFAULT);
@@ -2707,7 +2813,7 @@ int gsl_sinterp_eval_variance_resident(const gsl_sinterp *interp, const double *
   if (st->local_k) return local_eval_resident(interp, d_y, m, ytda, NULL, d_var, NULL);
   size_t chunk = (m + 63) / 64 * 64;
   if (chunk > 8192) chunk = 8192;
-  const size_t need = gsl_sinterp_hip_krige_variance_work(st->n, chunk);
+  const size_t need = st->drift ? gsl_sinterp_hip_ukrige_variance_work(st->n, chunk, st->drift_q) : gsl_sinterp_hip_krige_variance_work(st->n, chunk);
   if (need > st->vwork_doubles) {
     gsl_sinterp_hip_free(st->ctx, st->d_vwork);
     st->d_vwork = NULL; st->vwork_doubles = 0;
@@ -2715,8 +2821,14 @@ int gsl_sinterp_eval_variance_resident(const gsl_sinterp *interp, const double *
     st->vwork_doubles = need;
   }
   /* the factor lives on member 0, which evaluates every target (as gsl_sinterp_eval_resident does) */
-  HIP_TRY(gsl_sinterp_hip_krige_variance(st->ctx, st->kind, st->eps, st->d_x, st->n, (int)st->dim, st->dim, st->d_llt, st->llt_lda,
-                                         st->d_b, st->d_dinv, st->denom, d_y, m, ytda, d_var, st->d_vwork, chunk), st->ctx);
+  if (st->drift) {
+    HIP_TRY(gsl_sinterp_hip_ukrige_variance(st->ctx, st->kind, st->eps, st->drift, st->drift_shift, st->drift_scale, st->d_x, st->n, (int)st->dim,
+                                            st->dim, st->d_llt, st->llt_lda, st->d_B, st->n, st->d_dinv, st->drift_L, d_y, m, ytda, d_var,
+                                            st->d_vwork, chunk), st->ctx);
+  } else {
+    HIP_TRY(gsl_sinterp_hip_krige_variance(st->ctx, st->kind, st->eps, st->d_x, st->n, (int)st->dim, st->dim, st->d_llt, st->llt_lda,
+                                           st->d_b, st->d_dinv, st->denom, d_y, m, ytda, d_var, st->d_vwork, chunk), st->ctx);
+  }
   HIP_TRY(gsl_sinterp_hip_krige_variance_clamp(st->ctx, d_var, m), st->ctx);   /* rounding residue where sigma^2 = 0 */
   return GSL_SUCCESS;
 }
@@ -2808,8 +2920,11 @@ int gsl_sinterp_eval_grad_resident(const gsl_sinterp *interp, const double *d_y,
      gsl_sinterp_eval_resident does) */
   double tail[4] = {st->mean, 0.0, 0.0, 0.0};
   if (st->affine) memcpy(tail, st->poly, sizeof tail);
-  HIP_TRY(gsl_sinterp_hip_rbf_eval_grad(st->ctx, st->kind, st->eps, (st->affine || st->krige) ? tail : NULL, st->d_x, st->n, (int)st->dim,
-                                        st->dim, st->d_w, d_y, m, ytda, d_s, d_g, gtda, st->model_id), st->ctx);
+  HIP_TRY(gsl_sinterp_hip_rbf_eval_grad(st->ctx, st->kind, st->eps, (st->affine || (st->krige && !st->drift)) ? tail : NULL, st->d_x, st->n,
+                                        (int)st->dim, st->dim, st->d_w, d_y, m, ytda, d_s, d_g, gtda, st->model_id), st->ctx);
+  if (st->drift)                                        /* the drift and its gradient behind the plain sweep, as the value entries add it */
+    HIP_TRY(gsl_sinterp_hip_drift_add(st->ctx, st->drift, st->drift_shift, st->drift_scale, st->f_coef[0], 1, d_y, m, (int)st->dim, ytda, d_s, 1,
+                                      d_g, gtda), st->ctx);
   return GSL_SUCCESS;
 }
 
@@ -2920,8 +3035,14 @@ int gsl_sinterp_eval_fields_resident(const gsl_sinterp *interp, const double *d_
   const size_t td = st->dim + 1;
   for (size_t q = 0; q < st->nf; q++)
     for (size_t a = 0; a < td; a++) tail[q * td + a] = st->affine ? st->f_poly[q][a] : (a == 0 ? st->f_mean[q] : 0.0);
-  HIP_TRY(gsl_sinterp_hip_rbf_eval_fields(st->ctx, st->kind, st->eps, (st->affine || st->krige) ? tail : NULL, st->d_x, st->n, (int)st->dim,
-                                          st->dim, st->d_w, st->n, st->nf, d_y, m, ytda, d_s, stda, st->model_id), st->ctx);
+  HIP_TRY(gsl_sinterp_hip_rbf_eval_fields(st->ctx, st->kind, st->eps, (st->affine || (st->krige && !st->drift)) ? tail : NULL, st->d_x, st->n,
+                                          (int)st->dim, st->dim, st->d_w, st->n, st->nf, d_y, m, ytda, d_s, stda, st->model_id), st->ctx);
+  if (st->drift) {                                      /* f_coef rows are GSL_SINTERP_DRIFT_MAX_TERMS apart: pack q per field */
+    double coef[GSL_SINTERP_MAX_FIELDS * GSL_SINTERP_DRIFT_MAX_TERMS];
+    for (size_t q = 0; q < st->nf; q++) memcpy(coef + q * st->drift_q, st->f_coef[q], st->drift_q * sizeof(double));
+    HIP_TRY(gsl_sinterp_hip_drift_add(st->ctx, st->drift, st->drift_shift, st->drift_scale, coef, st->nf, d_y, m, (int)st->dim, ytda, d_s, stda,
+                                      NULL, 0), st->ctx);
+  }
   return GSL_SUCCESS;
 }
 
@@ -3115,6 +3236,7 @@ int gsl_sinterp_field_mean(const gsl_sinterp *interp, size_t q, double *mean)
   const rbf_state *st = field_state(interp, q, &status);
   if (!st) return status;
   if (!st->krige) GSL_ERROR("gsl_sinterp_field_mean: kriging interpolants only", GSL_EINVAL);
+  if (interp->drift > 0 || st->drift) GSL_ERROR("gsl_sinterp_field_mean: with a drift there is no single mean (gsl_sinterp_drift_coefficients)", GSL_EUNSUP);
   *mean = st->f_mean[q];
   return GSL_SUCCESS;
 }
@@ -3147,6 +3269,7 @@ int gsl_sinterp_mean(const gsl_sinterp *interp, double *mean)
   if (!interp || !mean) GSL_ERROR("gsl_sinterp_mean: null argument", GSL_EFAULT);
   if (!desc_of(interp->type)->krige) GSL_ERROR("gsl_sinterp_mean: kriging interpolants only", GSL_EINVAL);
   if (is_local(interp)) GSL_ERROR("gsl_sinterp_mean: not with gsl_sinterp_set_neighbours (every neighbourhood estimates its own mean)", GSL_EUNSUP);
+  if (interp->drift > 0 || rbf_of(interp)->drift) GSL_ERROR("gsl_sinterp_mean: with a drift there is no single mean (gsl_sinterp_drift_coefficients)", GSL_EUNSUP);
   const rbf_state *st = rbf_of(interp);
   if (!st->d_w) GSL_ERROR("gsl_sinterp_mean: interpolant not initialised", GSL_EINVAL);
   *mean = st->mean;
@@ -3467,9 +3590,14 @@ int gsl_sinterp_fprintf_grid(FILE *stream, const gsl_vector *min, const gsl_vect
 static const char INTERP_MAGIC[8] = {'G', 'S', 'L', 'S', 'I', 'N', 'T', '1'};
 
 /* 1 when the whole header went out */
+/* the header id under which a kriging interpolant WITH a drift is written: 17 / 18 / 19 for the types 4 / 10 / 11 */
+static uint64_t drift_type_id(const type_desc *d) { return d->id == 4 ? 17 : d->id == 10 ? 18 : 19; }
+
 static int header_fwrite(FILE *stream, const gsl_sinterp *interp, double eps, int64_t flags)
 {
-  const uint64_t head[3] = {(uint64_t)desc_of(interp->type)->id, (uint64_t)interp->dim, (uint64_t)interp->size};
+  const rbf_state *rst = rbf_of(interp);
+  const uint64_t id = rst && rst->drift ? drift_type_id(desc_of(interp->type)) : (uint64_t)desc_of(interp->type)->id;
+  const uint64_t head[3] = {id, (uint64_t)interp->dim, (uint64_t)interp->size};
   return fwrite(INTERP_MAGIC, 1, 8, stream) == 8 && fwrite(head, sizeof head[0], 3, stream) == 3 &&
          fwrite(&eps, sizeof eps, 1, stream) == 1 && fwrite(&flags, sizeof flags, 1, stream) == 1;
 }
@@ -3536,11 +3664,20 @@ int gsl_sinterp_fwrite(FILE *stream, const gsl_sinterp *interp)
   if (!h) GSL_ERROR("gsl_sinterp_fwrite: out of memory", GSL_ENOMEM);
   int s = gsl_sinterp_hip_d2h(st->ctx, h, st->d_x, cnt * sizeof(double));      /* the model buffer: [centres | weights] */
   int64_t flags = 0;
-  if (st->krige) memcpy(&flags, &st->mean, sizeof flags);                       /* kriging: the word carries the mean's bits */
+  if (st->krige && !st->drift) memcpy(&flags, &st->mean, sizeof flags);         /* ordinary kriging: the word carries the mean's bits */
   if (!s && (!header_fwrite(stream, interp, st->eps, flags) || fwrite(h, sizeof(double), cnt, stream) != cnt ||
              (st->affine && fwrite(st->poly, sizeof(double), 4, stream) != 4))) {      /* affine tail: c_0 .. c_3 behind the weights */
     free(h);
     GSL_ERROR("fwrite failed", GSL_EFAILED);
+  }
+  if (!s && st->drift) {                                /* drift: order | shift | scale | the q coefficients behind the weights */
+    const uint64_t order = (uint64_t)st->drift;
+    if (fwrite(&order, sizeof order, 1, stream) != 1 || fwrite(st->drift_shift, sizeof(double), st->dim, stream) != st->dim ||
+        fwrite(st->drift_scale, sizeof(double), st->dim, stream) != st->dim ||
+        fwrite(st->f_coef[0], sizeof(double), st->drift_q, stream) != st->drift_q) {
+      free(h);
+      GSL_ERROR("fwrite failed", GSL_EFAILED);
+    }
   }
   free(h);
   HIP_TRY(s, st->ctx);
@@ -3561,7 +3698,9 @@ int gsl_sinterp_fread(FILE *stream, gsl_sinterp *interp)
   if (fread(head, sizeof head[0], 3, stream) != 3 || fread(&eps, sizeof eps, 1, stream) != 1 ||
       fread(&flags, sizeof flags, 1, stream) != 1)
     GSL_ERROR("fread failed", GSL_EFAILED);
-  if (head[0] != (uint64_t)desc_of(interp->type)->id || head[1] != interp->dim || head[2] != interp->size)
+  /* a kriging interpolant accepts its plain id and its drift id: the file decides the drift */
+  const int drift_file = desc_of(interp->type)->krige && head[0] == drift_type_id(desc_of(interp->type));
+  if ((head[0] != (uint64_t)desc_of(interp->type)->id && !drift_file) || head[1] != interp->dim || head[2] != interp->size)
     GSL_ERROR("gsl_sinterp_fread: checkpoint does not match the type / dim / size of the interpolant", GSL_EBADLEN);
   if (tree_of(interp)) {
     simplex_state *st = tree_of(interp);
@@ -3652,6 +3791,16 @@ int gsl_sinterp_fread(FILE *stream, gsl_sinterp *interp)
   if (fread(h, sizeof(double), cnt, stream) != cnt) { free(h); GSL_ERROR("fread failed", GSL_EFAILED); }
   double poly[4] = {0.0, 0.0, 0.0, 0.0};
   if (st->affine && fread(poly, sizeof(double), 4, stream) != 4) { free(h); GSL_ERROR("fread failed", GSL_EFAILED); }
+  uint64_t order = 0;
+  double dshift[3] = {0.0, 0.0, 0.0}, dscale[3] = {1.0, 1.0, 1.0}, dcoef[GSL_SINTERP_DRIFT_MAX_TERMS];
+  size_t dq = 0;
+  if (drift_file) {
+    int ok = fread(&order, sizeof order, 1, stream) == 1 && (order == 1 || order == 2);
+    if (ok) dq = gsl_sinterp_drift_terms(st->dim, (int)order);
+    ok = ok && fread(dshift, sizeof(double), st->dim, stream) == st->dim && fread(dscale, sizeof(double), st->dim, stream) == st->dim &&
+         fread(dcoef, sizeof(double), dq, stream) == dq;
+    if (!ok) { free(h); GSL_ERROR("gsl_sinterp_fread: short or corrupt drift block", GSL_EFAILED); }
+  }
   rbf_release_variance(st);                             /* a factor kept by an earlier init belongs to another model */
   int s = rbf_prepare_devices(interp, st, 1);
   if (s) { free(h); return s; }
@@ -3661,6 +3810,13 @@ int gsl_sinterp_fread(FILE *stream, gsl_sinterp *interp)
   st->loo_state = 3;                                    /* ... and no leave-one-out data */
   st->eps = eps;
   if (st->krige) memcpy(&st->mean, &flags, sizeof st->mean);
+  if (st->krige) {                                      /* the file decides: a plain file switches a drift off, a drift file on */
+    st->drift = (int)order; st->drift_q = dq; interp->drift = (int)order;
+    memcpy(st->drift_shift, dshift, sizeof dshift); memcpy(st->drift_scale, dscale, sizeof dscale);
+    memset(st->f_coef, 0, sizeof st->f_coef);
+    memcpy(st->f_coef[0], dcoef, dq * sizeof(double));
+    if (order) st->mean = 0.0;
+  }
   if (st->affine) memcpy(st->poly, poly, sizeof poly);
   st->f_mean[0] = st->mean; memcpy(st->f_poly[0], st->poly, sizeof st->poly);
   st->model_id = next_model_id();

@@ -359,6 +359,7 @@ struct gsl_sinterp_struct {
   int want_variance; /* kriging: the next init keeps the Cholesky factor for gsl_sinterp_eval_variance_* (default 0) */
   int want_loo;      /* positive definite RBF types (Gaussian / Wendland / Matern / inverse multiquadric) and kriging: the next init computes the leave-one-out residuals and variances (default 0) */
   size_t neighbours; /* kriging: > 0 = local kriging on that many nearest centres per target (gsl_sinterp_set_neighbours); 0 = the global model (default) */
+  int drift;         /* kriging: order of the polynomial drift of the next init, 0 = ordinary kriging (default), 1 linear, 2 quadratic (gsl_sinterp_set_drift) */
 };
 
 extern const gsl_sinterp_type *gsl_sinterp_rbf_gaussian;
@@ -470,6 +471,51 @@ int gsl_sinterp_mean(const gsl_sinterp *interp, double *mean);     /* the estima
    GSL_EUNSUP: the init took the pivoted LDL^T route 8 (covariance matrix only semi-definite).  With a device list the
    factor lives on the first device, which evaluates every target. */
 int gsl_sinterp_set_variance(gsl_sinterp *interp, int want);            /* the three kriging types only (GSL_EINVAL otherwise); before init */
+/* Universal kriging: kriging with a polynomial drift (kt3d of GSLIB, UniversalKriging of PyKrige) on the three kriging types,
+       s(y) = p(u(y))^T c + sum_j w_j C(|y - x_j|),     [K P; P^T 0] [w; c] = [f; 0],     K = C + nugget I.
+   Ordinary kriging returns to one constant far from the data and its variance saturates at 1 + 1/(1^T K^-1 1): data with a
+   trend is extrapolated badly and its error mis-stated.  With a drift the predictor reproduces every polynomial of the
+   drift's order exactly -- also far outside the cloud -- and the variance grows with the distance as the trend's own
+   uncertainty does.
+   gsl_sinterp_set_drift(interp, order) BEFORE gsl_sinterp_init: 0 = ordinary kriging, the default, every bit as without the
+   call; 1 = linear; 2 = quadratic.  The basis is taken in standardised coordinates u_a = (y_a - shift_a) scale_a, shift the
+   centre of the sites' bounding box and scale 1 / half-extent per axis (1 for a zero extent), so that coordinates of UTM
+   size cost no digits.  Term order: 1; u_1 .. u_d; u_a u_b for a <= b, lexicographic.  gsl_sinterp_drift_terms(dim, order) =
+   q = C(dim + order, order), at most 10 (0 for arguments out of range).  gsl_sinterp_drift is the order in force: the one
+   set, or the one a checkpoint brought.
+   INIT (gsl_sinterp_route = 12): one fill and one Cholesky factorisation carry the fields and the q drift functions;
+   the q x q system for c is solved on the host.  GSL_EDOM, the interpolant left uninitialised, when K is not positive
+   definite -- there is NO pivoted route-8 fall-back with a drift: duplicate sites need a nugget -- or when the drift
+   functions are linearly dependent on the sites (collinear sites for order 1, sites on a conic for order 2).  GSL_EINVAL
+   when size < q.
+   With a drift and neighbours == 0 these work as for ordinary kriging: eval_e / _many / _resident / _grid, eval_grad_*,
+   init_fields / eval_fields_*, get_weights / get_field_weights (w only), set_variance with eval_variance_*
+       sigma^2(y) = C(0) - k^T K^-1 k + r^T S^-1 r,   r = p(u(y)) - B^T k(y),   B = K^-1 P,   S = P^T B,
+   clamped at 0, not bounded by the sill; set_loo with loo_* (Dubrule's rule with a drift: diag_i = (K^-1)_ii - B_i S^-1
+   B_i^T); device lists (the coefficients travel by value to every member).  The value bits of a target are the same alone,
+   in any batch, with or without the gradient, and as a column of a fields call.
+   gsl_sinterp_drift_coefficients: c (q entries, in the term order above, for STANDARDISED coordinates) of field `field`;
+   shift and scale (dim entries each, or NULL) tell the standardisation.  GSL_EINVAL: not a kriging interpolant, not
+   initialised, initialised without a drift, no such field; GSL_EBADLEN: sizes.
+   gsl_sinterp_mean / _field_mean: GSL_EUNSUP with a drift (there is no single mean).
+   LOCAL route (gsl_sinterp_set_neighbours(k), k > 0) with order 1: every target solves universal kriging with a linear drift
+   on its k nearest centres, in the local basis u = (x_i - y) / h, h the distance of the k-th neighbour
+   (gsl_sinterp_hip_local_ukrige); eval_*, eval_variance_* and eval_local_many work, everything else is refused exactly as
+   for the ordinary local route, and drift_coefficients is GSL_EUNSUP (every neighbourhood has its own).  A target whose
+   neighbourhood does not determine the drift (collinear sites in 2-D, coplanar in 3-D), has a covariance matrix that is not
+   positive definite, or has h = 0 gets NaN in value and variance and the call returns GSL_EDOM after every other target has
+   been stored.  k < dim + 2: GSL_EINVAL at init; order 2 with k > 0: GSL_EUNSUP at init.
+   Checkpoints: an interpolant with a drift is written under type id 17 / 18 / 19 (gsl_sinterp_kriging / _matern32 /
+   _matern52); payload [centres | weights], a uint64 order, shift, scale, the q coefficients.  gsl_sinterp_fread into a
+   kriging interpolant accepts its plain id and its drift id and sets the drift from the file; several fields: GSL_EUNSUP,
+   as without a drift.  Ordinary checkpoints keep their bytes.
+   The fit workspace (gsl_sinterp_fit_*) scores the ORDINARY model whatever the drift says: a drift-aware likelihood
+   (REML) is not provided.  Not provided either: external-drift covariates, simple kriging, order > 2. */
+int gsl_sinterp_set_drift(gsl_sinterp *interp, int order);   /* the three kriging types only (GSL_EINVAL otherwise; order outside 0..2: GSL_EINVAL); before init */
+int gsl_sinterp_drift(const gsl_sinterp *interp);
+size_t gsl_sinterp_drift_terms(size_t dim, int order);
+int gsl_sinterp_drift_coefficients(const gsl_sinterp *interp, size_t field, gsl_vector *c /* q */, gsl_vector *shift /* dim or NULL */,
+                                   gsl_vector *scale /* dim or NULL */);
 int gsl_sinterp_eval_variance_e(const gsl_sinterp *interp, const gsl_vector *y, double *var);
 int gsl_sinterp_eval_variance_many(const gsl_sinterp *interp, const gsl_matrix *y, gsl_vector *var);
 int gsl_sinterp_eval_variance_resident(const gsl_sinterp *interp, const double *d_y, size_t m, size_t ytda, double *d_var);
@@ -492,7 +538,8 @@ int gsl_sinterp_eval_variance_resident(const gsl_sinterp *interp, const double *
    fwrite / fread and the leave-one-out accessors return GSL_EUNSUP without touching the device.  eval_local_many: GSL_EINVAL
    when the interpolant was not initialised with k > 0, GSL_EBADLEN for a size mismatch.
    Not provided: search by radius or by octant, gradients (the predictor jumps where the neighbour set changes), several
-   fields, simple / universal kriging, sharding over a device group, checkpoints, k > 64. */
+   fields, simple kriging, a quadratic drift (gsl_sinterp_set_drift(2) with k > 0: GSL_EUNSUP at init; a linear one is
+   provided, see gsl_sinterp_set_drift), sharding over a device group, checkpoints, k > 64. */
 #define GSL_SINTERP_MAX_NEIGHBOURS 64
 int gsl_sinterp_set_neighbours(gsl_sinterp *interp, size_t k);
 int gsl_sinterp_eval_local_many(const gsl_sinterp *interp, const gsl_matrix *y, gsl_vector *s /* or NULL */, gsl_vector *var /* or NULL */,

@@ -560,6 +560,78 @@ int gsl_sinterp_hip_chol_inv_diag(gsl_sinterp_hip_ctx *ctx, size_t n, const doub
    GSL_EINVAL: nf > 64, ldw or lde < n with nf > 0; GSL_EFAULT: a NULL pointer (other than d_b) with work to do. */
 int gsl_sinterp_hip_loo_combine(gsl_sinterp_hip_ctx *ctx, size_t n, size_t nf, const double *d_g, const double *d_b,
                                 double denom, const double *d_w, size_t ldw, double *d_e, size_t lde, double *d_v);
+
+/* ---- universal kriging: a polynomial drift (csrc/hip/drift.hip; DESIGN.md 4, "Universal kriging") ---- */
+/* The model: s(y) = p(u(y))^T c + sum_j w_j phi(|y - x_j|),  [K P; P^T 0] [w; c] = [f; 0],  K = Phi + nugget I.
+   The basis is taken in STANDARDISED coordinates u_a = (y_a - h_shift[a]) * h_scale[a] (the facade passes the centre of
+   the sites' bounding box and 1 / half-extent per axis, 1 for a zero extent; monomials in raw coordinates of UTM size
+   would cost every digit).  order 1: q = dim + 1 terms {1, u_1 .. u_d}; order 2: q = (dim + 1)(dim + 2) / 2, the products
+   u_a u_b, a <= b, in lexicographic order behind them.  q <= GSL_SINTERP_DRIFT_MAX_TERMS.  h_shift / h_scale: dim host
+   doubles.  Every entry below takes order 1 or 2 (GSL_EINVAL otherwise: order 0 is ordinary kriging, whose entries stay
+   as they are) and checks its arguments before anything touches the device.
+     drift_terms    q for (dim, order), order 0 included (1); 0 for arguments out of range.
+     drift_factor   host only: S = Ls Ls^T of the q x q row-major h_S into the lower triangle of h_L (row-major, upper part
+                    zeroed).  GSL_EDOM when a pivot is not above 64 DBL_EPSILON times that diagonal entry of S before
+                    elimination, or not finite: the drift functions are linearly dependent on the sites.
+     drift_basis    column t of P at d_P + t * ldp (ldp >= n), row i = term t at site i.
+     ukrige_solve   route 12.  d_w holds F on entry (column f at d_w + f * ldw) and the weights on exit; ONE fill and ONE
+                    factorisation carry the nf + q right-hand sides [F | P] (A = K^-1 F, B = K^-1 P), S = P^T B and
+                    T = P^T A are reduced on the device in a fixed order (same bits every run), S c = T is solved on the
+                    host through drift_factor, w = A - B c.  h_coef receives nf * q coefficients, field f at h_coef + f * q;
+                    d_B (or NULL) receives B, column t at d_B + t * ldb; h_S (or NULL) the q * q entries of S; h_L (or NULL)
+                    its factor as drift_factor returns it; d_dinv (or NULL; ceil(n / 32) * 1024 doubles) the inverted 32 x 32
+                    diagonal blocks of L that ukrige_variance takes (what krige_variance_prepare returns).  The factor
+                    is left in the lower triangle of d_phi as krige_solve leaves it.  GSL_EDOM: K is not positive definite
+                    (there is NO pivoted route-8 fall-back with a drift) or S is not (drift_factor); GSL_EINVAL: 0 < n < q,
+                    a kind that is not positive definite, nf outside 1..64, a pitch below n.  Synchronises.
+     drift_add      the tail after a plain sweep: d_s[k * stda + f] += p(u(y_k))^T c_f and (d_g) d_g[k * gtda + f * dim + a]
+                    += d/dy_a of it in raw coordinates, f < nf; either of d_s / d_g may be NULL.  h_coef as ukrige_solve
+                    returns it; coefficients and geometry reach the kernel by value (8 fields per launch), so any context
+                    may call.  The value bits of a target are those of the plain sweep plus ONE addition of p^T c, formed
+                    in one fixed order: the same alone, in any batch, with or without gradients, for any nf.
+     ukrige_variance  sigma^2(y) = 1 - |L^-1 k|^2 + r^T S^-1 r, r = p(u(y)) - B^T k(y): the recursion of krige_variance for
+                    the second term, the fields sweep with the q columns of B as weights for B^T k (per pass of `chunk`
+                    targets), then the combine.  d_dinv as ukrige_solve or krige_variance_prepare return it, h_L from
+                    ukrige_solve or drift_factor.  The recursion always takes the default panel of 128 columns: the
+                    developer switch GSL_SINTERP_KRIGE_PANEL belongs to krige_variance and its timing tool;
+                    d_work: ukrige_variance_work(n, chunk, q) doubles.  Not clamped.
+     loo_combine_drift  Dubrule's rule with a drift: diag_i = g_i - B_i S^-1 B_i^T (S^-1 through h_L), d_e[f * lde + i] =
+                    d_w[f * ldw + i] / diag_i, d_v[i] = 1 / diag_i; g from gsl_sinterp_hip_chol_inv_diag.  q must be a
+                    value drift_terms returns for order 1 or 2. */
+/*   local_ukrige   gsl_sinterp_hip_local_krige with a LINEAR drift: the same arguments, search, statuses and bit contract (a
+                    target's result does not depend on the batch).  Local basis u = (x_i - y) / h, h the distance of the
+                    k-th neighbour, so p = e_0 at the target; with V = L^-1 [1 | u], g = L^-1 f_S, u = L^-1 k_S:
+                    S = V^T V, c = S^-1 V^T g, s = c_0 + u^T (g - V c), sigma^2 = phi(0) - u^T u + r^T S^-1 r, r = e_0 - V^T u.
+                    NaN in value and variance, counted in *h_n_failed, GSL_EDOM after every other target has been stored: a
+                    failed pivot of K_S, a pivot of S not above 64 DBL_EPSILON times that diagonal entry before elimination
+                    or not finite (a collinear / coplanar neighbourhood), h = 0.  GSL_EINVAL: k < dim + 2, and what
+                    local_krige refuses. */
+#define GSL_SINTERP_DRIFT_MAX_TERMS 10
+int gsl_sinterp_hip_local_ukrige(gsl_sinterp_hip_ctx *ctx, int kind, double eps, double nugget, const double *d_x, size_t n, int dim,
+                                 size_t xtda, const double *d_f, const double *d_y, size_t m, size_t ytda, size_t k, double *d_s,
+                                 double *d_var, int *d_idx, size_t *h_n_failed, unsigned long long model_id);
+size_t gsl_sinterp_hip_drift_terms(int dim, int order);
+int gsl_sinterp_hip_drift_factor(size_t q, const double *h_S, double *h_L);
+int gsl_sinterp_hip_drift_basis(gsl_sinterp_hip_ctx *ctx, int order, const double *h_shift, const double *h_scale,
+                                const double *d_x, size_t n, int dim, size_t xtda, double *d_P, size_t ldp);
+int gsl_sinterp_hip_ukrige_solve(gsl_sinterp_hip_ctx *ctx, int kind, double eps, double nugget, int order,
+                                 const double *h_shift, const double *h_scale, const double *d_x, size_t n, int dim,
+                                 size_t xtda, double *d_phi, size_t lda, double *d_w, size_t ldw, size_t nf,
+                                 double *h_coef, double *d_B, size_t ldb, double *h_S, double *h_L, double *d_dinv,
+                                 int *h_route);
+int gsl_sinterp_hip_drift_add(gsl_sinterp_hip_ctx *ctx, int order, const double *h_shift, const double *h_scale,
+                              const double *h_coef, size_t nf, const double *d_y, size_t m, int dim, size_t ytda,
+                              double *d_s, size_t stda, double *d_g, size_t gtda);
+size_t gsl_sinterp_hip_ukrige_variance_work(size_t n, size_t chunk, size_t q);
+int gsl_sinterp_hip_ukrige_variance(gsl_sinterp_hip_ctx *ctx, int kind, double eps, int order, const double *h_shift,
+                                    const double *h_scale, const double *d_x, size_t n, int dim, size_t xtda,
+                                    const double *d_llt, size_t lda, const double *d_B, size_t ldb, const double *d_dinv,
+                                    const double *h_L, const double *d_y, size_t m, size_t ytda, double *d_var,
+                                    double *d_work, size_t chunk);
+int gsl_sinterp_hip_loo_combine_drift(gsl_sinterp_hip_ctx *ctx, size_t n, size_t nf, const double *d_g, const double *d_B,
+                                      size_t ldb, size_t q, const double *h_L, const double *d_w, size_t ldw, double *d_e,
+                                      size_t lde, double *d_v);
+
 /* The scalars of the model-selection criteria (gsl_sinterp_fit_score).
    From a Cholesky factor (lower triangle of d_llt, as routes 1 / 7 leave it), the right-hand side d_f, the solved
    weights d_w and, optionally, g = diag(K^-1) (gsl_sinterp_hip_chol_inv_diag) and kriging's b = K^-1 1, denom = 1^T b:
