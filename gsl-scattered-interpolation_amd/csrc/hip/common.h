@@ -99,6 +99,19 @@ struct gsl_sinterp_hip_ctx {
   unsigned long long shep_packs, shep_fits;
 };
 
+/* A cached pack (local.hip, shepard.hip) is reused when the caller vouches for the model (id != 0) and every word that
+   describes the cloud matches; setting a key with id 0 records nothing. */
+static inline bool sinterp_key_vouches(const gsl_sinterp_hip_ctx::CentKey &key, unsigned long long id, const void *x, const void *w, size_t n,
+                                       size_t xtda, int dim)
+{
+  return id != 0 && key.id == id && key.x == x && key.w == w && key.n == n && key.xtda == xtda && key.dim == dim;
+}
+static inline void sinterp_key_set(gsl_sinterp_hip_ctx::CentKey &key, unsigned long long id, const void *x, const void *w, size_t n,
+                                   size_t xtda, int dim)
+{
+  if (id != 0) key = gsl_sinterp_hip_ctx::CentKey{id, x, w, n, xtda, 0, dim, 0, 0};
+}
+
 /* Graph helpers (shim.hip).  A key is up to GRAPH_KEY_WORDS - 1 argument words (unused words 0); the helpers append
    ctx->d_work.  sinterp_graph_try_launch sets *launched = 1 and launches the cached graph on the context's stream when
    slot `which` holds exactly this key.  Between sinterp_capture_begin / _end every launch on ctx->stream is recorded. */
@@ -328,6 +341,13 @@ int sinterp_route_end(gsl_sinterp_hip_ctx *ctx, const sinterp_route *r, size_t m
 int sinterp_outside_count(gsl_sinterp_hip_ctx *ctx, const unsigned long long *d_count, long long *h_n_outside, const char *what);
 /* sort.hip: bounding box of n points as order-preserving keys, box[2c] = min, box[2c+1] = max (device, 48 bytes) */
 int sinterp_bbox_keys(gsl_sinterp_hip_ctx *ctx, const double *d_p, size_t n, size_t tda, int dim, unsigned long long *d_box);
+/* local.hip: the n points of d_x binned on the g^dim grid over their bounding box (local_grid.h).  d_grid receives the
+   box, d_box its keys (48 bytes), d_off[cell] the first place of the cell in cell order and d_off[ncell] = n (room for
+   lk_off_words(ncell) words: the scan's scratch follows), d_cellid[i] the cell of point i and d_slot[i] its place inside
+   the cell, in the order the atomics hand out. */
+struct LkGrid;
+int sinterp_grid_bin(gsl_sinterp_hip_ctx *ctx, const double *d_x, size_t n, int dim, size_t xtda, int g, LkGrid *d_grid,
+                     unsigned long long *d_box, unsigned *d_off, unsigned *d_cellid, unsigned *d_slot);
 int sinterp_centbuf(gsl_sinterp_hip_ctx *ctx, size_t bytes, void **out);
 int sinterp_centbuf_fields(gsl_sinterp_hip_ctx *ctx, size_t bytes, void **out);
 int sinterp_localbuf(gsl_sinterp_hip_ctx *ctx, size_t bytes, void **out);

@@ -16,9 +16,9 @@
  *                          column order (no pivoting: the leading d x d block of R is the R of the linear fit), every
  *                          sum the fixed 64-lane butterfly.  Rank rule on rho(k) = min |R_jj| / max |R_jj|, j < k:
  *                          rho(nc) >= sqrt(eps) quadratic, else rho(d) >= sqrt(eps) linear, else constant.
- *   shepard_pack (once     the grid of local.hip over the nodes; records {x[d], f, Rw, 1/Rq, c[nc]} (80 B in 2-D, 128 B
- *   per model)             in 3-D) in cell order and ROW order inside a cell; per cell the box of its nodes and its largest
- *                          Rw; the largest Rw of all.
+ *   shepard_pack (once     the nodes binned by sinterp_grid_bin (local.hip); records {x[d], f, Rw, 1/Rq, c[nc]} (80 B in 2-D,
+ *   per model)             128 B in 3-D) in cell order and ROW order inside a cell; per cell the box of its nodes and its
+ *                          largest Rw; the largest Rw of all.
  *   shepard_sweep_kernel   one target per lane: the cells of the index block that covers y +- max Rw, a cell skipped when
  *                          its box is farther than its own largest Rw, the records of a cell in row order.
  *
@@ -29,12 +29,14 @@
  *               in it |fl(y_c - x_c)| >= gap_c (rounding is monotone), and the chain lb2 = fma(gap_c, gap_c, lb2) is below
  *               the node's r2 term by term.  The cell is skipped when lb2 >= fl(Rmax_cell^2) >= fl(Rw_i^2): then r2 >=
  *               fl(Rw_i^2) and the record would have failed the first test.
- *   index block lk_axis_cell is non-decreasing and bins the nodes too, so a node in a cell below a_c = cell(t), t = fl(y_c -
- *               R'), has x_c < t and fl(y_c - x_c) >= fl(y_c - t); the block starts at a_c only when fl(y_c - t) >= Rmax
- *               was CHECKED (otherwise at 0), and then r2 >= fl(Rmax^2) >= fl(Rw_i^2) again.  The high side is symmetric.
- * The in-cell order of local.hip's pack comes from atomics and varies from run to run; this pack ranks the rows of a
- * cell instead.  Value and value + gradient are one body (GRAD), contraction is off and every fused operation is
- * written out, so the value bits do not depend on GRAD.
+ *   index block lk_axis_cell is non-decreasing and bins the nodes too (local_grid.h, "The cell-function contract": that
+ *               also says why the binning, compiled with contraction on, and the queries made here agree), so a node in a
+ *               cell below a_c = cell(t), t = fl(y_c - R'), has x_c < t and fl(y_c - x_c) >= fl(y_c - t); the block starts
+ *               at a_c only when fl(y_c - t) >= Rmax was CHECKED (otherwise at 0), and then r2 >= fl(Rmax^2) >= fl(Rw_i^2)
+ *               again.  The high side is symmetric.
+ * The slots that the binning hands out come from atomics and vary from run to run; this pack ranks the rows of a cell
+ * instead.  Value and value + gradient are one body (GRAD), contraction is off and every fused operation is written out,
+ * so the value bits do not depend on GRAD.
  */
 #include "common.h"
 #include <math.h>
@@ -45,7 +47,7 @@
 
 #pragma clang fp contract(off)
 
-#define SH_HEAD 256                /* bytes: LkGrid | box keys at 64 | outside counter at 128 | largest Rw (bits) at 136 */
+#define SH_HEAD 256                /* bytes: LkGrid | box keys at 64 | outside counter (64 bits) at 128 | largest Rw (bits) at 136 */
 #define SH_FIT_CHUNK 8192          /* nodes per neighbour search of the fit: at most 64 x 12 bytes each */
 #define SH_SQRT_EPS 1.4901161193847656e-08   /* GSL_SQRT_DBL_EPSILON */
 #define SH_FIT_ID 0xffffffffffffffffULL      /* model id under which the fit keeps local.hip's pack between its chunks */
@@ -56,14 +58,6 @@ template <int DIM> struct ShDim {
 };
 
 __device__ __forceinline__ double sh_nan() { return __longlong_as_double(0x7ff8000000000000LL); }
-
-/* fixed-order sum over the 64 lanes; every lane receives the same bits */
-__device__ __forceinline__ double sh_sum(double v)
-{
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-  return v;
-}
 
 /* ---- fit ------------------------------------------------------------------------------------------------------------ */
 /* block b fits node node0 + b from row b of idx / r2 (k entries each, ascending key, slot 0 the node itself).
@@ -112,7 +106,7 @@ shepard_fit_kernel(const double *__restrict__ x, size_t xtda, const double *__re
   double nrm[NC];
 #pragma unroll
   for (int c = 0; c < NC; c++) {
-    nrm[c] = sqrt(sh_sum(a[c] * a[c]));
+    nrm[c] = sqrt(lk_sum(a[c] * a[c]));
     if (nrm[c] > 0.0) a[c] = a[c] / nrm[c];
   }
   /* Householder, rows = lanes, pivot row of column c = lane c.  Afterwards R_jc (j < c) is lane j's a[c], R_cc = diag[c]
@@ -121,7 +115,7 @@ shepard_fit_kernel(const double *__restrict__ x, size_t xtda, const double *__re
 #pragma unroll
   for (int c = 0; c < NC; c++) {
     const double xv = lane >= c ? a[c] : 0.0;
-    const double sigma = sh_sum(xv * xv);
+    const double sigma = lk_sum(xv * xv);
     const double xc = lane_bcast(a[c], c);
     const double len = sqrt(sigma);
     const double alpha = xc > 0.0 ? -len : len;
@@ -131,10 +125,10 @@ shepard_fit_kernel(const double *__restrict__ x, size_t xtda, const double *__re
       const double vtv = 2.0 * fma(fabs(xc), len, sigma);
 #pragma unroll
       for (int e = c + 1; e < NC; e++) {
-        const double tau = 2.0 * sh_sum(v * a[e]) / vtv;   /* v = 0 in the lanes above the pivot row */
+        const double tau = 2.0 * lk_sum(v * a[e]) / vtv;   /* v = 0 in the lanes above the pivot row */
         a[e] = fma(-tau, v, a[e]);
       }
-      const double tau = 2.0 * sh_sum(v * b) / vtv;
+      const double tau = 2.0 * lk_sum(v * b) / vtv;
       b = fma(-tau, v, b);
     }
   }
@@ -168,46 +162,13 @@ shepard_fit_kernel(const double *__restrict__ x, size_t xtda, const double *__re
 }
 
 /* ---- pack ----------------------------------------------------------------------------------------------------------- */
-__global__ void sh_head_kernel(const unsigned long long *__restrict__ box, int dim, LkGrid *__restrict__ out)
-{
-  if (threadIdx.x >= 6) return;
-  const int c = threadIdx.x >> 1;
-  double v = 0.0;
-  if (c < dim) {                                   /* the order-preserving keys of sinterp_bbox_keys back to doubles */
-    const unsigned long long k = box[threadIdx.x];
-    const unsigned long long u = (k >> 63) ? (k & 0x7fffffffffffffffULL) : ~k;
-    v = __longlong_as_double((long long)u);
-  }
-  if (threadIdx.x & 1) out->hi[c] = v; else out->lo[c] = v;
-}
-
-template <int DIM>
+/* the rows of every cell, in the order the binning's atomics handed out (not kept: sh_record_kernel ranks them) */
 __global__ void __launch_bounds__(256)
-sh_hist_kernel(const double *__restrict__ x, size_t n, size_t xtda, const LkGrid *__restrict__ grid, int g, unsigned *__restrict__ cellid,
-               unsigned *__restrict__ count)
-{
-  const LkGrid G = *grid;
-  const size_t stride = (size_t)gridDim.x * blockDim.x;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-    double v[DIM];
-#pragma unroll
-    for (int c = 0; c < DIM; c++) v[c] = x[i * xtda + c];
-    const unsigned cell = (unsigned)lk_cell<DIM>(G, g, v);
-    cellid[i] = cell;
-    atomicAdd(&count[cell], 1u);
-  }
-}
-
-/* the rows of every cell, in the order the atomics hand out (not kept: sh_record_kernel ranks them) */
-__global__ void __launch_bounds__(256)
-sh_scatter_kernel(size_t n, const unsigned *__restrict__ cellid, const unsigned *__restrict__ offset, unsigned *__restrict__ fill,
+sh_scatter_kernel(size_t n, const unsigned *__restrict__ cellid, const unsigned *__restrict__ slot, const unsigned *__restrict__ offset,
                   int *__restrict__ unordered)
 {
   const size_t stride = (size_t)gridDim.x * blockDim.x;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-    const unsigned cell = cellid[i];
-    unordered[offset[cell] + atomicAdd(&fill[cell], 1u)] = (int)i;
-  }
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) unordered[offset[cellid[i]] + slot[i]] = (int)i;
 }
 
 /* one thread per node: its place in its cell = the number of smaller rows there; then its record */
@@ -270,7 +231,7 @@ __global__ void __launch_bounds__(256)
 shepard_sweep_kernel(const LkGrid *__restrict__ grid, int g, const unsigned *__restrict__ off, const double *__restrict__ stat,
                      const int *__restrict__ rows, const double *__restrict__ rec, const unsigned long long *__restrict__ rmax_bits,
                      const double *__restrict__ yv, size_t ytda, size_t m, const int *__restrict__ perm, double *__restrict__ sout,
-                     double *__restrict__ gout, size_t gtda, int *__restrict__ leaf, unsigned *__restrict__ n_outside)
+                     double *__restrict__ gout, size_t gtda, int *__restrict__ leaf, unsigned long long *__restrict__ n_outside)
 {
   constexpr int RECD = ShDim<DIM>::RECD;
   const size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -372,7 +333,7 @@ shepard_sweep_kernel(const LkGrid *__restrict__ grid, int g, const unsigned *__r
         }
       }
     } else {
-      atomicAdd(n_outside, 1u);
+      atomicAdd(n_outside, 1ULL);
     }
   }
   if (sout) sout[t] = s;
@@ -390,7 +351,7 @@ struct sh_model {
   const double *stat;
   const int *rows;
   const double *rec;
-  unsigned *n_outside;
+  unsigned long long *n_outside;
   const unsigned long long *rmax_bits;
   int g;
 };
@@ -401,19 +362,17 @@ template <class F> static void sh_with_dim(int dim, F &&f)
   else f(std::integral_constant<int, 3>());
 }
 
-/* the packed nodes, cached per model like local.hip's: reused when the caller vouches for the model (model_id != 0) and
-   every word of the key matches */
+/* the packed nodes, cached per model like local.hip's */
 static int shepard_pack(gsl_sinterp_hip_ctx *ctx, const double *d_x, size_t n, int dim, size_t xtda, const double *d_f, const double *d_rq,
                         const double *d_rw, const double *d_coef, unsigned long long model_id, sh_model *out)
 {
   gsl_sinterp_hip_ctx::CentKey &key = ctx->shep_key;
-  const bool cached = model_id != 0 && key.id == model_id && key.x == d_x && key.w == d_coef && key.n == n && key.xtda == xtda &&
-                      key.dim == dim;
+  const bool cached = sinterp_key_vouches(key, model_id, d_x, d_coef, n, xtda, dim);
   const int g = cached ? ctx->shep_g : lk_grid_size(n, dim);
   size_t ncell = 1;
   for (int c = 0; c < dim; c++) ncell *= (size_t)g;
   const size_t recd = dim == 2 ? ShDim<2>::RECD : ShDim<3>::RECD;
-  const size_t off_bytes = round_up((ncell + 1 + ncell / 1024 + 8) * 4, 16), stat_bytes = ncell * 8 * sizeof(double);
+  const size_t off_bytes = round_up(lk_off_words(ncell) * 4, 16), stat_bytes = ncell * 8 * sizeof(double);
   const size_t rows_bytes = round_up(n * sizeof(int), 16);
   const size_t bytes = SH_HEAD + off_bytes + stat_bytes + rows_bytes + n * recd * sizeof(double);
   if (!cached) key.id = 0;                         /* the buffer may move or be rewritten */
@@ -427,30 +386,21 @@ static int shepard_pack(gsl_sinterp_hip_ctx *ctx, const double *d_x, size_t n, i
   int *rows = (int *)(b + SH_HEAD + off_bytes + stat_bytes);
   double *rec = (double *)(b + SH_HEAD + off_bytes + stat_bytes + rows_bytes);
   unsigned long long *rmax_bits = (unsigned long long *)(b + 136);
-  out->grid = grid; out->off = off; out->stat = stat; out->rows = rows; out->rec = rec; out->n_outside = (unsigned *)(b + 128);
+  out->grid = grid; out->off = off; out->stat = stat; out->rows = rows; out->rec = rec; out->n_outside = (unsigned long long *)(b + 128);
   out->rmax_bits = rmax_bits; out->g = g;
   if (cached) return ST_SUCCESS;
   void *tmp = NULL;
-  st = sinterp_sortbuf2(ctx, (2 * n + ncell) * 4, &tmp);
+  st = sinterp_sortbuf2(ctx, 3 * n * 4, &tmp);
   if (st) return st;
-  unsigned *cellid = (unsigned *)tmp, *fill = cellid + n;
-  int *unordered = (int *)(fill + ncell);
-  unsigned long long *box = (unsigned long long *)(b + 64);
-  st = sinterp_bbox_keys(ctx, d_x, n, xtda, dim, box);
+  unsigned *cellid = (unsigned *)tmp, *slot = cellid + n;
+  int *unordered = (int *)(slot + n);
+  st = sinterp_grid_bin(ctx, d_x, n, dim, xtda, g, grid, (unsigned long long *)(b + 64), off, cellid, slot);
   if (st) return st;
-  hipLaunchKernelGGL(sh_head_kernel, dim3(1), dim3(64), 0, ctx->stream, (const unsigned long long *)box, dim, grid);
-  HIP_OK(ctx, hipMemsetAsync(off, 0, ncell * 4, ctx->stream));
-  HIP_OK(ctx, hipMemsetAsync(fill, 0, ncell * 4, ctx->stream));
   HIP_OK(ctx, hipMemsetAsync(rmax_bits, 0, sizeof *rmax_bits, ctx->stream));
   size_t blocks = (n + 255) / 256;
   if (blocks > 2048) blocks = 2048;
-  sh_with_dim(dim, [&](auto D) {
-    hipLaunchKernelGGL((sh_hist_kernel<decltype(D)::value>), dim3((unsigned)blocks), dim3(256), 0, ctx->stream, d_x, n, xtda,
-                       (const LkGrid *)grid, g, cellid, off);
-  });
-  sinterp_scan_u32(ctx, off, ncell, off + ncell + 1);
-  hipLaunchKernelGGL(sh_scatter_kernel, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, n, (const unsigned *)cellid, (const unsigned *)off,
-                     fill, unordered);
+  hipLaunchKernelGGL(sh_scatter_kernel, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, n, (const unsigned *)cellid, (const unsigned *)slot,
+                     (const unsigned *)off, unordered);
   sh_with_dim(dim, [&](auto D) {
     constexpr int DIM = decltype(D)::value;
     hipLaunchKernelGGL((sh_record_kernel<DIM>), dim3((unsigned)blocks), dim3(256), 0, ctx->stream, d_x, n, xtda, d_f, d_rq, d_rw, d_coef,
@@ -461,9 +411,7 @@ static int shepard_pack(gsl_sinterp_hip_ctx *ctx, const double *d_x, size_t n, i
   LAUNCH_CHECK(ctx);
   ctx->shep_g = g;
   ctx->shep_packs++;
-  if (model_id != 0) {
-    key.id = model_id; key.x = d_x; key.w = d_coef; key.n = n; key.xtda = xtda; key.ldw = 0; key.dim = dim; key.kind = 0; key.nf = 0;
-  }
+  sinterp_key_set(key, model_id, d_x, d_coef, n, xtda, dim);
   return ST_SUCCESS;
 }
 
@@ -530,7 +478,7 @@ extern "C" int gsl_sinterp_hip_shepard_eval(gsl_sinterp_hip_ctx *ctx, const doub
     st = sinterp_sort_targets(ctx, d_y, m, ytda, dim, 64, &perm);
     if (st) return st;
   }
-  HIP_OK(ctx, hipMemsetAsync(sm.n_outside, 0, sizeof(unsigned), ctx->stream));
+  HIP_OK(ctx, hipMemsetAsync(sm.n_outside, 0, sizeof *sm.n_outside, ctx->stream));
   const dim3 grid((unsigned)((m + 255) / 256)), block(256);
   sh_with_dim(dim, [&](auto D) {
     constexpr int DIM = decltype(D)::value;
@@ -542,16 +490,13 @@ extern "C" int gsl_sinterp_hip_shepard_eval(gsl_sinterp_hip_ctx *ctx, const doub
                          sm.rmax_bits, d_y, ytda, m, (const int *)perm, d_s, (double *)NULL, (size_t)0, d_leaf, sm.n_outside);
   });
   LAUNCH_CHECK(ctx);
-  if (!h_n_outside) return ST_SUCCESS;                 /* asynchronous: the caller reads NaN / -1 */
-  /* the uncovered targets are the status: wait for the batch (everything else has been stored by then) */
-  unsigned outside = 0;
-  HIP_OK(ctx, hipMemcpyAsync(&outside, sm.n_outside, sizeof outside, hipMemcpyDeviceToHost, ctx->stream));
-  HIP_OK(ctx, hipStreamSynchronize(ctx->stream));
-  *h_n_outside = outside;
-  if (outside)
-    return sinterp_fail(ctx, ST_EDOM, "shepard_eval: target(s) outside every node's radius of influence (value and gradient NaN, leaf -1 there)",
-                        hipSuccess, __FILE__, __LINE__);
-  return ST_SUCCESS;
+  /* the uncovered targets are the status: with h_n_outside it waits for the batch (everything else has been stored by
+     then); without, the call stays asynchronous and the caller reads NaN / -1 */
+  long long outside = 0;
+  st = sinterp_outside_count(ctx, sm.n_outside, h_n_outside ? &outside : NULL,
+                             "shepard_eval: target(s) outside every node's radius of influence (value and gradient NaN, leaf -1 there)");
+  if (h_n_outside) *h_n_outside = (size_t)outside;
+  return st;
 }
 
 extern "C" unsigned long long gsl_sinterp_hip_shepard_pack_count(const gsl_sinterp_hip_ctx *ctx) { return ctx ? ctx->shep_packs : 0ULL; }
