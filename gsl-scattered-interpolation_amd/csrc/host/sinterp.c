@@ -1441,7 +1441,7 @@ typedef struct {
   double denom;
   /* leave-one-out (gsl_sinterp_set_loo): residuals (column q at loo_e + q * n, loo_nf columns) and variances of the last
      init, on the host.  loo_state: 0 nothing held (not asked for), 1 ready, 2 the init took a route without a Cholesky
-     factor, 3 restored from a checkpoint */
+     factor, 3 restored from a checkpoint, 4 kriging on no more sites than mean / drift functions (undefined) */
   int loo_state;
   size_t loo_nf;
   double *loo_e, *loo_v;
@@ -1603,6 +1603,35 @@ static void rbf_drift_geometry(const double *x, size_t n, size_t dim, double *sh
   for (size_t a = dim; a < 3; a++) { shift[a] = 0.0; scale[a] = 1.0; }
 }
 
+/* Whether the n centres (packed n x dim) lie in a hyperplane to rounding, so that [1, x] has dependent columns on them and
+   the affine tail of the thin-plate spline is not determined: modified Gram-Schmidt on the centred coordinate columns; a
+   column whose remainder is not above 1e-12 of its own norm depends on the ones before it (or has no extent).  Exactly
+   collinear / coplanar input leaves a remainder of a few ulp, 1e-16; at 1e-12 the bordered system's condition number is
+   past 1e12 and no digit of the tail is left.  -1: out of memory. */
+static int centres_in_a_hyperplane(const double *x, size_t n, size_t dim)
+{
+  double *c = (double *)malloc(n * dim * sizeof(double));
+  if (!c) return -1;
+  int flat = 0;
+  for (size_t a = 0; a < dim && !flat; a++) {
+    double *ca = c + a * n, mean = 0.0, norm0 = 0.0, rem = 0.0;
+    for (size_t i = 0; i < n; i++) mean += x[i * dim + a];
+    mean /= (double)n;
+    for (size_t i = 0; i < n; i++) { ca[i] = x[i * dim + a] - mean; norm0 += ca[i] * ca[i]; }
+    for (size_t b = 0; b < a; b++) {
+      const double *cb = c + b * n;
+      double dot = 0.0;
+      for (size_t i = 0; i < n; i++) dot += ca[i] * cb[i];
+      for (size_t i = 0; i < n; i++) ca[i] -= dot * cb[i];
+    }
+    for (size_t i = 0; i < n; i++) rem += ca[i] * ca[i];
+    if (!(sqrt(rem) > 1e-12 * sqrt(norm0))) flat = 1;
+    else { const double inv = 1.0 / sqrt(rem); for (size_t i = 0; i < n; i++) ca[i] *= inv; }
+  }
+  free(c);
+  return flat;
+}
+
 /* f(i, q) = fdata[i * frow + q * fcol], nf fields: gsl_sinterp_init (nf = 1) and gsl_sinterp_init_fields */
 static int rbf_init_fields(gsl_sinterp *interp, const gsl_matrix *x, const double *fdata, size_t frow, size_t fcol, size_t nf)
 {
@@ -1628,6 +1657,15 @@ static int rbf_init_fields(gsl_sinterp *interp, const gsl_matrix *x, const doubl
   for (size_t i = 0; i < n; i++) {
     for (size_t cdim = 0; cdim < dim; cdim++) h_x[i * dim + cdim] = x->data[i * x->tda + cdim];
     for (size_t q = 0; q < nf; q++) h_f[q * n + i] = fdata[i * frow + q * fcol];
+  }
+  if (st->affine) {
+    const int flat = centres_in_a_hyperplane(h_x, n, dim);
+    if (flat) {
+      free(h_x); free(h_f);
+      if (flat < 0) GSL_ERROR("gsl_sinterp_init: out of memory", GSL_ENOMEM);
+      GSL_ERROR("gsl_sinterp_init: affine thin-plate spline: the centres lie in a hyperplane (collinear / coplanar), the affine tail is not determined",
+                GSL_EDOM);
+    }
   }
   const size_t model_bytes = n * (dim + nf) * sizeof(double);
   double *d_phi = NULL;
@@ -1702,7 +1740,11 @@ static int rbf_init_fields(gsl_sinterp *interp, const gsl_matrix *x, const doubl
   /* leave-one-out asked for: routes 1 and 7 left L in the lower triangle of d_phi (with set_rcond too: the original
      stays ABOVE the diagonal), still alive here or just handed to the variance; every other route has no factor */
   if (!s && interp->want_loo) {
-    if (route == 1 || route == 7 || route == 12) s = rbf_compute_loo(st, st->d_llt ? st->d_llt : d_phi, lda, nf, d_B);
+    /* kriging estimates its mean (1 term) or drift (q terms) from the data: with no more sites than terms the model
+       without site i does not exist, Dubrule's diagonal is 0 in exact arithmetic and e_i = w_i / diag_i is 0 / 0 */
+    const size_t loo_terms = st->krige ? (drift ? gsl_sinterp_drift_terms(dim, drift) : 1) : 0;
+    if (n <= loo_terms) st->loo_state = 4;
+    else if (route == 1 || route == 7 || route == 12) s = rbf_compute_loo(st, st->d_llt ? st->d_llt : d_phi, lda, nf, d_B);
     else st->loo_state = 2;
   }
   /* replicate the solved model: ONE broadcast of the weight vector (+ centres) */
@@ -1806,7 +1848,7 @@ static int rbf_eval_resident(const gsl_sinterp *interp, const double *d_y, size_
 {
   (void)d_leaf;
   const rbf_state *st = rbf_of(interp);
-  if (!st->d_w) GSL_ERROR("gsl_sinterp_eval: interpolant not initialised", GSL_EINVAL);
+  if (!st->d_w || st->nf == 0) GSL_ERROR("gsl_sinterp_eval: interpolant not initialised", GSL_EINVAL);
   if (st->local_k) return local_eval_resident(interp, d_y, m, ytda, d_s, NULL, NULL);
   /* resident buffers live on ONE device: member 0 evaluates them (shard resident targets yourself with
      gsl_sinterp_hip_shard_bounds + one interpolant per device, as bench.py does per process) */
@@ -1832,7 +1874,7 @@ static int rbf_chunk_eval(void *state, const double *d_y, size_t m, double *d_s,
 static int rbf_eval_many(const gsl_sinterp *interp, const gsl_matrix *y, gsl_vector *sv, int *leaf)
 {
   rbf_state *st = rbf_of(interp);                       /* not const: the staging buffers are grow-only caches inside the state */
-  if (!st->d_w) GSL_ERROR("gsl_sinterp_eval_many: interpolant not initialised", GSL_EINVAL);
+  if (!st->d_w || st->nf == 0) GSL_ERROR("gsl_sinterp_eval_many: interpolant not initialised", GSL_EINVAL);
   const size_t m = y->size1, dim = st->dim;
   if (m == 0) return GSL_SUCCESS;
   if (st->local_k) {
@@ -2505,6 +2547,8 @@ static int loo_status(const gsl_sinterp *interp)
     GSL_ERROR("gsl_sinterp_loo: the interpolant was restored by gsl_sinterp_fread; a checkpoint carries no leave-one-out data", GSL_EINVAL);
   if (st->loo_state == 2)
     GSL_ERROR("gsl_sinterp_loo: the init took a route without a Cholesky factor", GSL_EUNSUP);
+  if (st->loo_state == 4)
+    GSL_ERROR("gsl_sinterp_loo: kriging needs more sites than mean / drift functions (nothing is left to predict from once a site is deleted)", GSL_EDOM);
   if (st->loo_state != 1)
     GSL_ERROR("gsl_sinterp_loo: initialised without gsl_sinterp_set_loo", GSL_EINVAL);
   return GSL_SUCCESS;
@@ -2791,7 +2835,7 @@ static int variance_status(const gsl_sinterp *interp)
   if (d->noun) return noun_error(d, "gsl_sinterp_eval_variance: not for %s interpolants", GSL_EUNSUP);
   if (!d->krige) GSL_ERROR("gsl_sinterp_eval_variance: kriging interpolants only", GSL_EINVAL);
   const rbf_state *st = rbf_of(interp);
-  if (!st->d_w) GSL_ERROR("gsl_sinterp_eval_variance: interpolant not initialised", GSL_EINVAL);
+  if (!st->d_w || st->nf == 0) GSL_ERROR("gsl_sinterp_eval_variance: interpolant not initialised", GSL_EINVAL);
   if (st->local_k) return GSL_SUCCESS;                  /* the local route keeps no factor and needs none */
   if (st->var_state == 3)
     GSL_ERROR("gsl_sinterp_eval_variance: the interpolant was restored by gsl_sinterp_fread; a checkpoint carries no factor", GSL_EINVAL);
@@ -2873,7 +2917,7 @@ int gsl_sinterp_eval_local_many(const gsl_sinterp *interp, const gsl_matrix *y, 
   if (!interp || !y) GSL_ERROR("gsl_sinterp_eval_local_many: null argument", GSL_EFAULT);
   if (!desc_of(interp->type)->krige) GSL_ERROR("gsl_sinterp_eval_local_many: kriging interpolants only", GSL_EINVAL);
   const rbf_state *st = rbf_of(interp);
-  if (!st->d_w) GSL_ERROR("gsl_sinterp_eval_local_many: interpolant not initialised", GSL_EINVAL);
+  if (!st->d_w || st->nf == 0) GSL_ERROR("gsl_sinterp_eval_local_many: interpolant not initialised", GSL_EINVAL);
   if (!st->local_k) GSL_ERROR("gsl_sinterp_eval_local_many: initialised without gsl_sinterp_set_neighbours", GSL_EINVAL);
   if (y->size2 != interp->dim) GSL_ERROR("target matrix must have dim columns", GSL_EBADLEN);
   if ((s && s->size != y->size1) || (var && var->size != y->size1)) GSL_ERROR("output length must equal the number of targets", GSL_EBADLEN);
@@ -2915,7 +2959,7 @@ int gsl_sinterp_eval_grad_resident(const gsl_sinterp *interp, const double *d_y,
     return m == 0 ? GSL_SUCCESS : shepard_sweep(sh, d_y, m, ytda, d_s, d_g, gtda, NULL);
   }
   const rbf_state *st = rbf_of(interp);
-  if (!st->d_w) GSL_ERROR("gsl_sinterp_eval_grad: interpolant not initialised", GSL_EINVAL);
+  if (!st->d_w || st->nf == 0) GSL_ERROR("gsl_sinterp_eval_grad: interpolant not initialised", GSL_EINVAL);
   /* the tail: the affine polynomial, or kriging's constant mean; member 0 evaluates every target (as
      gsl_sinterp_eval_resident does) */
   double tail[4] = {st->mean, 0.0, 0.0, 0.0};
@@ -2954,7 +2998,7 @@ int gsl_sinterp_eval_grad_many(const gsl_sinterp *interp, const gsl_matrix *y, g
     return shepard_eval_host(sh, y, sv, g, NULL);
   }
   const rbf_state *st = rbf_of(interp);
-  if (!st->d_w) GSL_ERROR("gsl_sinterp_eval_grad: interpolant not initialised", GSL_EINVAL);
+  if (!st->d_w || st->nf == 0) GSL_ERROR("gsl_sinterp_eval_grad: interpolant not initialised", GSL_EINVAL);
   if (m == 0) return GSL_SUCCESS;
   gsl_sinterp_hip_ctx *c = st->ctx;
   stage_out out[2] = {STAGE_MATRIX(g), STAGE_VECTOR(sv)};     /* no sv: no room for values, nothing downloaded for them */
@@ -3258,7 +3302,7 @@ int gsl_sinterp_poly(const gsl_sinterp *interp, gsl_vector *c)
   if (!interp || !c) GSL_ERROR("gsl_sinterp_poly: null argument", GSL_EFAULT);
   if (!desc_of(interp->type)->affine) GSL_ERROR("gsl_sinterp_poly: affine thin-plate-spline interpolants only", GSL_EINVAL);
   const rbf_state *st = rbf_of(interp);
-  if (!st->d_w) GSL_ERROR("gsl_sinterp_poly: interpolant not initialised", GSL_EINVAL);
+  if (!st->d_w || st->nf == 0) GSL_ERROR("gsl_sinterp_poly: interpolant not initialised", GSL_EINVAL);
   if (c->size != st->dim + 1) GSL_ERROR("gsl_sinterp_poly: vector length must be dim + 1", GSL_EBADLEN);
   for (size_t a = 0; a <= st->dim; a++) gsl_vector_set(c, a, st->poly[a]);
   return GSL_SUCCESS;
@@ -3271,7 +3315,7 @@ int gsl_sinterp_mean(const gsl_sinterp *interp, double *mean)
   if (is_local(interp)) GSL_ERROR("gsl_sinterp_mean: not with gsl_sinterp_set_neighbours (every neighbourhood estimates its own mean)", GSL_EUNSUP);
   if (interp->drift > 0 || rbf_of(interp)->drift) GSL_ERROR("gsl_sinterp_mean: with a drift there is no single mean (gsl_sinterp_drift_coefficients)", GSL_EUNSUP);
   const rbf_state *st = rbf_of(interp);
-  if (!st->d_w) GSL_ERROR("gsl_sinterp_mean: interpolant not initialised", GSL_EINVAL);
+  if (!st->d_w || st->nf == 0) GSL_ERROR("gsl_sinterp_mean: interpolant not initialised", GSL_EINVAL);
   *mean = st->mean;
   return GSL_SUCCESS;
 }
@@ -3495,7 +3539,7 @@ int gsl_sinterp_get_weights(const gsl_sinterp *interp, gsl_vector *w)
   const rbf_state *st = rbf_of(interp);
   if (!st) GSL_ERROR("gsl_sinterp_get_weights: not an RBF interpolant", GSL_EINVAL);
   if (is_local(interp)) GSL_ERROR("gsl_sinterp_get_weights: not with gsl_sinterp_set_neighbours (no global weight vector exists)", GSL_EUNSUP);
-  if (!st->d_w) GSL_ERROR("gsl_sinterp_get_weights: interpolant not initialised", GSL_EINVAL);
+  if (!st->d_w || st->nf == 0) GSL_ERROR("gsl_sinterp_get_weights: interpolant not initialised", GSL_EINVAL);
   if (w->size != st->n) GSL_ERROR("gsl_sinterp_get_weights: wrong length", GSL_EBADLEN);
   double *h = (double *)malloc(st->n * sizeof(double));
   if (!h) GSL_ERROR("gsl_sinterp_get_weights: out of memory", GSL_ENOMEM);
@@ -3657,7 +3701,7 @@ int gsl_sinterp_fwrite(FILE *stream, const gsl_sinterp *interp)
     return GSL_SUCCESS;
   }
   const rbf_state *st = rbf_of(interp);
-  if (!st->d_w) GSL_ERROR("gsl_sinterp_fwrite: interpolant not initialised", GSL_EINVAL);
+  if (!st->d_w || st->nf == 0) GSL_ERROR("gsl_sinterp_fwrite: interpolant not initialised", GSL_EINVAL);
   if (st->nf > 1) GSL_ERROR("gsl_sinterp_fwrite: the GSLSINT1 format holds one weight vector (interpolant with several fields)", GSL_EUNSUP);
   const size_t cnt = st->n * (st->dim + 1);
   double *h = (double *)malloc(cnt * sizeof(double));

@@ -561,7 +561,9 @@ int gsl_sinterp_eval_local_many(const gsl_sinterp *interp, const gsl_matrix *y, 
    types, not initialised, initialised
    without set_loo, or restored by gsl_sinterp_fread (a checkpoint carries no leave-one-out data, and reading one drops
    what was held); GSL_EUNSUP: the init took a route without a Cholesky factor (an explicit gsl_sinterp_set_solver, the
-   pivoted LDL^T route 8 of kriging): gsl_sinterp_route is then neither 1 nor 7; GSL_EBADLEN: E is not size x K
+   pivoted LDL^T route 8 of kriging): gsl_sinterp_route is then neither 1 nor 7; GSL_EDOM: kriging on no more sites than
+   it has mean / drift functions (size 1; size <= gsl_sinterp_drift_terms with a drift): the model without a site does not
+   exist, the init itself succeeds and evaluates; GSL_EBADLEN: E is not size x K
    (K = gsl_sinterp_n_fields; E->tda honoured, padding untouched), v does not have size entries. */
 int gsl_sinterp_set_loo(gsl_sinterp *interp, int want);
 int gsl_sinterp_loo_residuals(const gsl_sinterp *interp, gsl_matrix *E);
