@@ -303,6 +303,16 @@ SIGNATURES = {
     "gsl_sinterp_hip_ukrige_variance": (_i, [_vp, _i, _d, _i, _pd, _pd, _vp, _sz, _i, _sz, _vp, _sz, _vp, _sz, _vp, _pd, _vp, _sz, _sz, _vp,
                                              _vp, _sz]),
     "gsl_sinterp_hip_loo_combine_drift": (_i, [_vp, _sz, _sz, _vp, _vp, _sz, _sz, _pd, _vp, _sz, _vp, _sz, _vp]),
+    "gsl_sinterp_hip_krige_covariance_work": (_sz, [_sz, _sz, _sz, _sz]),
+    "gsl_sinterp_hip_krige_covariance": (_i, [_vp, _i, _d, _i, _pd, _pd, _vp, _sz, _i, _sz, _vp, _sz, _vp, _sz, _vp, _pd, _vp, _sz, _sz, _vp,
+                                              _sz, _sz, _vp, _sz, _vp]),
+    "gsl_sinterp_hip_krige_simulate_work": (_sz, [_sz, _sz, _sz, _sz]),
+    "gsl_sinterp_hip_krige_simulate": (_i, [_vp, _i, _d, _i, _pd, _pd, _vp, _sz, _i, _sz, _vp, _sz, _vp, _sz, _vp, _pd, _vp, _sz, _sz, _vp,
+                                            _d, _d, _vp, _sz, _sz, _vp, _sz, _vp]),
+    "gsl_sinterp_eval_covariance_many": (_i, [C.POINTER(gsl_sinterp), _pm, _pm, _pm]),
+    "gsl_sinterp_eval_covariance_resident": (_i, [C.POINTER(gsl_sinterp), _vp, _sz, _sz, _vp, _sz, _sz, _vp, _sz]),
+    "gsl_sinterp_simulate_many": (_i, [C.POINTER(gsl_sinterp), _pm, _d, _d, _pm, _pm]),
+    "gsl_sinterp_simulate_resident": (_i, [C.POINTER(gsl_sinterp), _vp, _sz, _sz, _d, _d, _vp, _sz, _sz, _vp, _sz]),
     "gsl_sinterp_set_drift": (_i, [C.POINTER(gsl_sinterp), _i]),
     "gsl_sinterp_drift": (_i, [C.POINTER(gsl_sinterp)]),
     "gsl_sinterp_drift_terms": (_sz, [_sz, _i]),
@@ -683,6 +693,36 @@ class HipContext:
     def loo_combine_drift(self, n, nf, d_g, d_B, ldb, q, L, d_w, ldw, d_e, lde, d_v):
         L = np.ascontiguousarray(L, dtype=np.float64)
         return lib().gsl_sinterp_hip_loo_combine_drift(self._h, n, nf, d_g, d_B, ldb, q, L.ctypes.data_as(_pd), d_w, ldw, d_e, lde, d_v)
+
+    @staticmethod
+    def krige_covariance_work(n, ma, mb, q):
+        """doubles of d_work that krige_covariance needs (mb = 0: one target set)"""
+        return lib().gsl_sinterp_hip_krige_covariance_work(n, ma, mb, q)
+
+    @staticmethod
+    def _drift_args(shift, scale, L):
+        pd = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.float64)
+        keep = [pd(shift), pd(scale), pd(L)]
+        return keep, [None if a is None else a.ctypes.data_as(_pd) for a in keep]
+
+    def krige_covariance(self, kind, eps, order, shift, scale, d_x, n, dim, xtda, d_llt, lda, d_B, ldb, d_dinv, L, d_ya, ma, yatda, d_yb, mb,
+                         ybtda, d_cov, ctda, d_work):
+        """d_cov = the joint posterior covariance of the targets d_ya x d_yb (d_yb = None: d_ya with itself, symmetric to the bit);
+        order 0: shift = scale = None, d_B = b, L = [sqrt(1^T b)]; returns the status"""
+        keep, (p_shift, p_scale, p_L) = self._drift_args(shift, scale, L)
+        return lib().gsl_sinterp_hip_krige_covariance(self._h, kind, eps, order, p_shift, p_scale, d_x, n, dim, xtda, d_llt, lda, d_B, ldb,
+                                                      d_dinv, p_L, d_ya, ma, yatda, d_yb, mb, ybtda, d_cov, ctda, d_work)
+
+    @staticmethod
+    def krige_simulate_work(n, m, n_draws, q):
+        return lib().gsl_sinterp_hip_krige_simulate_work(n, m, n_draws, q)
+
+    def krige_simulate(self, kind, eps, order, shift, scale, d_x, n, dim, xtda, d_llt, lda, d_B, ldb, d_dinv, L, d_y, m, ytda, d_mean, sigma2,
+                       jitter, d_zn, ztda, n_draws, d_out, otda, d_work):
+        """d_out = d_mean + sqrt(sigma2) chol(Sigma + jitter I) d_zn; returns the status (GSL_EDOM: not positive definite, NaN)"""
+        keep, (p_shift, p_scale, p_L) = self._drift_args(shift, scale, L)
+        return lib().gsl_sinterp_hip_krige_simulate(self._h, kind, eps, order, p_shift, p_scale, d_x, n, dim, xtda, d_llt, lda, d_B, ldb, d_dinv,
+                                                    p_L, d_y, m, ytda, d_mean, sigma2, jitter, d_zn, ztda, n_draws, d_out, otda, d_work)
 
     def device(self):
         return lib().gsl_sinterp_hip_ctx_device(self._h)
@@ -1356,6 +1396,28 @@ class Sinterp:
 
     def eval_variance_resident(self, d_y, m, ytda, d_var):
         return lib().gsl_sinterp_eval_variance_resident(self._p, d_y, m, ytda, d_var)
+
+    def eval_covariance_many(self, ya, yb=None, out=None):
+        """joint posterior covariance of the rows of ya with the rows of yb (None: ya, symmetric to the bit), not clamped;
+        returns (status, Cov ma x mb)"""
+        mb = ya.shape[0] if yb is None else yb.shape[0]
+        cov = np.full((ya.shape[0], mb), np.nan) if out is None else out
+        st = lib().gsl_sinterp_eval_covariance_many(self._p, C.byref(as_matrix(ya)), None if yb is None else C.byref(as_matrix(yb)),
+                                                    C.byref(as_matrix(cov)))
+        return st, cov
+
+    def eval_covariance_resident(self, d_ya, ma, yatda, d_yb, mb, ybtda, d_cov, ctda):
+        return lib().gsl_sinterp_eval_covariance_resident(self._p, d_ya, ma, yatda, d_yb, mb, ybtda, d_cov, ctda)
+
+    def simulate_many(self, y, sigma2, jitter, zn, out=None):
+        """conditional draws at the rows of y from the caller's standard normals zn (m x S): mean + sqrt(sigma2) chol(Sigma +
+        jitter I) zn; returns (status, Out m x S)"""
+        o = np.full(zn.shape, np.nan) if out is None else out
+        st = lib().gsl_sinterp_simulate_many(self._p, C.byref(as_matrix(y)), sigma2, jitter, C.byref(as_matrix(zn)), C.byref(as_matrix(o)))
+        return st, o
+
+    def simulate_resident(self, d_y, m, ytda, sigma2, jitter, d_zn, ztda, n_draws, d_out, otda):
+        return lib().gsl_sinterp_simulate_resident(self._p, d_y, m, ytda, sigma2, jitter, d_zn, ztda, n_draws, d_out, otda)
 
     def set_neighbours(self, k):
         """kriging: k > 0 = the next init takes the local route (kriging on the k nearest centres of every target), 0 = global"""

@@ -248,18 +248,27 @@ struct KvPass {
 int sinterp_kv_update(const KvPass &p, size_t c0, size_t cw, size_t k0, size_t kw);
 /* Z[:, j0 : j0 + 128] <- Z[:, j0 : j0 + 128] L_JJ^-T and q_k += |Z[k][j0 : j0 + 128]|^2 (krige_trsm128_kernel) */
 int sinterp_kv_diag(const KvPass &p, size_t j0);
+/* the fill Z[k][j] = phi(|y_k - x_j|) of rows_pad rows (a multiple of 16; rows >= rows and columns >= n are zeros; clears
+   q) for a run-time positive definite kind, and the whole substitution Z <- Z L^-T of one pass at the default panel:
+   what the joint covariance (krige_cov.hip) takes over from the variance entries */
+int sinterp_kv_cross_fill(gsl_sinterp_hip_ctx *ctx, int kind, double coef, const double *tbl, const double *d_x, size_t n, int dim,
+                          size_t xtda, const double *d_y, size_t rows, size_t ytda, double *Z, size_t ldw, size_t rows_pad, double *q);
+int sinterp_kv_solve(const KvPass &p);
 /* inverse of every 32 x 32 diagonal block of L -> d_dinv[ceil(n / 32) * 1024] (krige_inv32_kernel) */
 int sinterp_krige_inv32(gsl_sinterp_hip_ctx *ctx, size_t n, const double *d_llt, size_t lda, double *d_dinv);
 /* drift.hip: the launchers behind the universal-kriging entries of solve.hip and krige_var.hip (order 1 or 2, arguments
    checked by the callers).  basis: column t of P at d_P + t * ldp.  gram: d_G[a * ncols + b] = sum_i P_a[i] Y_b[i], a < q,
    b < ncols, fixed summation order.  var_combine: d_var[k] = (1 - d_q[k]) + |Ls^-1 (p(u(y_k)) - d_bk[k * q ..])|^2, h_L = the
-   q x q row-major factor of gsl_sinterp_hip_drift_factor. */
+   q x q row-major factor of gsl_sinterp_hip_drift_factor.  cov_terms (order 0 .. 2; order 0 = ordinary kriging: p = 1, q = 1,
+   h_L = {sqrt(1^T b)}, h_shift / h_scale not read): row k of d_bk, B^T k(y_k) on entry, becomes t_k = Ls^-1 (p(u(y_k)) - B^T k(y_k)). */
 int sinterp_drift_basis(gsl_sinterp_hip_ctx *ctx, int order, const double *h_shift, const double *h_scale, const double *d_x, size_t n,
                         int dim, size_t xtda, double *d_P, size_t ldp);
 int sinterp_drift_gram(gsl_sinterp_hip_ctx *ctx, const double *d_P, size_t ldp, const double *d_Y, size_t ldy, size_t n, int q, int ncols,
                        double *d_G);
 int sinterp_drift_var_combine(gsl_sinterp_hip_ctx *ctx, int order, const double *h_shift, const double *h_scale, const double *h_L, int dim,
                               const double *d_y, size_t rows, size_t ytda, const double *d_bk, const double *d_q, double *d_var);
+int sinterp_drift_cov_terms(gsl_sinterp_hip_ctx *ctx, int order, const double *h_shift, const double *h_scale, const double *h_L, int dim,
+                            const double *d_y, size_t rows, size_t ytda, double *d_bk);
 /* second grow-only buffer for vectors that must outlive factorisation workspaces */
 int sinterp_aux(gsl_sinterp_hip_ctx *ctx, size_t bytes, void **out);
 int sinterp_invbuf(gsl_sinterp_hip_ctx *ctx, size_t bytes, void **out);

@@ -178,6 +178,30 @@ drift_var_combine_kernel(DriftGeom g, DriftTri L, const double *__restrict__ y, 
   var[k] = (1.0 - qn[k]) + drift_quad<Q>(L, r);
 }
 
+/* the joint covariance's T (krige_cov.hip): row k of bk, B^T k(y_k) on entry, becomes t_k = Ls^-1 (p(u_k) - bk_k), the forward
+   substitution of drift_quad with Ls in registers.  ORDER 0 is ordinary kriging: p = 1, Q = 1, Ls = sqrt(1^T b). */
+template <int DIM, int ORDER>
+__global__ void __launch_bounds__(256)
+drift_cov_terms_kernel(DriftGeom g, DriftTri L, const double *__restrict__ y, size_t rows, size_t ytda, double *__restrict__ bk)
+{
+  constexpr int Q = drift_q(DIM, ORDER);
+  const size_t k = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (k >= rows) return;
+  double r[Q];
+  if constexpr (ORDER == 0) {
+    r[0] = 1.0;
+  } else {
+    double u[DIM];
+    drift_u<DIM>(g, y + k * ytda, u);
+    drift_terms<DIM, ORDER>(u, r);
+  }
+#pragma unroll
+  for (int t = 0; t < Q; t++) r[t] -= bk[k * Q + t];
+  (void)drift_quad<Q>(L, r);
+#pragma unroll
+  for (int t = 0; t < Q; t++) bk[k * Q + t] = r[t];
+}
+
 /* diag_i = g_i - |Ls^-1 B_i|^2; e[f][i] = w[f][i] / diag_i, v_i = 1 / diag_i (loo_combine_kernel with the drift's correction) */
 template <int Q>
 __global__ void __launch_bounds__(256)
@@ -287,6 +311,23 @@ int sinterp_drift_var_combine(gsl_sinterp_hip_ctx *ctx, int order, const double 
   with_dim_order(dim, order, [&](auto D, auto O) {
     hipLaunchKernelGGL((drift_var_combine_kernel<decltype(D)::value, decltype(O)::value>), grid, dim3(256), 0, ctx->stream, g, L, d_y, rows,
                        ytda, d_bk, d_q, d_var);
+  });
+  LAUNCH_CHECK(ctx);
+  return ST_SUCCESS;
+}
+
+int sinterp_drift_cov_terms(gsl_sinterp_hip_ctx *ctx, int order, const double *h_shift, const double *h_scale, const double *h_L, int dim,
+                            const double *d_y, size_t rows, size_t ytda, double *d_bk)
+{
+  static const double zero[3] = {0.0, 0.0, 0.0}, one[3] = {1.0, 1.0, 1.0};
+  const DriftGeom g = order == 0 ? make_geom(dim, zero, one) : make_geom(dim, h_shift, h_scale);
+  const DriftTri L = make_tri(drift_q(dim, order), h_L);
+  const dim3 grid((unsigned)((rows + 255) / 256));
+  with_dim(dim, [&](auto D) {
+    constexpr int d = decltype(D)::value;
+    if (order == 0) hipLaunchKernelGGL((drift_cov_terms_kernel<d, 0>), grid, dim3(256), 0, ctx->stream, g, L, d_y, rows, ytda, d_bk);
+    else if (order == 1) hipLaunchKernelGGL((drift_cov_terms_kernel<d, 1>), grid, dim3(256), 0, ctx->stream, g, L, d_y, rows, ytda, d_bk);
+    else hipLaunchKernelGGL((drift_cov_terms_kernel<d, 2>), grid, dim3(256), 0, ctx->stream, g, L, d_y, rows, ytda, d_bk);
   });
   LAUNCH_CHECK(ctx);
   return ST_SUCCESS;

@@ -235,6 +235,20 @@ static int kv_solve(const KvPass &p, size_t panel)
   return ST_SUCCESS;
 }
 
+/* the fill and the whole substitution for the joint covariance (krige_cov.hip): a run-time kind, the default panel */
+int sinterp_kv_cross_fill(gsl_sinterp_hip_ctx *ctx, int kind, double coef, const double *tbl, const double *d_x, size_t n, int dim,
+                          size_t xtda, const double *d_y, size_t rows, size_t ytda, double *Z, size_t ldw, size_t rows_pad, double *q)
+{
+  with_kind(kind, [&](auto K) {
+    if constexpr (kind_is_pd(decltype(K)::value))            /* the callers require kind_is_pd(kind) */
+      launch_cross_fill<decltype(K)::value>(ctx, coef, tbl, d_x, n, dim, xtda, d_y, rows, ytda, Z, ldw, rows_pad, q);
+  });
+  LAUNCH_CHECK(ctx);
+  return ST_SUCCESS;
+}
+
+int sinterp_kv_solve(const KvPass &p) { return kv_solve(p, PB); }
+
 extern "C" size_t gsl_sinterp_hip_krige_variance_work(size_t n, size_t chunk)
 {
   /* Z (rows padded to KV_RP, pitch n rounded up to 128) + q + two words to align Z to 16 bytes */

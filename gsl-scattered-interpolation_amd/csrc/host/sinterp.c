@@ -2846,6 +2846,17 @@ static int variance_status(const gsl_sinterp *interp)
   return GSL_SUCCESS;
 }
 
+/* the grow-only workspace of the variance, covariance and simulation entries: at least `need` doubles */
+static int variance_workspace(rbf_state *st, size_t need)
+{
+  if (need <= st->vwork_doubles) return GSL_SUCCESS;
+  gsl_sinterp_hip_free(st->ctx, st->d_vwork);
+  st->d_vwork = NULL; st->vwork_doubles = 0;
+  int s = gsl_sinterp_hip_malloc(st->ctx, (void **)&st->d_vwork, need * sizeof(double));
+  if (!s) st->vwork_doubles = need;
+  return s;
+}
+
 int gsl_sinterp_eval_variance_resident(const gsl_sinterp *interp, const double *d_y, size_t m, size_t ytda, double *d_var)
 {
   if (!interp) GSL_ERROR("gsl_sinterp_eval_variance: null interpolant", GSL_EFAULT);
@@ -2858,12 +2869,7 @@ int gsl_sinterp_eval_variance_resident(const gsl_sinterp *interp, const double *
   size_t chunk = (m + 63) / 64 * 64;
   if (chunk > 8192) chunk = 8192;
   const size_t need = st->drift ? gsl_sinterp_hip_ukrige_variance_work(st->n, chunk, st->drift_q) : gsl_sinterp_hip_krige_variance_work(st->n, chunk);
-  if (need > st->vwork_doubles) {
-    gsl_sinterp_hip_free(st->ctx, st->d_vwork);
-    st->d_vwork = NULL; st->vwork_doubles = 0;
-    HIP_TRY(gsl_sinterp_hip_malloc(st->ctx, (void **)&st->d_vwork, need * sizeof(double)), st->ctx);
-    st->vwork_doubles = need;
-  }
+  HIP_TRY(variance_workspace(st, need), st->ctx);
   /* the factor lives on member 0, which evaluates every target (as gsl_sinterp_eval_resident does) */
   if (st->drift) {
     HIP_TRY(gsl_sinterp_hip_ukrige_variance(st->ctx, st->kind, st->eps, st->drift, st->drift_shift, st->drift_scale, st->d_x, st->n, (int)st->dim,
@@ -2910,6 +2916,149 @@ int gsl_sinterp_eval_variance_e(const gsl_sinterp *interp, const gsl_vector *y, 
   int st = gsl_sinterp_eval_variance_many(interp, &Y.matrix, &V.vector);
   if (st == GSL_SUCCESS) *var = out;
   return st;
+}
+
+/* ---- joint covariance and conditional simulation (csrc/hip/krige_cov.hip) ---- */
+/* the state conditions of the variance entries, and the local route refused: it has no joint model */
+static int covariance_status(const gsl_sinterp *interp)
+{
+  if (is_local(interp))
+    GSL_ERROR("gsl_sinterp_eval_covariance / _simulate: not with gsl_sinterp_set_neighbours (the local route has no joint model)", GSL_EUNSUP);
+  return variance_status(interp);
+}
+
+/* what the raw entries take of the kept model: ordinary kriging is order 0, q = 1, B = b and the 1 x 1 factor sqrt(1^T b) */
+typedef struct {
+  int order;
+  size_t q;
+  const double *shift, *scale, *d_B, *h_L;
+  double l1;
+} joint_model;
+
+static void joint_model_of(const rbf_state *st, joint_model *j)
+{
+  j->order = st->drift; j->q = st->drift ? st->drift_q : 1;
+  j->shift = st->drift ? st->drift_shift : NULL; j->scale = st->drift ? st->drift_scale : NULL;
+  j->d_B = st->drift ? st->d_B : st->d_b;
+  j->l1 = sqrt(st->denom);
+  j->h_L = st->drift ? st->drift_L : &j->l1;
+}
+
+int gsl_sinterp_eval_covariance_resident(const gsl_sinterp *interp, const double *d_ya, size_t ma, size_t yatda, const double *d_yb,
+                                         size_t mb, size_t ybtda, double *d_cov, size_t ctda)
+{
+  if (!interp) GSL_ERROR("gsl_sinterp_eval_covariance: null interpolant", GSL_EFAULT);
+  int vs = covariance_status(interp);
+  if (vs) return vs;
+  rbf_state *st = rbf_of(interp);           /* the workspace is a grow-only cache inside the state */
+  if (!d_yb) { mb = ma; ybtda = yatda; }
+  if (ma == 0 || mb == 0) return GSL_SUCCESS;
+  if (!d_ya || !d_cov) GSL_ERROR("gsl_sinterp_eval_covariance: null argument", GSL_EFAULT);
+  if (yatda < st->dim || ybtda < st->dim) GSL_ERROR("gsl_sinterp_eval_covariance: a target pitch is below dim", GSL_EINVAL);
+  if (ctda < mb) GSL_ERROR("gsl_sinterp_eval_covariance: ctda is below the number of columns", GSL_EINVAL);
+  joint_model j;
+  joint_model_of(st, &j);
+  HIP_TRY(variance_workspace(st, gsl_sinterp_hip_krige_covariance_work(st->n, ma, d_yb ? mb : 0, j.q)), st->ctx);
+  /* the factor lives on member 0, which does all the work */
+  HIP_TRY(gsl_sinterp_hip_krige_covariance(st->ctx, st->kind, st->eps, j.order, j.shift, j.scale, st->d_x, st->n, (int)st->dim, st->dim,
+                                           st->d_llt, st->llt_lda, j.d_B, st->n, st->d_dinv, j.h_L, d_ya, ma, yatda, d_yb, mb, ybtda, d_cov,
+                                           ctda, st->d_vwork), st->ctx);
+  return GSL_SUCCESS;
+}
+
+/* an m x cols host matrix, repacked dense and uploaded into a device buffer of its own (the caller frees *d) */
+static int upload_dense(gsl_sinterp_hip_ctx *c, const gsl_matrix *a, double **d)
+{
+  const size_t cnt = a->size1 * a->size2;
+  *d = NULL;
+  double *h = (double *)malloc(cnt * sizeof(double));
+  if (!h) return GSL_ENOMEM;
+  for (size_t i = 0; i < a->size1; i++)
+    for (size_t k = 0; k < a->size2; k++) h[i * a->size2 + k] = a->data[i * a->tda + k];
+  int s = gsl_sinterp_hip_malloc(c, (void **)d, cnt * sizeof(double));
+  if (!s) s = gsl_sinterp_hip_h2d(c, *d, h, cnt * sizeof(double));
+  free(h);
+  return s;
+}
+
+int gsl_sinterp_eval_covariance_many(const gsl_sinterp *interp, const gsl_matrix *ya, const gsl_matrix *yb, gsl_matrix *Cov)
+{
+  if (!interp || !ya || !Cov) GSL_ERROR("gsl_sinterp_eval_covariance_many: null argument", GSL_EFAULT);
+  const size_t dim = interp->dim, ma = ya->size1, mb = yb ? yb->size1 : ma;
+  if (ya->size2 != dim || (yb && yb->size2 != dim)) GSL_ERROR("target matrix must have dim columns", GSL_EBADLEN);
+  if (Cov->size1 != ma || Cov->size2 != mb) GSL_ERROR("gsl_sinterp_eval_covariance_many: Cov must be ma x mb", GSL_EBADLEN);
+  int vs = covariance_status(interp);
+  if (vs || ma == 0 || mb == 0) return vs;
+  gsl_sinterp_hip_ctx *c = rbf_of(interp)->ctx;
+  stage_out out[1] = {STAGE_MATRIX(Cov)};
+  host_stage hs;
+  double *d_yb = NULL;
+  int s = host_stage_begin(&hs, c, ya, dim, out, 1), es = GSL_SUCCESS;
+  if (!hs.h) GSL_ERROR("gsl_sinterp_eval_covariance_many: out of memory", GSL_ENOMEM);
+  if (!s && yb) s = upload_dense(c, yb, &d_yb);
+  if (!s) es = gsl_sinterp_eval_covariance_resident(interp, hs.d_y, ma, dim, d_yb, mb, dim, (double *)out[0].d, mb);
+  s = host_stage_end(&hs, s, !es);
+  gsl_sinterp_hip_free(c, d_yb);
+  HIP_TRY(s, c);
+  return es;
+}
+
+int gsl_sinterp_simulate_resident(const gsl_sinterp *interp, const double *d_y, size_t m, size_t ytda, double sigma2, double jitter,
+                                  const double *d_zn, size_t ztda, size_t n_draws, double *d_out, size_t otda)
+{
+  if (!interp) GSL_ERROR("gsl_sinterp_simulate: null interpolant", GSL_EFAULT);
+  int vs = covariance_status(interp);
+  if (vs) return vs;
+  rbf_state *st = rbf_of(interp);
+  if (!isfinite(sigma2) || !(sigma2 > 0.0)) GSL_ERROR("gsl_sinterp_simulate: sigma2 must be finite and positive", GSL_EINVAL);
+  if (!isfinite(jitter) || jitter < 0.0) GSL_ERROR("gsl_sinterp_simulate: jitter must be finite and not negative", GSL_EINVAL);
+  if (n_draws < 1) GSL_ERROR("gsl_sinterp_simulate: at least one draw", GSL_EBADLEN);
+  if (m == 0) return GSL_SUCCESS;
+  if (!d_y || !d_zn || !d_out) GSL_ERROR("gsl_sinterp_simulate: null argument", GSL_EFAULT);
+  if (ytda < st->dim) GSL_ERROR("gsl_sinterp_simulate: the target pitch is below dim", GSL_EINVAL);
+  if (ztda < n_draws || otda < n_draws) GSL_ERROR("gsl_sinterp_simulate: ztda or otda is below the number of draws", GSL_EINVAL);
+  joint_model j;
+  joint_model_of(st, &j);
+  /* [mean (m, rounded up to even) | the raw entry's work] */
+  const size_t m2 = (m + 1) / 2 * 2;
+  HIP_TRY(variance_workspace(st, m2 + gsl_sinterp_hip_krige_simulate_work(st->n, m, n_draws, j.q)), st->ctx);
+  double *d_mean = st->d_vwork;
+  HIP_TRY(rbf_sweep(st, st->ctx, st->d_x, st->d_w, d_y, m, ytda, d_mean), st->ctx);        /* field 0's predictor: the bits of eval */
+  int s = gsl_sinterp_hip_krige_simulate(st->ctx, st->kind, st->eps, j.order, j.shift, j.scale, st->d_x, st->n, (int)st->dim, st->dim,
+                                         st->d_llt, st->llt_lda, j.d_B, st->n, st->d_dinv, j.h_L, d_y, m, ytda, d_mean, sigma2, jitter, d_zn,
+                                         ztda, n_draws, d_out, otda, st->d_vwork + m2);
+  if (s == GSL_EDOM)
+    GSL_ERROR("gsl_sinterp_simulate: the joint covariance of the targets plus jitter is not numerically positive definite (targets on data sites of a nugget-free model, or repeated targets): every draw is NaN; pass a jitter such as 1e-10",
+              GSL_EDOM);
+  HIP_TRY(s, st->ctx);
+  return GSL_SUCCESS;
+}
+
+int gsl_sinterp_simulate_many(const gsl_sinterp *interp, const gsl_matrix *y, double sigma2, double jitter, const gsl_matrix *Zn,
+                              gsl_matrix *Out)
+{
+  if (!interp || !y || !Zn || !Out) GSL_ERROR("gsl_sinterp_simulate_many: null argument", GSL_EFAULT);
+  const size_t dim = interp->dim, m = y->size1, S = Zn->size2;
+  if (y->size2 != dim) GSL_ERROR("target matrix must have dim columns", GSL_EBADLEN);
+  if (S < 1 || Zn->size1 != m || Out->size1 != m || Out->size2 != S)
+    GSL_ERROR("gsl_sinterp_simulate_many: Zn and Out must be m x S with S >= 1", GSL_EBADLEN);
+  int vs = covariance_status(interp);
+  if (vs) return vs;
+  if (!isfinite(sigma2) || !(sigma2 > 0.0)) GSL_ERROR("gsl_sinterp_simulate: sigma2 must be finite and positive", GSL_EINVAL);
+  if (!isfinite(jitter) || jitter < 0.0) GSL_ERROR("gsl_sinterp_simulate: jitter must be finite and not negative", GSL_EINVAL);
+  if (m == 0) return GSL_SUCCESS;
+  gsl_sinterp_hip_ctx *c = rbf_of(interp)->ctx;
+  stage_out out[1] = {STAGE_MATRIX(Out)};
+  host_stage hs;
+  double *d_zn = NULL;
+  int s = host_stage_begin(&hs, c, y, dim, out, 1), es = GSL_SUCCESS;
+  if (!hs.h) GSL_ERROR("gsl_sinterp_simulate_many: out of memory", GSL_ENOMEM);
+  if (!s) s = upload_dense(c, Zn, &d_zn);
+  if (!s) es = gsl_sinterp_simulate_resident(interp, hs.d_y, m, dim, sigma2, jitter, d_zn, S, S, (double *)out[0].d, S);
+  s = host_stage_end(&hs, s, !es || es == GSL_EDOM);      /* GSL_EDOM: every entry is NaN, and says so in Out */
+  gsl_sinterp_hip_free(c, d_zn);
+  HIP_TRY(s, c);
+  return es;
 }
 
 int gsl_sinterp_eval_local_many(const gsl_sinterp *interp, const gsl_matrix *y, gsl_vector *s, gsl_vector *var, int *idx)

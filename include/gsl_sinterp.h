@@ -519,6 +519,44 @@ int gsl_sinterp_drift_coefficients(const gsl_sinterp *interp, size_t field, gsl_
 int gsl_sinterp_eval_variance_e(const gsl_sinterp *interp, const gsl_vector *y, double *var);
 int gsl_sinterp_eval_variance_many(const gsl_sinterp *interp, const gsl_matrix *y, gsl_vector *var);
 int gsl_sinterp_eval_variance_resident(const gsl_sinterp *interp, const double *d_y, size_t m, size_t ytda, double *d_var);
+/* Joint posterior covariance and conditional simulation (return_cov / sample_y of scikit-learn, LU simulation of GSLIB) for
+   the three kriging types, ordinary or with a drift of order 1 or 2, from what gsl_sinterp_set_variance keeps.  For target
+   sets Ya (ma rows) and Yb (mb rows; NULL = Ya), sill 1, the nugget measurement noise as in eval_variance_*:
+       Cov[i][j] = Cov[Z(ya_i), Z(yb_j) | data] = C(|ya_i - yb_j|) - k(ya_i)^T K^-1 k(yb_j) + r(ya_i)^T S^-1 r(yb_j),
+   r = p(u(y)) - B^T k(y), B = K^-1 P, S = P^T B (ordinary kriging: p = 1, B = K^-1 1).  C carries no nugget, also for
+   coincident targets (C = 1).  The diagonal of the one-set form is the kriging variance of eval_variance_* BEFORE their
+   clamp: NOTHING is clamped here, so where sigma^2 = 0 (a data site of a nugget-free model) the diagonal carries rounding
+   residue of either sign; the variance entries stay the clamped ones.  With yb == NULL only the lower triangle is computed
+   and then mirrored: Cov is symmetric to the bit.  Cost: (ma + mb) N^2 flops for the substitution the variance does too,
+   plus ma mb N for the product.
+   gsl_sinterp_simulate_*: conditional realisations at the m rows of y from standard normals Zn (m x S) that the CALLER
+   supplies -- the library draws no random numbers, every result is reproducible:
+       Out[:, s] = s(Y) + sqrt(sigma2) A Zn[:, s],     A A^T = Cov(Y, Y) + jitter I,
+   A the lower Cholesky factor taken in target order (value i of a draw depends on the normals 0 .. i only), s(Y) field 0's
+   predictor: a column of Zn that is all zeros returns the bits of gsl_sinterp_eval_many, equal columns give equal bits.
+   sigma2 scales the unit-sill model to the units of f: pass 1, or what gsl_sinterp_fit_sigma2 returned.  The matrix is
+   factored by the library's blocked Cholesky; when it is not numerically positive definite -- targets on data sites of a
+   nugget-free model, repeated targets -- every entry of Out is NaN and the call returns GSL_EDOM through the handler: pass a
+   jitter such as 1e-10.  There is no pivoted fall-back and no automatic jitter.
+   STATE: exactly the conditions of eval_variance_* (GSL_EINVAL: not a kriging interpolant, not initialised, initialised
+   without set_variance, restored by fread; GSL_EUNSUP: route 8), and GSL_EUNSUP with neighbours > 0 (the local route has no
+   joint model), before anything touches the device.  ARGUMENTS: GSL_EFAULT a NULL argument; GSL_EBADLEN ya / yb / y without
+   dim columns, Cov not ma x mb, Zn or Out not m x S with S >= 1; GSL_EINVAL ctda < mb, ztda or otda < S, sigma2 not finite or
+   <= 0, jitter not finite or < 0; ma, mb or m = 0 succeeds and writes nothing.  Every tda is honoured and padding left
+   untouched; a target with a NaN coordinate gives NaN in its row and column of Cov and is no error.  With a device list the
+   first device does the work.  Work memory is the grow-only workspace of the variance entries, which holds ALL of Z at once
+   here: when it cannot grow -- m so large that m^2 doubles, or (ma + mb) N doubles, do not fit -- GSL_ENOMEM through the
+   handler, the outputs untouched.
+   Not provided: random-number generation, draws for more than field 0, the local route, sharding over a device group,
+   checkpoints of a factor, a pivoted or eigenvalue factor for a singular covariance, sequential simulation. */
+int gsl_sinterp_eval_covariance_many(const gsl_sinterp *interp, const gsl_matrix *ya, const gsl_matrix *yb /* or NULL = ya */,
+                                     gsl_matrix *Cov /* ma x mb */);
+int gsl_sinterp_eval_covariance_resident(const gsl_sinterp *interp, const double *d_ya, size_t ma, size_t yatda,
+                                         const double *d_yb /* or NULL */, size_t mb, size_t ybtda, double *d_cov, size_t ctda /* >= mb */);
+int gsl_sinterp_simulate_many(const gsl_sinterp *interp, const gsl_matrix *y /* m x dim */, double sigma2, double jitter,
+                              const gsl_matrix *Zn /* m x S */, gsl_matrix *Out /* m x S */);
+int gsl_sinterp_simulate_resident(const gsl_sinterp *interp, const double *d_y, size_t m, size_t ytda, double sigma2, double jitter,
+                                  const double *d_zn, size_t ztda, size_t n_draws, double *d_out, size_t otda);
 /* Local kriging (a moving neighbourhood) for clouds past the size a dense N x N factorisation holds:
    gsl_sinterp_set_neighbours(interp, k), 1 <= k <= GSL_SINTERP_MAX_NEIGHBOURS = 64, BEFORE gsl_sinterp_init makes the init
    upload the centres and the responses and bin them on a grid -- nothing is factored, gsl_sinterp_route is 11 -- and every

@@ -632,6 +632,45 @@ int gsl_sinterp_hip_loo_combine_drift(gsl_sinterp_hip_ctx *ctx, size_t n, size_t
                                       size_t ldb, size_t q, const double *h_L, const double *d_w, size_t ldw, double *d_e,
                                       size_t lde, double *d_v);
 
+/* ---- joint posterior covariance and conditional simulation (csrc/hip/krige_cov.hip) ---- */
+/* For target sets Ya (ma rows) and Yb (mb rows), sill 1, the nugget measurement noise as in krige_variance:
+       d_cov[i * ctda + j] = C(|ya_i - yb_j|) - z_i . z_j + t_i . t_j,   z = L^-1 k(y),   t = Ls^-1 (p(u(y)) - B^T k(y)),
+   B = K^-1 P, S = P^T B = Ls Ls^T.  C carries no nugget, also for coincident targets (C = 1).  ONE body serves every order:
+   order 1 or 2 takes d_B (column t at d_B + t * ldb), h_L, h_shift and h_scale as ukrige_variance does; order 0 is ordinary
+   kriging, q = 1: d_B = b = K^-1 1 and h_L = {sqrt(1^T b)} (krige_variance_prepare), h_shift / h_scale not read (NULL).
+   d_yb == NULL: Yb = Ya (mb and ybtda are not read): only the tiles on and below the diagonal are computed, the strict
+   lower triangle is then copied to the upper one, so the result is symmetric to the bit.  Nothing is clamped: the diagonal
+   is the kriging variance BEFORE the clamp, rounding residue of either sign where sigma^2 = 0.  Nothing outside the
+   ma x mb window of d_cov is written (ctda >= mb).  A target with a NaN coordinate gives NaN in its row and column.
+   All of Z_a, and of Z_b, is held at once in d_work (krige_covariance_work(n, ma, mb, q) doubles, mb = 0 for one set;
+   q = drift_terms(dim, order)): rows padded to 128, pitch n rounded up to 128, Z_b stacked under Z_a so that one
+   substitution pass serves both.  Asynchronous on the context's stream; every buffer is the caller's.
+   GSL_EINVAL: dim, a pitch below its width, n = 0, a kind that is not positive definite, order outside 0..2; GSL_EFAULT: a
+   NULL pointer with work to do; ma = 0 or mb = 0 succeeds and touches nothing. */
+size_t gsl_sinterp_hip_krige_covariance_work(size_t n, size_t ma, size_t mb, size_t q);
+int gsl_sinterp_hip_krige_covariance(gsl_sinterp_hip_ctx *ctx, int kind, double eps, int order, const double *h_shift,
+                                     const double *h_scale, const double *d_x, size_t n, int dim, size_t xtda,
+                                     const double *d_llt, size_t lda, const double *d_B, size_t ldb, const double *d_dinv,
+                                     const double *h_L, const double *d_ya, size_t ma, size_t yatda, const double *d_yb,
+                                     size_t mb, size_t ybtda, double *d_cov, size_t ctda, double *d_work);
+/* Conditional simulation at the m rows of d_y, on top of the two entries above:
+       d_out[i * otda + s] = d_mean[i] + sqrt(sigma2) (A Zn)[i][s],     A A^T = Sigma_YY + jitter I,   s < n_draws,
+   A the lower Cholesky factor in target order (gsl_sinterp_hip_cholesky_decomp1 on an m x m work matrix), d_zn the caller's
+   standard normals (m x n_draws, pitch ztda; no random numbers are drawn here), d_mean the predictor at the targets
+   (krige_eval, or rbf_eval_model + drift_add).  A column of zeros returns the bits of d_mean; equal columns give equal
+   bits; value i depends on the normals 0 .. i only.  d_work: krige_simulate_work(n, m, n_draws, q) doubles.  Waits for the
+   pivot status of the factorisation.  GSL_EDOM: Sigma_YY + jitter I is not numerically positive definite (targets on data
+   sites of a nugget-free model, repeated targets) -- every entry of d_out is NaN; there is no pivoted fall-back and no
+   automatic jitter: pass one such as 1e-10.  GSL_EINVAL: n_draws = 0, ztda or otda < n_draws, sigma2 not finite or <= 0,
+   jitter not finite or < 0, and what krige_covariance refuses; m = 0 succeeds and touches nothing. */
+size_t gsl_sinterp_hip_krige_simulate_work(size_t n, size_t m, size_t n_draws, size_t q);
+int gsl_sinterp_hip_krige_simulate(gsl_sinterp_hip_ctx *ctx, int kind, double eps, int order, const double *h_shift,
+                                   const double *h_scale, const double *d_x, size_t n, int dim, size_t xtda,
+                                   const double *d_llt, size_t lda, const double *d_B, size_t ldb, const double *d_dinv,
+                                   const double *h_L, const double *d_y, size_t m, size_t ytda, const double *d_mean,
+                                   double sigma2, double jitter, const double *d_zn, size_t ztda, size_t n_draws,
+                                   double *d_out, size_t otda, double *d_work);
+
 /* The scalars of the model-selection criteria (gsl_sinterp_fit_score).
    From a Cholesky factor (lower triangle of d_llt, as routes 1 / 7 leave it), the right-hand side d_f, the solved
    weights d_w and, optionally, g = diag(K^-1) (gsl_sinterp_hip_chol_inv_diag) and kriging's b = K^-1 1, denom = 1^T b:
