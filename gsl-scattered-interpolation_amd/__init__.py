@@ -14,5 +14,5 @@ from . import capi, sharding  # noqa: F401
 from .capi import (  # noqa: F401
     GSL_SUCCESS, GSL_EDOM, GSL_EINVAL, GSL_EFAILED, GSL_EUNSUP, RBF_GAUSSIAN, RBF_TPS, RBF_WENDLAND,
     RBF_MATERN32, RBF_MATERN52, RBF_IMQ,
-    HipContext, SimplexMesh, SimplexTree, Sinterp, SinterpFit, FIT_LOO, FIT_ML, lib, library_path,
+    HipContext, SimplexMesh, SimplexTree, Sinterp, SinterpFit, FIT_LOO, FIT_ML, Variogram, lib, library_path,
 )

@@ -17,6 +17,8 @@ GSL_EMAXITER = 11
 RBF_GAUSSIAN, RBF_TPS, RBF_WENDLAND = 0, 1, 2
 RBF_MATERN32, RBF_MATERN52, RBF_IMQ = 3, 4, 5
 FIT_LOO, FIT_ML = 0, 1
+VARIOGRAM_MATHERON, VARIOGRAM_CRESSIE = 0, 1
+VARIOGRAM_W_COUNT, VARIOGRAM_W_COUNT_H2, VARIOGRAM_W_NONE = 0, 1, 2
 SOLVER_DEFAULT, SOLVER_CHOLESKY2, SOLVER_PCHOLESKY, SOLVER_LU_REFINE = 0, 1, 2, 3
 TREE_DEFAULT, TREE_NOSTANDARDIZE, TREE_ISOSCALE = 0, 1, 2
 TREE_RECORD_BYTES, TREE_LEAFTAB_BYTES = 64, 32
@@ -348,6 +350,21 @@ SIGNATURES = {
     "gsl_sinterp_fit_n_eval": (_sz, [_vp]),
     "gsl_sinterp_fit_trace": (_i, [_vp, _pv, _pv]),
     "gsl_sinterp_fit_sigma2": (_i, [_vp, _pd]),
+    "gsl_sinterp_hip_variogram": (_i, [_vp, _vp, _sz, _i, _sz, _vp, _d, _i, C.POINTER(C.c_uint64), _pi]),
+    "gsl_sinterp_hip_variogram_pairs_tested": (C.c_uint64, [_vp]),
+    "gsl_sinterp_hip_bbox": (_i, [_vp, _vp, _sz, _i, _sz, _pd]),
+    "gsl_sinterp_variogram_alloc": (_vp, [_sz, _sz]),
+    "gsl_sinterp_variogram_set_device": (_i, [_vp, _i]),
+    "gsl_sinterp_variogram_compute": (_i, [_vp, _pm, _pv, _d]),
+    "gsl_sinterp_variogram_compute_resident": (_i, [_vp, _vp, _sz, _sz, _vp, _d]),
+    "gsl_sinterp_variogram_get": (_i, [_vp, _i, _pv, _pv, _pv]),
+    "gsl_sinterp_variogram_h_max": (_d, [_vp]),
+    "gsl_sinterp_variogram_fit": (_i, [_vp, _vp, _i, _i, _d, _d, _pd, _pd, _pd, _pd]),
+    "gsl_sinterp_variogram_apply": (_i, [_vp, C.POINTER(gsl_sinterp)]),
+    "gsl_sinterp_variogram_free": (None, [_vp]),
+    "gsl_sinterp_variogram_fit_model": (_i, [_i, _i, _pd, _pd, _pd, _sz, _d, _d, _sz, _d, _sz, _pd, _pd, _pd, _pd]),
+    "gsl_sinterp_variogram_fit_model_n_eval": (_sz, []),
+    "gsl_sinterp_variogram_fit_model_trace": (_i, [_pv, _pv]),
     "gsl_sinterp_eval_grad_e": (_i, [C.POINTER(gsl_sinterp), _pv, _pd, _pv]),
     "gsl_sinterp_eval_grad_many": (_i, [C.POINTER(gsl_sinterp), _pm, _pv, _pm]),
     "gsl_sinterp_eval_grad_resident": (_i, [C.POINTER(gsl_sinterp), _vp, _sz, _sz, _vp, _vp, _sz]),
@@ -833,6 +850,24 @@ class HipContext:
 
     def local_pack(self, d_x, n, dim, xtda, d_f=None, model_id=0):
         return lib().gsl_sinterp_hip_local_pack(self._h, d_x, n, dim, xtda, d_f, model_id)
+
+    def variogram(self, d_x, n, dim, xtda, d_f, h_max, n_bins):
+        """(status, acc [n_bins x 7] uint64, shift [3]): the binned pair sums as exact integers"""
+        acc = np.full((max(n_bins, 0), 7), 0xFFFFFFFFFFFFFFFF, dtype=np.uint64)
+        shift = (C.c_int * 3)(-1, -1, -1)
+        st = lib().gsl_sinterp_hip_variogram(self._h, d_x, n, dim, xtda, d_f, h_max, n_bins,
+                                             acc.ctypes.data_as(C.POINTER(C.c_uint64)), shift)
+        return st, acc, [int(s) for s in shift]
+
+    def variogram_pairs_tested(self):
+        """unordered pairs whose r2 the last variogram call on this context computed"""
+        return int(lib().gsl_sinterp_hip_variogram_pairs_tested(self._h))
+
+    def bbox(self, d_x, n, dim, xtda):
+        """(status, box [dim x 2]): min and max of every coordinate"""
+        box = np.full((dim, 2), np.nan)
+        st = lib().gsl_sinterp_hip_bbox(self._h, d_x, n, dim, xtda, box.ctypes.data_as(_pd))
+        return st, box
 
     def local_pack_count(self):
         """how often this context has binned a set of centres for knn / local_krige"""
@@ -1720,6 +1755,85 @@ class SinterpFit:
     def close(self):
         if self._h:
             lib().gsl_sinterp_fit_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+# ------------------------------------------------------------------ empirical variogram
+def variogram_fit_model(kind, weights, lag, gamma, count, eps_lo, eps_hi, n_grid=0, tol=0.0, max_eval=0):
+    """gsl_sinterp_variogram_fit_model on host arrays (no device): (status, eps, c0, c, wss); 0 selects a search default"""
+    lag, gamma, count = (None if a is None else np.ascontiguousarray(a, dtype=np.float64) for a in (lag, gamma, count))
+    out = [C.c_double(0) for _ in range(4)]
+    st = lib().gsl_sinterp_variogram_fit_model(kind, weights, *(None if a is None else a.ctypes.data_as(_pd) for a in (lag, gamma, count)),
+                                               0 if lag is None else lag.shape[0], eps_lo, eps_hi, n_grid, tol, max_eval,
+                                               *(C.byref(o) for o in out))
+    return (st, *(o.value for o in out))
+
+
+def variogram_fit_model_trace():
+    """(status, eps, wss): the evaluations of the last variogram_fit_model call, in order"""
+    k = int(lib().gsl_sinterp_variogram_fit_model_n_eval())
+    p, v = np.full(k, np.nan), np.full(k, np.nan)
+    st = lib().gsl_sinterp_variogram_fit_model_trace(C.byref(as_vector(p)), C.byref(as_vector(v)))
+    return st, p, v
+
+
+class Variogram:
+    """gsl_sinterp_variogram: the empirical semivariogram of (x, f) as exact binned pair sums from the device, the
+    covariance model fitted to it on the host, and its transfer to a kriging interpolant.  Raises GslError with the status
+    of gsl_sinterp_variogram_alloc when no workspace comes back."""
+    MATHERON, CRESSIE = VARIOGRAM_MATHERON, VARIOGRAM_CRESSIE
+    W_COUNT, W_COUNT_H2, W_NONE = VARIOGRAM_W_COUNT, VARIOGRAM_W_COUNT_H2, VARIOGRAM_W_NONE
+
+    def __init__(self, dim, n_bins, device=None):
+        self._h = None
+        with ErrorCalls() as calls:
+            h = lib().gsl_sinterp_variogram_alloc(dim, n_bins)
+        if not h:
+            raise GslError(calls[-1][1] if calls else GSL_FAILURE, calls[-1][0] if calls else "gsl_sinterp_variogram_alloc")
+        self._h = C.c_void_p(h)
+        self.n_bins = n_bins
+        if device is not None:
+            lib().gsl_sinterp_variogram_set_device(self._h, device)
+
+    def set_device(self, device):
+        return lib().gsl_sinterp_variogram_set_device(self._h, device)
+
+    def compute(self, x, f, h_max=0.0):
+        return lib().gsl_sinterp_variogram_compute(self._h, C.byref(as_matrix(x)) if x is not None else None,
+                                                   C.byref(as_vector(f)) if f is not None else None, h_max)
+
+    def compute_resident(self, d_x, n, xtda, d_f, h_max=0.0):
+        return lib().gsl_sinterp_variogram_compute_resident(self._h, d_x, n, xtda, d_f, h_max)
+
+    def h_max(self):
+        return lib().gsl_sinterp_variogram_h_max(self._h)
+
+    def get(self, estimator=VARIOGRAM_MATHERON):
+        """(status, lag, gamma, count); an empty bin has NaN, NaN, 0"""
+        lag, gamma, count = (np.full(self.n_bins, np.nan) for _ in range(3))
+        st = lib().gsl_sinterp_variogram_get(self._h, estimator, C.byref(as_vector(lag)), C.byref(as_vector(gamma)), C.byref(as_vector(count)))
+        return st, lag, gamma, count
+
+    def fit(self, kind, estimator=VARIOGRAM_MATHERON, weights=VARIOGRAM_W_COUNT_H2, eps_lo=0.0, eps_hi=0.0):
+        """(status, eps, nugget = c0 / c, sigma2 = c, wss) for the kriging type named `kind` as in Sinterp.TYPES"""
+        T = _ptr(Sinterp.TYPES[kind] if kind in Sinterp.TYPES else Sinterp.MORE_TYPES[kind]) if kind is not None else None
+        out = [C.c_double(0) for _ in range(4)]
+        st = lib().gsl_sinterp_variogram_fit(self._h, T, estimator, weights, eps_lo, eps_hi, *(C.byref(o) for o in out))
+        return (st, *(o.value for o in out))
+
+    def apply(self, interp):
+        """set_shape + set_nugget of the last fit on a Sinterp"""
+        return lib().gsl_sinterp_variogram_apply(self._h, interp._p if interp is not None else None)
+
+    def close(self):
+        if self._h:
+            lib().gsl_sinterp_variogram_free(self._h)
             self._h = None
 
     def __del__(self):

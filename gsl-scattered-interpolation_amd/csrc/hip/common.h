@@ -97,6 +97,7 @@ struct gsl_sinterp_hip_ctx {
   CentKey shep_key;
   int shep_g;
   unsigned long long shep_packs, shep_fits;
+  unsigned long long vg_pairs_tested;   /* variogram.hip: unordered pairs whose r2 the last call computed */
 };
 
 /* A cached pack (local.hip, shepard.hip) is reused when the caller vouches for the model (id != 0) and every word that

@@ -2828,6 +2828,393 @@ int gsl_sinterp_fit_sigma2(const gsl_sinterp_fit_workspace *w, double *s2)
   return GSL_SUCCESS;
 }
 
+/* ------------------------------------------------------------------------ */
+/* Empirical variogram and the covariance model fitted to it (DESIGN_VARIOGRAM.md): the binned pair sums come from
+   gsl_sinterp_hip_variogram as exact integers; everything below them is host arithmetic on n_bins numbers. */
+
+/* 1 - phi_kind(eps h), phi as include/gsl_sinterp_hip.h defines the three covariances */
+static double vario_rise(int kind, double eps, double h)
+{
+  if (kind == GSL_SINTERP_RBF_GAUSSIAN) { const double t = eps * h; return 1.0 - exp(-(t * t)); }
+  if (kind == GSL_SINTERP_RBF_MATERN32) { const double t = sqrt(3.0) * eps * h; return 1.0 - (1.0 + t) * exp(-t); }
+  const double t = sqrt(5.0) * eps * h;
+  return 1.0 - (1.0 + t + t * t / 3.0) * exp(-t);
+}
+
+typedef struct {
+  int kind;
+  size_t m;                                            /* usable bins */
+  const double *h, *y, *w;                             /* their lags, semivariances and weights */
+} vario_problem;
+
+static double vario_wss(const vario_problem *p, double eps, double c0, double c)
+{
+  double s = 0.0;
+  for (size_t b = 0; b < p->m; b++) {
+    const double r = p->y[b] - c0 - c * vario_rise(p->kind, eps, p->h[b]);
+    s += p->w[b] * r * r;
+  }
+  return s;
+}
+
+/* gamma = c0 + c g(eps) by weighted least squares with c0 >= 0 and c >= 0: both free first; when a coefficient comes out
+   negative (or the two columns are dependent) the better of the two one-column fits, the nugget-only one on a tie */
+static double vario_wls(const vario_problem *p, double eps, double *c0_out, double *c_out)
+{
+  double sw = 0.0, sg = 0.0, sgg = 0.0, sy = 0.0, sgy = 0.0;
+  for (size_t b = 0; b < p->m; b++) {
+    const double g = vario_rise(p->kind, eps, p->h[b]), w = p->w[b];
+    sw += w; sg += w * g; sgg += w * g * g; sy += w * p->y[b]; sgy += w * g * p->y[b];
+  }
+  const double det = sw * sgg - sg * sg;
+  if (det > 0.0) {
+    const double c = (sw * sgy - sg * sy) / det, c0 = (sy - c * sg) / sw;
+    if (c0 >= 0.0 && c >= 0.0) { *c0_out = c0; *c_out = c; return vario_wss(p, eps, c0, c); }
+  }
+  double a0 = sy / sw, a1 = sgg > 0.0 ? sgy / sgg : 0.0;
+  if (!(a0 > 0.0)) a0 = 0.0;
+  if (!(a1 > 0.0)) a1 = 0.0;
+  const double w0 = vario_wss(p, eps, a0, 0.0), w1 = vario_wss(p, eps, 0.0, a1);
+  if (w1 < w0) { *c0_out = 0.0; *c_out = a1; return w1; }
+  *c0_out = a0; *c_out = 0.0;
+  return w0;
+}
+
+/* the evaluations of the last gsl_sinterp_variogram_fit_model in order (the facade is single-threaded) */
+static struct { size_t n, cap; double *eps, *wss; } vario_trace;
+
+/* The fixed search rule of fit_search over t = log eps, on the weighted sum of squares of vario_wls: n_grid points from lo to
+   hi with the ends included, golden section on the two cells around the first smallest grid value, until the bracket is no
+   wider than tol or max_eval evaluations are spent; the best point ever evaluated wins. */
+static int vario_search(const vario_problem *p, double lo, double hi, size_t n_grid, double tol, size_t max_eval, double *eps_best,
+                        double *c0_best, double *c_best, double *wss_best)
+{
+  if (max_eval > vario_trace.cap) {
+    double *a = (double *)malloc(max_eval * sizeof(double)), *b = (double *)malloc(max_eval * sizeof(double));
+    if (!a || !b) { free(a); free(b); return GSL_ENOMEM; }
+    free(vario_trace.eps); free(vario_trace.wss);
+    vario_trace.eps = a; vario_trace.wss = b; vario_trace.cap = max_eval;
+  }
+  vario_trace.n = 0;
+  const double tlo = log(lo), thi = log(hi);
+  double s_best = INFINITY;
+#define VARIO_EVAL(t, pp, dst)                                                                    \
+  do {                                                                                            \
+    (dst) = INFINITY;                                                                             \
+    if (vario_trace.n < max_eval) {                                                               \
+      const double _p = (pp) != 0.0 ? (pp) : exp(t);                                              \
+      double _c0, _c;                                                                             \
+      const double _v = vario_wls(p, _p, &_c0, &_c);                                              \
+      vario_trace.eps[vario_trace.n] = _p; vario_trace.wss[vario_trace.n] = _v; vario_trace.n++;  \
+      if (_v < s_best) { s_best = _v; *eps_best = _p; *c0_best = _c0; *c_best = _c; }             \
+      (dst) = _v;                                                                                 \
+    }                                                                                             \
+  } while (0)
+  size_t k = 0;
+  double g_best = INFINITY;
+  for (size_t j = 0; j < n_grid; j++) {
+    const double t = tlo + (thi - tlo) * ((double)j / (double)(n_grid - 1));
+    double v;
+    VARIO_EVAL(t, j == 0 ? lo : j == n_grid - 1 ? hi : 0.0, v);
+    if (v < g_best) { g_best = v; k = j; }
+  }
+  if (isfinite(g_best)) {
+    const size_t ka = k > 0 ? k - 1 : 0, kb = k + 1 < n_grid ? k + 1 : k;
+    double a = tlo + (thi - tlo) * ((double)ka / (double)(n_grid - 1)), b = tlo + (thi - tlo) * ((double)kb / (double)(n_grid - 1));
+    const double r = 0.6180339887498949;               /* (sqrt 5 - 1) / 2 */
+    double cpt = b - r * (b - a), dpt = a + r * (b - a), fc, fd;
+    VARIO_EVAL(cpt, 0.0, fc);
+    VARIO_EVAL(dpt, 0.0, fd);
+    while (b - a > tol && vario_trace.n < max_eval) {
+      if (fc <= fd) {
+        b = dpt; dpt = cpt; fd = fc; cpt = b - r * (b - a);
+        if (b - a > tol) VARIO_EVAL(cpt, 0.0, fc);
+      } else {
+        a = cpt; cpt = dpt; fc = fd; dpt = a + r * (b - a);
+        if (b - a > tol) VARIO_EVAL(dpt, 0.0, fd);
+      }
+    }
+  }
+#undef VARIO_EVAL
+  *wss_best = s_best;
+  return isfinite(s_best) ? GSL_SUCCESS : GSL_EDOM;
+}
+
+int gsl_sinterp_variogram_fit_model(int kind, int weights, const double *lag, const double *gamma, const double *count, size_t n_bins,
+                                    double eps_lo, double eps_hi, size_t n_grid, double tol, size_t max_eval, double *eps, double *nugget_abs,
+                                    double *psill, double *wss)
+{
+  if (eps) *eps = GSL_NAN;
+  if (nugget_abs) *nugget_abs = GSL_NAN;
+  if (psill) *psill = GSL_NAN;
+  if (wss) *wss = GSL_NAN;
+  vario_trace.n = 0;
+  /* the numbers first */
+  if (kind != GSL_SINTERP_RBF_GAUSSIAN && kind != GSL_SINTERP_RBF_MATERN32 && kind != GSL_SINTERP_RBF_MATERN52)
+    GSL_ERROR("gsl_sinterp_variogram_fit_model: the kind must be a kriging covariance (Gaussian, Matern 3/2, Matern 5/2)", GSL_EINVAL);
+  if (weights != GSL_SINTERP_VARIOGRAM_W_COUNT && weights != GSL_SINTERP_VARIOGRAM_W_COUNT_H2 && weights != GSL_SINTERP_VARIOGRAM_W_NONE)
+    GSL_ERROR("gsl_sinterp_variogram_fit_model: unknown weights", GSL_EINVAL);
+  if (n_grid == 0) n_grid = 9;
+  if (tol == 0.0) tol = 1e-2;
+  if (max_eval == 0) max_eval = 40;
+  if (n_grid < 3 || !(tol > 0.0) || max_eval < n_grid)
+    GSL_ERROR("gsl_sinterp_variogram_fit_model: needs n_grid >= 3, tol > 0, max_eval >= n_grid (0 = the defaults 9, 1e-2, 40)", GSL_EINVAL);
+  if (!(eps_lo > 0.0) || !(eps_hi > eps_lo) || !isfinite(eps_hi))
+    GSL_ERROR("gsl_sinterp_variogram_fit_model: the bracket needs 0 < eps_lo < eps_hi < infinity", GSL_EINVAL);
+  if (!lag || !gamma || !count || !eps || !nugget_abs || !psill) GSL_ERROR("gsl_sinterp_variogram_fit_model: null argument", GSL_EFAULT);
+  double *buf = (double *)malloc((n_bins ? n_bins : 1) * 3 * sizeof(double));
+  if (!buf) GSL_ERROR("gsl_sinterp_variogram_fit_model: out of memory", GSL_ENOMEM);
+  double *h = buf, *y = buf + n_bins, *w = buf + 2 * n_bins;
+  size_t m = 0;
+  for (size_t b = 0; b < n_bins; b++) {
+    if (!(count[b] > 0.0) || !isfinite(count[b]) || !isfinite(gamma[b]) || !isfinite(lag[b]) || lag[b] < 0.0) continue;
+    if (weights == GSL_SINTERP_VARIOGRAM_W_COUNT_H2 && !(lag[b] > 0.0)) continue;    /* a bin of coincident sites has no finite N / h^2 */
+    h[m] = lag[b]; y[m] = gamma[b];
+    w[m] = weights == GSL_SINTERP_VARIOGRAM_W_COUNT ? count[b] : weights == GSL_SINTERP_VARIOGRAM_W_COUNT_H2 ? count[b] / (lag[b] * lag[b]) : 1.0;
+    m++;
+  }
+  if (m < 3) {
+    free(buf);
+    GSL_ERROR("gsl_sinterp_variogram_fit_model: fewer than 3 usable bins", GSL_EDOM);
+  }
+  const vario_problem p = {kind, m, h, y, w};
+  double e = GSL_NAN, c0 = GSL_NAN, c = GSL_NAN, s = GSL_NAN;
+  const int st = vario_search(&p, eps_lo, eps_hi, n_grid, tol, max_eval, &e, &c0, &c, &s);
+  free(buf);
+  if (st == GSL_ENOMEM) GSL_ERROR("gsl_sinterp_variogram_fit_model: out of memory", GSL_ENOMEM);
+  if (st) GSL_ERROR("gsl_sinterp_variogram_fit_model: no candidate in the bracket has a finite sum of squares", GSL_EDOM);
+  *eps = e; *nugget_abs = c0; *psill = c;
+  if (wss) *wss = s;
+  return GSL_SUCCESS;
+}
+
+size_t gsl_sinterp_variogram_fit_model_n_eval(void) { return vario_trace.n; }
+
+int gsl_sinterp_variogram_fit_model_trace(gsl_vector *eps, gsl_vector *wss)
+{
+  if (!eps || !wss) GSL_ERROR("gsl_sinterp_variogram_fit_model_trace: null argument", GSL_EFAULT);
+  if (eps->size != vario_trace.n || wss->size != vario_trace.n)
+    GSL_ERROR("gsl_sinterp_variogram_fit_model_trace: the vectors need gsl_sinterp_variogram_fit_model_n_eval entries", GSL_EBADLEN);
+  for (size_t i = 0; i < vario_trace.n; i++) {
+    eps->data[i * eps->stride] = vario_trace.eps[i];
+    wss->data[i * wss->stride] = vario_trace.wss[i];
+  }
+  return GSL_SUCCESS;
+}
+
+struct gsl_sinterp_variogram {
+  size_t dim, n_bins;
+  int device;
+  gsl_sinterp_hip_ctx *ctx;                            /* created by the first compute */
+  double *d_stage; size_t stage_cap;                   /* grow-only [x | f] of gsl_sinterp_variogram_compute */
+  int have;                                            /* a variogram is held */
+  double h_max;
+  int shift[3];
+  unsigned long long *acc;                             /* n_bins x 7 */
+  const gsl_sinterp_type *fit_type;                    /* the last successful fit, NULL before one */
+  double fit_eps, fit_nugget;
+};
+
+gsl_sinterp_variogram *gsl_sinterp_variogram_alloc(size_t dim, size_t n_bins)
+{
+  if (dim < 1 || dim > 3) GSL_ERROR_NULL("gsl_sinterp_variogram_alloc: dim must be 1, 2 or 3", GSL_EINVAL);
+  if (n_bins < 1 || n_bins > 256) GSL_ERROR_NULL("gsl_sinterp_variogram_alloc: 1 .. 256 bins", GSL_EINVAL);
+  gsl_sinterp_variogram *v = (gsl_sinterp_variogram *)calloc(1, sizeof *v);
+  unsigned long long *acc = (unsigned long long *)calloc(n_bins * 7, sizeof *acc);
+  if (!v || !acc) {
+    free(v); free(acc);
+    GSL_ERROR_NULL("gsl_sinterp_variogram_alloc: out of memory", GSL_ENOMEM);
+  }
+  v->dim = dim; v->n_bins = n_bins; v->device = default_device(); v->acc = acc; v->h_max = GSL_NAN;
+  return v;
+}
+
+void gsl_sinterp_variogram_free(gsl_sinterp_variogram *v)
+{
+  if (!v) return;
+  if (v->ctx) {
+    gsl_sinterp_hip_free(v->ctx, v->d_stage);
+    gsl_sinterp_hip_ctx_destroy(v->ctx);
+  }
+  free(v->acc);
+  free(v);
+}
+
+int gsl_sinterp_variogram_set_device(gsl_sinterp_variogram *v, int device)
+{
+  if (!v) GSL_ERROR("gsl_sinterp_variogram_set_device: null workspace", GSL_EFAULT);
+  if (device < 0) GSL_ERROR("gsl_sinterp_variogram_set_device: negative ordinal", GSL_EINVAL);
+  if (v->ctx && device != v->device) {                 /* the context and its staging buffer belong to the old device */
+    gsl_sinterp_hip_free(v->ctx, v->d_stage);
+    gsl_sinterp_hip_ctx_destroy(v->ctx);
+    v->ctx = NULL; v->d_stage = NULL; v->stage_cap = 0;
+  }
+  v->device = device;
+  return GSL_SUCCESS;
+}
+
+double gsl_sinterp_variogram_h_max(const gsl_sinterp_variogram *v) { return v && v->have ? v->h_max : GSL_NAN; }
+
+/* what every compute does first: the workspace loses its variogram and its fit */
+static void vario_drop(gsl_sinterp_variogram *v)
+{
+  v->have = 0; v->h_max = GSL_NAN; v->fit_type = NULL;
+  memset(v->acc, 0, v->n_bins * 7 * sizeof *v->acc);
+}
+
+static int vario_ctx(gsl_sinterp_variogram *v)
+{
+  if (v->ctx) return GSL_SUCCESS;
+  if (gsl_sinterp_hip_ctx_create(&v->ctx, v->device, NULL) != GSL_SUCCESS) {
+    v->ctx = NULL;
+    GSL_ERROR("gsl_sinterp_variogram_compute: no usable HIP device (GPU path has no CPU fallback)", GSL_EFAILED);
+  }
+  return GSL_SUCCESS;
+}
+
+int gsl_sinterp_variogram_compute_resident(gsl_sinterp_variogram *v, const double *d_x, size_t n, size_t xtda, const double *d_f, double h_max)
+{
+  if (!v) GSL_ERROR("gsl_sinterp_variogram_compute_resident: null workspace", GSL_EFAULT);
+  vario_drop(v);
+  if (n > 0 && (!d_x || !d_f)) GSL_ERROR("gsl_sinterp_variogram_compute_resident: null argument", GSL_EFAULT);
+  if (xtda < v->dim) GSL_ERROR("gsl_sinterp_variogram_compute_resident: rows shorter than the dimension", GSL_EBADLEN);
+  if (!isfinite(h_max)) GSL_ERROR("gsl_sinterp_variogram_compute_resident: h_max must be finite (<= 0 selects a third of the box diagonal)", GSL_EINVAL);
+  if (n > 0x7fffffffULL) GSL_ERROR("gsl_sinterp_variogram_compute_resident: at most 2^31 - 1 sites", GSL_EINVAL);
+  const int st0 = vario_ctx(v);
+  if (st0) return st0;
+  if (!(h_max > 0.0)) {                                /* gstat's default: a third of the diagonal of the bounding box */
+    double box[6], d2 = 0.0;
+    if (n < 2) GSL_ERROR("gsl_sinterp_variogram_compute: the default h_max needs at least two sites", GSL_EDOM);
+    HIP_TRY(gsl_sinterp_hip_bbox(v->ctx, d_x, n, (int)v->dim, xtda, box), v->ctx);
+    for (size_t c = 0; c < v->dim; c++) { const double e = box[2 * c + 1] - box[2 * c]; d2 += e * e; }
+    h_max = sqrt(d2) / 3.0;
+    if (!(h_max > 0.0) || !isfinite(h_max))
+      GSL_ERROR("gsl_sinterp_variogram_compute: the default h_max needs finite sites that do not all coincide", GSL_EDOM);
+  }
+  const int st = gsl_sinterp_hip_variogram(v->ctx, d_x, n, (int)v->dim, xtda, d_f, h_max, (int)v->n_bins, v->acc, v->shift);
+  if (st) {
+    memset(v->acc, 0, v->n_bins * 7 * sizeof *v->acc);
+    HIP_TRY(st, v->ctx);
+  }
+  v->have = 1; v->h_max = h_max;
+  return GSL_SUCCESS;
+}
+
+int gsl_sinterp_variogram_compute(gsl_sinterp_variogram *v, const gsl_matrix *x, const gsl_vector *f, double h_max)
+{
+  if (!v) GSL_ERROR("gsl_sinterp_variogram_compute: null workspace", GSL_EFAULT);
+  vario_drop(v);
+  if (!x || !f) GSL_ERROR("gsl_sinterp_variogram_compute: null argument", GSL_EFAULT);
+  if (x->size2 != v->dim) GSL_ERROR("gsl_sinterp_variogram_compute: x must be n x dim", GSL_EBADLEN);
+  if (f->size != x->size1) GSL_ERROR("gsl_sinterp_variogram_compute: f must have one entry per row of x", GSL_EBADLEN);
+  if (!isfinite(h_max)) GSL_ERROR("gsl_sinterp_variogram_compute: h_max must be finite (<= 0 selects a third of the box diagonal)", GSL_EINVAL);
+  if (x->size1 > 0x7fffffffULL) GSL_ERROR("gsl_sinterp_variogram_compute: at most 2^31 - 1 sites", GSL_EINVAL);
+  const size_t n = x->size1, dim = v->dim;
+  const int st0 = vario_ctx(v);
+  if (st0) return st0;
+  if (n == 0) return gsl_sinterp_variogram_compute_resident(v, NULL, 0, dim, NULL, h_max);
+  double *h = (double *)malloc(n * (dim + 1) * sizeof(double));                  /* [x | f] packed */
+  if (!h) GSL_ERROR("gsl_sinterp_variogram_compute: out of memory", GSL_ENOMEM);
+  for (size_t i = 0; i < n; i++) {
+    for (size_t a = 0; a < dim; a++) h[i * dim + a] = x->data[i * x->tda + a];
+    h[n * dim + i] = f->data[i * f->stride];
+  }
+  int s = GSL_SUCCESS;
+  if (n * (dim + 1) > v->stage_cap) {
+    gsl_sinterp_hip_free(v->ctx, v->d_stage);
+    v->d_stage = NULL; v->stage_cap = 0;
+    s = gsl_sinterp_hip_malloc(v->ctx, (void **)&v->d_stage, n * (dim + 1) * sizeof(double));
+    if (!s) v->stage_cap = n * (dim + 1);
+  }
+  if (!s) s = gsl_sinterp_hip_h2d(v->ctx, v->d_stage, h, n * (dim + 1) * sizeof(double));
+  free(h);
+  HIP_TRY(s, v->ctx);
+  return gsl_sinterp_variogram_compute_resident(v, v->d_stage, n, dim, v->d_stage + n * dim, h_max);
+}
+
+/* (hi 2^64 + lo) 2^-shift as a double: the integer is converted with one rounding, the scaling is exact */
+static double vario_sum(unsigned long long lo, unsigned long long hi, int shift)
+{
+  const unsigned __int128 s = ((unsigned __int128)hi << 64) | (unsigned __int128)lo;
+  return ldexp((double)s, -shift);
+}
+
+/* lag, semivariance and count of bin b (NaN, NaN, 0 for an empty bin) */
+static void vario_bin(const gsl_sinterp_variogram *v, int estimator, size_t b, double *lag, double *gamma, double *count)
+{
+  const unsigned long long *a = v->acc + 7 * b;
+  const double nb = (double)a[0];
+  *count = nb; *lag = GSL_NAN; *gamma = GSL_NAN;
+  if (a[0] == 0) return;
+  *lag = vario_sum(a[3], a[4], v->shift[1]) / nb;
+  if (estimator == GSL_SINTERP_VARIOGRAM_MATHERON) *gamma = vario_sum(a[1], a[2], v->shift[0]) / (2.0 * nb);
+  else {
+    const double m = vario_sum(a[5], a[6], v->shift[2]) / nb, m2 = m * m;
+    *gamma = 0.5 * (m2 * m2) / (0.457 + 0.494 / nb);
+  }
+}
+
+int gsl_sinterp_variogram_get(const gsl_sinterp_variogram *v, int estimator, gsl_vector *lag, gsl_vector *gamma, gsl_vector *count)
+{
+  if (!v) GSL_ERROR("gsl_sinterp_variogram_get: null workspace", GSL_EFAULT);
+  if (estimator != GSL_SINTERP_VARIOGRAM_MATHERON && estimator != GSL_SINTERP_VARIOGRAM_CRESSIE)
+    GSL_ERROR("gsl_sinterp_variogram_get: unknown estimator", GSL_EINVAL);
+  if (!v->have) GSL_ERROR("gsl_sinterp_variogram_get: no variogram computed", GSL_EINVAL);
+  if ((lag && lag->size != v->n_bins) || (gamma && gamma->size != v->n_bins) || (count && count->size != v->n_bins))
+    GSL_ERROR("gsl_sinterp_variogram_get: the vectors need n_bins entries", GSL_EBADLEN);
+  for (size_t b = 0; b < v->n_bins; b++) {
+    double l, g, c;
+    vario_bin(v, estimator, b, &l, &g, &c);
+    if (lag) lag->data[b * lag->stride] = l;
+    if (gamma) gamma->data[b * gamma->stride] = g;
+    if (count) count->data[b * count->stride] = c;
+  }
+  return GSL_SUCCESS;
+}
+
+int gsl_sinterp_variogram_fit(gsl_sinterp_variogram *v, const gsl_sinterp_type *T, int estimator, int weights, double eps_lo, double eps_hi,
+                              double *eps, double *nugget, double *sigma2, double *wss)
+{
+  if (eps) *eps = GSL_NAN;
+  if (nugget) *nugget = GSL_NAN;
+  if (sigma2) *sigma2 = GSL_NAN;
+  if (wss) *wss = GSL_NAN;
+  if (!v || !T || !eps || !nugget || !sigma2) GSL_ERROR("gsl_sinterp_variogram_fit: null argument", GSL_EFAULT);
+  v->fit_type = NULL;
+  const type_desc *d = desc_of(T);
+  if (!d) GSL_ERROR("gsl_sinterp_variogram_fit: not one of the gsl_sinterp types", GSL_EINVAL);
+  if (d->family != FAM_RBF) GSL_ERROR("gsl_sinterp_variogram_fit: mesh and Shepard types have no covariance model", GSL_EUNSUP);
+  if (!d->krige) GSL_ERROR("gsl_sinterp_variogram_fit: kriging types only (an RBF type takes no nugget)", GSL_EINVAL);
+  if (estimator != GSL_SINTERP_VARIOGRAM_MATHERON && estimator != GSL_SINTERP_VARIOGRAM_CRESSIE)
+    GSL_ERROR("gsl_sinterp_variogram_fit: unknown estimator", GSL_EINVAL);
+  if (weights != GSL_SINTERP_VARIOGRAM_W_COUNT && weights != GSL_SINTERP_VARIOGRAM_W_COUNT_H2 && weights != GSL_SINTERP_VARIOGRAM_W_NONE)
+    GSL_ERROR("gsl_sinterp_variogram_fit: unknown weights", GSL_EINVAL);
+  if (!v->have) GSL_ERROR("gsl_sinterp_variogram_fit: no variogram computed", GSL_EINVAL);
+  if (!(eps_lo > 0.0)) { eps_lo = 0.1 / v->h_max; eps_hi = 100.0 / v->h_max; }
+  double *buf = (double *)malloc(v->n_bins * 3 * sizeof(double));
+  if (!buf) GSL_ERROR("gsl_sinterp_variogram_fit: out of memory", GSL_ENOMEM);
+  double *lag = buf, *gam = buf + v->n_bins, *cnt = buf + 2 * v->n_bins;
+  for (size_t b = 0; b < v->n_bins; b++) vario_bin(v, estimator, b, lag + b, gam + b, cnt + b);
+  double e, c0, c, s;
+  const int st = gsl_sinterp_variogram_fit_model(d->kind, weights, lag, gam, cnt, v->n_bins, eps_lo, eps_hi, 0, 0.0, 0, &e, &c0, &c, &s);
+  free(buf);
+  if (st) return st;                                   /* the handler has been called */
+  if (!(c > 0.0)) GSL_ERROR("gsl_sinterp_variogram_fit: the fitted model is a pure nugget (c = 0): the relative nugget does not exist", GSL_EDOM);
+  *eps = e; *nugget = c0 / c; *sigma2 = c;
+  if (wss) *wss = s;
+  v->fit_type = T; v->fit_eps = e; v->fit_nugget = c0 / c;
+  return GSL_SUCCESS;
+}
+
+int gsl_sinterp_variogram_apply(const gsl_sinterp_variogram *v, gsl_sinterp *interp)
+{
+  if (!v || !interp) GSL_ERROR("gsl_sinterp_variogram_apply: null argument", GSL_EFAULT);
+  if (!v->fit_type) GSL_ERROR("gsl_sinterp_variogram_apply: no successful fit yet", GSL_EINVAL);
+  if (interp->type != v->fit_type) GSL_ERROR("gsl_sinterp_variogram_apply: the interpolant is of another type than the one fitted", GSL_EINVAL);
+  const int st = gsl_sinterp_set_shape(interp, v->fit_eps);
+  return st ? st : gsl_sinterp_set_nugget(interp, v->fit_nugget);
+}
+
 /* whether variances can be evaluated, as a status (the table of include/gsl_sinterp.h) */
 static int variance_status(const gsl_sinterp *interp)
 {

@@ -659,6 +659,69 @@ int    gsl_sinterp_fit_set_search(gsl_sinterp_fit_workspace *w, size_t n_grid, d
 size_t gsl_sinterp_fit_n_eval(const gsl_sinterp_fit_workspace *w);           /* evaluations of the last search */
 int    gsl_sinterp_fit_trace(const gsl_sinterp_fit_workspace *w, gsl_vector *param, gsl_vector *score);  /* in order of evaluation */
 int    gsl_sinterp_fit_sigma2(const gsl_sinterp_fit_workspace *w, double *s2); /* f.w / N of the last successful score */
+/* Empirical semivariogram and the covariance model fitted to it: the first step of a kriging study, and the one estimator of
+   eps, the nugget and the process variance that never forms a matrix -- memory O(N + bins), work proportional to the pairs
+   closer than h_max -- so it runs on the whole cloud that gsl_sinterp_set_neighbours is for, where gsl_sinterp_fit_* needs a
+   subsample.  GSL's workspace idiom:
+     v = gsl_sinterp_variogram_alloc(dim, n_bins);  gsl_sinterp_variogram_compute(v, x, f, 0.0);
+     gsl_sinterp_variogram_fit(v, gsl_sinterp_kriging_matern32, MATHERON, W_COUNT_H2, 0, 0, &eps, &nugget, &sigma2, NULL);
+     gsl_sinterp_variogram_apply(v, interp);  gsl_sinterp_set_neighbours(interp, 32);  gsl_sinterp_init(interp, x, f);
+   and sigma2 is what gsl_sinterp_simulate_* takes.
+   compute / compute_resident: the binned pair sums of gsl_sinterp_hip_variogram (exact integers: the same bits for every row
+   order and every run) of the n sites, n_bins equal bins on [0, h_max).  h_max <= 0 selects a third of the diagonal of the
+   sites' bounding box (gstat's default); gsl_sinterp_variogram_h_max returns the value in force (NaN without a variogram).
+   get: lag_b = sum h / N_b, count_b = N_b and
+     GSL_SINTERP_VARIOGRAM_MATHERON  gamma_b = sum (f_i - f_j)^2 / (2 N_b);
+     GSL_SINTERP_VARIOGRAM_CRESSIE   gamma_b = (1/2) (sum sqrt|f_i - f_j| / N_b)^4 / (0.457 + 0.494 / N_b)   (Cressie-Hawkins);
+   every 128-bit sum is converted to a double with one rounding; an empty bin gives NaN, NaN, 0; any output may be NULL.
+   fit_model (host arrays, no device): gamma(h) = c0 + c (1 - phi_kind(eps h)) with phi as gsl_sinterp_hip.h defines
+   GSL_SINTERP_RBF_GAUSSIAN, _MATERN32 and _MATERN52 (any other kind: GSL_EINVAL).  Bins with count 0, a non-finite gamma or
+   lag (and, under W_COUNT_H2, lag 0) are skipped; fewer than 3 usable bins: GSL_EDOM.  Weights N_b (W_COUNT), N_b / lag_b^2
+   (W_COUNT_H2, gstat's default) or 1 (W_NONE).  For a fixed eps the model is linear: weighted least squares over (c0, c) with
+   c0 >= 0 and c >= 0 (both free first; if a coefficient comes out negative, the better of the two one-column fits).  Over
+   eps THE SEARCH of gsl_sinterp_fit_shape on the weighted sum of squares: t = log eps, n_grid points from eps_lo to eps_hi
+   with the ends included, golden section on the two cells around the first smallest grid value until the bracket is no
+   wider than tol or max_eval evaluations are spent, the best point ever evaluated wins.  0 selects the defaults 9, 1e-2, 40;
+   GSL_EINVAL for n_grid < 3, tol not > 0, max_eval < n_grid, eps_lo <= 0, eps_hi <= eps_lo or not finite -- the numbers are
+   judged before the pointers (GSL_EFAULT; wss may be NULL).  *wss: the weighted sum of squares at the answer.  A fitted
+   c = 0 (pure nugget) is returned as such.  fit_model_n_eval / fit_model_trace: the evaluations of the last fit_model call
+   of the process in order (GSL_EBADLEN unless both vectors have n_eval entries).
+   fit: fit_model on get's arrays with the default search, for one of the three kriging types (an RBF type takes no nugget:
+   GSL_EINVAL; mesh, tree and Shepard types: GSL_EUNSUP).  eps_lo <= 0 selects the bracket 0.1 / h_max .. 100 / h_max.
+   *nugget = c0 / c, the library's relative nugget, *sigma2 = c.  A fitted c = 0 is GSL_EDOM with NaN outputs: the relative
+   nugget does not exist.  GSL_EINVAL without a variogram.
+   apply: gsl_sinterp_set_shape + gsl_sinterp_set_nugget with the last successful fit; GSL_EINVAL before one and for an
+   interpolant of another type than the one fitted.  It calls the setters only, so the interpolant may then take
+   gsl_sinterp_set_neighbours, a drift, a device list.
+   STATUS: GSL_EFAULT a NULL argument; GSL_EBADLEN x not n x dim, f not n long, xtda < dim, a vector of get that is not n_bins
+   long; GSL_EINVAL alloc with dim outside 1 .. 3 or n_bins outside 1 .. 256 (NULL returned), h_max NaN or infinite, an unknown
+   estimator or weights, more than 2^31 - 1 sites; all through the handler and decided before anything touches a device.
+   GSL_EDOM: a NaN or infinite site or response; the default h_max with fewer than 2 sites or sites that all coincide.
+   GSL_EFAILED: no device.  A compute that fails leaves the workspace without a variogram (and every compute drops the
+   fit).  The workspace owns a context on its device (set_device; default as gsl_sinterp_alloc), created by the first compute.
+   Not provided: directional or anisotropic variograms, several responses, the variogram cloud, nested models, a residual
+   variogram for universal kriging (pass the residuals as f), subsampling of the pairs, sharding over a device group. */
+#define GSL_SINTERP_VARIOGRAM_MATHERON 0
+#define GSL_SINTERP_VARIOGRAM_CRESSIE  1
+#define GSL_SINTERP_VARIOGRAM_W_COUNT    0   /* N_b            */
+#define GSL_SINTERP_VARIOGRAM_W_COUNT_H2 1   /* N_b / lag_b^2  */
+#define GSL_SINTERP_VARIOGRAM_W_NONE     2   /* 1              */
+typedef struct gsl_sinterp_variogram gsl_sinterp_variogram;
+gsl_sinterp_variogram *gsl_sinterp_variogram_alloc(size_t dim, size_t n_bins);          /* dim 1..3, n_bins 1..256 */
+int    gsl_sinterp_variogram_set_device(gsl_sinterp_variogram *v, int device);
+int    gsl_sinterp_variogram_compute(gsl_sinterp_variogram *v, const gsl_matrix *x, const gsl_vector *f, double h_max);
+int    gsl_sinterp_variogram_compute_resident(gsl_sinterp_variogram *v, const double *d_x, size_t n, size_t xtda, const double *d_f, double h_max);
+int    gsl_sinterp_variogram_get(const gsl_sinterp_variogram *v, int estimator, gsl_vector *lag, gsl_vector *gamma, gsl_vector *count);
+double gsl_sinterp_variogram_h_max(const gsl_sinterp_variogram *v);
+int    gsl_sinterp_variogram_fit(gsl_sinterp_variogram *v, const gsl_sinterp_type *T, int estimator, int weights, double eps_lo, double eps_hi,
+                                 double *eps, double *nugget /* c0 / c */, double *sigma2 /* c */, double *wss /* or NULL */);
+int    gsl_sinterp_variogram_apply(const gsl_sinterp_variogram *v, gsl_sinterp *interp);
+void   gsl_sinterp_variogram_free(gsl_sinterp_variogram *v);
+int    gsl_sinterp_variogram_fit_model(int kind, int weights, const double *lag, const double *gamma, const double *count, size_t n_bins,
+                                       double eps_lo, double eps_hi, size_t n_grid, double tol, size_t max_eval,
+                                       double *eps, double *nugget_abs /* c0 */, double *psill /* c */, double *wss /* or NULL */);
+size_t gsl_sinterp_variogram_fit_model_n_eval(void);
+int    gsl_sinterp_variogram_fit_model_trace(gsl_vector *eps, gsl_vector *wss);
 int gsl_sinterp_poly(const gsl_sinterp *interp, gsl_vector *c);    /* c_0 .. c_dim of an initialised gsl_sinterp_rbf_tps_affine interpolant */
 int gsl_sinterp_set_solver(gsl_sinterp *interp, int solver);
 int gsl_sinterp_set_rcond(gsl_sinterp *interp, int want);

@@ -497,6 +497,36 @@ int gsl_sinterp_hip_local_pack(gsl_sinterp_hip_ctx *ctx, const double *d_x, size
                                unsigned long long model_id);
 unsigned long long gsl_sinterp_hip_local_pack_count(const gsl_sinterp_hip_ctx *ctx);
 
+/* Empirical semivariogram: the binned sums over the unordered pairs i < j of sites closer than h_max -- memory
+   O(N + cells + bins), work proportional to the pairs inside the pruning stencil, no N x N matrix, so it runs on the whole
+   cloud that local kriging takes (DESIGN_VARIOGRAM.md).
+   BIN RULE, on r2 so that a host reference reproduces it to the bit: r2 = ((dx*dx) + (dy*dy)) + (dz*dz) left to right over the
+   axes present, no contraction; edge2[b] = e*e with e = b * (h_max / n_bins), edge2[n_bins] = h_max*h_max; a pair with
+   r2 < edge2[n_bins] goes into the bin b with edge2[b] <= r2 < edge2[b + 1]; coincident sites (r2 = 0) fall into bin 0.
+   acc (HOST, n_bins x 7 words), per bin b at acc[7 b + ..]:
+     0      the pair count;
+     1, 2   lo, hi of sum (f_i - f_j)^2;
+     3, 4   lo, hi of sum h, h = sqrt(r2);
+     5, 6   lo, hi of sum sqrt|f_i - f_j| (Cressie-Hawkins).
+   The three sums are 128-bit fixed-point integers: a term t enters as q = (unsigned long long) rint(ldexp(t, shift[k])),
+   shift[k] = 62 - E_k with E_k the frexp exponent of an upper bound of the terms -- (fmax - fmin)^2, h_max and
+   sqrt(fmax - fmin), the range of f taken by a reduction pass; fmax = fmin gives shift[0] = shift[2] = 0 and terms 0.
+   sum = (hi 2^64 + lo) 2^-shift[k].  Only integer additions are made, so the 7 words of a bin are the same for every row
+   order of x, every grid, every launch shape and every run; the count and the words 1, 2 are a pure function of the input
+   under IEEE arithmetic, the words 3 .. 6 contain one device sqrt per term.  A term with q = 0 still counts as a pair.
+   n < 2: every word 0, shift = {0, shift of h_max, 0}, success, nothing touches the device (the input is not inspected).
+   GSL_EINVAL: dim outside 1 .. 3, n_bins outside 1 .. 256, h_max not finite or <= 0, xtda < dim, n > 2^31 - 1 -- all checked
+   first; then GSL_EFAULT: a NULL context, acc, shift or (n > 0) d_x, d_f.  GSL_EDOM, acc zeroed, before any pair is visited:
+   a NaN or infinite entry in the dim leading columns of x or in f, or a range of f whose square overflows.  Synchronises.
+   The sites are binned into the buffer of the local route: a pack cached by gsl_sinterp_hip_local_pack is dropped.
+   gsl_sinterp_hip_variogram_pairs_tested: the unordered pairs whose r2 the last call on the context computed.
+   gsl_sinterp_hip_bbox: box[2 c] = min, box[2 c + 1] = max of coordinate c < dim over the n >= 1 rows (NaN skipped; HOST,
+   2 dim doubles); synchronises.  Same checks; n = 0 is GSL_EINVAL. */
+int gsl_sinterp_hip_variogram(gsl_sinterp_hip_ctx *ctx, const double *d_x, size_t n, int dim, size_t xtda, const double *d_f,
+                              double h_max, int n_bins, unsigned long long *acc /* HOST, n_bins x 7 */, int shift[3] /* HOST */);
+unsigned long long gsl_sinterp_hip_variogram_pairs_tested(const gsl_sinterp_hip_ctx *ctx);
+int gsl_sinterp_hip_bbox(gsl_sinterp_hip_ctx *ctx, const double *d_x, size_t n, int dim, size_t xtda, double *box /* HOST, 2 dim */);
+
 /* Modified quadratic Shepard interpolation (Renka, ACM TOMS 660 / 661; Franke & Nielson 1980) in dim 2 or 3: C1, exact at the
    data, reproduces quadratics, local, O(N) memory, no solve, no mesh, no shape parameter, analytic gradient.
    With r2 the FMA chain of the sweeps, r = sqrt(r2), and integer parameters nq, nw:
